@@ -36,6 +36,10 @@ VALU_ISSUE_PEAK = 256 * 4 * 16 * 2.4e9     # fp64-rate lane-instructions per sec
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
 FP64_VALU_PEAK_TFLOPS = 78.6   # 256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz
 FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X_MICROARCH.md: the fp64 matrix path has the vector unit's peak on this part
+# --dump-outputs: the spectral arrays (tau, M+, M- and the wavenumbers they belong to) of at most this many bytes, a fixed seeded
+# sample of wavenumber columns when the whole grid is larger; the band fluxes are always written whole
+DUMP_SPECTRAL_BYTES = 56 * 2 ** 20
+DUMP_SEED = 20260101
 
 
 def source_stamp():
@@ -71,7 +75,12 @@ def main():
     ap.add_argument("--no-calibrate", action="store_true", help="N > 1: keep the cost model's partition instead of re-cutting it from the shards' measured times")
     ap.add_argument("--no-emulated-shards", action="store_true", help="skip the emulated_shards block (shards 0, 3, 7 of 8 and 1 of 4 timed after the headline)")
     ap.add_argument("--cpu-stride", type=int, default=0, help="cpu_baseline evaluates every n-th wavenumber (0 = size the sample for ~15 s)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64): Fup, Fdn [np]; tau [nl, m], Mup, Mdn [np, m] "
+                         "and nu [m] on m wavenumbers (all of them, or a fixed seeded sample when the grid holds more than 56 MiB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as fresh child processes, BEFORE anything
@@ -273,6 +282,41 @@ def main():
     value = points * args.steps / dt
     Fh = F.cpu().numpy()
     olr = float(Fh[0])
+
+    # what the last timed step left for its caller, fetched before anything else runs on the column: the band fluxes (all-reduced
+    # over the ranks) and tau, M+, M- on a sample of wavenumbers drawn from the whole grid -- the same sample whatever the partition,
+    # each rank filling the columns of its own range and one sum combining them
+    dumped = None
+    if args.dump_outputs:
+        dist_dump = use_dist and N > 1
+        lo, hi = (0, len(nu)) if dist_dump else (col.j0, col.j1)
+        rows = col.nl + 2 * col.np
+        m = min(hi - lo, DUMP_SPECTRAL_BYTES // (8 * (rows + 1)))
+        if m < hi - lo:
+            idx = lo + np.sort(np.random.default_rng(DUMP_SEED).choice(hi - lo, m, replace=False))
+        else:
+            idx = np.arange(lo, hi)
+        tau_d = np.zeros((col.nl, col.nnu), order="F"); Mu_d = np.zeros((col.np, col.nnu), order="F"); Md_d = np.zeros((col.np, col.nnu), order="F")
+        col.fetch(tau_d, Mu_d, Md_d)
+        mine = (idx >= col.j0) & (idx < col.j1)
+        S = np.zeros((rows, m))
+        S[:col.nl, mine] = tau_d[:, idx[mine] - col.j0]
+        S[col.nl:col.nl + col.np, mine] = Mu_d[:, idx[mine] - col.j0]
+        S[col.nl + col.np:, mine] = Md_d[:, idx[mine] - col.j0]
+        del tau_d, Mu_d, Md_d
+        if dist_dump:
+            St = torch.from_numpy(S).to(f"cuda:{dev}" if args.dist_backend == "nccl" else "cpu")
+            dist.all_reduce(St)
+            S = St.cpu().numpy()
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            arrays = dict(Fup=Fh[:col.np], Fdn=Fh[col.np:], tau=S[:col.nl], Mup=S[col.nl:col.nl + col.np], Mdn=S[col.nl + col.np:],
+                          nu=nu[idx])
+            for name, a in arrays.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+            dumped = dict(dir=os.path.abspath(args.dump_outputs), files=sorted(n + ".npy" for n in arrays),
+                          wavenumbers=int(m), of=int(hi - lo), sample_seed=(DUMP_SEED if m < hi - lo else None))
+        del S
 
     # per-kernel HIP-event timing on the launch stream (rank-local) and the roofline of every line-stage kernel class
     # (cs_column_profile runs the step on ONE stream with events between the classes; the timed loop above overlaps the node
@@ -576,7 +620,7 @@ def main():
                                nnu=len(nu), layers=nl, lines=lines_total, parallelism=f"nu-shard x{N}"),
                    collective=(f"{args.dist_backend} all_reduce of {2 * col.np} doubles per step" if use_dist else None),
                    olr_wm2=olr, setup_ms=setup_ms, launches_per_step=int(info["launches"]), launch_groups=int(info["groups"]), host_pointer_ms=host_ptr, kernel_source_sha16=source_stamp(),
-                   partition=partition, emulated_shards=emu, roofline=roofline, cpu_baseline=cpu)
+                   partition=partition, emulated_shards=emu, roofline=roofline, cpu_baseline=cpu, dumped_outputs=dumped)
         print(json.dumps(out))
     if use_dist:
         dist.destroy_process_group()
