@@ -1252,7 +1252,8 @@ class Column:
                     line_kernel=out[7])
 
     def work(self):
-        """Evaluations the last run issued for its Voigt gases: per-point, at interpolation nodes; levels in use."""
+        """Evaluations the last run issued for its Voigt gases: per-point, at interpolation nodes; levels in use.  `dispatch`: the
+        kernel forms the last run (or batch) chose (cs_column_work out[34..39], include/clearsky_hip_dev.h)."""
         self._require_resident("work")
         out = (C.c_int64 * 40)()
         check(lib().cs_column_work(self.ctx.handle, out))
@@ -1262,7 +1263,10 @@ class Column:
                     direct_evals_matrix=out[14], matrix_evals_3term=out[15], sub_evals=out[16], core_tile_states=out[17], matrix_evals_8term=out[18], node_evals_matrix_3term=out[19],
                     near_pairs_tier0=out[20], near_pairs_tier1=out[21], edge_mx_flops_useful=out[22], edge_mx_flops_issued=out[23],
                     nodes_mx_flops_useful=out[24], nodes_mx_flops_issued=out[25], apply_flops=out[26],
-                    edge_mx_record_bytes_requested=out[32], nodes_mx_record_bytes_requested=out[33])
+                    flux_scan_ns=[out[27 + q] for q in range(5)],
+                    edge_mx_record_bytes_requested=out[32], nodes_mx_record_bytes_requested=out[33],
+                    dispatch=dict(far_split=out[34], tables=out[35], near_prio=out[36], streams=out[37], nodes_split=out[38],
+                                  flags=out[39]))
 
     def fetch(self, tau=None, Mup=None, Mdn=None):
         """Copy results to host.  Returns (Fup, Fdn); fills the optional Fortran-order matrices in place."""

@@ -45,6 +45,11 @@ int fail(int code, const char *fmt, ...)
 thread_local int g_nlaunch = 0;   // kernel launches since the last reset (cs_column_run reports its count)
 thread_local int g_near_launches = 0, g_line_kernel = 0;   // of the step being enqueued: near-line launches (all groups), and what summed the per-point
                                                            // far lines of its last group: 0 = k_voigt_far, 1 = k_linesum<shape>, 2 = k_phco2
+// which forms the step being enqueued dispatched (cs_column_work out[34..39]): the fields of its last Voigt group, the flags of the whole step
+struct Dispatch { int far_split, tables, near_prio, streams, nodes_split, flags; };
+enum { CS_DF_TNODES = 1, CS_DF_NEAR_MEMSET = 2, CS_DF_RT_STREAMS = 4, CS_DF_BAND_SUM = 8, CS_DF_FAR64_SHARED = 16, CS_DF_CHUNK4 = 32,
+       CS_DF_CASCADE_ASIDE = 64 };
+thread_local Dispatch g_disp = {};
 #define CS_LAUNCH(...) do { g_nlaunch++; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
 #define HIPCHK(expr)                                                                                   \
@@ -257,6 +262,7 @@ struct Column {
     DevBuf ticket;             // k_flux: blocks finished (the last one adds the block partials up)
     int flux_form_last = 0;      // which flux kernel the last run used (flux_form)
     int near_launches_last = 0, line_kernel_last = 0;   // cs_column_info out[6], out[7]
+    Dispatch disp_last = {};     // cs_column_work out[34..39]
     bool sigma_partial = false;  // the last run finished the cross-sections on chip (k_flux): cs_column_sigma_fetch evaluates them again, in HBM
     ChebGrid cheb;             // interpolation levels of the nu grid (nlev = 0: off)
     DevBuf chebF;              // node sums F [nItot][64][Kpad], summed over the column's gases (k_cheb_nodes accumulates)
@@ -1252,6 +1258,8 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
             // (cs_set_tuning key 21: 1 = never, 2 = always, A/B)
             mx_merged = !mx_one_thread && itp.mxzones_merge != 1 && (itp.mxzones_merge == 2 || nt64 < 1024);
         }
+        g_disp.far_split = 0; g_disp.tables = 0; g_disp.near_prio = near_prio; g_disp.streams = 0; g_disp.nodes_split = 0;
+        if (use_sep_s || use_edge) g_disp.tables = mx_merged ? 1 : (mx_one_thread ? 3 : 2);
         if (mx_merged) {
             const unsigned nb_sep = use_sep_s ? (unsigned)(((int64_t)(itp.nItot - q0s) * ngrp_s + 15) / 16) : 0u;
             const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp_s + 15) / 16) : 0u;
@@ -1266,6 +1274,7 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
             const int q_acc = (defer && defer->ngas > 0 && defer->l0[0] < itp.nlev) ? itp.ioff[defer->l0[0]] : itp.nItot;
             // short grids: four waves per (interval, state) (cs_set_tuning key 13: 0 = below 16384 waves, 1 = always, 2 = never)
             const bool nsplit4 = itp.nodes_split == 1 || (itp.nodes_split == 0 && (int64_t)(itp.nItot - q0) * kn < 16384);
+            g_disp.nodes_split = nsplit4 ? 1 : 0;
             const dim3 gridn(nsplit4 ? (unsigned)kn * (unsigned)(itp.nItot - q0) : (unsigned)((kn + 3) / 4) * (unsigned)(itp.nItot - q0));
             const int ngrp = ngrp_s;
             const bool use_sep = use_sep_s;
@@ -1287,6 +1296,7 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
                 (void)hipEventRecord(fork->ev_fork, s);
                 (void)hipStreamWaitEvent(fork->s2, fork->ev_fork, 0);
                 forked_here = true;
+                g_disp.streams |= 1;
                 s = fork->s2;     // the two node kernels below run beside what follows them on the main stream
             }
 #define NODES_LAUNCH(M, L_, M4, L4, S4) do { if (nsplit4) CS_LAUNCH((k_cheb_nodes<M4, L4, S4>), gridn, dim3(256), 0, s, itp.nodes, G.L, hot, hot32, G.nu.as<double>(), itp.iz, \
@@ -1314,6 +1324,7 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
                 for (int l = 0; l < itp.nlev; l++) { mf.ioff[l] = itp.ioff[l]; mf.nfar[l] = itp.nfar[l] > 0 ? itp.nfar[l] : CS_NC; }
                 mf.ioff[itp.nlev] = itp.nItot;
                 mf.R = (itp.far_shared_full && nsplit == nq) ? nullptr : itp.R;
+                if (itp.R && !mf.R) g_disp.flags |= CS_DF_FAR64_SHARED;
                 CS_LAUNCH(k_cheb_nodes_mx, dim3(nblk_mx), dim3(256), 0, s, itp.nodes, G.L, hot, itp.sep, itp.nItot, q0, nsplit, kn,
                                    itp.Kpad, ngrp, itp.F, itp.iz, mf);
             }
@@ -1365,6 +1376,7 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
         const int64_t nwave = (int64_t)nt64 * kn;
         int split = nwave >= 16384 ? 1 : (nwave >= 4096 ? 2 : 4);   // (re-tuned with the far wings interpolated: waves are 3x shorter)
         if (itp.far_split == 1 || itp.far_split == 2 || itp.far_split == 4) split = itp.far_split;   // (cs_set_tuning key 22, A/B)
+        g_disp.far_split = split;
         const int nblk_s = (nt64 * split + 3) / 4;
         // 8 x (blocks of the longest XCD stretch): XCD-aware tile mapping (tile_block); xtiles is a multiple of 4 tiles
         const dim3 grid_s((unsigned)(8 * (xtiles * split / 4)), kn);
@@ -1387,7 +1399,11 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
             // elsewhere: cs_set_tuning key 19 = 1 keeps the memset for A/B), else a memset
             const bool sub_here = use_edge && itp.core;
             const bool sub_assigns = sub_here && !fork->zeroed && !itp.near_memset;
-            if (!fork->zeroed && !sub_assigns) (void)hipMemsetAsync(fork->sigma2, 0, (size_t)kn * nnu * sizeof(double), fork->s3);
+            if (!fork->zeroed && !sub_assigns) {
+                (void)hipMemsetAsync(fork->sigma2, 0, (size_t)kn * nnu * sizeof(double), fork->s3);
+                g_disp.flags |= CS_DF_NEAR_MEMSET;
+            }
+            g_disp.streams |= 2;
             fork->zeroed = true;
             if (sub_here)
                 CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, fork->s3, dnu, nnu, G.L, hot,
@@ -1446,6 +1462,7 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
         if (use_edge)
         {
             if (fuse) fork_join(fork, s);   // (it reads F)
+            if (mx_big(nt64, kn, 1024) && itp.edge_phases && itp.tnodes) g_disp.flags |= CS_DF_TNODES;
             if (mx_big(nt64, kn, 1024))
                 CS_LAUNCH(k_voigt_edge_mx<1>, dim3((unsigned)((nt64 + 3) / 4), (unsigned)((kn + 15) / 16)), dim3(256), 0, s, dnu, nnu, G.L, hot, win,
                           itp.edge, nt64, kn, cut, sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), itp.edge_phases,
@@ -2728,6 +2745,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     HIPCHK(dpart.reserve((size_t)B * bg.nblk * 2 * np * sizeof(double)));
     HIPCHK(dF.reserve((size_t)B * 2 * np * sizeof(double)));
     double *sig = shared_sigma ? c.sigma.as<double>() : dsig.as<double>();
+    g_disp = Dispatch();
     if (shared_sigma) {
         int e = 0;
         if ((rc = sigma_impl(ctx, s, nullptr, e))) return rc;
@@ -2841,6 +2859,8 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
             HIPCHK(hipStreamSynchronize(s));
         }
     }
+    if (bg.streams) g_disp.flags |= CS_DF_RT_STREAMS;
+    c.disp_last = g_disp;
     launch_rt(c.nstream, bg, B, s, c.rt, c.nu.as<double>(),
                     c.wts.as<double>(), c.nnu, sig, dmuk.as<double>(), c.P.as<double>(), dTlev.as<double>(),
                     c.has_S ? c.S_toa.as<double>() : nullptr, c.has_alb ? c.albedo.as<double>() : nullptr, (double *)nullptr, nullptr,
@@ -2943,6 +2963,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
         launch_apply_cascade(fk.s2, apply, Rc, c.cheb.itv, c.cheb.nI, 1, cheb_kpad(K), c.nnu, K, 0.0, nullptr, sig, 1, &carried);
         (void)hipEventRecord(fk.ev_join, fk.s2);   // (the main stream has not waited yet: it will wait for this later record)
         cascaded_aside = true;
+        g_disp.flags |= CS_DF_CASCADE_ASIDE;
     }
     fork_join(&fk, s, true, false);   // the node sums; the near-line kernels may run on beside what follows (none of it touches their plane)
     // interpolated far wings of all gases: sigma += sum_level C (sum_gas F)  (one pass over C and sigma)
@@ -3017,6 +3038,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
     g_nlaunch = 0;
     g_near_launches = 0;
     g_line_kernel = 0;
+    g_disp = Dispatch();
     c.last_stream = s;
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
     bool near_live = false;
@@ -3040,6 +3062,8 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
         fuse.ticket = (fblk <= 512 && !(ctx->tune[15] & 4) && ctx->gfx950) ? c.ticket.as<unsigned>() : nullptr;   // (| 4: k_freduce always, for A/B)
         fuse.gpartial = c.partial.as<double>() + (size_t)std::max<int64_t>(c.rtg.nblk, (c.nnu + 63) / 64) * 2 * c.np;
         reduced = fuse.ticket != nullptr;
+        if (reduced) g_disp.flags |= CS_DF_BAND_SUM;
+        if (form == 2 && (ctx->tune[15] & 8)) g_disp.flags |= CS_DF_CHUNK4;
         if ((ctx->tune[15] & 128) && c.fluxdbg.reserve((8 + 2 * (size_t)fblk + 32) * sizeof(unsigned long long)) == hipSuccess) fuse.dbg = c.fluxdbg.as<unsigned long long>();
         // the chunked form always writes the layer optical depths (its upward sweep reads them back): into the caller's plane or scratch
         double *dtau = (c.want_tau || form == 2) ? c.tau.as<double>() : nullptr;   // (forms 1 and 3 keep the optical depths in LDS)
@@ -3051,6 +3075,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
         }
 #undef CS_FLUX_CASE
     } else {
+        if (c.rtg.streams) g_disp.flags |= CS_DF_RT_STREAMS;
         launch_rt(c.nstream, c.rtg, 1, s, c.rt, c.nu.as<double>(), c.wts.as<double>(),
                   c.nnu, sig, c.muk.as<double>(), c.P.as<double>(), c.Tlev.as<double>(), dS, dA, c.want_tau ? c.tau.as<double>() : nullptr,
                   dMu, dMd, c.partial.as<double>(), 0, near_live ? c.sigma2.as<double>() : nullptr);
@@ -3062,6 +3087,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
     c.launches = g_nlaunch;
     c.near_launches_last = g_near_launches;
     c.line_kernel_last = g_line_kernel;
+    c.disp_last = g_disp;
     HIPCHK(hipGetLastError());
     return CS_OK;
 }
@@ -3610,7 +3636,12 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
     }
     out[32] = rec_edge * (int64_t)sizeof(LineHot);
     out[33] = rec_nodes * (int64_t)sizeof(LineHot);
-    for (int q = 34; q < 40; q++) out[q] = 0;
+    out[34] = c.disp_last.far_split;
+    out[35] = c.disp_last.tables;
+    out[36] = c.disp_last.near_prio;
+    out[37] = c.disp_last.streams;
+    out[38] = c.disp_last.nodes_split;
+    out[39] = c.disp_last.flags;
     out[0] = direct;
     out[1] = nodes;
     out[2] = c.cheb.nlev;

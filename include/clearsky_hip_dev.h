@@ -132,7 +132,14 @@ int cs_column_info(cs_ctx *ctx, int64_t *out);
  * first pass over its layer chunk, hand-over of the incoming intensities, and out[31] = from its first instruction to the last block's
  * store of the band fluxes (100 MHz wall clock; 0 otherwise); out[32], out[33] = bytes of per-(state, line) records k_voigt_edge_mx and
  * k_cheb_nodes_mx REQUEST per launch (lines of every piece x 16 states x 32 B: neighbouring tiles / intervals ask for the same record again --
- * the unique ones are K x lines in range x 32 B).  `out` holds 40 values.
+ * the unique ones are K x lines in range x 32 B); out[34..39] = what the last cs_column_run (or cs_column_batch) dispatched, with
+ * out[34..38] for its last Voigt group (0 where it had none): out[34] = waves per 64-point tile of k_voigt_far (1, 2, 4; key 22),
+ * out[35] = the matrix-core piece tables: 0 none, 1 blocks of k_gas_setup_mx, 2 k_mxzones16, 3 k_mxzones (one thread per item; key 21,
+ * key 15 | 16), out[36] = wave priority of the near-line kernels (0, 3; key 16), out[37] = side streams: 1 node sums, 2 near-line
+ * kernels (keys 2, 7), out[38] = 1 where k_cheb_nodes ran four waves per (interval, state) (key 13), out[39] = flags of the whole step:
+ * 1 window ends on the 16 tile nodes in k_voigt_edge_mx (key 23), 2 near-line plane cleared by a memset (key 19), 4 k_rt_streams
+ * (key 5), 8 band sum inside the flux kernel (key 15 | 4), 16 far pieces of shared items on 64 nodes (key 17), 32 k_flux_chunk with
+ * four waves per SIMD (key 15 | 8), 64 levels folded on the node-sum side stream (key 15 | 256).  `out` holds 40 values.
  * cs_column_counts is the reference's count. */
 int cs_column_work(cs_ctx *ctx, int64_t *out);
 
