@@ -490,6 +490,9 @@ voigt_, voigt = _shape_inplace("voigt", 25.0)        # line_shapes.jl:412-448
 lorentz_, lorentz = _shape_inplace("lorentz", 25.0)  # :313-348
 doppler_, doppler = _shape_inplace("doppler", 25.0)  # :200-235
 PHCO2_, PHCO2 = _shape_inplace("PHCO2", 500.0)       # :527-564
+# pedestal-removed Voigt (MT_CKD convention; no reference counterpart): sum of S [fvoigt(nu - nul) - fvoigt(dnu_cut)] over the same
+# lines as voigt, max(0, .) -- the line shape an MT_CKD-style water-vapour continuum is defined against (include/clearsky_hip.h)
+voigtCKD_, voigtCKD = _shape_inplace("voigtCKD", 25.0)
 
 
 def faddeeva(x, y, ctx: Optional[Context] = None):

@@ -217,6 +217,8 @@ struct ColGas {
     GasInterp itp;            // interpolated far wings (nlev = 0: off)
     int64_t jlo = 0, jhi = 0;
     int xtiles = 0;           // longest XCD stretch of the far kernel's tile order, in tiles (wave_windows)
+    bool ped = false;         // shape code 4: shape is SH_VOIGT and launch_pedestal follows the line sum over [pa, pb)
+    int64_t pa = 0, pb = 0;
 };
 
 // k_rt launch geometry (rt_geometry)
@@ -258,6 +260,7 @@ struct Column {
     std::vector<double> h_Tk;
     DevBuf nu, wts, P, Pk, Tk, muk, Tlev, extra, S_toa, albedo;
     DevBuf hot, cold, sigma, sigma2, tau, Mup, Mdn, partial, F, stage, ranges;   // sigma2: the near-line plane (k_voigt_near on a side stream)
+    DevBuf ped;                // launch_pedestal's workspace for K states (columns with a code-4 group)
     DevBuf fluxdbg;            // k_flux_scan: phase time stamps of block 0 (cs_set_tuning key 15 | 128; cs_column_work out[27..])
     DevBuf ticket;             // k_flux: blocks finished (the last one adds the block partials up)
     int flux_form_last = 0;      // which flux kernel the last run used (flux_form)
@@ -1579,6 +1582,30 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
     }
 }
 
+// workspace of launch_pedestal for kn states of a table of L lines: p, in-block prefix and suffix sums [3][kn][L], block sums [kn][ceil(L / CS_PED_B)]
+static size_t ped_bytes(int64_t kn, int64_t L) { return (size_t)kn * ((size_t)3 * L + (L + CS_PED_B - 1) / CS_PED_B) * sizeof(double); }
+
+// shape code 4 behind a code-0 launch_gas on the same stream (whose K1 left the Voigt records of these kn states in hot / cold):
+// sigma[k][i] -= sum of p[k][l] over the lines l of [a, b) with |nu_i - nul_l| <= cut; clamp: then max(0, .) (sigma complete).
+// [a, b) = the lines the line sum included (the strict end-point pre-filter of the vector method, or every line) within the records'
+// range; J0, J1: the line kernels' windows of the 256-point tiles (tile_windows).  ws: ped_bytes(kn, G.L).  Runs before the next group's K1 overwrites the records (stream order).
+static void launch_pedestal(hipStream_t s, const GasTable &G, int64_t a, int64_t b, const int32_t *J0, const int32_t *J1, int kn,
+                            const LineHot *hot, const LineCold *cold, const double *dnu, int64_t nnu, double cut, double *sigma, bool clamp,
+                            double *ws)
+{
+    const int64_t nqt = (G.L + CS_PED_B - 1) / CS_PED_B;
+    const size_t kl = (size_t)kn * G.L;
+    double *p = ws, *pre = ws + kl, *suf = ws + 2 * kl, *bsum = ws + 3 * kl;
+    b = std::max(a, b);
+    if (b > a) {
+        const int64_t q0 = a / CS_PED_B, q1 = (b - 1) / CS_PED_B + 1;
+        CS_LAUNCH(k_ped_values, dim3((unsigned)((q1 - q0 + 3) / 4), (unsigned)kn), dim3(256), 0, s, hot, cold, G.L, a, b, cut, q0, q1 - q0,
+                  nqt, p, pre, suf, bsum);
+    }
+    CS_LAUNCH(k_ped_sub, dim3((unsigned)((nnu + 255) / 256), (unsigned)((kn + CS_PED_KC - 1) / CS_PED_KC)), dim3(256), 0, s, dnu, nnu,
+              G.nu.as<double>(), G.L, a, b, J0, J1, cut, kn, p, pre, suf, bsum, nqt, sigma, clamp ? 1 : 0);
+}
+
 int check_gas_states(const GasTable &G, int K, const double *T)
 {
     for (int k = 0; k < K; k++)
@@ -1898,8 +1925,10 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
 {
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (slot < 0 || slot >= CS_MAX_GAS || !ctx->gas[slot].present) return fail(CS_EINVAL, "gas slot %d is empty", slot);
-    if (shape < 0 || shape > 3) return fail(CS_EINVAL, "unknown shape %d", shape);
+    if (shape < 0 || shape > SH_VOIGT_CKD) return fail(CS_EINVAL, "unknown shape %d", shape);
     if (K < 1 || ld_state < nnu) return fail(CS_EINVAL, "bad K/ld_state");
+    const bool ped = shape == SH_VOIGT_CKD;   // the Voigt line sum, then the pedestal behind it
+    if (ped) shape = SH_VOIGT;
     int rc;
     if ((rc = check_ascending(nu, nnu))) return rc;
     GasTable &G = ctx->gas[slot];
@@ -1927,8 +1956,11 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
         (rc = upload(dwin, win.data(), win.size(), s)))
         return rc;
     // bound the workspace: process the states in chunks
-    const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * (sizeof(double) + sizeof(int2));
+    const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * (sizeof(double) + sizeof(int2)) +
+                             (ped ? ped_bytes(1, G.L) : 0);
     int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));   // gridDim.y limit
+    DevBuf dped;
+    if (ped) HIPCHK(dped.reserve(ped_bytes(kc, G.L)));
     HIPCHK(hot.reserve(((size_t)kc * G.L + 4) * sizeof(LineHot)));
     HIPCHK(cold.reserve((size_t)kc * G.L * sizeof(LineCold)));
     HIPCHK(dsig.reserve((size_t)kc * nnu * sizeof(double)));
@@ -1963,6 +1995,10 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
                    dlrt.as<double>() + k0, dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(),
                    dwin.as<WaveWin>(), xtiles, dzones.as<Zone>(), dranges.as<int2>(), dgmax.as<double>() + k0, dnu_cut, 0.0, nullptr, dsig.as<double>(), 0, nullptr,
                    mix32, ctx->far_s, itp, nullptr, &ctx->ph);
+        if (ped)
+            launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
+                            hot.as<LineHot>(), cold.as<LineCold>(),
+                            dnu.as<double>(), nnu, dnu_cut, dsig.as<double>(), true, dped.as<double>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpy2DAsync(sigma + (size_t)k0 * ld_state, ld_state * sizeof(double), dsig.p, nnu * sizeof(double),
                                 nnu * sizeof(double), kn, hipMemcpyDeviceToHost, s));
@@ -1977,8 +2013,10 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (gas_slot < 0 || gas_slot >= CS_MAX_GAS || !ctx->gas[gas_slot].present) return fail(CS_EINVAL, "gas slot %d is empty", gas_slot);
     if (table_slot < 0 || table_slot >= CS_MAX_TABLE) return fail(CS_EINVAL, "table slot %d out of range", table_slot);
-    if (shape < 0 || shape > 3) return fail(CS_EINVAL, "unknown shape %d", shape);
+    if (shape < 0 || shape > SH_VOIGT_CKD) return fail(CS_EINVAL, "unknown shape %d", shape);
     if (nT < 2 || nP < 2) return fail(CS_EINVAL, "need at least 2 x 2 grid points");
+    const bool ped = shape == SH_VOIGT_CKD;   // the Voigt line sum, then the pedestal behind it (clamped before k_table_log)
+    if (ped) shape = SH_VOIGT;
     int rc;
     if ((rc = check_ascending(nu, nnu))) return rc;
     for (int64_t i = 0; i < nnu; i++)
@@ -2021,8 +2059,10 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
         (rc = upload(dwin, win.data(), win.size(), s)) || (rc = upload(dgb, gb.data(), M, s)))
         return rc;
     HIPCHK(tb.Z.reserve((size_t)M * nnu * sizeof(double)));
-    const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * sizeof(int2);
+    const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * sizeof(int2) + (ped ? ped_bytes(1, G.L) : 0);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)M, ((size_t)4 << 30) / per_state, (size_t)65535}));
+    DevBuf dped;
+    if (ped) HIPCHK(dped.reserve(ped_bytes(kc, G.L)));
     HIPCHK(hot.reserve(((size_t)kc * G.L + 4) * sizeof(LineHot)));
     HIPCHK(cold.reserve((size_t)kc * G.L * sizeof(LineCold)));
     HIPCHK(dzones.reserve((size_t)kc * win.size() * sizeof(Zone)));
@@ -2051,6 +2091,10 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
                    dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(), dwin.as<WaveWin>(), xtiles,
                    dzones.as<Zone>(), dranges.as<int2>(), dgb.as<double>() + k0, dnu_cut, 0.0, nullptr, tb.Z.as<double>() + (size_t)k0 * nnu, 0, nullptr,
                    mix32, ctx->far_s, itp, nullptr, &ctx->ph);
+        if (ped)
+            launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
+                            hot.as<LineHot>(), cold.as<LineCold>(),
+                            dnu.as<double>(), nnu, dnu_cut, tb.Z.as<double>() + (size_t)k0 * nnu, true, dped.as<double>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
     }
@@ -2545,7 +2589,8 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     if (ctx->interp) {   // interval sizes from the narrowest Voigt cut-off of the column
         double cmin = 0.0;
         for (int gi = 0; gi < ngas; gi++)
-            if ((shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT || (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_LORENTZ) {
+            if ((shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT || (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_LORENTZ ||
+                (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_CKD) {
                 const double cu = dnu_cuts ? dnu_cuts[gi] : 25.0;
                 cmin = cmin > 0.0 ? std::min(cmin, cu) : cu;
             }
@@ -2560,15 +2605,15 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         if (ug.slot < 0 || ug.slot >= CS_MAX_GAS || !ctx->gas[ug.slot].present)
             return fail(CS_EINVAL, "gas slot %d is empty", ug.slot);
         ug.generation = ctx->gas[ug.slot].generation;
-        if (ug.shape < 0 || ug.shape > 3) return fail(CS_EINVAL, "unknown shape %d", ug.shape);
+        if (ug.shape < 0 || ug.shape > SH_VOIGT_CKD) return fail(CS_EINVAL, "unknown shape %d", ug.shape);
         const GasTable &G = ctx->gas[ug.slot];
         ug.pairs_per_state = -1;   // counted on demand (cs_column_counts): O(nnu log L) on the host
         ug.lines_in_range = std::upper_bound(G.h_nu.begin(), G.h_nu.end(), nu[nnu - 1] + ug.cut) -
                             std::lower_bound(G.h_nu.begin(), G.h_nu.end(), nu[0] - ug.cut);   // (the reference's count: inside the cut-off)
-        // Voigt (Lorentz) gases with the same cut-off go into one group; a slot named twice stays apart (a merged table tags a
-        // line with ONE member)
+        // Voigt (Lorentz, pedestal-removed Voigt) gases with the same shape and cut-off go into one group -- never code 4 with code 0:
+        // the pedestal is subtracted for every line of a group; a slot named twice stays apart (a merged table tags a line with ONE member)
         bool placed = false;
-        if (ctx->merge && (ug.shape == SH_VOIGT || ug.shape == SH_LORENTZ))
+        if (ctx->merge && (ug.shape == SH_VOIGT || ug.shape == SH_LORENTZ || ug.shape == SH_VOIGT_CKD))
             for (auto &grp : groups) {
                 const UserGas &h = c.ugas[grp[0]];
                 bool dup = false;
@@ -2583,6 +2628,8 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         ColGas &cg = c.gas[qi];
         cg.mem = groups[qi];
         cg.shape = c.ugas[cg.mem[0]].shape;
+        cg.ped = cg.shape == SH_VOIGT_CKD;
+        if (cg.ped) cg.shape = SH_VOIGT;   // every kernel of a Voigt group, then the pedestal
         cg.cut = c.ugas[cg.mem[0]].cut;
         if (cg.mem.size() == 1) {
             cg.tab = &ctx->gas[c.ugas[cg.mem[0]].slot];
@@ -2600,6 +2647,8 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(cg.shape, G, nu[nnu - 1], cg.cut), J0, J1, pairs_unused, inr_unused);
         cg.jlo = J0.front();
         cg.jhi = J1.back();
+        cg.pa = std::max(g0, cg.jlo);
+        cg.pb = std::min(g1, cg.jhi);
         std::vector<WaveWin> win;
         cg.xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, cg.cut, win);
         if ((rc = upload(cg.J0, J0.data(), J0.size(), s)) || (rc = upload(cg.J1, J1.data(), J1.size(), s)) ||
@@ -2623,8 +2672,9 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     HIPCHK(c.hot.reserve(((size_t)K * maxL + 4) * sizeof(LineHot)));
     HIPCHK(c.cold.reserve((size_t)K * maxL * sizeof(LineCold)));
     HIPCHK(c.sigma.reserve((size_t)K * nnu * sizeof(double)));
-    bool any_voigt = false;
-    for (auto &cg : c.gas) any_voigt = any_voigt || cg.shape == SH_VOIGT;
+    bool any_voigt = false, any_ped = false;
+    for (auto &cg : c.gas) any_voigt = any_voigt || cg.shape == SH_VOIGT, any_ped = any_ped || cg.ped;
+    if (any_ped) HIPCHK(c.ped.reserve(ped_bytes(K, maxL)));
     if (any_voigt) HIPCHK(c.sigma2.reserve((size_t)K * nnu * sizeof(double)));
     if (ngas > 0) HIPCHK(c.ranges.reserve((size_t)K * nnu * sizeof(int2) + (size_t)2 * K * ((nnu + 63) / 64) * sizeof(int)));   // + per-(tile, state) flags
     HIPCHK(c.tau.reserve((size_t)nl * nnu * sizeof(double)));   // the caller's output, or k_flux_chunk's scratch between its two sweeps
@@ -2736,7 +2786,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     const double *extra = c.has_extra ? c.extra.as<double>() : nullptr;
     if (extra) return fail(CS_EINVAL, "host-evaluated sigma(nu,T,P) terms are not supported in batch mode");
     const bool shared_sigma = c.accel.slot >= 0;   // AcceleratedAbsorber: cross-sections do not depend on the thermal state (absorbers.jl:203)
-    DevBuf dTk, dPk, dmuk, dTlev, dsig, dtau, dpart, dF, dranges, dconc, dPp, dgb, dzones, dizones, dF2, dsep, dedge, hot, cold, dlrt, dqref;
+    DevBuf dped, dTk, dPk, dmuk, dTlev, dsig, dtau, dpart, dF, dranges, dconc, dPp, dgb, dzones, dizones, dF2, dsep, dedge, hot, cold, dlrt, dqref;
     if ((rc = upload(dTk, Tk.data(), BK, s)) || (rc = upload(dPk, Pk.data(), BK, s)) || (rc = upload(dmuk, muk.data(), BK, s)) ||
         (rc = upload(dTlev, T_levels, (size_t)B * np, s)))
         return rc;
@@ -2755,13 +2805,17 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     }
     size_t maxL = 0;
     for (auto &g : c.gas) maxL = std::max(maxL, (size_t)g.tab->L);
-    const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + (size_t)c.nnu * sizeof(int2);
+    bool any_ped = false;
+    for (auto &cg : c.gas) any_ped = any_ped || cg.ped;
+    const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + (size_t)c.nnu * sizeof(int2) +
+                             (any_ped ? ped_bytes(1, (int64_t)maxL) : 0);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BK, ((size_t)8 << 30) / std::max<size_t>(per_state, 1), (size_t)65535}));
     if (c.ngas > 0) {
         HIPCHK(hot.reserve(((size_t)kc * maxL + 4) * sizeof(LineHot)));
         HIPCHK(cold.reserve((size_t)kc * maxL * sizeof(LineCold)));
         HIPCHK(dranges.reserve((size_t)kc * c.nnu * sizeof(int2) + (size_t)2 * kc * ((c.nnu + 63) / 64) * sizeof(int)));
         if (ctx->mixed) HIPCHK(ctx->hot32.reserve(((size_t)kc * maxL + 4) * sizeof(LineF32)));
+        if (any_ped) HIPCHK(dped.reserve(ped_bytes(kc, (int64_t)maxL)));
     }
     for (auto &cg : c.gas)
         if (cg.shape == SH_PHCO2) { ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id); break; }
@@ -2815,6 +2869,9 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
                        cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), cg.win.as<WaveWin>(), cg.xtiles, dzones.as<Zone>(), dranges.as<int2>(),
                        dgb.as<double>() + k0, cg.cut, c.sigma_gray, nullptr, sig + (size_t)k0 * c.nnu, qi > 0, nullptr,
                        (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, nullptr, &ctx->ph);
+            if (cg.ped)
+                launch_pedestal(s, G, cg.pa, cg.pb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), kn, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut,
+                                sig + (size_t)k0 * c.nnu, false, dped.as<double>());
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipStreamSynchronize(s));   // cc/pp/gb are locals; the device buffers are reused by the next group
@@ -2941,6 +2998,9 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
                    ev ? ev + e : nullptr,
                    (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, &apply, &ctx->ph,
                    use_fork ? &fk : nullptr);
+        if (cg.ped)   // (into the plane the group's first kernel initialised; the near-line plane and the wings still to come only add)
+            launch_pedestal(s, G, cg.pa, cg.pb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), K, c.hot.as<LineHot>(), c.cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, sig, false,
+                            c.ped.as<double>());
         if (ev) { e += 6; HIPCHK(hipEventRecord(ev[e++], s)); }
     }
     if (fuse) { fuse->apply = 0; fuse->ncia = 0; fuse->Kpad = cheb_kpad(K); }
@@ -3005,6 +3065,12 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
     else if (fk.live) {
         const int64_t tot = (int64_t)K * c.nnu;
         CS_LAUNCH(k_fold, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, sig, c.sigma2.as<double>());
+    }
+    if (!near_plane_live) {   // the cross-sections are the result: complete here, so the max(0, .) of a code-4 group applies
+        bool any_ped = false;
+        for (auto &cg : c.gas) any_ped = any_ped || cg.ped;
+        const int64_t tot = (int64_t)K * c.nnu;
+        if (any_ped) CS_LAUNCH(k_clamp0, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, sig);
     }
     HIPCHK(hipGetLastError());
     return CS_OK;

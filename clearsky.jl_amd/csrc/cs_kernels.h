@@ -35,6 +35,8 @@ constexpr double kOSqPiLn2 = 0.46971863934982566;  // 1/sqrt(pi/ln 2)       line
 constexpr double kC2 = 100.0 * kHp * kC / kKb;     // 100 h c / k           line_shapes.jl:5
 
 enum { SH_VOIGT = 0, SH_LORENTZ = 1, SH_DOPPLER = 2, SH_PHCO2 = 3 };
+// shape code 4 (pedestal-removed Voigt) never reaches a line kernel: its groups run as SH_VOIGT, then k_ped_values / k_ped_sub
+constexpr int SH_VOIGT_CKD = 4;
 
 // per-(state, line) parameters.  "hot" is what the far-wing loops read through scalar loads -- 32 bytes per line is
 // the budget at which those loops stay VALU-bound (64-byte records made them SMEM-bound: profiles/r01_notes.md);
@@ -4140,6 +4142,98 @@ __global__ void k_faddeeva(int64_t n, const double *__restrict__ x, const double
 {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = fad_re(x[i], y[i]);
+}
+
+// ---- pedestal-removed Voigt (shape code 4, CS_SHAPE_VOIGT_CKD) ------------------------------------------------------------
+// sigma = sum over included lines of C S [f_V(nu - nul) - f_V(cut)].  The Voigt part is a code-0 line sum; these two kernels subtract
+// the pedestal P(nu, k) = sum_{|nu - nul| <= cut} p[k][l] behind it.  p[k][l] = A Re w(cut d, y) = C S f_V(cut; alpha, gamma) comes from
+// the Voigt records k_gas_setup just wrote (cold.A, hot.p1 = d = sqrt(ln 2)/alpha, cold.y), at the same x = cut * d the line kernels
+// reach at |nu - nul| = cut.  A window [j0, j1) is summed as head partial block + whole aligned blocks of CS_PED_B lines + tail partial
+// block, the two partial blocks read as ONE value each: the in-block suffix sum at j0 and the in-block prefix sum at j1 - 1, sums of
+// window lines only.  Never as a difference of prefix sums (over the table, or over a block): that rounding would scale with the strong
+// lines outside the window instead of with the window's own sum |p| (all p >= 0); the bound here is ~(2 + j1/64 - j0/64) eps x sum_window p.
+#define CS_PED_B 64
+#define CS_PED_KC 8   // states per thread of k_ped_sub (the window search is done once for them)
+
+// one wave per (aligned block q of CS_PED_B lines, state): p of the lines of [a, b) in it, their in-block prefix and suffix sums, and the
+// block's sum (0 for lines outside)
+__global__ __launch_bounds__(256) void k_ped_values(const LineHot *__restrict__ hot, const LineCold *__restrict__ cold, int64_t L, int64_t a,
+                                                    int64_t b, double cut, int64_t q0, int64_t nq, int64_t nqt, double *__restrict__ p,
+                                                    double *__restrict__ pre, double *__restrict__ suf, double *__restrict__ bsum)
+{
+    const int k = blockIdx.y;
+    const int64_t q = q0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= q0 + nq) return;   // (wave-uniform)
+    const int64_t j = q * CS_PED_B + (threadIdx.x & 63);
+    const int lane = threadIdx.x & 63;
+    const bool in = j >= a && j < b;
+    const size_t idx = (size_t)k * L + j;
+    double v = 0.0;
+    if (in) {
+        const LineCold c = cold[idx];
+        v = c.A * fad_re(cut * hot[idx].p1, c.y);
+    }
+    double up = v, dn = v;   // inclusive scans up and down the wave (Hillis-Steele: sums of the lines in between only)
+    for (int d = 1; d < 64; d <<= 1) {
+        const double u = __shfl_up(up, d, 64), w = __shfl_down(dn, d, 64);
+        if (lane >= d) up += u;
+        if (lane + d < 64) dn += w;
+    }
+    if (in) { p[idx] = v; pre[idx] = up; suf[idx] = dn; }
+    if (lane == 63) bsum[(size_t)k * nqt + q] = up;
+}
+
+// one thread per (point, CS_PED_KC states): sigma[k][i] -= P(nu_i, k), then max(0, .) when the plane is complete (clamp).  The window
+// [j0, j1) of [a, b) is found with the line kernels' own test !(|nu - nul| > cut) (cutline, line_shapes.jl:10), so the pedestal covers
+// exactly the lines whose Voigt term was summed; the search runs inside the 256-point tile's window [tJ0, tJ1) of the line kernels (a
+// superset of every point's), not over the whole table.
+__global__ __launch_bounds__(256) void k_ped_sub(const double *__restrict__ nu, int64_t nnu, const double *__restrict__ nul, int64_t L,
+                                                 int64_t a, int64_t b, const int32_t *__restrict__ tJ0, const int32_t *__restrict__ tJ1,
+                                                 double cut, int K, const double *__restrict__ p,
+                                                 const double *__restrict__ pre, const double *__restrict__ suf, const double *__restrict__ bsum,
+                                                 int64_t nqt, double *__restrict__ sigma, int clamp)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nnu) return;
+    const double v = nu[i];
+    const int64_t wa = max(a, (int64_t)tJ0[blockIdx.x]), wb = max(wa, min(b, (int64_t)tJ1[blockIdx.x]));
+    int64_t lo = wa, hi = wb;
+    while (lo < hi) {   // first line with v - nul <= cut
+        const int64_t m = (lo + hi) >> 1;
+        if (v - nul[m] > cut) lo = m + 1; else hi = m;
+    }
+    const int64_t j0 = lo;
+    hi = wb;
+    while (lo < hi) {   // first line with nul - v > cut
+        const int64_t m = (lo + hi) >> 1;
+        if (!(nul[m] - v > cut)) lo = m + 1; else hi = m;
+    }
+    const int64_t j1 = lo;
+    const int64_t b0 = j0 / CS_PED_B, b1 = (max(j1, j0 + 1) - 1) / CS_PED_B;   // blocks of the first and the last line of the window
+    const int k0 = blockIdx.y * CS_PED_KC, k1 = min(k0 + CS_PED_KC, K);
+    for (int k = k0; k < k1; k++) {
+        const size_t o0 = (size_t)k * L;
+        const double *__restrict__ bk = bsum + (size_t)k * nqt;
+        double s = 0.0;
+        if (b0 == b1) {   // inside one block (or empty): the lines one by one
+            for (int64_t j = j0; j < j1; j++) s += p[o0 + j];
+        } else {          // suffix of the first block, whole blocks between, prefix of the last
+            s = suf[o0 + j0];
+            for (int64_t q = b0 + 1; q < b1; q++) s += bk[q];
+            s += pre[o0 + j1 - 1];
+        }
+        const size_t o = (size_t)k * nnu + i;
+        const double r = sigma[o] - s;
+        sigma[o] = clamp ? fmax(r, 0.0) : r;
+    }
+}
+
+// max(0, sigma) over a complete cross-section plane of a column holding a code-4 group (sigma_run / accel_store): rounding of the
+// pedestal difference must not reach a logarithm as a negative
+__global__ __launch_bounds__(256) void k_clamp0(int64_t n, double *__restrict__ sigma)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) sigma[i] = fmax(sigma[i], 0.0);
 }
 
 }  // namespace csdev

@@ -40,8 +40,19 @@ enum {
     CS_ESTATE = -6     /* call sequence error (e.g. run before setup) */
 };
 
-/* line shapes: voigt! line_shapes.jl:412, lorentz! :313, doppler! :200, PHCO2! :527 */
-enum { CS_SHAPE_VOIGT = 0, CS_SHAPE_LORENTZ = 1, CS_SHAPE_DOPPLER = 2, CS_SHAPE_PHCO2 = 3 };
+/* line shapes: voigt! line_shapes.jl:412, lorentz! :313, doppler! :200, PHCO2! :527, and one the reference does not build in:
+ * CS_SHAPE_VOIGT_CKD, the pedestal-removed ("base-subtracted") Voigt of the MT_CKD water-vapour continuum convention.  With S_l(T),
+ * alpha_l(T), gamma_l(T, P, Pp) exactly as voigt! takes them (scaleintensity, alphadoppler, gammalorentz) and the SAME included lines
+ * (vector methods: strict end-point pre-filter + inclusive cut-off; scalar method cs_shape_points: inclusive cut-off),
+ *     sigma(nu) = max(0, sum_l S_l [fvoigt(nu, nul, alpha_l, gamma_l) - fvoigt(nul + dnu_cut, nul, alpha_l, gamma_l)])
+ * Every term is >= 0 and vanishes at |nu - nul| = dnu_cut (the profile falls monotonically), so sigma is continuous at the cut-off;
+ * max(0, .) only absorbs rounding (cs_bake takes ln sigma).  Usual cut-off: 25 cm^-1.  Accepted wherever a shape code is: B1, cs_bake,
+ * the Mode D calls, resident columns, cs_column_batch, cs_accel_store.  In a column the pedestal is subtracted from the summed
+ * cross-section plane, and the max(0, .) can only act on that TOTAL plane (every member: the other gases, sigma_gray, sigma_extra,
+ * CIA pairs, baked tables): it does so in cs_column_sigma_run and cs_accel_store of a column holding a code-4 gas, and nowhere else --
+ * not in cs_column_run / cs_column_batch, whose flux kernels finish the plane on chip (a rounding-level negative there is a
+ * rounding-level optical depth), so cs_column_sigma_fetch after cs_column_run returns the plane unclamped. */
+enum { CS_SHAPE_VOIGT = 0, CS_SHAPE_LORENTZ = 1, CS_SHAPE_DOPPLER = 2, CS_SHAPE_PHCO2 = 3, CS_SHAPE_VOIGT_CKD = 4 };
 
 #define CS_MAX_GAS 16
 #define CS_MAX_TABLE 16

@@ -23,7 +23,7 @@
 #         kept on the device by the `update!` method below                        -> cs_accel_store
 #   * `DirectGas <: ClearSky.AbstractGas`: equivalent to the function absorber (ν,T,P) -> C*voigt(ν, sl, T, P, C*P)
 #     [src/absorption/absorbers.jl:16,24; src/absorption/line_shapes.jl:399-405].
-#   * `hipvoigt!`, `hiplorentz!`, `hipdoppler!`, `hipPHCO2!`: drop-in `shape!` arguments of `Gas(sl, fC, ν, Ω, shape!, Δνcut)`
+#   * `hipvoigt!`, `hiplorentz!`, `hipdoppler!`, `hipPHCO2!` (and `hipvoigtCKD!`, the pedestal-removed Voigt): drop-in `shape!` arguments of `Gas(sl, fC, ν, Ω, shape!, Δνcut)`
 #     [src/absorption/gases.jl:225-231, invoked at :126], and `hipbake!`, which evaluates all nT*nP states in ONE launch.
 module ClearSkyHIP
 
@@ -39,7 +39,7 @@ const CS_MAX_GAS = 16        # gas slots per context (include/clearsky_hip.h)
 const CS_MAX_TABLE = 16      # opacity-table slots
 const CS_MAX_CIA = 8         # CIA slots
 const CS_MAX_ACCEL = 4       # accelerated-absorber slots
-const SHAPES = Dict(:voigt=>0, :lorentz=>1, :doppler=>2, :PHCO2=>3)
+const SHAPES = Dict(:voigt=>0, :lorentz=>1, :doppler=>2, :PHCO2=>3, :voigtCKD=>4)   # 4: pedestal-removed Voigt (CS_SHAPE_VOIGT_CKD)
 
 lasterror() = unsafe_string(ccall((:cs_last_error, LIB), Cstring, ()))
 check(rc::Cint) = rc == 0 ? nothing : error("clearsky_hip ($rc): $(lasterror())")
@@ -191,6 +191,19 @@ hipvoigt!(σ, ν, sl, T, P, Pₚ, Δνcut=25.0)   = hipshape!(:voigt,   σ, ν, 
 hiplorentz!(σ, ν, sl, T, P, Pₚ, Δνcut=25.0) = hipshape!(:lorentz, σ, ν, sl, T, P, Pₚ, Δνcut)
 hipdoppler!(σ, ν, sl, T, P, Pₚ, Δνcut=25.0) = hipshape!(:doppler, σ, ν, sl, T, P, Pₚ, Δνcut)
 hipPHCO2!(σ, ν, sl, T, P, Pₚ, Δνcut=500.0)  = hipshape!(:PHCO2,   σ, ν, sl, T, P, Pₚ, Δνcut)
+# pedestal-removed Voigt, the MT_CKD convention (shape code 4, include/clearsky_hip.h): no reference counterpart
+hipvoigtCKD!(σ, ν, sl, T, P, Pₚ, Δνcut=25.0) = hipshape!(:voigtCKD, σ, ν, sl, T, P, Pₚ, Δνcut)
+
+# the scalar-ν method of shape code 4, for the scalar-access path below: the lines of voigt(ν, sl, T, P, Pₚ, Δνcut)
+# [line_shapes.jl:399-405], each minus its own value at the cut-off, max(0, ·) -- ClearSky has no such function
+function voigtCKD(ν::Real, sl::SpectralLines, T, P, Pₚ, Δνcut=25.0)
+    i = ClearSky.includedlines(ν, sl.ν, Δνcut)
+    S = ClearSky.scaleintensity(sl, i, T)
+    α = ClearSky.αdoppler(sl, i, T)
+    γ = ClearSky.γlorentz(sl, i, T, P, Pₚ)
+    νl = view(sl.ν, i)
+    max(0.0, sum(S .* (ClearSky.fvoigt.(ν, νl, α, γ) .- ClearSky.fvoigt.(νl .+ Δνcut, νl, α, γ)); init=0.0))
+end
 
 # all nT*nP states of bake [gases.jl:109-130] in one launch: σ[nν, nT, nP] is exactly [state][ν] with ld = nν
 function hipbake!(σ::Array{Float64,3}, sl::SpectralLines, fC, ν::Vector{Float64}, Ω; shape::Symbol=:voigt, Δνcut=25.0)
@@ -244,7 +257,8 @@ concentration(g::DirectGas, T, P) = g.fC(T,P)     # gases.jl:270
 # scalar access keeps the reference semantics (σchain, absorbers.jl:84-92), e.g. for the Radau core
 function (g::DirectGas)(i::Int, T, P)
     C = g.fC(T,P)
-    f = g.shape == :voigt ? ClearSky.voigt : g.shape == :lorentz ? ClearSky.lorentz : g.shape == :doppler ? ClearSky.doppler : ClearSky.PHCO2
+    f = g.shape == :voigt ? ClearSky.voigt : g.shape == :lorentz ? ClearSky.lorentz : g.shape == :doppler ? ClearSky.doppler :
+        g.shape == :voigtCKD ? voigtCKD : ClearSky.PHCO2
     C*f(g.ν[i], g.sl, T, P, C*P, g.Δνcut)
 end
 
@@ -766,7 +780,7 @@ function batchfluxes(core::HIPDiscretized, P::AbstractVector{<:Real}, Ts::Abstra
     return F⁺, F⁻
 end
 
-export HIPDiscretized, DirectGas, HIPGas, HIPCIA, hipvoigt!, hiplorentz!, hipdoppler!, hipPHCO2!, hipbake!, hipshapepoints, batchfluxes,
+export HIPDiscretized, DirectGas, HIPGas, HIPCIA, hipvoigt!, hiplorentz!, hipdoppler!, hipPHCO2!, hipvoigtCKD!, hipbake!, hipshapepoints, batchfluxes,
        hipfluxes, hipnetfluxes
 
 end # module
