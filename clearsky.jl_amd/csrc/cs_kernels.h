@@ -536,10 +536,24 @@ __device__ __forceinline__ int tile_block(const int32_t *__restrict__ xc, int ti
 constexpr double kChebMargin = 0.3;   // default of ZoneArgs::margin
 // per (state, interval): own set = [E0,Z0) U [Z1,E1), cut into the 2-/3-/4-term zones of the far body; [P0,P1) and [P2,P3)
 // is the part of it the parent interval (next level up) has already summed.
-// S0, S1: the lines below S0 and from S1 on are at least R4(state) = 133.6 sqrt(gamma_max^2 + 4.33 alpha_max^2) from the interval -- where
+// S0, S1: the lines below S0 and from S1 on are at least R4(state) (sep_radii) from the interval -- where
 // the 4-term series in 1/dnu^2 holds for THIS state (k_cheb_nodes_mx sums them for the states of a group it holds for, k_cheb_nodes
 // the rest: a group of 16 states spans a factor 3-7 in pressure, and one radius for all of it -- its widest line's -- left the
 // lower-pressure states' lines to the vector unit)
+// Radii of the truncated series in w = 1/dnu^2 that the matrix-core kernels use (tools/voigt_series.py): the relative truncation error
+// after n terms is below ((y^2 + a_n)/x^2)^n, a_3 = 3.5, a_4 = 3.0, a_8 = 4.4, so it is at most kSepEps where
+//     |dnu| >= kSepR_n sqrt(gamma^2 + kSepA_n alpha^2),   kSepR_n = kSepEps^(-1/(2n)),  kSepA_n = a_n / ln 2   (both rounded up)
+// -- the level of the vector-unit far bodies the series replaces (1e-15; every line's term is positive, so a per-line bound holds for
+// sigma too).  gamma, alpha: upper bounds of the state's Lorentz and Doppler widths over the lines concerned.
+constexpr double kSepEps = 1e-15;
+constexpr double kSepR3 = 316.3, kSepR4 = 74.99, kSepR8 = 8.66;
+constexpr double kSepA3 = 5.05, kSepA4 = 4.33, kSepA8 = 6.35;
+struct SepRadii { double r3, r4, r8; };
+__device__ __forceinline__ SepRadii sep_radii(double gamma, double alpha)
+{
+    const double g2 = gamma * gamma, a2 = alpha * alpha, safe = 1.0 + 1e-6;
+    return {kSepR3 * sqrt(g2 + kSepA3 * a2) * safe, kSepR4 * sqrt(g2 + kSepA4 * a2) * safe, kSepR8 * sqrt(g2 + kSepA8 * a2) * safe};
+}
 struct __attribute__((aligned(16))) IZone { int32_t E0, Q0, M0, Z0, Z1, M1, Q1, E1, P0, P1, P2, P3, S0, S1, pad0, pad1; };
 
 // nodes[T][m] = centre + h cos(pi m/63) and C[T][m][i] = l_m(nu_i): Lagrange basis of the extrema, barycentric form
@@ -653,7 +667,7 @@ __device__ __forceinline__ IZone izone_compute(const IzParams &P, const ZoneArgs
     // this state's radius of the 4-term series in 1/dnu^2 (sepzones_body takes the group's pieces from these)
     const double R4 = [&] {
         const double amax = ((vhi + cut) / kC) * vth / sqrt(mu_min), gb = gbound[k];
-        return 133.6 * sqrt(gb * gb + 4.33 * amax * amax) * (1.0 + 1e-6);
+        return sep_radii(gb, amax).r4;
     }();
     // own Z0, Z1 (set stays dZ away), M0, M1 (4-term zone), Q0, Q1 (3-term zone), parent's Z0, Z1, series radius: ten searches side by side
     const double sv[10] = {vlo - dZ, vlo - dAA, vlo - dQ, pvlo - pdZ, vlo - R4, vhi + dZ, vhi + dAA, vhi + dQ, pvhi + pdZ, vhi + R4};
@@ -830,8 +844,8 @@ __global__ __launch_bounds__(256) void k_cheb_nodes(const double *__restrict__ n
 // ---- K2d: state-separable far wings on the matrix cores ------------------------------------------------------------------------
 // Far from the line the Voigt term is a power series in w = 1/dnu^2 whose coefficients carry ALL the state dependence
 // (tools/voigt_series.py):  A K(x,y) = sum_{n=1..4} C_n w^n,  C_n = (A y/sqrt(pi)) c_n(y^2) / d^(2n),  c_1 = 1, c_2 = 3/2 - y^2,
-// c_3 = 15/4 - 5 y^2 + y^4, c_4 = 105/8 - 105/4 y^2 + 21/2 y^4 - y^6; truncation below 1e-17 where
-// |dnu| >= 133.6 sqrt(gamma^2 + 4.33 alpha^2).  The node sums of 16 states are then a matrix product
+// c_3 = 15/4 - 5 y^2 + y^4, c_4 = 105/8 - 105/4 y^2 + 21/2 y^4 - y^6; truncation below kSepEps where
+// |dnu| >= R4 (sep_radii).  The node sums of 16 states are then a matrix product
 //     F[state][node] += sum_line sum_n C_n[state][line] * w[line][node]^n
 // which v_mfma_f64_16x16x4 does with K = four LINES per instruction and one instruction per term: every lane owns one
 // (node, line) pair of a 16-node sub-tile, forms w .. w^4 (10 VALU instructions) and, as (state, line), the four coefficients
@@ -859,11 +873,6 @@ __device__ __forceinline__ void search4(const double *__restrict__ a, const doub
     for (int q = 0; q < 4; q++) r[q] = lo[q];
 }
 
-// validity of the truncated series (tools/voigt_series.py): relative truncation error <= 1e-17 where
-//   4 terms: (y^2 + 3.0) / x^2 <= 5.6e-5   <=>  |dnu| >= 133.6 sqrt(gamma^2 + 4.33 alpha^2)
-//   3 terms: (y^2 + 3.5) / x^2 <= 2.15e-6  <=>  |dnu| >= 682.0 sqrt(gamma^2 + 5.05 alpha^2)
-//   8 terms: (y^2 + 4.4) / x^2 <= 7.5e-3   <=>  |dnu| >= 11.55 sqrt(gamma^2 + 6.35 alpha^2)
-constexpr double kSep4 = 133.6, kSep3 = 682.0, kSep8 = 11.55;
 typedef double v4f64_sep __attribute__((ext_vector_type(4)));
 // one step of the matrix-core sums: 4 lines x 64 columns (nodes or points) x 16 states.  The lane's record as (state lr, line lq)
 // gives the NT coefficients (A operands) and, as (column lr, line lq), the line position; vn[st] = the lane's column of sub-tile
@@ -1001,7 +1010,7 @@ __device__ __forceinline__ void sepzones_body(unsigned bid, const SepArgs &a)
         s0v[kk] = z.S0; s1v[kk] = z.S1; ns = kk + 1;
         const double amax = ((vhi + a.cut) / kC) * sqrt(2.0 * kRgas * a.Tk[k]) / sqrt(a.mu_min);
         const double gb = a.gbound[k];
-        R3 = fmax(R3, kSep3 * sqrt(gb * gb + 5.05 * amax * amax) * (1.0 + 1e-6));
+        R3 = fmax(R3, sep_radii(gb, amax).r3);
     }
     // A matrix step costs the same whether one or sixteen states of the group can use a line (the others' coefficients are zero:
     // IZone::S0, S1), the vector unit per (state, line): a line joins the piece when at least min_states states are beyond their own
@@ -1601,9 +1610,8 @@ __device__ __forceinline__ void edgezones_body(unsigned bid, const EdgeArgs &a)
         mR0 = max(mR0, z.N1); mR1 = min(mR1, sb0);
         const double amax = ((vhi + a.cut) / kC) * sqrt(2.0 * kRgas * a.Tk[k]) / sqrt(a.mu_min);
         const double gb = a.gbound[k];
-        R = fmax(R, kSep4 * sqrt(gb * gb + 4.33 * amax * amax) * (1.0 + 1e-6));
-        R3 = fmax(R3, kSep3 * sqrt(gb * gb + 5.05 * amax * amax) * (1.0 + 1e-6));
-        R8 = fmax(R8, kSep8 * sqrt(gb * gb + 6.35 * amax * amax) * (1.0 + 1e-6));
+        const SepRadii sr = sep_radii(gb, amax);
+        R = fmax(R, sr.r4); R3 = fmax(R3, sr.r3); R8 = fmax(R8, sr.r8);
     }
     int sr[4];
     {
@@ -1690,7 +1698,7 @@ __device__ __forceinline__ void sepzones_body16(unsigned bid, const SepArgs &a, 
     if (have) {
         const double amax = ((vhi + a.cut) / kC) * sqrt(2.0 * kRgas * a.Tk[k]) / sqrt(a.mu_min);
         const double gb = a.gbound[k];
-        R3 = kSep3 * sqrt(gb * gb + 5.05 * amax * amax) * (1.0 + 1e-6);
+        R3 = sep_radii(gb, amax).r3;
     }
     R3 = red16(R3, [](double x, double y) { return fmax(x, y); });
     // rank of this state's series bounds among the group's (ties: the lower state first), as in the one-thread body
@@ -1752,9 +1760,8 @@ __device__ __forceinline__ void edgezones_body16(unsigned bid, const EdgeArgs &a
         mR0 = max(mR0, z.N1); mR1 = min(mR1, sb0);
         const double amax = ((vhi + a.cut) / kC) * sqrt(2.0 * kRgas * a.Tk[k]) / sqrt(a.mu_min);
         const double gb = a.gbound[k];
-        R = kSep4 * sqrt(gb * gb + 4.33 * amax * amax) * (1.0 + 1e-6);
-        R3 = kSep3 * sqrt(gb * gb + 5.05 * amax * amax) * (1.0 + 1e-6);
-        R8 = kSep8 * sqrt(gb * gb + 6.35 * amax * amax) * (1.0 + 1e-6);
+        const SepRadii sr = sep_radii(gb, amax);
+        R = sr.r4; R3 = sr.r3; R8 = sr.r8;
     }
     const auto imax = [](int x, int y) { return max(x, y); };
     const auto imin = [](int x, int y) { return min(x, y); };

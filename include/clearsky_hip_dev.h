@@ -20,8 +20,8 @@ extern "C" {
  * Results do not depend on the plan beyond rounding (tests/test_gpu_interp.py); it only moves work between kernels. */
 int cs_set_interp_plan(cs_ctx *ctx, int first_level, int size_min, int size_max);
 
-/* Far lines on the matrix cores: where the 4-term series in 1/dnu^2 holds for every state of a group of 16 (|dnu| >= 133.6
- * sqrt(gamma^2 + 4.33 alpha^2)), the node sums of the interpolated far wings and the window ends of the
+/* Far lines on the matrix cores: where the 4-term series in 1/dnu^2 holds to 1e-15 relative for every state of a group of 16
+ * (|dnu| >= 74.99 sqrt(gamma^2 + 4.33 alpha^2)), the node sums of the interpolated far wings and the window ends of the
  * per-point sum -- cut-off edges included, as a mask (K2e) -- are matrix products on v_mfma_f64_16x16x4.  on = 1 (default):
  * where the grid has enough (interval | tile, state group) blocks to fill the chip; 2: always; 0: everything on the vector
  * unit; | 4 keeps the tile-wide near-zone pass where the default hands the core of a window to 16-point sub-tiles (k_voigt_sub).
