@@ -13,6 +13,7 @@ from .core import (interp_plan, phco2_plan, MultiContext, balanced_ranges, rebal
                    lobattoevaluations, lobattonodes, logrange, lorentz, lorentz_, monochromaticfluxes,
                    monochromaticfluxes_, netfluxes, nodepressures, nodevalues, opticaldepth, ozonelayer, planck,
                    pressuregrid, psatH2O, radiate, radiate_, shape_batch, stefanboltzmann, streamnodes, transmittance,
-                   trapz, trapz_weights, unifyabsorbers, voigt, voigt_, voigtCKD, voigtCKD_)
+                   trapz, trapz_weights, unifyabsorbers, voigt, voigt_, voigtCKD, voigtCKD_,
+                   voigtVVH, voigtVVH_)
 
 __version__ = "0.1.0"

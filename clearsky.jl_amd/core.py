@@ -493,6 +493,9 @@ PHCO2_, PHCO2 = _shape_inplace("PHCO2", 500.0)       # :527-564
 # pedestal-removed Voigt (MT_CKD convention; no reference counterpart): sum of S [fvoigt(nu - nul) - fvoigt(dnu_cut)] over the same
 # lines as voigt, max(0, .) -- the line shape an MT_CKD-style water-vapour continuum is defined against (include/clearsky_hip.h)
 voigtCKD_, voigtCKD = _shape_inplace("voigtCKD", 25.0)
+# Van Vleck-Huber Voigt (the LBLRTM / MT_CKD form; no reference counterpart): sum of S R(nu)/R(nul) [fvoigt(nu - nul) + fvoigt(nu + nul)]
+# over the same lines as voigt, R(x) = x tanh(c2 x / 2T); the mirror term where nu + nul <= dnu_cut (include/clearsky_hip.h)
+voigtVVH_, voigtVVH = _shape_inplace("voigtVVH", 25.0)
 
 
 def faddeeva(x, y, ctx: Optional[Context] = None):

@@ -219,6 +219,8 @@ struct ColGas {
     int xtiles = 0;           // longest XCD stretch of the far kernel's tile order, in tiles (wave_windows)
     bool ped = false;         // shape code 4: shape is SH_VOIGT and launch_pedestal follows the line sum over [pa, pb)
     int64_t pa = 0, pb = 0;
+    bool vvh = false;         // shape code 5: shape is SH_VOIGT, the records carry S / R(nul, T) and launch_vvh follows the line sum
+    int64_t mb = 0;           // ... with the mirror lines [pa, mb) (vvh_mirror_end)
 };
 
 // k_rt launch geometry (rt_geometry)
@@ -261,6 +263,7 @@ struct Column {
     DevBuf nu, wts, P, Pk, Tk, muk, Tlev, extra, S_toa, albedo;
     DevBuf hot, cold, sigma, sigma2, tau, Mup, Mdn, partial, F, stage, ranges;   // sigma2: the near-line plane (k_voigt_near on a side stream)
     DevBuf ped;                // launch_pedestal's workspace for K states (columns with a code-4 group)
+    DevBuf vvh;                // the line sum of a code-5 group that is not the column's first, before launch_vvh (K x nnu)
     DevBuf fluxdbg;            // k_flux_scan: phase time stamps of block 0 (cs_set_tuning key 15 | 128; cs_column_work out[27..])
     DevBuf ticket;             // k_flux: blocks finished (the last one adds the block partials up)
     int flux_form_last = 0;      // which flux kernel the last run used (flux_form)
@@ -1194,6 +1197,8 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
                 Fork *fork = nullptr, bool records_ready = false /* hot / cold already hold this gas at these states: zones and sums only */)
 {
     fork_join(fork, s);   // (an earlier group's node kernels may still read the records this launch overwrites)
+    const bool vvh = shape == SH_VOIGT_VVH;   // shape code 5: every Voigt kernel, over records of S / R(nul, T) (k_gas_setup*_vvh); the caller runs launch_vvh
+    if (vvh) shape = SH_VOIGT;
     // only the lines some window can reach (windows are sorted: first tile's start .. last tile's end)
     const int64_t jlo = jrange0, jhi = std::max(jrange1, jrange0);
     PrepArgs pa;
@@ -1266,9 +1271,9 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
         if (mx_merged) {
             const unsigned nb_sep = use_sep_s ? (unsigned)(((int64_t)(itp.nItot - q0s) * ngrp_s + 15) / 16) : 0u;
             const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp_s + 15) / 16) : 0u;
-            CS_LAUNCH(k_gas_setup_mx, dim3(nb_prep + nb_zones + nb_iz + nb_sep + nb_edge), dim3(256), 0, s, nb_prep, nb_zones, nb_iz, nb_sep, pa, za, P, itp.iz, sa, ea);
+            CS_LAUNCH(vvh ? k_gas_setup_mx_vvh : k_gas_setup_mx, dim3(nb_prep + nb_zones + nb_iz + nb_sep + nb_edge), dim3(256), 0, s, nb_prep, nb_zones, nb_iz, nb_sep, pa, za, P, itp.iz, sa, ea);
         } else {
-            CS_LAUNCH(k_gas_setup, dim3(nb_prep + nb_zones + nb_iz), dim3(256), 0, s, nb_prep, nb_zones, pa, za, P, itp.iz);
+            CS_LAUNCH(vvh ? k_gas_setup_vvh : k_gas_setup, dim3(nb_prep + nb_zones + nb_iz), dim3(256), 0, s, nb_prep, nb_zones, pa, za, P, itp.iz);
         }
         if (evg && itp.nlev == 0) (void)hipEventRecord(evg[0], s);
         if (itp.nlev > 0) {   // sigma = base + extra + interpolated far wings; the per-point kernels add the rest
@@ -1606,6 +1611,28 @@ static void launch_pedestal(hipStream_t s, const GasTable &G, int64_t a, int64_t
               G.nu.as<double>(), G.L, a, b, J0, J1, cut, kn, p, pre, suf, bsum, nqt, sigma, clamp ? 1 : 0);
 }
 
+// shape code 5 behind a launch_gas(SH_VOIGT_VVH) on the same stream, whose line sum of these kn states is in src (base 0, nothing
+// else added; src may be sigma): sigma = (accumulate ? sigma : base + extra) + R(nu, T) (src + mirror term of the lines [a, m)).
+// Reads the records the line sum used: runs before the next group's K1 overwrites them (stream order).
+static void launch_vvh(hipStream_t s, const GasTable &G, int64_t a, int64_t m, int kn, const double *Tk, const LineHot *hot,
+                       const LineCold *cold, const double *dnu, int64_t nnu, double cut, const double *src, double base, const double *extra,
+                       double *sigma, int accumulate)
+{
+    CS_LAUNCH(k_vvh_finish, dim3((unsigned)((nnu + 255) / 256), (unsigned)kn), dim3(256), 0, s, dnu, nnu, Tk, hot, cold, G.L, a,
+              std::max(a, m), cut, src, base, extra, sigma, accumulate);
+}
+
+// end of the mirror lines of shape code 5 among the included lines [a, b) whose records exist: nu + nul <= cut can hold for some point
+// only where nul <= cut - nu_0 (taken a little wide here: k_vvh_finish applies the exact test).  = a on grids that start at the cut-off
+// or above, where k_vvh_finish then only scales.
+static int64_t vvh_mirror_end(const std::vector<double> &nul, int64_t a, int64_t b, double nu0, double cut)
+{
+    b = std::max(a, b);
+    const double lim = cut - nu0;
+    if (!(lim >= 0.0)) return a;
+    return std::upper_bound(nul.begin() + a, nul.begin() + b, lim + 1e-9 * cut) - nul.begin();
+}
+
 int check_gas_states(const GasTable &G, int K, const double *T)
 {
     for (int k = 0; k < K; k++)
@@ -1925,10 +1952,11 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
 {
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (slot < 0 || slot >= CS_MAX_GAS || !ctx->gas[slot].present) return fail(CS_EINVAL, "gas slot %d is empty", slot);
-    if (shape < 0 || shape > SH_VOIGT_CKD) return fail(CS_EINVAL, "unknown shape %d", shape);
+    if (shape < 0 || shape > SH_VOIGT_VVH) return fail(CS_EINVAL, "unknown shape %d", shape);
     if (K < 1 || ld_state < nnu) return fail(CS_EINVAL, "bad K/ld_state");
     const bool ped = shape == SH_VOIGT_CKD;   // the Voigt line sum, then the pedestal behind it
-    if (ped) shape = SH_VOIGT;
+    const bool vvh = shape == SH_VOIGT_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
+    if (ped || vvh) shape = SH_VOIGT;
     int rc;
     if ((rc = check_ascending(nu, nnu))) return rc;
     GasTable &G = ctx->gas[slot];
@@ -1991,7 +2019,7 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
     }
     for (int k0 = 0; k0 < K; k0 += kc) {
         const int kn = std::min(kc, K - k0);
-        launch_gas(s, shape, G, J0.front(), J1.back(), kn, dT.as<double>() + k0, dP.as<double>() + k0, dPp.as<double>() + k0, nullptr, 0,
+        launch_gas(s, vvh ? SH_VOIGT_VVH : shape, G, J0.front(), J1.back(), kn, dT.as<double>() + k0, dP.as<double>() + k0, dPp.as<double>() + k0, nullptr, 0,
                    dlrt.as<double>() + k0, dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(),
                    dwin.as<WaveWin>(), xtiles, dzones.as<Zone>(), dranges.as<int2>(), dgmax.as<double>() + k0, dnu_cut, 0.0, nullptr, dsig.as<double>(), 0, nullptr,
                    mix32, ctx->far_s, itp, nullptr, &ctx->ph);
@@ -1999,6 +2027,11 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
             launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
                             hot.as<LineHot>(), cold.as<LineCold>(),
                             dnu.as<double>(), nnu, dnu_cut, dsig.as<double>(), true, dped.as<double>());
+        if (vvh) {
+            const int64_t a = std::max<int64_t>(g0, J0.front());
+            launch_vvh(s, G, a, vvh_mirror_end(G.h_nu, a, std::min<int64_t>(g1, J1.back()), nu[0], dnu_cut), kn, dT.as<double>() + k0,
+                       hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, dnu_cut, dsig.as<double>(), 0.0, nullptr, dsig.as<double>(), 0);
+        }
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpy2DAsync(sigma + (size_t)k0 * ld_state, ld_state * sizeof(double), dsig.p, nnu * sizeof(double),
                                 nnu * sizeof(double), kn, hipMemcpyDeviceToHost, s));
@@ -2013,10 +2046,11 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (gas_slot < 0 || gas_slot >= CS_MAX_GAS || !ctx->gas[gas_slot].present) return fail(CS_EINVAL, "gas slot %d is empty", gas_slot);
     if (table_slot < 0 || table_slot >= CS_MAX_TABLE) return fail(CS_EINVAL, "table slot %d out of range", table_slot);
-    if (shape < 0 || shape > SH_VOIGT_CKD) return fail(CS_EINVAL, "unknown shape %d", shape);
+    if (shape < 0 || shape > SH_VOIGT_VVH) return fail(CS_EINVAL, "unknown shape %d", shape);
     if (nT < 2 || nP < 2) return fail(CS_EINVAL, "need at least 2 x 2 grid points");
     const bool ped = shape == SH_VOIGT_CKD;   // the Voigt line sum, then the pedestal behind it (clamped before k_table_log)
-    if (ped) shape = SH_VOIGT;
+    const bool vvh = shape == SH_VOIGT_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
+    if (ped || vvh) shape = SH_VOIGT;
     int rc;
     if ((rc = check_ascending(nu, nnu))) return rc;
     for (int64_t i = 0; i < nnu; i++)
@@ -2087,7 +2121,7 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
     }
     for (int k0 = 0; k0 < M; k0 += kc) {
         const int kn = std::min(kc, M - k0);
-        launch_gas(s, shape, G, J0.front(), J1.back(), kn, dT.as<double>() + k0, dP.as<double>() + k0, dPp.as<double>() + k0, nullptr, 0, dlrt.as<double>() + k0,
+        launch_gas(s, vvh ? SH_VOIGT_VVH : shape, G, J0.front(), J1.back(), kn, dT.as<double>() + k0, dP.as<double>() + k0, dPp.as<double>() + k0, nullptr, 0, dlrt.as<double>() + k0,
                    dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(), dwin.as<WaveWin>(), xtiles,
                    dzones.as<Zone>(), dranges.as<int2>(), dgb.as<double>() + k0, dnu_cut, 0.0, nullptr, tb.Z.as<double>() + (size_t)k0 * nnu, 0, nullptr,
                    mix32, ctx->far_s, itp, nullptr, &ctx->ph);
@@ -2095,6 +2129,12 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
             launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
                             hot.as<LineHot>(), cold.as<LineCold>(),
                             dnu.as<double>(), nnu, dnu_cut, tb.Z.as<double>() + (size_t)k0 * nnu, true, dped.as<double>());
+        if (vvh) {
+            const int64_t a = std::max<int64_t>(g0, J0.front());
+            double *z = tb.Z.as<double>() + (size_t)k0 * nnu;
+            launch_vvh(s, G, a, vvh_mirror_end(G.h_nu, a, std::min<int64_t>(g1, J1.back()), nu[0], dnu_cut), kn, dT.as<double>() + k0,
+                       hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, dnu_cut, z, 0.0, nullptr, z, 0);
+        }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
     }
@@ -2590,7 +2630,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         double cmin = 0.0;
         for (int gi = 0; gi < ngas; gi++)
             if ((shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT || (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_LORENTZ ||
-                (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_CKD) {
+                (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_CKD || (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_VVH) {
                 const double cu = dnu_cuts ? dnu_cuts[gi] : 25.0;
                 cmin = cmin > 0.0 ? std::min(cmin, cu) : cu;
             }
@@ -2605,15 +2645,16 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         if (ug.slot < 0 || ug.slot >= CS_MAX_GAS || !ctx->gas[ug.slot].present)
             return fail(CS_EINVAL, "gas slot %d is empty", ug.slot);
         ug.generation = ctx->gas[ug.slot].generation;
-        if (ug.shape < 0 || ug.shape > SH_VOIGT_CKD) return fail(CS_EINVAL, "unknown shape %d", ug.shape);
+        if (ug.shape < 0 || ug.shape > SH_VOIGT_VVH) return fail(CS_EINVAL, "unknown shape %d", ug.shape);
         const GasTable &G = ctx->gas[ug.slot];
         ug.pairs_per_state = -1;   // counted on demand (cs_column_counts): O(nnu log L) on the host
         ug.lines_in_range = std::upper_bound(G.h_nu.begin(), G.h_nu.end(), nu[nnu - 1] + ug.cut) -
                             std::lower_bound(G.h_nu.begin(), G.h_nu.end(), nu[0] - ug.cut);   // (the reference's count: inside the cut-off)
-        // Voigt (Lorentz, pedestal-removed Voigt) gases with the same shape and cut-off go into one group -- never code 4 with code 0:
-        // the pedestal is subtracted for every line of a group; a slot named twice stays apart (a merged table tags a line with ONE member)
+        // Voigt (Lorentz, pedestal-removed Voigt, Van Vleck-Huber Voigt) gases with the same shape and cut-off go into one group -- never
+        // code 4 or 5 with code 0: the pedestal, or R(nu, T) and the mirror term, act on every line of a group; a slot named twice stays
+        // apart (a merged table tags a line with ONE member)
         bool placed = false;
-        if (ctx->merge && (ug.shape == SH_VOIGT || ug.shape == SH_LORENTZ || ug.shape == SH_VOIGT_CKD))
+        if (ctx->merge && (ug.shape == SH_VOIGT || ug.shape == SH_LORENTZ || ug.shape == SH_VOIGT_CKD || ug.shape == SH_VOIGT_VVH))
             for (auto &grp : groups) {
                 const UserGas &h = c.ugas[grp[0]];
                 bool dup = false;
@@ -2622,6 +2663,9 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
             }
         if (!placed) groups.push_back(std::vector<int>{gi});
     }
+    // code-5 groups first: each runs on its own (no deferred node-sum apply, no side streams: R(nu, T) multiplies everything its line
+    // sum adds) and the first one's sum is the plane itself; the groups after them share the deferred apply and the near-line plane as before
+    std::stable_partition(groups.begin(), groups.end(), [&](const std::vector<int> &g) { return c.ugas[g[0]].shape == SH_VOIGT_VVH; });
     c.gas.resize(groups.size());
     size_t maxL = 0;
     for (size_t qi = 0; qi < groups.size(); qi++) {
@@ -2629,7 +2673,8 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         cg.mem = groups[qi];
         cg.shape = c.ugas[cg.mem[0]].shape;
         cg.ped = cg.shape == SH_VOIGT_CKD;
-        if (cg.ped) cg.shape = SH_VOIGT;   // every kernel of a Voigt group, then the pedestal
+        cg.vvh = cg.shape == SH_VOIGT_VVH;
+        if (cg.ped || cg.vvh) cg.shape = SH_VOIGT;   // every kernel of a Voigt group, then the pedestal (or R(nu, T) and the mirror term)
         cg.cut = c.ugas[cg.mem[0]].cut;
         if (cg.mem.size() == 1) {
             cg.tab = &ctx->gas[c.ugas[cg.mem[0]].slot];
@@ -2649,6 +2694,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         cg.jhi = J1.back();
         cg.pa = std::max(g0, cg.jlo);
         cg.pb = std::min(g1, cg.jhi);
+        cg.mb = cg.vvh ? vvh_mirror_end(G.h_nu, cg.pa, cg.pb, nu[0], cg.cut) : cg.pa;
         std::vector<WaveWin> win;
         cg.xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, cg.cut, win);
         if ((rc = upload(cg.J0, J0.data(), J0.size(), s)) || (rc = upload(cg.J1, J1.data(), J1.size(), s)) ||
@@ -2675,6 +2721,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     bool any_voigt = false, any_ped = false;
     for (auto &cg : c.gas) any_voigt = any_voigt || cg.shape == SH_VOIGT, any_ped = any_ped || cg.ped;
     if (any_ped) HIPCHK(c.ped.reserve(ped_bytes(K, maxL)));
+    if (c.gas.size() > 1 && c.gas[1].vvh) HIPCHK(c.vvh.reserve((size_t)K * nnu * sizeof(double)));   // (a second code-5 group)
     if (any_voigt) HIPCHK(c.sigma2.reserve((size_t)K * nnu * sizeof(double)));
     if (ngas > 0) HIPCHK(c.ranges.reserve((size_t)K * nnu * sizeof(int2) + (size_t)2 * K * ((nnu + 63) / 64) * sizeof(int)));   // + per-(tile, state) flags
     HIPCHK(c.tau.reserve((size_t)nl * nnu * sizeof(double)));   // the caller's output, or k_flux_chunk's scratch between its two sweeps
@@ -2786,7 +2833,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     const double *extra = c.has_extra ? c.extra.as<double>() : nullptr;
     if (extra) return fail(CS_EINVAL, "host-evaluated sigma(nu,T,P) terms are not supported in batch mode");
     const bool shared_sigma = c.accel.slot >= 0;   // AcceleratedAbsorber: cross-sections do not depend on the thermal state (absorbers.jl:203)
-    DevBuf dped, dTk, dPk, dmuk, dTlev, dsig, dtau, dpart, dF, dranges, dconc, dPp, dgb, dzones, dizones, dF2, dsep, dedge, hot, cold, dlrt, dqref;
+    DevBuf dped, dvvh, dTk, dPk, dmuk, dTlev, dsig, dtau, dpart, dF, dranges, dconc, dPp, dgb, dzones, dizones, dF2, dsep, dedge, hot, cold, dlrt, dqref;
     if ((rc = upload(dTk, Tk.data(), BK, s)) || (rc = upload(dPk, Pk.data(), BK, s)) || (rc = upload(dmuk, muk.data(), BK, s)) ||
         (rc = upload(dTlev, T_levels, (size_t)B * np, s)))
         return rc;
@@ -2807,8 +2854,9 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     for (auto &g : c.gas) maxL = std::max(maxL, (size_t)g.tab->L);
     bool any_ped = false;
     for (auto &cg : c.gas) any_ped = any_ped || cg.ped;
+    const bool vvh2 = c.gas.size() > 1 && c.gas[1].vvh;   // a second code-5 group: its line sum goes to a plane of its own first
     const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + (size_t)c.nnu * sizeof(int2) +
-                             (any_ped ? ped_bytes(1, (int64_t)maxL) : 0);
+                             (any_ped ? ped_bytes(1, (int64_t)maxL) : 0) + (vvh2 ? (size_t)c.nnu * sizeof(double) : 0);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BK, ((size_t)8 << 30) / std::max<size_t>(per_state, 1), (size_t)65535}));
     if (c.ngas > 0) {
         HIPCHK(hot.reserve(((size_t)kc * maxL + 4) * sizeof(LineHot)));
@@ -2816,6 +2864,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
         HIPCHK(dranges.reserve((size_t)kc * c.nnu * sizeof(int2) + (size_t)2 * kc * ((c.nnu + 63) / 64) * sizeof(int)));
         if (ctx->mixed) HIPCHK(ctx->hot32.reserve(((size_t)kc * maxL + 4) * sizeof(LineF32)));
         if (any_ped) HIPCHK(dped.reserve(ped_bytes(kc, (int64_t)maxL)));
+        if (vvh2) HIPCHK(dvvh.reserve((size_t)kc * c.nnu * sizeof(double)));
     }
     for (auto &cg : c.gas)
         if (cg.shape == SH_PHCO2) { ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id); break; }
@@ -2864,11 +2913,16 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
         }
         for (int64_t k0 = 0; k0 < BK; k0 += kc) {
             const int kn = (int)std::min<int64_t>(kc, BK - k0);
-            launch_gas(s, cg.shape, G, cg.jlo, cg.jhi, kn, dTk.as<double>() + k0, dPk.as<double>() + k0, dPp.as<double>() + k0,
+            double *sk = sig + (size_t)k0 * c.nnu;
+            double *dst = (cg.vvh && qi > 0) ? dvvh.as<double>() : sk;   // code 5: the bare line sum (base 0), then launch_vvh
+            launch_gas(s, cg.vvh ? SH_VOIGT_VVH : cg.shape, G, cg.jlo, cg.jhi, kn, dTk.as<double>() + k0, dPk.as<double>() + k0, dPp.as<double>() + k0,
                        dconc.as<double>() + k0, (int)BK, dlrt.as<double>() + k0, dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, c.ntile,
                        cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), cg.win.as<WaveWin>(), cg.xtiles, dzones.as<Zone>(), dranges.as<int2>(),
-                       dgb.as<double>() + k0, cg.cut, c.sigma_gray, nullptr, sig + (size_t)k0 * c.nnu, qi > 0, nullptr,
+                       dgb.as<double>() + k0, cg.cut, cg.vvh ? 0.0 : c.sigma_gray, nullptr, dst, cg.vvh ? 0 : qi > 0, nullptr,
                        (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, nullptr, &ctx->ph);
+            if (cg.vvh)
+                launch_vvh(s, G, cg.pa, cg.mb, kn, dTk.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, dst,
+                           c.sigma_gray, nullptr, sk, qi > 0);
             if (cg.ped)
                 launch_pedestal(s, G, cg.pa, cg.pb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), kn, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut,
                                 sig + (size_t)k0 * c.nnu, false, dped.as<double>());
@@ -2968,7 +3022,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
     for (auto &cg : c.gas)
         if (cg.shape == SH_PHCO2) { ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id); break; }
     int n_itp = 0;
-    for (auto &cg : c.gas) n_itp += cg.itp.nlev > 0 ? 1 : 0;
+    for (auto &cg : c.gas) n_itp += cg.itp.nlev > 0 && !cg.vvh ? 1 : 0;   // (the groups whose node sums go into the deferred apply)
     // cs_set_tuning key 2: node sums on a side stream -- 1: where the grid is short (fewer than 16384 (tile, state) waves), 2: always
     // key 7: the near-line kernels on a second side stream, into a plane of their own (1, default; 0: after k_voigt_edge_mx, into sigma)
     Fork fk;
@@ -2992,12 +3046,19 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
         interp_settings(ctx, itp);
         itp.core = ctx->matrix_core != 0;
         itp.fuse_apply = ctx->tune[0] != 0 && n_itp == 1;
-        launch_gas(s, cg.shape, G, cg.jlo, cg.jhi, K, c.Tk.as<double>(), c.Pk.as<double>(), cg.Pp.as<double>(), cg.conc.as<double>(), K,
+        // code 5 (first in the column): the bare line sum, applied at once and without side streams -- into sigma itself for the first
+        // group, else into a plane of its own -- then launch_vvh; the other groups as they were
+        double *dst = (cg.vvh && gi > 0) ? c.vvh.as<double>() : sig;
+        launch_gas(s, cg.vvh ? SH_VOIGT_VVH : cg.shape, G, cg.jlo, cg.jhi, K, c.Tk.as<double>(), c.Pk.as<double>(), cg.Pp.as<double>(), cg.conc.as<double>(), K,
                    cg.lrt.as<double>(), cg.qref.as<double>(), c.hot.as<LineHot>(), c.cold.as<LineCold>(), c.nu.as<double>(), c.nnu, c.ntile, cg.J0.as<int32_t>(),
-                   cg.J1.as<int32_t>(), cg.win.as<WaveWin>(), cg.xtiles, cg.zones.as<Zone>(), c.ranges.as<int2>(), cg.gmax.as<double>(), cg.cut, c.sigma_gray, extra, sig, gi > 0,
+                   cg.J1.as<int32_t>(), cg.win.as<WaveWin>(), cg.xtiles, cg.zones.as<Zone>(), c.ranges.as<int2>(), cg.gmax.as<double>(), cg.cut,
+                   cg.vvh ? 0.0 : c.sigma_gray, cg.vvh ? nullptr : extra, dst, cg.vvh ? 0 : gi > 0,
                    ev ? ev + e : nullptr,
-                   (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, &apply, &ctx->ph,
-                   use_fork ? &fk : nullptr);
+                   (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, cg.vvh ? nullptr : &apply, &ctx->ph,
+                   (use_fork && !cg.vvh) ? &fk : nullptr);
+        if (cg.vvh)
+            launch_vvh(s, G, cg.pa, cg.mb, K, c.Tk.as<double>(), c.hot.as<LineHot>(), c.cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, dst,
+                       c.sigma_gray, extra, sig, gi > 0);
         if (cg.ped)   // (into the plane the group's first kernel initialised; the near-line plane and the wings still to come only add)
             launch_pedestal(s, G, cg.pa, cg.pb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), K, c.hot.as<LineHot>(), c.cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, sig, false,
                             c.ped.as<double>());

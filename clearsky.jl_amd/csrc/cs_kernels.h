@@ -37,6 +37,9 @@ constexpr double kC2 = 100.0 * kHp * kC / kKb;     // 100 h c / k           line
 enum { SH_VOIGT = 0, SH_LORENTZ = 1, SH_DOPPLER = 2, SH_PHCO2 = 3 };
 // shape code 4 (pedestal-removed Voigt) never reaches a line kernel: its groups run as SH_VOIGT, then k_ped_values / k_ped_sub
 constexpr int SH_VOIGT_CKD = 4;
+// shape code 5 (Van Vleck-Huber Voigt) neither: its groups run as SH_VOIGT on records whose intensity is S / R(nul, T) (prep_body<true>),
+// then k_vvh_finish applies R(nu, T) and adds the mirror term
+constexpr int SH_VOIGT_VVH = 5;
 
 // per-(state, line) parameters.  "hot" is what the far-wing loops read through scalar loads -- 32 bytes per line is
 // the budget at which those loops stay VALU-bound (64-byte records made them SMEM-bound: profiles/r01_notes.md);
@@ -99,6 +102,8 @@ struct PrepArgs {
     double *phfac;    // PHCO2 fast path: [6][K][L] line factors exp(+-b_r(T) (nul - nu_c)), r = 1..3 (NULL: not needed)
     double nu_c;      // reference wavenumber of those factors (centre of the grid)
 };
+// VVH: shape code 5 -- the Voigt records carry S / R(nul, T) instead of S (k_gas_setup_vvh, k_gas_setup_mx_vvh)
+template <bool VVH = false>
 __device__ __forceinline__ void prep_body(unsigned bid, const PrepArgs &pa)
 {
     const int shape = pa.shape, K = pa.K;
@@ -123,7 +128,9 @@ __device__ __forceinline__ void prep_body(unsigned bid, const PrepArgs &pa)
     for (int k = k0; k < k1; k++) {
         const size_t idx = (size_t)k * g.L + j;   // records are addressed by the line's index in the full table
         const double T = Tk[k], P = Pk[k], Pp = Ppk[mo + k], C = scale ? scale[mo + k] : 1.0;
-        const double n = exp(a / T) * (1.0 - exp(b / T));
+        // shape code 5: S / R(nul, T) with R(x, T) = x tanh(c2 x / 2T); as tanh(x/2) = (1 - e^-x) / (1 + e^-x), the factor 1 - e^(b/T) of S
+        // cancels exactly and no difference of nearly equal numbers is formed for lines at nul -> 0
+        const double n = VVH ? exp(a / T) * (1.0 + exp(b / T)) / nul : exp(a / T) * (1.0 - exp(b / T));
         const double QrefQ = pa.qrefq[(size_t)k * pa.niso + (I - 1)];
         const double S = sref * QrefQ * n;   // the factor at Tref is folded into sref at upload (two exp and a divide less per record)
         // alphadoppler :144, gammalorentz :255-257; (Tref/T)^na as exp(na ln(Tref/T)): a third of the instructions of pow()
@@ -715,12 +722,23 @@ __device__ __forceinline__ void izones_body(unsigned bid, const IzParams &P, con
 // dependent kernel boundaries per gas -- which is what a nu-shard of a multi-GPU run, a few hundred tiles, spends its time on.
 // The zone blocks go first: they are chains of dependent loads (binary searches) that the record blocks, a stream of stores,
 // then run beside instead of before.
-__global__ __launch_bounds__(256) void k_gas_setup(unsigned nb_prep, unsigned nb_zones, PrepArgs pa, ZoneArgs za, IzParams ip, IZone *__restrict__ iz)
+template <bool VVH>
+__device__ __forceinline__ void gas_setup_body(unsigned nb_prep, unsigned nb_zones, const PrepArgs &pa, const ZoneArgs &za, const IzParams &ip,
+                                               IZone *__restrict__ iz)
 {
     const unsigned nb_iz = gridDim.x - nb_prep - nb_zones;
     if (blockIdx.x < nb_zones) zones_body(blockIdx.x, za);
     else if (blockIdx.x < nb_zones + nb_iz) izones_body(blockIdx.x - nb_zones, ip, za, iz);
-    else prep_body(blockIdx.x - nb_zones - nb_iz, pa);
+    else prep_body<VVH>(blockIdx.x - nb_zones - nb_iz, pa);
+}
+__global__ __launch_bounds__(256) void k_gas_setup(unsigned nb_prep, unsigned nb_zones, PrepArgs pa, ZoneArgs za, IzParams ip, IZone *__restrict__ iz)
+{
+    gas_setup_body<false>(nb_prep, nb_zones, pa, za, ip, iz);
+}
+// the same for a group of shape code 5 (a kernel of its own, so that k_gas_setup stays as it is)
+__global__ __launch_bounds__(256) void k_gas_setup_vvh(unsigned nb_prep, unsigned nb_zones, PrepArgs pa, ZoneArgs za, IzParams ip, IZone *__restrict__ iz)
+{
+    gas_setup_body<true>(nb_prep, nb_zones, pa, za, ip, iz);
 }
 
 // one wave = the 64 Chebyshev nodes of one interval x one node state: far-wing sums at the nodes -> F[interval][node][state].
@@ -1812,8 +1830,10 @@ __global__ __launch_bounds__(256) void k_mxzones16(unsigned nb_sep, SepArgs sa, 
 }
 // k_gas_setup and k_mxzones16 in ONE launch: zone blocks, interval-zone blocks, the piece tables of the matrix-core kernels (which
 // compute the zones they need themselves), record blocks
-__global__ __launch_bounds__(256) void k_gas_setup_mx(unsigned nb_prep, unsigned nb_zones, unsigned nb_iz, unsigned nb_sep, PrepArgs pa, ZoneArgs za, IzParams ip,
-                                                      IZone *__restrict__ iz, SepArgs sa, EdgeArgs ea)
+template <bool VVH>
+__device__ __forceinline__ void gas_setup_mx_body(unsigned nb_prep, unsigned nb_zones, unsigned nb_iz, unsigned nb_sep, const PrepArgs &pa,
+                                                  const ZoneArgs &za, const IzParams &ip, IZone *__restrict__ iz, const SepArgs &sa,
+                                                  const EdgeArgs &ea)
 {
     unsigned b = blockIdx.x;
     if (b < nb_zones) { zones_body(b, za); return; }
@@ -1826,7 +1846,18 @@ __global__ __launch_bounds__(256) void k_gas_setup_mx(unsigned nb_prep, unsigned
         else edgezones_body16<true>(b - nb_sep, ea, &ip, &za);
         return;
     }
-    prep_body(b - nb_mx, pa);
+    prep_body<VVH>(b - nb_mx, pa);
+}
+__global__ __launch_bounds__(256) void k_gas_setup_mx(unsigned nb_prep, unsigned nb_zones, unsigned nb_iz, unsigned nb_sep, PrepArgs pa, ZoneArgs za, IzParams ip,
+                                                      IZone *__restrict__ iz, SepArgs sa, EdgeArgs ea)
+{
+    gas_setup_mx_body<false>(nb_prep, nb_zones, nb_iz, nb_sep, pa, za, ip, iz, sa, ea);
+}
+// the same for a group of shape code 5
+__global__ __launch_bounds__(256) void k_gas_setup_mx_vvh(unsigned nb_prep, unsigned nb_zones, unsigned nb_iz, unsigned nb_sep, PrepArgs pa, ZoneArgs za,
+                                                          IzParams ip, IZone *__restrict__ iz, SepArgs sa, EdgeArgs ea)
+{
+    gas_setup_mx_body<true>(nb_prep, nb_zones, nb_iz, nb_sep, pa, za, ip, iz, sa, ea);
 }
 
 // (three waves per SIMD, with the 164 registers that allows: the 8-term step of the cores wants them -- left alone the allocator
@@ -4241,6 +4272,36 @@ __global__ __launch_bounds__(256) void k_clamp0(int64_t n, double *__restrict__ 
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) sigma[i] = fmax(sigma[i], 0.0);
+}
+
+// ---- Van Vleck-Huber Voigt (shape code 5, CS_SHAPE_VOIGT_VVH) -------------------------------------------------------------
+// sigma = R(nu, T) sum over included lines of C S~ [f_V(nu - nul) + f_V(nu + nul)],  S~ = S / R(nul, T),  R(x, T) = x tanh(c2 x / 2T).
+// The direct term is a code-0 line sum over records that carry S~ (prep_body<true>), written into its own plane src with base 0 (or into sigma
+// itself when the group is the column's first).  One thread per (point, state) then adds the mirror term of the lines [ma, mb) -- the
+// included lines with nul <= cut - nu_0, ascending -- with the inclusive test nu + nul <= cut, and multiplies by R(nu, T_k):
+//   sigma[k][i] = (accumulate ? sigma[k][i] : base + extra[k][i]) + R(nu_i, T_k) (src[k][i] + mirror).
+// The mirror pair is A Re w((nu + nul) d, y) from the same records (cold.A, hot.p1 = d, cold.y) as the near-line kernels.  R is formed
+// as nu tanh(.), which is exact to rounding for small arguments (nu -> 0: sigma -> 0).  src may be sigma (no __restrict__ on either).
+__global__ __launch_bounds__(256) void k_vvh_finish(const double *__restrict__ nu, int64_t nnu, const double *__restrict__ Tk,
+                                                    const LineHot *__restrict__ hot, const LineCold *__restrict__ cold, int64_t L,
+                                                    int64_t ma, int64_t mb, double cut, const double *src, double base,
+                                                    const double *__restrict__ extra, double *sigma, int accumulate)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nnu) return;
+    const int k = blockIdx.y;
+    const double v = nu[i];
+    const size_t o = (size_t)k * nnu + i;
+    double s = src[o];
+    for (int64_t j = ma; j < mb; j++) {
+        const size_t idx = (size_t)k * L + j;
+        const double x = v + hot[idx].nul;
+        if (x > cut) break;   // (ascending lines: so are all after it)
+        const LineCold c = cold[idx];
+        s += c.A * fad_re(x * hot[idx].p1, c.y);
+    }
+    const double r = v * tanh(kC2 * v / (2.0 * Tk[k])) * s;
+    sigma[o] = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
 }
 
 }  // namespace csdev

@@ -51,8 +51,13 @@ enum {
  * cross-section plane, and the max(0, .) can only act on that TOTAL plane (every member: the other gases, sigma_gray, sigma_extra,
  * CIA pairs, baked tables): it does so in cs_column_sigma_run and cs_accel_store of a column holding a code-4 gas, and nowhere else --
  * not in cs_column_run / cs_column_batch, whose flux kernels finish the plane on chip (a rounding-level negative there is a
- * rounding-level optical depth), so cs_column_sigma_fetch after cs_column_run returns the plane unclamped. */
-enum { CS_SHAPE_VOIGT = 0, CS_SHAPE_LORENTZ = 1, CS_SHAPE_DOPPLER = 2, CS_SHAPE_PHCO2 = 3, CS_SHAPE_VOIGT_CKD = 4 };
+ * rounding-level optical depth), so cs_column_sigma_fetch after cs_column_run returns the plane unclamped.
+ * CS_SHAPE_VOIGT_VVH, the Van Vleck-Huber Voigt (the LBLRTM / MT_CKD form): with R(x, T) = x tanh(c2 x / 2T), c2 = 100 h c / k [cm K],
+ *     sigma(nu) = sum_l S_l R(nu, T) / R(nul, T) [fvoigt(nu, nul, alpha_l, gamma_l) + fvoigt(nu, -nul, alpha_l, gamma_l)]
+ * with S_l, alpha_l, gamma_l and the included lines exactly those of CS_SHAPE_VOIGT.  The direct term counts where |nu - nul| <=
+ * dnu_cut, the mirror term (the resonance at -nul) where nu + nul <= dnu_cut, both inclusive.  sigma >= 0 and -> 0 as nu -> 0.  Usual
+ * cut-off: 25 cm^-1.  Accepted wherever a shape code is, like CS_SHAPE_VOIGT_CKD; merged only with code 5 of the same cut-off. */
+enum { CS_SHAPE_VOIGT = 0, CS_SHAPE_LORENTZ = 1, CS_SHAPE_DOPPLER = 2, CS_SHAPE_PHCO2 = 3, CS_SHAPE_VOIGT_CKD = 4, CS_SHAPE_VOIGT_VVH = 5 };
 
 #define CS_MAX_GAS 16
 #define CS_MAX_TABLE 16
