@@ -496,6 +496,9 @@ voigtCKD_, voigtCKD = _shape_inplace("voigtCKD", 25.0)
 # Van Vleck-Huber Voigt (the LBLRTM / MT_CKD form; no reference counterpart): sum of S R(nu)/R(nul) [fvoigt(nu - nul) + fvoigt(nu + nul)]
 # over the same lines as voigt, R(x) = x tanh(c2 x / 2T); the mirror term where nu + nul <= dnu_cut (include/clearsky_hip.h)
 voigtVVH_, voigtVVH = _shape_inplace("voigtVVH", 25.0)
+# pedestal-removed Van Vleck-Huber Voigt (LBLRTM's line calculation, the one MT_CKD is defined against; no reference counterpart):
+# code 5 with each resonance, direct and mirror, minus its own value at dnu_cut, max(0, .) (include/clearsky_hip.h)
+voigtCKDVVH_, voigtCKDVVH = _shape_inplace("voigtCKDVVH", 25.0)
 
 
 def faddeeva(x, y, ctx: Optional[Context] = None):

@@ -220,6 +220,7 @@ struct ColGas {
     bool ped = false;         // shape code 4: shape is SH_VOIGT and launch_pedestal follows the line sum over [pa, pb)
     int64_t pa = 0, pb = 0;
     bool vvh = false;         // shape code 5: shape is SH_VOIGT, the records carry S / R(nul, T) and launch_vvh follows the line sum
+                              // (shape code 6: ped and vvh, and launch_vvh_ped follows it instead of both)
     int64_t mb = 0;           // ... with the mirror lines [pa, mb) (vvh_mirror_end)
 };
 
@@ -1622,6 +1623,36 @@ static void launch_vvh(hipStream_t s, const GasTable &G, int64_t a, int64_t m, i
               std::max(a, m), cut, src, base, extra, sigma, accumulate);
 }
 
+// shape code 6 in place of launch_vvh, behind the same launch_gas(SH_VOIGT_VVH): k_ped_values over the included lines [a, b) of the
+// S~ records, then ONE pass k_vvh_ped_finish that subtracts each point's direct pedestals, adds the mirror pairs of [a, m) minus theirs,
+// multiplies by R(nu, T) and writes sigma = (accumulate ? sigma : base + extra) + r, then max(0, .) if clamp (the gas's own sigma
+// complete: B1, bake).  J0, J1, ws: as launch_pedestal's; nu: the grid on the host (dnu on the device).
+static void launch_vvh_ped(hipStream_t s, const GasTable &G, int64_t a, int64_t b, int64_t m, const int32_t *J0, const int32_t *J1, int kn,
+                           const double *Tk, const LineHot *hot, const LineCold *cold, const double *nu, const double *dnu, int64_t nnu,
+                           double cut, const double *src, double base, const double *extra, double *sigma, int accumulate, bool clamp, double *ws)
+{
+    const int64_t nqt = (G.L + CS_PED_B - 1) / CS_PED_B;
+    const size_t kl = (size_t)kn * G.L;
+    double *p = ws, *pre = ws + kl, *suf = ws + 2 * kl, *bsum = ws + 3 * kl;
+    b = std::max(a, b);
+    m = std::min(std::max(a, m), b);
+    if (b > a) {
+        const int64_t q0 = a / CS_PED_B, q1 = (b - 1) / CS_PED_B + 1;
+        CS_LAUNCH(k_ped_values, dim3((unsigned)((q1 - q0 + 3) / 4), (unsigned)kn), dim3(256), 0, s, hot, cold, G.L, a, b, cut, q0, q1 - q0,
+                  nqt, p, pre, suf, bsum);
+    }
+    // the tiles [0, tm) whose first point can reach a mirror line (nu + nul_a <= cut) get one state per block
+    const int64_t ntile = (nnu + 255) / 256;
+    int64_t tm = 0;
+    if (m > a) {
+        const double lim = cut - G.h_nu[a];
+        while (tm < ntile && nu[tm * 256] <= lim) tm++;
+    }
+    const int64_t nblk = tm * kn + (ntile - tm) * ((kn + CS_PED_KC - 1) / CS_PED_KC);
+    CS_LAUNCH(k_vvh_ped_finish, dim3((unsigned)nblk), dim3(256), 0, s, dnu, nnu, Tk, G.nu.as<double>(), hot, cold, G.L, a, b, a, m, J0, J1, cut,
+              kn, p, pre, suf, bsum, nqt, src, base, extra, sigma, accumulate, clamp ? 1 : 0, (int)tm);
+}
+
 // end of the mirror lines of shape code 5 among the included lines [a, b) whose records exist: nu + nul <= cut can hold for some point
 // only where nul <= cut - nu_0 (taken a little wide here: k_vvh_finish applies the exact test).  = a on grids that start at the cut-off
 // or above, where k_vvh_finish then only scales.
@@ -1952,10 +1983,10 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
 {
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (slot < 0 || slot >= CS_MAX_GAS || !ctx->gas[slot].present) return fail(CS_EINVAL, "gas slot %d is empty", slot);
-    if (shape < 0 || shape > SH_VOIGT_VVH) return fail(CS_EINVAL, "unknown shape %d", shape);
+    if (shape < 0 || shape > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", shape);
     if (K < 1 || ld_state < nnu) return fail(CS_EINVAL, "bad K/ld_state");
-    const bool ped = shape == SH_VOIGT_CKD;   // the Voigt line sum, then the pedestal behind it
-    const bool vvh = shape == SH_VOIGT_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
+    const bool ped = shape == SH_VOIGT_CKD || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum, then the pedestal behind it
+    const bool vvh = shape == SH_VOIGT_VVH || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
     if (ped || vvh) shape = SH_VOIGT;
     int rc;
     if ((rc = check_ascending(nu, nnu))) return rc;
@@ -2023,14 +2054,19 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
                    dlrt.as<double>() + k0, dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(),
                    dwin.as<WaveWin>(), xtiles, dzones.as<Zone>(), dranges.as<int2>(), dgmax.as<double>() + k0, dnu_cut, 0.0, nullptr, dsig.as<double>(), 0, nullptr,
                    mix32, ctx->far_s, itp, nullptr, &ctx->ph);
-        if (ped)
+        if (ped && !vvh)
             launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
                             hot.as<LineHot>(), cold.as<LineCold>(),
                             dnu.as<double>(), nnu, dnu_cut, dsig.as<double>(), true, dped.as<double>());
         if (vvh) {
-            const int64_t a = std::max<int64_t>(g0, J0.front());
-            launch_vvh(s, G, a, vvh_mirror_end(G.h_nu, a, std::min<int64_t>(g1, J1.back()), nu[0], dnu_cut), kn, dT.as<double>() + k0,
-                       hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, dnu_cut, dsig.as<double>(), 0.0, nullptr, dsig.as<double>(), 0);
+            const int64_t a = std::max<int64_t>(g0, J0.front()), b = std::min<int64_t>(g1, J1.back());
+            const int64_t m = vvh_mirror_end(G.h_nu, a, b, nu[0], dnu_cut);
+            if (ped)
+                launch_vvh_ped(s, G, a, b, m, dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn, dT.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(),
+                               nu, dnu.as<double>(), nnu, dnu_cut, dsig.as<double>(), 0.0, nullptr, dsig.as<double>(), 0, true, dped.as<double>());
+            else
+                launch_vvh(s, G, a, m, kn, dT.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, dnu_cut,
+                           dsig.as<double>(), 0.0, nullptr, dsig.as<double>(), 0);
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpy2DAsync(sigma + (size_t)k0 * ld_state, ld_state * sizeof(double), dsig.p, nnu * sizeof(double),
@@ -2046,10 +2082,10 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (gas_slot < 0 || gas_slot >= CS_MAX_GAS || !ctx->gas[gas_slot].present) return fail(CS_EINVAL, "gas slot %d is empty", gas_slot);
     if (table_slot < 0 || table_slot >= CS_MAX_TABLE) return fail(CS_EINVAL, "table slot %d out of range", table_slot);
-    if (shape < 0 || shape > SH_VOIGT_VVH) return fail(CS_EINVAL, "unknown shape %d", shape);
+    if (shape < 0 || shape > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", shape);
     if (nT < 2 || nP < 2) return fail(CS_EINVAL, "need at least 2 x 2 grid points");
-    const bool ped = shape == SH_VOIGT_CKD;   // the Voigt line sum, then the pedestal behind it (clamped before k_table_log)
-    const bool vvh = shape == SH_VOIGT_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
+    const bool ped = shape == SH_VOIGT_CKD || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum, then the pedestal behind it (clamped before k_table_log)
+    const bool vvh = shape == SH_VOIGT_VVH || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
     if (ped || vvh) shape = SH_VOIGT;
     int rc;
     if ((rc = check_ascending(nu, nnu))) return rc;
@@ -2125,15 +2161,20 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
                    dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(), dwin.as<WaveWin>(), xtiles,
                    dzones.as<Zone>(), dranges.as<int2>(), dgb.as<double>() + k0, dnu_cut, 0.0, nullptr, tb.Z.as<double>() + (size_t)k0 * nnu, 0, nullptr,
                    mix32, ctx->far_s, itp, nullptr, &ctx->ph);
-        if (ped)
+        if (ped && !vvh)
             launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
                             hot.as<LineHot>(), cold.as<LineCold>(),
                             dnu.as<double>(), nnu, dnu_cut, tb.Z.as<double>() + (size_t)k0 * nnu, true, dped.as<double>());
         if (vvh) {
-            const int64_t a = std::max<int64_t>(g0, J0.front());
+            const int64_t a = std::max<int64_t>(g0, J0.front()), b = std::min<int64_t>(g1, J1.back());
+            const int64_t m = vvh_mirror_end(G.h_nu, a, b, nu[0], dnu_cut);
             double *z = tb.Z.as<double>() + (size_t)k0 * nnu;
-            launch_vvh(s, G, a, vvh_mirror_end(G.h_nu, a, std::min<int64_t>(g1, J1.back()), nu[0], dnu_cut), kn, dT.as<double>() + k0,
-                       hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, dnu_cut, z, 0.0, nullptr, z, 0);
+            if (ped)
+                launch_vvh_ped(s, G, a, b, m, dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn, dT.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(),
+                               nu, dnu.as<double>(), nnu, dnu_cut, z, 0.0, nullptr, z, 0, true, dped.as<double>());
+            else
+                launch_vvh(s, G, a, m, kn, dT.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, dnu_cut, z, 0.0,
+                           nullptr, z, 0);
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
@@ -2630,7 +2671,8 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         double cmin = 0.0;
         for (int gi = 0; gi < ngas; gi++)
             if ((shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT || (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_LORENTZ ||
-                (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_CKD || (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_VVH) {
+                (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_CKD || (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_VVH ||
+                (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_CKD_VVH) {
                 const double cu = dnu_cuts ? dnu_cuts[gi] : 25.0;
                 cmin = cmin > 0.0 ? std::min(cmin, cu) : cu;
             }
@@ -2645,16 +2687,17 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         if (ug.slot < 0 || ug.slot >= CS_MAX_GAS || !ctx->gas[ug.slot].present)
             return fail(CS_EINVAL, "gas slot %d is empty", ug.slot);
         ug.generation = ctx->gas[ug.slot].generation;
-        if (ug.shape < 0 || ug.shape > SH_VOIGT_VVH) return fail(CS_EINVAL, "unknown shape %d", ug.shape);
+        if (ug.shape < 0 || ug.shape > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", ug.shape);
         const GasTable &G = ctx->gas[ug.slot];
         ug.pairs_per_state = -1;   // counted on demand (cs_column_counts): O(nnu log L) on the host
         ug.lines_in_range = std::upper_bound(G.h_nu.begin(), G.h_nu.end(), nu[nnu - 1] + ug.cut) -
                             std::lower_bound(G.h_nu.begin(), G.h_nu.end(), nu[0] - ug.cut);   // (the reference's count: inside the cut-off)
-        // Voigt (Lorentz, pedestal-removed Voigt, Van Vleck-Huber Voigt) gases with the same shape and cut-off go into one group -- never
-        // code 4 or 5 with code 0: the pedestal, or R(nu, T) and the mirror term, act on every line of a group; a slot named twice stays
-        // apart (a merged table tags a line with ONE member)
+        // Voigt (Lorentz, pedestal-removed Voigt, Van Vleck-Huber Voigt, both) gases with the same shape and cut-off go into one group --
+        // never codes 4, 5, 6 with code 0 or with each other: the pedestal, or R(nu, T) and the mirror term, act on every line of a group; a
+        // slot named twice stays apart (a merged table tags a line with ONE member)
         bool placed = false;
-        if (ctx->merge && (ug.shape == SH_VOIGT || ug.shape == SH_LORENTZ || ug.shape == SH_VOIGT_CKD || ug.shape == SH_VOIGT_VVH))
+        if (ctx->merge && (ug.shape == SH_VOIGT || ug.shape == SH_LORENTZ || ug.shape == SH_VOIGT_CKD || ug.shape == SH_VOIGT_VVH ||
+                           ug.shape == SH_VOIGT_CKD_VVH))
             for (auto &grp : groups) {
                 const UserGas &h = c.ugas[grp[0]];
                 bool dup = false;
@@ -2663,18 +2706,20 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
             }
         if (!placed) groups.push_back(std::vector<int>{gi});
     }
-    // code-5 groups first: each runs on its own (no deferred node-sum apply, no side streams: R(nu, T) multiplies everything its line
-    // sum adds) and the first one's sum is the plane itself; the groups after them share the deferred apply and the near-line plane as before
-    std::stable_partition(groups.begin(), groups.end(), [&](const std::vector<int> &g) { return c.ugas[g[0]].shape == SH_VOIGT_VVH; });
+    // code-5 and code-6 groups first: each runs on its own (no deferred node-sum apply, no side streams: R(nu, T) multiplies everything its
+    // line sum adds) and the first one's sum is the plane itself; the groups after them share the deferred apply and the near-line plane as before
+    std::stable_partition(groups.begin(), groups.end(), [&](const std::vector<int> &g) {
+        return c.ugas[g[0]].shape == SH_VOIGT_VVH || c.ugas[g[0]].shape == SH_VOIGT_CKD_VVH;
+    });
     c.gas.resize(groups.size());
     size_t maxL = 0;
     for (size_t qi = 0; qi < groups.size(); qi++) {
         ColGas &cg = c.gas[qi];
         cg.mem = groups[qi];
         cg.shape = c.ugas[cg.mem[0]].shape;
-        cg.ped = cg.shape == SH_VOIGT_CKD;
-        cg.vvh = cg.shape == SH_VOIGT_VVH;
-        if (cg.ped || cg.vvh) cg.shape = SH_VOIGT;   // every kernel of a Voigt group, then the pedestal (or R(nu, T) and the mirror term)
+        cg.ped = cg.shape == SH_VOIGT_CKD || cg.shape == SH_VOIGT_CKD_VVH;
+        cg.vvh = cg.shape == SH_VOIGT_VVH || cg.shape == SH_VOIGT_CKD_VVH;
+        if (cg.ped || cg.vvh) cg.shape = SH_VOIGT;   // every kernel of a Voigt group, then the pedestal and / or R(nu, T) and the mirror term
         cg.cut = c.ugas[cg.mem[0]].cut;
         if (cg.mem.size() == 1) {
             cg.tab = &ctx->gas[c.ugas[cg.mem[0]].slot];
@@ -2920,10 +2965,13 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
                        cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), cg.win.as<WaveWin>(), cg.xtiles, dzones.as<Zone>(), dranges.as<int2>(),
                        dgb.as<double>() + k0, cg.cut, cg.vvh ? 0.0 : c.sigma_gray, nullptr, dst, cg.vvh ? 0 : qi > 0, nullptr,
                        (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, nullptr, &ctx->ph);
-            if (cg.vvh)
+            if (cg.vvh && cg.ped)
+                launch_vvh_ped(s, G, cg.pa, cg.pb, cg.mb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), kn, dTk.as<double>() + k0, hot.as<LineHot>(),
+                               cold.as<LineCold>(), c.h_nu.data(), c.nu.as<double>(), c.nnu, cg.cut, dst, c.sigma_gray, nullptr, sk, qi > 0, false, dped.as<double>());
+            else if (cg.vvh)
                 launch_vvh(s, G, cg.pa, cg.mb, kn, dTk.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, dst,
                            c.sigma_gray, nullptr, sk, qi > 0);
-            if (cg.ped)
+            if (cg.ped && !cg.vvh)
                 launch_pedestal(s, G, cg.pa, cg.pb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), kn, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut,
                                 sig + (size_t)k0 * c.nnu, false, dped.as<double>());
             HIPCHK(hipGetLastError());
@@ -3056,10 +3104,13 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
                    ev ? ev + e : nullptr,
                    (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, cg.vvh ? nullptr : &apply, &ctx->ph,
                    (use_fork && !cg.vvh) ? &fk : nullptr);
-        if (cg.vvh)
+        if (cg.vvh && cg.ped)
+            launch_vvh_ped(s, G, cg.pa, cg.pb, cg.mb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), K, c.Tk.as<double>(), c.hot.as<LineHot>(),
+                           c.cold.as<LineCold>(), c.h_nu.data(), c.nu.as<double>(), c.nnu, cg.cut, dst, c.sigma_gray, extra, sig, gi > 0, false, c.ped.as<double>());
+        else if (cg.vvh)
             launch_vvh(s, G, cg.pa, cg.mb, K, c.Tk.as<double>(), c.hot.as<LineHot>(), c.cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, dst,
                        c.sigma_gray, extra, sig, gi > 0);
-        if (cg.ped)   // (into the plane the group's first kernel initialised; the near-line plane and the wings still to come only add)
+        if (cg.ped && !cg.vvh)   // (into the plane the group's first kernel initialised; the near-line plane and the wings still to come only add)
             launch_pedestal(s, G, cg.pa, cg.pb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), K, c.hot.as<LineHot>(), c.cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, sig, false,
                             c.ped.as<double>());
         if (ev) { e += 6; HIPCHK(hipEventRecord(ev[e++], s)); }
@@ -3127,7 +3178,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
         const int64_t tot = (int64_t)K * c.nnu;
         CS_LAUNCH(k_fold, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, sig, c.sigma2.as<double>());
     }
-    if (!near_plane_live) {   // the cross-sections are the result: complete here, so the max(0, .) of a code-4 group applies
+    if (!near_plane_live) {   // the cross-sections are the result: complete here, so the max(0, .) of a code-4 or code-6 group applies
         bool any_ped = false;
         for (auto &cg : c.gas) any_ped = any_ped || cg.ped;
         const int64_t tot = (int64_t)K * c.nnu;

@@ -40,6 +40,8 @@ constexpr int SH_VOIGT_CKD = 4;
 // shape code 5 (Van Vleck-Huber Voigt) neither: its groups run as SH_VOIGT on records whose intensity is S / R(nul, T) (prep_body<true>),
 // then k_vvh_finish applies R(nu, T) and adds the mirror term
 constexpr int SH_VOIGT_VVH = 5;
+// shape code 6 (pedestal-removed Van Vleck-Huber Voigt) is code 5's line sum, then k_ped_values and k_vvh_ped_finish
+constexpr int SH_VOIGT_CKD_VVH = 6;
 
 // per-(state, line) parameters.  "hot" is what the far-wing loops read through scalar loads -- 32 bytes per line is
 // the budget at which those loops stay VALU-bound (64-byte records made them SMEM-bound: profiles/r01_notes.md);
@@ -4302,6 +4304,83 @@ __global__ __launch_bounds__(256) void k_vvh_finish(const double *__restrict__ n
     }
     const double r = v * tanh(kC2 * v / (2.0 * Tk[k])) * s;
     sigma[o] = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
+}
+
+// ---- pedestal-removed Van Vleck-Huber Voigt (shape code 6, CS_SHAPE_VOIGT_CKD_VVH) --------------------------------------------
+// sigma = max(0, R(nu, T) sum over included lines of C S~ [(f_V(nu - nul) - f_V(cut)) 1{|nu - nul| <= cut}
+//                                                        + (f_V(nu + nul) - f_V(cut)) 1{nu + nul <= cut}]).
+// The direct Voigt part is code 5's line sum over S~ records, in src with base 0; k_ped_values then writes p[k][l] = C S~ f_V(cut) and its
+// in-block sums from those same records.  One thread per (point, CS_PED_KC states) finishes the plane in ONE pass: it finds the point's
+// direct window [j0, j1) as k_ped_sub does (once for its states) and subtracts its pedestals the same way (in-block suffix, whole blocks,
+// in-block prefix: never a difference of prefix sums), adds the mirror pairs A Re w((nu + nul) d, y) - p of the lines [ma, mb) as
+// k_vvh_finish does (inclusive test nu + nul <= cut), multiplies by R(nu, T_k) and writes
+//   sigma[k][i] = (accumulate ? sigma[k][i] : base + extra[k][i]) + r,   r = R (src - direct pedestals + mirror),  max(0, .) if clamp.
+// [ma, mb) lies inside [a, b), so every p it reads was written.  src may be sigma (no __restrict__ on either).
+// Blocks: the first tm tiles (those whose points can reach a mirror line) one state per block, tile-major, so that their loops over the
+// mirror lines run side by side and first; every other tile CS_PED_KC states per block.
+__global__ __launch_bounds__(256) void k_vvh_ped_finish(const double *__restrict__ nu, int64_t nnu, const double *__restrict__ Tk,
+                                                        const double *__restrict__ nul, const LineHot *__restrict__ hot,
+                                                        const LineCold *__restrict__ cold, int64_t L, int64_t a, int64_t b, int64_t ma,
+                                                        int64_t mb, const int32_t *__restrict__ tJ0, const int32_t *__restrict__ tJ1,
+                                                        double cut, int K, const double *__restrict__ p, const double *__restrict__ pre,
+                                                        const double *__restrict__ suf, const double *__restrict__ bsum, int64_t nqt,
+                                                        const double *src, double base, const double *__restrict__ extra, double *sigma,
+                                                        int accumulate, int clamp, int tm)
+{
+    const unsigned nm = (unsigned)tm * (unsigned)K, ng = (unsigned)(K + CS_PED_KC - 1) / CS_PED_KC;
+    unsigned t;
+    int k0, k1;
+    if (blockIdx.x < nm) {
+        t = blockIdx.x / (unsigned)K;
+        k0 = (int)(blockIdx.x - t * (unsigned)K);
+        k1 = k0 + 1;
+    } else {
+        const unsigned r = blockIdx.x - nm;
+        t = (unsigned)tm + r / ng;
+        k0 = (int)(r % ng) * CS_PED_KC;
+        k1 = min(k0 + CS_PED_KC, K);
+    }
+    const int64_t i = (int64_t)t * 256 + threadIdx.x;
+    if (i >= nnu) return;
+    const double v = nu[i];
+    const int64_t wa = max(a, (int64_t)tJ0[t]), wb = max(wa, min(b, (int64_t)tJ1[t]));
+    int64_t lo = wa, hi = wb;
+    while (lo < hi) {   // first line with v - nul <= cut
+        const int64_t m = (lo + hi) >> 1;
+        if (v - nul[m] > cut) lo = m + 1; else hi = m;
+    }
+    const int64_t j0 = lo;
+    hi = wb;
+    while (lo < hi) {   // first line with nul - v > cut
+        const int64_t m = (lo + hi) >> 1;
+        if (!(nul[m] - v > cut)) lo = m + 1; else hi = m;
+    }
+    const int64_t j1 = lo;
+    const int64_t b0 = j0 / CS_PED_B, b1 = (max(j1, j0 + 1) - 1) / CS_PED_B;
+    for (int k = k0; k < k1; k++) {
+        const size_t o0 = (size_t)k * L;
+        const double *__restrict__ bk = bsum + (size_t)k * nqt;
+        double ps = 0.0;
+        if (b0 == b1) {
+            for (int64_t j = j0; j < j1; j++) ps += p[o0 + j];
+        } else {
+            ps = suf[o0 + j0];
+            for (int64_t q = b0 + 1; q < b1; q++) ps += bk[q];
+            ps += pre[o0 + j1 - 1];
+        }
+        const size_t o = (size_t)k * nnu + i;
+        double s = src[o] - ps;
+        for (int64_t j = ma; j < mb; j++) {
+            const size_t idx = o0 + j;
+            const double x = v + hot[idx].nul;
+            if (x > cut) break;   // (ascending lines: so are all after it)
+            const LineCold c = cold[idx];
+            s += c.A * fad_re(x * hot[idx].p1, c.y) - p[idx];
+        }
+        const double r = v * tanh(kC2 * v / (2.0 * Tk[k])) * s;
+        const double out = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
+        sigma[o] = clamp ? fmax(out, 0.0) : out;
+    }
 }
 
 }  // namespace csdev

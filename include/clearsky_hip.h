@@ -56,8 +56,18 @@ enum {
  *     sigma(nu) = sum_l S_l R(nu, T) / R(nul, T) [fvoigt(nu, nul, alpha_l, gamma_l) + fvoigt(nu, -nul, alpha_l, gamma_l)]
  * with S_l, alpha_l, gamma_l and the included lines exactly those of CS_SHAPE_VOIGT.  The direct term counts where |nu - nul| <=
  * dnu_cut, the mirror term (the resonance at -nul) where nu + nul <= dnu_cut, both inclusive.  sigma >= 0 and -> 0 as nu -> 0.  Usual
- * cut-off: 25 cm^-1.  Accepted wherever a shape code is, like CS_SHAPE_VOIGT_CKD; merged only with code 5 of the same cut-off. */
-enum { CS_SHAPE_VOIGT = 0, CS_SHAPE_LORENTZ = 1, CS_SHAPE_DOPPLER = 2, CS_SHAPE_PHCO2 = 3, CS_SHAPE_VOIGT_CKD = 4, CS_SHAPE_VOIGT_VVH = 5 };
+ * cut-off: 25 cm^-1.  Accepted wherever a shape code is, like CS_SHAPE_VOIGT_CKD; merged only with code 5 of the same cut-off.
+ * CS_SHAPE_VOIGT_CKD_VVH, both at once (LBLRTM's line calculation, the one the MT_CKD continuum is defined against): with S_l, alpha_l,
+ * gamma_l and the included lines exactly those of CS_SHAPE_VOIGT, S~_l = S_l / R(nul, T) as code 5 forms it, f_l(d) = fvoigt of line l
+ * at offset d and D = dnu_cut,
+ *     sigma(nu) = max(0, R(nu, T) sum_l S~_l [(f_l(nu - nul) - f_l(D)) 1{|nu - nul| <= D} + (f_l(nu + nul) - f_l(D)) 1{nu + nul <= D}])
+ * Each resonance loses its own pedestal: every term is >= 0 and vanishes at its own cut-off, so sigma is continuous at nu = nul +- D
+ * and at the mirror edge nu = D - nul (where code 5 steps by R S~_l f_l(D)), and sigma -> 0 as nu -> 0.  max(0, .) only absorbs
+ * rounding, and is placed exactly as for code 4: B1 and cs_bake clamp the gas's own sigma; in a column, cs_column_sigma_run and
+ * cs_accel_store clamp the total plane of a column holding a code-4 or code-6 gas, cs_column_run and cs_column_batch never.  Usual
+ * cut-off: 25 cm^-1.  Accepted wherever a shape code is; merged only with code 6 of the same cut-off. */
+enum { CS_SHAPE_VOIGT = 0, CS_SHAPE_LORENTZ = 1, CS_SHAPE_DOPPLER = 2, CS_SHAPE_PHCO2 = 3, CS_SHAPE_VOIGT_CKD = 4, CS_SHAPE_VOIGT_VVH = 5,
+       CS_SHAPE_VOIGT_CKD_VVH = 6 };
 
 #define CS_MAX_GAS 16
 #define CS_MAX_TABLE 16

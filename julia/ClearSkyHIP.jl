@@ -23,7 +23,7 @@
 #         kept on the device by the `update!` method below                        -> cs_accel_store
 #   * `DirectGas <: ClearSky.AbstractGas`: equivalent to the function absorber (ν,T,P) -> C*voigt(ν, sl, T, P, C*P)
 #     [src/absorption/absorbers.jl:16,24; src/absorption/line_shapes.jl:399-405].
-#   * `hipvoigt!`, `hiplorentz!`, `hipdoppler!`, `hipPHCO2!` (and `hipvoigtCKD!`, the pedestal-removed Voigt, and `hipvoigtVVH!`, the Van Vleck-Huber Voigt): drop-in `shape!` arguments of `Gas(sl, fC, ν, Ω, shape!, Δνcut)`
+#   * `hipvoigt!`, `hiplorentz!`, `hipdoppler!`, `hipPHCO2!` (and `hipvoigtCKD!`, the pedestal-removed Voigt, `hipvoigtVVH!`, the Van Vleck-Huber Voigt, and `hipvoigtCKDVVH!`, both): drop-in `shape!` arguments of `Gas(sl, fC, ν, Ω, shape!, Δνcut)`
 #     [src/absorption/gases.jl:225-231, invoked at :126], and `hipbake!`, which evaluates all nT*nP states in ONE launch.
 module ClearSkyHIP
 
@@ -39,7 +39,7 @@ const CS_MAX_GAS = 16        # gas slots per context (include/clearsky_hip.h)
 const CS_MAX_TABLE = 16      # opacity-table slots
 const CS_MAX_CIA = 8         # CIA slots
 const CS_MAX_ACCEL = 4       # accelerated-absorber slots
-const SHAPES = Dict(:voigt=>0, :lorentz=>1, :doppler=>2, :PHCO2=>3, :voigtCKD=>4, :voigtVVH=>5)   # 4: pedestal-removed Voigt (CS_SHAPE_VOIGT_CKD), 5: Van Vleck-Huber Voigt (CS_SHAPE_VOIGT_VVH)
+const SHAPES = Dict(:voigt=>0, :lorentz=>1, :doppler=>2, :PHCO2=>3, :voigtCKD=>4, :voigtVVH=>5, :voigtCKDVVH=>6)   # 4: pedestal-removed Voigt (CS_SHAPE_VOIGT_CKD), 5: Van Vleck-Huber Voigt (CS_SHAPE_VOIGT_VVH), 6: both (CS_SHAPE_VOIGT_CKD_VVH)
 
 lasterror() = unsafe_string(ccall((:cs_last_error, LIB), Cstring, ()))
 check(rc::Cint) = rc == 0 ? nothing : error("clearsky_hip ($rc): $(lasterror())")
@@ -223,6 +223,22 @@ function voigtVVH(ν::Real, sl::SpectralLines, T, P, Pₚ, Δνcut=25.0)
     vvhR(ν, T) * sum(S ./ vvhR.(νl, T) .* (ClearSky.fvoigt.(ν, νl, α, γ) .+ m .* ClearSky.fvoigt.(ν, .-νl, α, γ)); init=0.0)
 end
 
+# pedestal-removed Van Vleck-Huber Voigt (shape code 6, include/clearsky_hip.h): no reference counterpart
+hipvoigtCKDVVH!(σ, ν, sl, T, P, Pₚ, Δνcut=25.0) = hipshape!(:voigtCKDVVH, σ, ν, sl, T, P, Pₚ, Δνcut)
+
+# the scalar-ν method of shape code 6: voigtVVH with each resonance minus its own value at the cut-off, fvoigt(νl + Δνcut, νl)
+function voigtCKDVVH(ν::Real, sl::SpectralLines, T, P, Pₚ, Δνcut=25.0)
+    i = ClearSky.includedlines(ν, sl.ν, Δνcut)
+    S = ClearSky.scaleintensity(sl, i, T)
+    α = ClearSky.αdoppler(sl, i, T)
+    γ = ClearSky.γlorentz(sl, i, T, P, Pₚ)
+    νl = view(sl.ν, i)
+    p = ClearSky.fvoigt.(νl .+ Δνcut, νl, α, γ)
+    m = (ν .+ νl) .<= Δνcut
+    max(0.0, vvhR(ν, T) * sum(S ./ vvhR.(νl, T) .* ((ClearSky.fvoigt.(ν, νl, α, γ) .- p) .+
+                                                    m .* (ClearSky.fvoigt.(ν, .-νl, α, γ) .- p)); init=0.0))
+end
+
 # all nT*nP states of bake [gases.jl:109-130] in one launch: σ[nν, nT, nP] is exactly [state][ν] with ld = nν
 function hipbake!(σ::Array{Float64,3}, sl::SpectralLines, fC, ν::Vector{Float64}, Ω; shape::Symbol=:voigt, Δνcut=25.0)
     ctx = context()
@@ -276,7 +292,8 @@ concentration(g::DirectGas, T, P) = g.fC(T,P)     # gases.jl:270
 function (g::DirectGas)(i::Int, T, P)
     C = g.fC(T,P)
     f = g.shape == :voigt ? ClearSky.voigt : g.shape == :lorentz ? ClearSky.lorentz : g.shape == :doppler ? ClearSky.doppler :
-        g.shape == :voigtCKD ? voigtCKD : g.shape == :voigtVVH ? voigtVVH : ClearSky.PHCO2
+        g.shape == :voigtCKD ? voigtCKD : g.shape == :voigtVVH ? voigtVVH :
+        g.shape == :voigtCKDVVH ? voigtCKDVVH : ClearSky.PHCO2
     C*f(g.ν[i], g.sl, T, P, C*P, g.Δνcut)
 end
 
@@ -798,7 +815,7 @@ function batchfluxes(core::HIPDiscretized, P::AbstractVector{<:Real}, Ts::Abstra
     return F⁺, F⁻
 end
 
-export HIPDiscretized, DirectGas, HIPGas, HIPCIA, hipvoigt!, hiplorentz!, hipdoppler!, hipPHCO2!, hipvoigtCKD!, hipvoigtVVH!, hipbake!, hipshapepoints, batchfluxes,
+export HIPDiscretized, DirectGas, HIPGas, HIPCIA, hipvoigt!, hiplorentz!, hipdoppler!, hipPHCO2!, hipvoigtCKD!, hipvoigtVVH!, hipvoigtCKDVVH!, hipbake!, hipshapepoints, batchfluxes,
        hipfluxes, hipnetfluxes
 
 end # module
