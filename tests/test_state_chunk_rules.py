@@ -1,0 +1,86 @@
+"""The chunk rules of tests/test_gpu_state_chunks.py (RULES) against clearsky.jl_amd/csrc/cs_api.hip: the per-state bytes and the kc
+expressions of cs_shape_batch / cs_shape_points (shape_impl), cs_bake and cs_column_batch, the pedestal workspace and the record sizes they
+count.  If one of them changes, the GPU tests may no longer cross a chunk boundary; this fails first.  No GPU needed."""
+import os
+import re
+
+import test_gpu_state_chunks as SC
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "clearsky.jl_amd", "csrc")
+
+# function -> (per-state bytes, kc) as written in the source, whitespace collapsed
+SOURCE = {
+    "static int shape_impl(": ("shape",
+        "const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * (sizeof(double) + sizeof(int2)) + "
+        "(ped ? ped_bytes(1, G.L) : 0);",
+        "int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));"),
+    "int cs_bake(": ("bake",
+        "const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * sizeof(int2) + "
+        "(ped ? ped_bytes(1, G.L) : 0);",
+        "const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)M, ((size_t)4 << 30) / per_state, (size_t)65535}));"),
+    "int cs_column_batch(": ("column",
+        "const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + "
+        "(size_t)c.nnu * sizeof(int2) + (any_ped ? ped_bytes(1, (int64_t)maxL) : 0) + (vvh2 ? (size_t)c.nnu * sizeof(double) : 0);",
+        "const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BK, ((size_t)8 << 30) / std::max<size_t>(per_state, 1), "
+        "(size_t)65535}));"),
+}
+
+
+def _norm(s):
+    return re.sub(r"\s+", " ", s)
+
+
+def _read(name):
+    with open(os.path.join(CSRC, name), encoding="utf-8") as f:
+        return f.read()
+
+
+def _body(src, head):
+    """the text of the function whose definition (not a declaration) starts with head, up to the next top-level closing brace"""
+    i = src.index(head)
+    while src.index(";", i) < src.index("{", i):
+        i = src.index(head, i + 1)
+    j = src.index("\n}\n", i)
+    return _norm(src[i:j])
+
+
+def test_kc_expressions_match_the_rule_table():
+    src = _read("cs_api.hip")
+    for head, (rule, per_state, kc) in SOURCE.items():
+        body = _body(src, head)
+        assert _norm(per_state) in body, (rule, "per-state bytes")
+        assert _norm(kc) in body, (rule, "kc")
+        assert re.search(r"for \(int(64_t)? k0 = 0; k0 < (K|M|BK); k0 \+= kc\)", body), (rule, "chunk loop")
+    budgets = {r: b for r, (b, _) in SC.RULES.items()}
+    assert budgets == {"shape": 4 << 30, "bake": 4 << 30, "column": 8 << 30}
+    assert SC.GRID_Y == 65535
+    # the column's second code-5/6 plane: the groups are ordered codes 5/6 first, so group 1 is one when there are two
+    assert "const bool vvh2 = c.gas.size() > 1 && c.gas[1].vvh;" in src
+
+
+def test_sizes_the_rules_count():
+    src = _read("cs_api.hip")
+    k = _norm(_read("cs_kernels.h"))
+    assert "static size_t ped_bytes(int64_t kn, int64_t L) { return (size_t)kn * ((size_t)3 * L + (L + CS_PED_B - 1) / CS_PED_B) * " \
+           "sizeof(double); }" in _norm(src)
+    assert re.search(r"#define CS_PED_B (\d+)", k).group(1) == str(SC.PED_B)
+    assert "struct __attribute__((aligned(32))) LineHot { double nul, p1, p2, p3; };" in k and SC.HOT == 32
+    assert "struct __attribute__((aligned(16))) LineCold { double y, A; };" in k and SC.COLD == 16
+    assert "struct __attribute__((aligned(16))) LineF32 { float d, y2, ay, c2; };" in k and SC.F32 == 16
+    assert SC.ped_bytes(1, 100) == (300 + 2) * 8
+
+
+def test_rule_arithmetic():
+    """the table's own arithmetic on the tests' inputs: 400 000 lines on a 400-point grid"""
+    L, n = SC.NLINES, 400
+    assert SC.chunk_size("shape", 10 ** 6, L, n) == (4 << 30) // (L * 48 + n * 16)
+    assert SC.chunk_size("bake", 10 ** 6, L, n, ped=True) == (4 << 30) // (L * 48 + n * 8 + (3 * L + -(-L // 64)) * 8)
+    assert SC.chunk_size("column", 10 ** 6, L, n, mixed=True, vvh2=True) == (8 << 30) // (L * 64 + n * 8 + n * 8)
+    assert SC.chunk_size("shape", 70000, 20, 64) == 65535 and SC.chunk_size("shape", 100, 20, 64) == 100
+    for rule, kw in (("shape", {}), ("shape", {"ped": True}), ("bake", {}), ("column", {"vvh2": True, "ped": True}), ("column", {"mixed": True})):
+        for step in (1, 17, 31):
+            N = SC.states_for(rule, L, n, step=step, **kw)
+            assert N % step == 0
+            kc, b = SC.boundaries(rule, N, L, n, **kw)
+            assert len(b) == 2 and b == [kc, 2 * kc]

@@ -79,9 +79,10 @@ def test_line_terms_vs_one_line_slices(cs, O, low_h2o):
             assert np.max(np.abs(v - ref) / ref) < 1e-12, (T, x)
 
 
-def _exact(cs, O, sl, v, T, P, Pp, cut, lines):
+def _exact(cs, O, sl, v, T, P, Pp, cut, lines, ped=True, vvh=True):
     """the definition at 40 digits: S_l(T) as scaleintensity writes it, divided by R(nul, T); Voigt as Re w(z) = Re exp(-z^2) erfc(-iz);
-    each resonance minus its own value at the cut-off"""
+    each resonance minus its own value at the cut-off.  vvh=False (code 4): no R and no mirror resonance; ped=False (code 5): no
+    value at the cut-off subtracted and no clamp"""
     mp.mp.dps = 40
     C_ = cs.constants
     k2 = mp.mpf(100) * mp.mpf(C_.h) * mp.mpf(C_.c) / mp.mpf(C_.k)
@@ -107,16 +108,18 @@ def _exact(cs, O, sl, v, T, P, Pp, cut, lines):
         def f(x):
             z = mp.mpc(x * dd, y)
             return mp.sqrt(mp.log(2) / mp.pi) / alpha * mp.re(mp.exp(-z * z) * mp.erfc(-1j * z))
-        pc = f(mp.mpf(cut))
+        pc = f(mp.mpf(cut)) if ped else mp.mpf(0)
         term = mp.mpf(0)
         if abs(v - nul) <= cut:
             term += f(v - nul) - pc
-        if v + nul <= cut:
+        if vvh and v + nul <= cut:
             term += f(v + nul) - pc
-        tot += S / Rm(nul) * term
+        rr = Rm(v) / Rm(nul) if vvh else mp.mpf(1)
+        tot += S * rr * term
         if l == 0:
-            t0 = abs(float(Rm(v) * S / Rm(nul) * term))
-    return max(0.0, float(Rm(v) * tot)), (t0 if 0 in lines else 0.0)
+            t0 = abs(float(rr * S * term))
+    val = float(tot)
+    return (max(0.0, val) if ped else val), (t0 if 0 in lines else 0.0)
 
 
 def test_restatement_vs_definition(cs, O, low_h2o):
@@ -153,3 +156,57 @@ def test_continuous_at_the_mirror_edge(cs, O, low_h2o):
     b = _exact(cs, O, sl, e + 1e-9, T, P, Pp, CUT, keep)[0]
     step = X.R(cs, e, T) * X.line_terms(cs, O, sl, [CUT], T, P, Pp, [l])[0]
     assert abs(a - b) < 1e-6 * step
+
+
+FLAGS = {4: dict(ped=True, vvh=False), 5: dict(ped=False, vvh=True), 6: dict(ped=True, vvh=True)}
+
+
+def _points(sl, cut):
+    """nu -> 0, points inside and beyond the cut-off, both sides of the mirror edge cut - nul and of the direct edges nul +- cut of a
+    low line, all below the table's last line"""
+    lo = sl.nu[3]
+    p = [1e-9, 1e-4, 0.5, 3.0, 0.5 * cut, cut - lo - 1e-6, cut - lo + 1e-6, lo + cut - 1e-3, lo + cut + 1e-3, 30.0, 97.3, 149.0]
+    return np.unique(np.array([x for x in p if 0.0 < x < 150.0]))
+
+
+@pytest.mark.parametrize("cut", [1.0, 5.0, 25.0, 100.0])
+def test_flagged_forms_at_any_cutoff(cs, O, low_h2o, cut):
+    """ckdvvh_ref.expected with its flags -- code 4 (ped), code 5 (vvh), code 6 (both) -- at cut-offs 1 to 100 cm^-1: against the code-4
+    restatement of test_gpu_voigt_ckd (one-line oracle slices as pedestals), the code-5 restatements of test_voigt_vvh and
+    test_gpu_voigt_vvh, and the definition at 40 digits"""
+    import test_gpu_voigt_ckd as CKD
+    import test_gpu_voigt_vvh as GV
+    import test_voigt_vvh as V
+    sl = low_h2o
+    T, P, Pp = 250.0, 3e4, 300.0
+    x = _points(sl, cut)
+    grid = np.linspace(0.5, 140.0, 400)
+    # (the restatements without the line at 8.4e-5 cm^-1: test_voigt_vvh.restate cancels its 1 - exp(-c2 nul / T) exactly, line_terms
+    # carries that factor's rounding, 3e-10 of the line's term -- the 40-digit check below allows for it)
+    rest = CKD._slice(sl, 1, len(sl.nu))
+    for strict in (True, False):
+        for code, fl in FLAGS.items():
+            val, scale = X.expected(cs, O, rest, grid, T, P, Pp, cut=cut, strict=strict, **fl)
+            assert np.all(np.isfinite(val)) and np.all(scale >= np.abs(val)) and np.any(val > 0)
+            if code == 4:
+                others = [CKD.restate(O, rest, grid, T, P, Pp, cut, strict)]
+            elif code == 5:
+                others = [V.restate(cs, O, rest, grid, T, P, Pp, cut, strict), GV.expected(cs, O, rest, grid, T, P, Pp, cut, strict)]
+                assert np.array_equal(val, scale)
+            else:
+                others = []
+            for o in others:
+                assert np.max(np.abs(o - val) / np.maximum(scale, 1e-300)) < 1e-12, (code, strict)
+    # the default is code 6, bitwise
+    a, b = X.expected(cs, O, sl, grid, T, P, Pp, cut=cut), X.expected(cs, O, sl, grid, T, P, Pp, cut=cut, ped=True, vvh=True)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    # the definition at 40 digits (strict: the vector methods' lines).  At 1 and 5 cm^-1 a point's value is that of one or two lines
+    # near their centres, at y ~ 1e2, where the oracle's Re w is good to some 1e-11 against mpmath (7e-12 measured); from 25 cm^-1 on the
+    # many lines of a window bring it to the 1e-13 of test_restatement_vs_definition
+    tol = 1e-13 if cut >= 25.0 else 2e-11
+    keep = np.nonzero(X.included(sl, x, cut, True))[0]
+    for code, fl in FLAGS.items():
+        val, scale = X.expected(cs, O, sl, x, T, P, Pp, cut=cut, **fl)
+        for i, v in enumerate(x):
+            e, t0 = _exact(cs, O, sl, v, T, P, Pp, cut, keep, **fl)
+            assert abs(val[i] - e) <= tol * scale[i] + 5e-10 * t0 + 1e-300, (code, v, val[i], e, scale[i], t0)
