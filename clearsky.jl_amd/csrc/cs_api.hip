@@ -231,6 +231,7 @@ struct Column {
     double *F_dst = nullptr;   // cs_column_set_flux_dst: caller-owned device memory the band fluxes [2 np] are written to (NULL: the column's own F)
     double *flux_out() { return F_dst ? F_dst : F.as<double>(); }
     bool ready = false;
+    bool swept = false;        // the column's own cross-section stage has run since setup: its windows / zones (cs_column_work reads them) are written
     int64_t nnu = 0;
     int np = 0, nl = 0, nlob = 0, K = 0, nstream = 0, ngas = 0, ntile = 0;
     RtGeom rtg = {};
@@ -2782,6 +2783,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     HIPCHK(c.F.reserve((size_t)2 * np * sizeof(double)));
     HIPCHK(hipStreamSynchronize(s));
     c.ready = true;  // state upload below needs the sizes
+    c.swept = false;
     c.tab.clear();
     c.cia.clear();
     c.accel.slot = -1;
@@ -3185,6 +3187,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
         if (any_ped) CS_LAUNCH(k_clamp0, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, sig);
     }
     HIPCHK(hipGetLastError());
+    c.swept = true;
     return CS_OK;
 }
 
@@ -3518,7 +3521,8 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
                                                      // near-zone pass; node lines: 2-, 3-, 4-term
     auto seg = [](int lo, int hi, int p0, int p1) { return (int64_t)std::max(0, std::min(hi, p1) - std::max(lo, p0)); };
     for (auto &g : c.gas) {
-        if (g.shape != SH_VOIGT && g.shape != SH_LORENTZ) continue;
+        // (a batch right after setup writes its windows and zones into buffers of its own: nothing to count, and the column's are unwritten)
+        if (!c.swept || (g.shape != SH_VOIGT && g.shape != SH_LORENTZ)) continue;
         std::vector<WaveWin> win(nt64);
         std::vector<Zone> zn((size_t)K * nt64);
         HIPCHK(hipMemcpy(win.data(), g.win.p, win.size() * sizeof(WaveWin), hipMemcpyDeviceToHost));

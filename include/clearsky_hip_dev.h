@@ -139,7 +139,8 @@ int cs_column_info(cs_ctx *ctx, int64_t *out);
  * kernels (keys 2, 7), out[38] = 1 where k_cheb_nodes ran four waves per (interval, state) (key 13), out[39] = flags of the whole step:
  * 1 window ends on the 16 tile nodes in k_voigt_edge_mx (key 23), 2 near-line plane cleared by a memset (key 19), 4 k_rt_streams
  * (key 5), 8 band sum inside the flux kernel (key 15 | 4), 16 far pieces of shared items on 64 nodes (key 17), 32 k_flux_chunk with
- * four waves per SIMD (key 15 | 8), 64 levels folded on the node-sum side stream (key 15 | 256).  `out` holds 40 values.
+ * four waves per SIMD (key 15 | 8), 64 levels folded on the node-sum side stream (key 15 | 256).  out[0..26] and out[32..33] describe
+ * the column's own last cross-section stage: zero while only cs_column_batch has run since cs_column_setup.  `out` holds 40 values.
  * cs_column_counts is the reference's count. */
 int cs_column_work(cs_ctx *ctx, int64_t *out);
 
