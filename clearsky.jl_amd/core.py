@@ -15,7 +15,8 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import constants as K
-from ._lib import (CHEB_LD, CS_MAX_ACCEL, CS_MAX_CIA, CS_MAX_GAS, CS_MAX_TABLE, SHAPES, ClearSkyHIPError, as_f64, check, dptr, lib)
+from ._lib import (CHEB_LD, CS_MAX_ACCEL, CS_MAX_CIA, CS_MAX_GAS, CS_MAX_TABLE, CS_SHAPE_PSHIFT, SHAPES, ClearSkyHIPError, as_f64, check,
+                   dptr, lib)
 from .hitran import TMAX, TMIN, SpectralLines
 from .cia import CIATables, cia, readcia
 
@@ -225,6 +226,7 @@ class Context:
         check(lib().cs_create(int(device), C.byref(self._h)))
         self.device = device
         self._slots = {}   # id(sl) -> (slot, sl)
+        self._shifted = set()   # id(sl) of the slots whose pressure shifts are attached (cs_gas_upload_par)
         self._next = 0
         self._tables = {}  # id(Gas) -> slot
         self._free_tables = list(range(CS_MAX_TABLE))
@@ -273,13 +275,25 @@ class Context:
         stream, series radius rank, PHCO2 core and node counts, low-order far pieces, level cascade, fused flux tail, ..."""
         check(lib().cs_set_tuning(self._h, int(key), int(value)))
 
-    def slot_of(self, sl: SpectralLines, keep=()) -> int:
+    def slot_of(self, sl: SpectralLines, keep=(), shift: bool = False) -> int:
         """Upload `sl` (once) and return its gas slot.  `keep`: tables that must stay where they are (the other gases of the call this
-        one belongs to): with every slot taken, the oldest table NOT among them makes room."""
+        one belongs to): with every slot taken, the oldest table NOT among them makes room.  `shift`: a use with pressure_shift=True --
+        the slot is loaded from sl's .par file through the native parser, which keeps the shifts (once; see _attach_shift)."""
         key = id(sl)
         if key in self._slots:
-            return self._slots[key][0]
+            slot = self._slots[key][0]
+            if shift:
+                self._attach_shift(slot, sl)
+            return slot
         slot = self._take_slot(keep)
+        self._shifted.discard(key)
+        self._upload_arrays(slot, sl)
+        self._slots[key] = (slot, sl)
+        if shift:
+            self._attach_shift(slot, sl)
+        return slot
+
+    def _upload_arrays(self, slot: int, sl: SpectralLines):
         iso = np.ascontiguousarray(sl.I, dtype=np.int16)
         ncheb = np.ascontiguousarray(sl.ncheb, dtype=np.int32)
         cheb = as_f64(sl.cheb)
@@ -288,19 +302,50 @@ class Context:
         check(lib().cs_gas_upload(self._h, slot, len(arrs[0]), *[dptr(a) for a in arrs],
                                   iso.ctypes.data_as(C.POINTER(C.c_int16)), len(ncheb),
                                   ncheb.ctypes.data_as(C.POINTER(C.c_int32)), dptr(cheb)))
-        self._slots[key] = (slot, sl)
-        return slot
+
+    def _attach_shift(self, slot: int, sl: SpectralLines):
+        """the slot of `sl` with its pressure shifts: the library takes them from the .par file alone (cs_gas_upload_par), so a table
+        read from a file is loaded again through the native parser, with the same filters, into the same slot; a table without a file
+        cannot take them: ValueError"""
+        if id(sl) in self._shifted:
+            return
+        if getattr(sl, "source", None) is None:
+            raise ValueError("pressure_shift=True needs a line table read from a HITRAN .par file (SpectralLines(filename) or "
+                             "Context.load_par): the library takes the shifts from the file")
+        from .hitran import MOLPARAM, ISOINDEX
+        src, kw = sl.source
+        mp = MOLPARAM[sl.M]
+        keep = np.array([ISOINDEX[c] if isinstance(c, str) else int(c) for c in kw.get("I", ())], dtype=np.int32)
+        mu, ncheb, cheb = as_f64(mp.mu), np.ascontiguousarray(mp.ncheb_table(), dtype=np.int32), as_f64(mp.cheb_table())
+        L = C.c_int64()
+        check(lib().cs_gas_upload_par(self._h, slot, src.encode(), float(kw.get("numin", 0.0)), float(min(kw.get("numax", np.inf), 1e300)),
+                                      float(kw.get("Scut", 0.0)), keep.ctypes.data_as(C.POINTER(C.c_int)), len(keep),
+                                      int(kw.get("maxlines", -1)), int(sl.M), dptr(mu), len(mu), ncheb.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      dptr(cheb), C.byref(L)))
+        names = ("nu", "S", "gamma_a", "gamma_s", "Epp", "na", "mu")
+        got = {n: np.zeros(L.value) for n in names}
+        iso = np.zeros(L.value, dtype=np.int16)
+        if L.value == len(sl.nu):
+            check(lib().cs_gas_fetch(self._h, slot, L.value, *[dptr(got[n]) for n in names], iso.ctypes.data_as(C.POINTER(C.c_int16))))
+        if L.value != len(sl.nu) or not all(np.array_equal(got[n], getattr(sl, n)) for n in names) or not np.array_equal(iso, sl.I):
+            # (the object's arrays were changed after reading, or the file was: put the object's own table back and say so)
+            self._upload_arrays(slot, sl)
+            raise ValueError(f"{src}: this SpectralLines object no longer matches its file, so its pressure shifts cannot be taken from it")
+        self._shifted.add(id(sl))
 
 
-    def slots_of(self, tables):
-        """Slots of all the line tables of ONE call: none of them is evicted to make room for another of them."""
-        return [self.slot_of(sl, keep=tables) for sl in tables]
+    def slots_of(self, tables, shifts=None):
+        """Slots of all the line tables of ONE call: none of them is evicted to make room for another of them.  shifts[i]: table i is
+        used with pressure_shift=True."""
+        shifts = shifts if shifts is not None else [False] * len(tables)
+        return [self.slot_of(sl, keep=tables, shift=bool(sh)) for sl, sh in zip(tables, shifts)]
 
     def _take_slot(self, keep=()):
         if len(self._slots) >= CS_MAX_GAS:   # evict the oldest table that the current call does not use
             pinned = {id(x) for x in keep}
             for old in self._slots:
                 if old not in pinned:
+                    self._shifted.discard(old)
                     return self._slots.pop(old)[0]
             raise ClearSkyHIPError(-1, f"all {CS_MAX_GAS} gas slots hold tables of the current call")
         slot = self._next
@@ -333,6 +378,7 @@ class Context:
                                  dptr(a["na"]), None, iso.ctypes.data_as(C.POINTER(C.c_int16))))
         sl = SpectralLines(dict(M=np.full(n, M, np.int16), I=iso, **a))
         self._slots[id(sl)] = (slot, sl)
+        self._shifted.add(id(sl))   # (cs_gas_upload_par attached the file's own pressure shifts)
         return sl
 
     def cia_slot(self, x: CIATables) -> int:
@@ -382,13 +428,14 @@ class MultiContext:
         self.ctxs = [Context(int(d)) for d in devices]
         assert len(self.ctxs) >= 1
 
-    def slot_of(self, sl: SpectralLines, keep=()) -> int:
-        slots = [c.slot_of(sl, keep) for c in self.ctxs]
+    def slot_of(self, sl: SpectralLines, keep=(), shift: bool = False) -> int:
+        slots = [c.slot_of(sl, keep, shift) for c in self.ctxs]
         assert all(s_ == slots[0] for s_ in slots), "contexts of a MultiContext must be used together from the start"
         return slots[0]
 
-    def slots_of(self, tables):
-        return [self.slot_of(sl, keep=tables) for sl in tables]
+    def slots_of(self, tables, shifts=None):
+        shifts = shifts if shifts is not None else [False] * len(tables)
+        return [self.slot_of(sl, keep=tables, shift=bool(sh)) for sl, sh in zip(tables, shifts)]
 
     def handles(self):
         return (C.c_void_p * len(self.ctxs))(*[c.handle.value for c in self.ctxs])
@@ -442,44 +489,56 @@ def default_context(device: int = 0) -> Context:
 # line shapes (B1)
 
 
-def shape_batch(sl: SpectralLines, shape, nu, T, P, Pp, dnu_cut=25.0, ctx: Optional[Context] = None):
+def shape_code(shape, pressure_shift: bool = False) -> int:
+    """The library's code of a shape name (or code), with CS_SHAPE_PSHIFT when pressure_shift: line centres at nul + delta_a P / P0
+    (include/clearsky_hip.h).  The shift applies to voigt, lorentz and doppler only; other shapes are refused here, before any device call."""
+    code = SHAPES[shape] if isinstance(shape, str) else int(shape)
+    if pressure_shift:
+        if code not in (0, 1, 2):
+            raise ValueError(f"pressure_shift applies to the voigt, lorentz and doppler shapes only, not {shape!r}")
+        code |= CS_SHAPE_PSHIFT
+    return code
+
+
+def shape_batch(sl: SpectralLines, shape, nu, T, P, Pp, dnu_cut=25.0, ctx: Optional[Context] = None, pressure_shift: bool = False):
     """sigma[k, :] = shape!(.., nu, sl, T[k], P[k], Pp[k], dnu_cut) for all states in one launch (bake's inner loop,
-    gases.jl:115-126).  Returns an array of shape (K, nnu)."""
+    gases.jl:115-126).  Returns an array of shape (K, nnu).  pressure_shift: line centres at nul + delta_a P[k] / P0."""
+    sh = shape_code(shape, pressure_shift)
     ctx = ctx or default_context()
     nu = as_f64(nu)
     T, P, Pp = (as_f64(np.atleast_1d(a)) for a in (T, P, Pp))
     Kn = len(T)
     assert len(P) == Kn and len(Pp) == Kn
     out = np.zeros((Kn, len(nu)))
-    sh = SHAPES[shape] if isinstance(shape, str) else int(shape)
-    check(lib().cs_shape_batch(ctx.handle, ctx.slot_of(sl), sh, float(dnu_cut), len(nu), dptr(nu), Kn, dptr(T), dptr(P),
+    check(lib().cs_shape_batch(ctx.handle, ctx.slot_of(sl, shift=pressure_shift), sh, float(dnu_cut), len(nu), dptr(nu), Kn, dptr(T), dptr(P),
                                dptr(Pp), dptr(out), len(nu)))
     return out
 
 
-def shape_points(sl: SpectralLines, shape, nu, T, P, Pp, dnu_cut=25.0, ctx: Optional[Context] = None):
+def shape_points(sl: SpectralLines, shape, nu, T, P, Pp, dnu_cut=25.0, ctx: Optional[Context] = None, pressure_shift: bool = False):
     """The scalar-wavenumber methods shape(nu, sl, T, P, Pp, dnu_cut) (line_shapes.jl:399-405 etc.) mapped over `nu` and over
-    the states: every line with |nu - nul| <= dnu_cut counts (includedlines(::Real), :12-16).  Returns (K, nnu)."""
+    the states: every line with |nu - nul| <= dnu_cut counts (includedlines(::Real), :12-16).  Returns (K, nnu).
+    pressure_shift: line centres at nul + delta_a P[k] / P0."""
+    sh = shape_code(shape, pressure_shift)
     ctx = ctx or default_context()
     nu = as_f64(np.atleast_1d(nu))
     T, P, Pp = (as_f64(np.atleast_1d(a)) for a in (T, P, Pp))
     out = np.zeros((len(T), len(nu)))
-    sh = SHAPES[shape] if isinstance(shape, str) else int(shape)
-    check(lib().cs_shape_points(ctx.handle, ctx.slot_of(sl), sh, float(dnu_cut), len(nu), dptr(nu), len(T), dptr(T), dptr(P), dptr(Pp),
+    check(lib().cs_shape_points(ctx.handle, ctx.slot_of(sl, shift=pressure_shift), sh, float(dnu_cut), len(nu), dptr(nu), len(T), dptr(T), dptr(P), dptr(Pp),
                                 dptr(out), len(nu)))
     return out
 
 
 def _shape_inplace(name, default_cut):
-    def f_(sigma, nu, sl, T, P, Pp, dnu_cut=default_cut, ctx=None):
-        r = shape_batch(sl, name, nu, [T], [P], [Pp], dnu_cut, ctx)
+    def f_(sigma, nu, sl, T, P, Pp, dnu_cut=default_cut, ctx=None, pressure_shift=False):
+        r = shape_batch(sl, name, nu, [T], [P], [Pp], dnu_cut, ctx, pressure_shift)
         sigma[...] = r[0]   # overwrite, line_shapes.jl:85
         return None
 
-    def f(nu, sl, T, P, Pp, dnu_cut=default_cut, ctx=None):
+    def f(nu, sl, T, P, Pp, dnu_cut=default_cut, ctx=None, pressure_shift=False):
         if np.ndim(nu) == 0:   # the scalar-nu method: inclusive cut-off, no end-point pre-filter (line_shapes.jl:12-16)
-            return float(shape_points(sl, name, [float(nu)], [T], [P], [Pp], dnu_cut, ctx)[0, 0])
-        return shape_batch(sl, name, nu, [T], [P], [Pp], dnu_cut, ctx)[0]
+            return float(shape_points(sl, name, [float(nu)], [T], [P], [Pp], dnu_cut, ctx, pressure_shift)[0, 0])
+        return shape_batch(sl, name, nu, [T], [P], [Pp], dnu_cut, ctx, pressure_shift)[0]
 
     f_.__doc__ = f"{name}!(sigma, nu, sl, T, P, Pp, dnu_cut={default_cut}) -- absorption/line_shapes.jl; fills sigma in place"
     f.__doc__ = f"{name}(nu, sl, T, P, Pp, dnu_cut={default_cut}) -- absorption/line_shapes.jl; returns cross-sections"
@@ -539,7 +598,9 @@ class DirectGas(AbstractGas):
     opacity-table interpolation error (gases.jl:7).  `fC` is a callable fC(T,P) or a number (molar concentration).
     """
 
-    def __init__(self, sl: SpectralLines, fC, nu, shape="voigt", dnu_cut=None):
+    def __init__(self, sl: SpectralLines, fC, nu, shape="voigt", dnu_cut=None, pressure_shift: bool = False):
+        shape_code(shape, pressure_shift)   # (refuses pressure_shift on a shape without it, before any device call)
+        self.pressure_shift = bool(pressure_shift)
         nu = np.array(nu, dtype=float)
         assert len(nu) > 0
         assert np.all(np.diff(nu) > 0), "wavenumbers must be unique and in ascending order"
@@ -566,10 +627,11 @@ class DirectGas(AbstractGas):
         if len(a) == 3:
             i, T, P = a
             Cv = self.fC(T, P)
-            return Cv * float(shape_points(self.sl, self.shape, [self.nu[int(i)]], [T], [P], [Cv * P], self.dnu_cut, ctx)[0, 0])
+            return Cv * float(shape_points(self.sl, self.shape, [self.nu[int(i)]], [T], [P], [Cv * P], self.dnu_cut, ctx,
+                                           self.pressure_shift)[0, 0])
         T, P = a
         Cv = self.fC(T, P)
-        return Cv * shape_points(self.sl, self.shape, self.nu, [T], [P], [Cv * P], self.dnu_cut, ctx)[0]
+        return Cv * shape_points(self.sl, self.shape, self.nu, [T], [P], [Cv * P], self.dnu_cut, ctx, self.pressure_shift)[0]
 
 
 class GrayGas(AbstractGas):
@@ -631,7 +693,9 @@ class Gas(AbstractGas):
     and interpolated afterwards (`OpacityTable`, gases.jl:68-85).  The ln(sigma) tables stay resident in HBM."""
 
     def __init__(self, sl, fC, nu, Omega: AtmosphericDomain, shape="voigt", dnu_cut=25.0, ctx: Optional["Context"] = None,
-                 keep_host_tables: bool = False, **readpar_kwargs):
+                 keep_host_tables: bool = False, pressure_shift: bool = False, **readpar_kwargs):
+        code = shape_code(shape, pressure_shift)   # (refuses pressure_shift on a shape without it, before any device call)
+        self.pressure_shift = bool(pressure_shift)
         if isinstance(sl, str):
             sl = SpectralLines(sl, **readpar_kwargs)
         nu = np.array(nu, dtype=float)
@@ -652,7 +716,7 @@ class Gas(AbstractGas):
         self.slot = self.ctx.table_slot(self)
         out = np.zeros((len(nu), Omega.nT, Omega.nP), order="F") if keep_host_tables else None
         try:
-            check(lib().cs_bake(self.ctx.handle, self.ctx.slot_of(sl), self.slot, SHAPES[shape], self.dnu_cut, len(nu), dptr(nu),
+            check(lib().cs_bake(self.ctx.handle, self.ctx.slot_of(sl, shift=pressure_shift), self.slot, code, self.dnu_cut, len(nu), dptr(nu),
                                 Omega.nT, dptr(as_f64(Omega.T)), Omega.nP, dptr(as_f64(Omega.P)), dptr(conc.ravel(order="F").copy()),
                                 out.ctypes.data_as(C.POINTER(C.c_double)) if out is not None else None))
         except Exception:
@@ -710,18 +774,21 @@ def reconcentrate(g: Gas, fC):
     return g.reconcentrate(fC)
 
 
-def opacityerror(g: Gas, i: int, N: int = 50, shape=None):
+def opacityerror(g: Gas, i: int, N: int = 50, shape=None, pressure_shift=None):
     """opacityerror(Π, Ω, sl, ν, C, shape=voigt, N=50) (gases.jl:152-175) for the table of wavenumber index i (0-based) of a baked Gas
     -- Π = that wavenumber's OpacityTable, Ω = g.Omega, sl = g.sl, ν = g.nu[i], C = the concentration the gas was baked with.
     Returns (T, P, aerr, rerr) on the reference's N x N grid (T linear over [Tmin, Tmax], P logarithmic over [Pmin, Pmax]):
     interpolated minus exact cross-section and that over the exact one.  The N*N exact values come from ONE cs_shape_points call
-    (the scalar-wavenumber `shape(ν, sl, T, P, C(T,P)*P)` at N*N states), the interpolated ones from cs_table_eval."""
+    (the scalar-wavenumber `shape(ν, sl, T, P, C(T,P)*P)` at N*N states), the interpolated ones from cs_table_eval.  pressure_shift:
+    of the exact values (None: as the gas was baked)."""
+    psh = g.pressure_shift if pressure_shift is None else bool(pressure_shift)
+    shape_code(shape or g.shape, psh)
     Om = g.Omega
     T = np.linspace(Om.Tmin, Om.Tmax, N)
     P = 10.0 ** np.linspace(math.log10(Om.Pmin), math.log10(Om.Pmax), N)
     TT, PP = np.meshgrid(T, P, indexing="ij")
     Pp = np.array([g.fC(t, p) * p for t, p in zip(TT.ravel(), PP.ravel())])
-    sex = shape_points(g.sl, shape or g.shape, [g.nu[int(i)]], TT.ravel(), PP.ravel(), Pp, g.dnu_cut, g.ctx)[:, 0].reshape(N, N)
+    sex = shape_points(g.sl, shape or g.shape, [g.nu[int(i)]], TT.ravel(), PP.ravel(), Pp, g.dnu_cut, g.ctx, psh)[:, 0].reshape(N, N)
     sop = np.array([[g.rawsigma(t, p, int(i)) for p in P] for t in T])
     aerr = sop - sex
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -1054,8 +1121,9 @@ class Column:
         for g_ in U.gas:
             if not isinstance(g_, (DirectGas, GrayGas, SemiGrayGas, Gas)):
                 raise TypeError(f"unsupported gas type {type(g_).__name__} for the HIP Discretized core")
-        self.slots = np.array(self.ctx.slots_of([g_.sl for g_ in self.gases]), dtype=np.int32)
-        self.shapes = np.array([SHAPES[g_.shape] for g_ in self.gases], dtype=np.int32)
+        psh = [getattr(g_, "pressure_shift", False) for g_ in self.gases]
+        self.slots = np.array(self.ctx.slots_of([g_.sl for g_ in self.gases], psh), dtype=np.int32)
+        self.shapes = np.array([shape_code(g_.shape, p_) for g_, p_ in zip(self.gases, psh)], dtype=np.int32)
         self.cuts = as_f64([g_.dnu_cut for g_ in self.gases])
         self.want_tau, self.want_M = bool(want_tau), bool(want_M)
         self._set = False

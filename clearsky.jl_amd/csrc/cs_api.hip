@@ -110,7 +110,10 @@ struct GasTable {
     std::vector<int32_t> h_ncheb;
     std::vector<uint8_t> h_gid;                          // merged tables only: member index of each line
     std::vector<std::pair<int, uint64_t>> members;       // merged tables only: (slot, generation) of each member, in member order
+    std::vector<double> h_da;                            // air pressure shifts delta_a [cm^-1/atm] (cs_gas_upload_par keeps them; empty: none)
+    double da_max = 0.0;                                 // max |delta_a| over the table
     DevBuf nu, S, ga, gs, Epp, na, mu, iso, ncheb, cheb, sref, gid;
+    mutable DevBuf da;                                   // h_da on the device, uploaded at the first CS_SHAPE_PSHIFT use (ensure_shifts)
     GasDev dev() const
     {
         GasDev g;
@@ -120,6 +123,7 @@ struct GasTable {
         g.iso = iso.as<int16_t>(); g.ncheb = ncheb.as<int32_t>(); g.cheb = cheb.as<double>();
         g.sref = sref.as<double>();
         g.gid = h_gid.empty() ? nullptr : gid.as<uint8_t>();
+        g.da = da.as<double>();
         return g;
     }
 };
@@ -200,6 +204,7 @@ struct UserGas {
     double cut = 25.0;
     uint64_t generation = 0;
     int64_t pairs_per_state = -1, lines_in_range = 0;
+    int64_t pairs_all = -1;   // CS_SHAPE_PSHIFT: pairs over all node states (the shifted centres move with the pressure)
 };
 // a launch group: one gas, or all Voigt (Lorentz) gases of the column with the same cut-off merged into ONE sorted line table --
 // sigma_total = sum_g C_g sigma_g (absorbers.jl:84-95) and a per-(state, line) record carries everything gas-specific (the
@@ -222,6 +227,8 @@ struct ColGas {
     bool vvh = false;         // shape code 5: shape is SH_VOIGT, the records carry S / R(nul, T) and launch_vvh follows the line sum
                               // (shape code 6: ped and vvh, and launch_vvh_ped follows it instead of both)
     int64_t mb = 0;           // ... with the mirror lines [pa, mb) (vvh_mirror_end)
+    bool pshift = false;      // CS_SHAPE_PSHIFT: records centred at nul + delta_a P / P0, summed by k_linesum<shape> over windows widened by ds
+    double ds = 0.0;          // ... the largest shift of the group at the column's node pressures (shift_width)
 };
 
 // k_rt launch geometry (rt_geometry)
@@ -626,14 +633,15 @@ void tile_windows(const std::vector<double> &nul, int64_t g0, int64_t g1, const 
 // The far kernel hands k_voigt_near the near-line ranges of every (nu, node) as 20-bit offsets into the tile's near zone and
 // 12-bit counts.  Bound both for any state (widest Doppler width: upper end of the grid, TMAX, lightest isotopologue) and
 // refuse tables too dense for the fields -- 4096 lines within a few Doppler widths is ~1e5 lines per cm^-1, far beyond HITEMP.
-int check_near_density(const GasTable &G, double nu_hi, double span, double cut);
-int check_near_density(const GasTable &G, const double *nu, int64_t nnu, double cut)
+int check_near_density(const GasTable &G, double nu_hi, double span, double cut, double ds = 0.0);
+int check_near_density(const GasTable &G, const double *nu, int64_t nnu, double cut, double ds = 0.0)
 {
     double span = 0.0;
     for (int64_t i0 = 0; i0 < nnu; i0 += 64) span = std::max(span, nu[std::min<int64_t>(i0 + 63, nnu - 1)] - nu[i0]);
-    return check_near_density(G, nu[nnu - 1], span, cut);
+    return check_near_density(G, nu[nnu - 1], span, cut, ds);
 }
-int check_near_density(const GasTable &G, double nu_hi, double span, double cut)   // span: widest 64-point tile of the grid
+// span: widest 64-point tile of the grid; ds: largest line shift of a CS_SHAPE_PSHIFT group (its zones and ranges span 2 ds more)
+int check_near_density(const GasTable &G, double nu_hi, double span, double cut, double ds)
 {
     const double amax = ((nu_hi + cut) / kC) * std::sqrt(2.0 * kRgas * kTmax / G.mu_min);
     const double dA = 100.0 * amax / kSqLn2 * (1.0 + 1e-6), r0 = std::sqrt(kSerS) * amax / kSqLn2 * 1.01;
@@ -647,7 +655,7 @@ int check_near_density(const GasTable &G, double nu_hi, double span, double cut)
         }
         return best;
     };
-    const int64_t nzone = max_in(span + 2.0 * dA), npt = max_in(2.0 * r0);
+    const int64_t nzone = max_in(span + 2.0 * dA + 2.0 * ds), npt = max_in(2.0 * r0 + 2.0 * ds);
     if (nzone >= (1 << 20) || npt >= (1 << 12))
         return fail(CS_EINVAL, "line table too dense for the near-line hand-off: %lld lines within %.3g cm^-1, %lld within %.3g cm^-1",
                     (long long)nzone, span + 2.0 * dA, (long long)npt, 2.0 * r0);
@@ -677,15 +685,17 @@ int64_t count_pairs(const std::vector<double> &nul, const double *nu, int64_t nn
 // xc[0..8] = tile indices (multiples of 4) of eight contiguous stretches of the spectrum, one per XCD, when the line table is
 // dense enough for its records to matter in that kernel's HBM traffic (32 B x lines against 16 B x wavenumbers per state:
 // contiguous from L >= nnu / 8); xc[0] = -1 = plain block order otherwise.  Returns the number of tiles per XCD (grid size).
+// ds > 0 (CS_SHAPE_PSHIFT): every line sits within ds of its table position -- the tile is widened by ds on both sides, so that [W0,W1)
+// holds every line that can reach it and [E0,E1) only lines inside every lane's cut-off wherever they are shifted to
 int wave_windows(const std::vector<double> &nul, int64_t g0, int64_t g1, const double *nu, int64_t nnu, double cut,
-                 std::vector<WaveWin> &win, int span = 64)
+                 std::vector<WaveWin> &win, int span = 64, double ds = 0.0)
 {
     const int nt = (int)((nnu + span - 1) / span);
     win.resize(nt);
     auto b = nul.begin() + g0, e = nul.begin() + g1;
     for (int t = 0; t < nt; t++) {
         const int64_t i0 = (int64_t)t * span, i1 = std::min<int64_t>(nnu, i0 + span) - 1;
-        const double vlo = nu[i0], vhi = nu[i1];
+        const double vlo = nu[i0] - ds, vhi = nu[i1] + ds;
         const double tol = 1e-9 * (std::fabs(vhi) + cut + 1.0);
         WaveWin w;
         w.W0 = (int32_t)(std::lower_bound(b, e, vlo - cut - tol) - nul.begin());
@@ -700,7 +710,7 @@ int wave_windows(const std::vector<double> &nul, int64_t g0, int64_t g1, const d
     int32_t xc[12] = {0};
     const int nt4 = (nt + 3) / 4 * 4;
     const int per = ((nt4 / 4 + 7) / 8) * 4;      // tiles per XCD, a multiple of 4
-    const int64_t inrange = (std::upper_bound(b, e, nu[nnu - 1] + cut) - std::lower_bound(b, e, nu[0] - cut));
+    const int64_t inrange = (std::upper_bound(b, e, nu[nnu - 1] + cut + ds) - std::lower_bound(b, e, nu[0] - cut - ds));
     for (int x = 0; x <= 8; x++) xc[x] = std::min(x * per, nt4);
     if (inrange * 8 < nnu) xc[0] = -1;
     win.resize(nt + 3);
@@ -894,7 +904,7 @@ int choose_l0(const ChebGrid &g, const double *nu, int64_t nnu, double cut, doub
 }
 
 int gas_interp_build(const cs_ctx *ctx, GasInterp &gi, ChebGrid &g, const std::vector<double> &nul, int64_t g0, int64_t g1,
-                     const double *nu, int64_t nnu, double cut, int K, hipStream_t s, bool own_F = true)
+                     const double *nu, int64_t nnu, double cut, int K, hipStream_t s, bool own_F = true, double ds = 0.0)
 {
     int rc;
     gi.nlev = g.nlev;
@@ -918,10 +928,11 @@ int gas_interp_build(const cs_ctx *ctx, GasInterp &gi, ChebGrid &g, const std::v
     for (int l = 0; l < g.nlev; l++) {
         gi.nfar[l] = (l > gi.l0 && g.span[l - 1] > 0.0 && g.span[l] > 0.0) ? far_node_count(cut - g.span[l - 1], 0.5 * g.span[l]) : CS_NC;
         if (gi.nfar[l] < CS_NC && !(ulp_hi <= 8e-14 * (cut - g.span[l - 1]))) gi.nfar[l] = CS_NC;
+        if (ds > 0.0) gi.nfar[l] = CS_NC;   // (a shifted group's far pieces are not at the distance far_node_count was given)
     }
     for (int l = 0; l < g.nlev; l++) {
         std::vector<WaveWin> iwin;
-        wave_windows(nul, g0, g1, nu, nnu, cut, iwin, g.itv[l]);
+        wave_windows(nul, g0, g1, nu, nnu, cut, iwin, g.itv[l], ds);
         if ((rc = upload(gi.iwin[l], iwin.data(), iwin.size(), s))) return rc;
         HIPCHK(hipStreamSynchronize(s));   // iwin is a local
     }
@@ -1196,11 +1207,18 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
                 const int32_t *J0, const int32_t *J1, const WaveWin *win, int xtiles, Zone *zones, int2 *ranges, const double *gbound, double cut, double base,
                 const double *extra, double *sigma, int accumulate, hipEvent_t *evg,   // NULL or 6 events: after K1 (+ zones), nodes (vector unit), nodes (matrix cores), far (vector unit), sub-tile cores, far (matrix cores)
                 LineF32 *hot32 = nullptr, double far_s = 1e6, Interp itp = Interp(), ChebApply *defer = nullptr, PhScratch *ph = nullptr,
-                Fork *fork = nullptr, bool records_ready = false /* hot / cold already hold this gas at these states: zones and sums only */)
+                Fork *fork = nullptr, bool records_ready = false /* hot / cold already hold this gas at these states: zones and sums only */,
+                bool pshift = false, double flo = -INFINITY, double fhi = INFINITY, double ds = 0.0)
 {
     fork_join(fork, s);   // (an earlier group's node kernels may still read the records this launch overwrites)
     const bool vvh = shape == SH_VOIGT_VVH;   // shape code 5: every Voigt kernel, over records of S / R(nul, T) (k_gas_setup*_vvh); the caller runs launch_vvh
     if (vvh) shape = SH_VOIGT;
+    // CS_SHAPE_PSHIFT (codes 0-2): records centred at nul + delta_a P / P0, lines whose shifted centre fails the strict pre-filter (flo, fhi)
+    // parked.  Every kernel reads the record's centre for the values and the cut-off tests; what is decided from TABLE positions -- the
+    // windows and zones of the tiles, the interval zones of the interpolated wings, J0 / J1 and the record range -- was (caller) or is
+    // (zones: ZoneArgs::ds) widened by the group's largest shift ds.  Off for such groups: the fp32 wings (far_term32 reads the table
+    // position) and the matrix-core pieces (their 1/dnu^2 operand is formed from table positions, state-independent)
+    if (pshift) hot32 = nullptr;
     // only the lines some window can reach (windows are sorted: first tile's start .. last tile's end)
     const int64_t jlo = jrange0, jhi = std::max(jrange1, jrange0);
     PrepArgs pa;
@@ -1208,6 +1226,7 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
     pa.Tk = Tk; pa.Pk = Pk; pa.Ppk = Ppk; pa.scale = scale; pa.mstride = mstride; pa.lrt = lrt; pa.qrefq = qrefq; pa.niso = G.niso; pa.hot = hot; pa.cold = cold; pa.hot32 = shape == SH_VOIGT ? hot32 : nullptr;
     pa.phfac = nullptr;
     pa.nu_c = 0.0;
+    pa.pshift = pshift ? 1 : 0; pa.flo = flo; pa.fhi = fhi;
     const unsigned nb_prep = records_ready ? 0u : (unsigned)((jhi - jlo + 255) / 256) * (unsigned)((kn + CS_PREP_KC - 1) / CS_PREP_KC);   // (line block, chunk of states)
     const bool lor = shape == SH_LORENTZ;   // lorentz! runs on the same far-wing machinery with its own (exact) body
     if (shape == SH_VOIGT || lor) {
@@ -1220,6 +1239,7 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
         za.lorentz = lor ? 1 : 0;
         za.ntile = nt64; za.K = kn; za.mu_min = G.mu_min; za.mu_max = G.mu_max; za.cut = cut; za.far_s = far_s;
         za.margin = itp.margin;
+        za.ds = pshift ? ds : 0.0;
         const unsigned nb_zones = (unsigned)(((int64_t)nt64 * kn + 255) / 256);
         IzParams P;
         memset(&P, 0, sizeof P);
@@ -1242,8 +1262,8 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
         // need the zones -- which their sixteen-lanes-per-item form computes itself, as blocks of the SAME launch (k_gas_setup_mx); the
         // one-thread-per-item form (from ~50 000 items on: BASELINE configs[4]) reads them, a launch of its own behind k_gas_setup
         const int q0s = itp.nlev > 0 ? itp.ioff[itp.l0] : 0, ngrp_s = (kn + 15) / 16;
-        const bool use_sep_s = itp.nlev > 0 && sep_in_use(itp.sep != nullptr, itp.sep_always, itp.nItot - q0s, kn, lor, hot32 != nullptr, itp.small_mx);
-        if (itp.nlev > 0) use_edge = edge_in_use(itp.edge != nullptr, itp.sep_always, nt64, kn, lor, hot32 != nullptr, jhi - jlo, itp.small_mx);
+        const bool use_sep_s = itp.nlev > 0 && !pshift && sep_in_use(itp.sep != nullptr, itp.sep_always, itp.nItot - q0s, kn, lor, hot32 != nullptr, itp.small_mx);
+        if (itp.nlev > 0 && !pshift) use_edge = edge_in_use(itp.edge != nullptr, itp.sep_always, nt64, kn, lor, hot32 != nullptr, jhi - jlo, itp.small_mx);
         SepArgs sa;
         EdgeArgs ea;
         memset(&sa, 0, sizeof sa);
@@ -1484,7 +1504,7 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
         }
         if (evg) (void)hipEventRecord(evg[5], s);
         if (!lor && !near_fork) launch_near(s, sigma);
-    } else if (shape == SH_PHCO2 && ph && phco2_fast_ok(G, nnu, cut, kn, ph)) {
+    } else if (shape == SH_PHCO2 && !pshift && ph && phco2_fast_ok(G, nnu, cut, kn, ph)) {
         // PHCO2 fast path (k_phco2): region-uniform far lines with factorised chi; needs the cut-off edges inside region 3 and the
         // near zone inside the chi = 1 core (phco2_fast_ok), else the generic kernel below
         const int nt64 = (int)((nnu + 63) / 64);
@@ -1495,6 +1515,7 @@ void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, in
         za.lorentz = 0;
         za.ntile = nt64; za.K = kn; za.mu_min = G.mu_min; za.mu_max = G.mu_max; za.cut = cut; za.far_s = far_s;
         za.margin = kChebMargin;
+        za.ds = 0.0;
         const unsigned nb_zones = (unsigned)(((int64_t)nt64 * kn + 255) / 256);
         IzParams P;
         memset(&P, 0, sizeof P);
@@ -1665,6 +1686,26 @@ static int64_t vvh_mirror_end(const std::vector<double> &nul, int64_t a, int64_t
     return std::upper_bound(nul.begin() + a, nul.begin() + b, lim + 1e-9 * cut) - nul.begin();
 }
 
+// a shape code as the entry points take it: base code 0..6, and CS_SHAPE_PSHIFT ORed onto codes 0, 1, 2; any other bit is refused
+static int decode_shape(int code, int &base, bool &pshift)
+{
+    pshift = code >= 0 && (code & CS_SHAPE_PSHIFT) != 0;
+    base = pshift ? (code & ~CS_SHAPE_PSHIFT) : code;
+    if (base < 0 || base > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", code);
+    if (pshift && base > SH_DOPPLER) return fail(CS_EINVAL, "CS_SHAPE_PSHIFT applies to shape codes 0, 1 and 2, not to %d", base);
+    return CS_OK;
+}
+// the largest pressure shift a line of G can take at pressures P[0..n): max |delta_a| x max P / P0 (every decision made from table positions
+// is widened by it).  A flagged group on a table without shifts is an error, not a shift of zero.
+static int shift_width(const GasTable &G, const double *P, int64_t n, double &ds)
+{
+    if (G.h_da.empty()) return fail(CS_EINVAL, "CS_SHAPE_PSHIFT on a gas without pressure shifts (load its table with cs_gas_upload_par)");
+    double pmax = 0.0;
+    for (int64_t k = 0; k < n; k++) pmax = std::max(pmax, std::fabs(P[k]));
+    ds = G.da_max * pmax / kAtm * (1.0 + 1e-12);
+    return CS_OK;
+}
+
 int check_gas_states(const GasTable &G, int K, const double *T)
 {
     for (int k = 0; k < K; k++)
@@ -1791,6 +1832,8 @@ static int table_to_device(GasTable &G, hipStream_t s)
         (rc = upload(G.cheb, G.h_cheb.data(), (size_t)G.niso * CS_CHEB_LD, s)))
         return rc;
     if (!G.h_gid.empty() && (rc = upload(G.gid, G.h_gid.data(), L, s))) return rc;
+    G.da_max = 0.0;
+    for (double d : G.h_da) G.da_max = std::max(G.da_max, std::fabs(d));
     HIPCHK(hipStreamSynchronize(s));   // (sref is a local)
     G.present = true;
     return CS_OK;
@@ -1825,9 +1868,35 @@ int cs_gas_upload(cs_ctx *ctx, int slot, int64_t L, const double *nu, const doub
     G.h_cheb.assign(cheb, cheb + (size_t)niso * CS_CHEB_LD);
     G.h_gid.clear();
     G.members.clear();
+    G.h_da.clear();   // (a new table drops the shifts of the old one)
+    G.da.release();
     int rc;
     if ((rc = table_to_device(G, ctx->stream))) return rc;
     G.generation = next_generation();
+    return CS_OK;
+}
+
+// HITRAN's air pressure shifts delta_a [cm^-1/atm] of the table just uploaded into `slot`, line for line (CS_SHAPE_PSHIFT): kept on the host
+// with the table (cs_gas_upload_par); the device copy is made at the first flagged use (ensure_shifts), so unflagged use costs nothing
+static int attach_shift(cs_ctx *ctx, int slot, int64_t L, const double *delta_a)
+{
+    GasTable &G = ctx->gas[slot];
+    if (L != G.L) return fail(CS_EINVAL, "%lld pressure shifts for a table of %lld lines", (long long)L, (long long)G.L);
+    for (int64_t j = 0; j < L; j++)
+        if (!std::isfinite(delta_a[j])) return fail(CS_EINVAL, "pressure shift of line %lld is not finite", (long long)j);
+    G.h_da.assign(delta_a, delta_a + L);
+    G.da_max = 0.0;
+    for (double d : G.h_da) G.da_max = std::max(G.da_max, std::fabs(d));
+    return CS_OK;
+}
+
+// the device copy of a table's shifts, made once (the caller has checked that there are shifts: shift_width)
+static int ensure_shifts(const GasTable &G, hipStream_t s)
+{
+    if (G.da.p) return CS_OK;
+    int rc;
+    if ((rc = upload(G.da, G.h_da.data(), (size_t)G.L, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
     return CS_OK;
 }
 
@@ -1877,6 +1946,9 @@ static int merged_table(cs_ctx *ctx, const std::vector<int> &slots, std::shared_
     }
     G.h_nu.resize(L); G.h_S.resize(L); G.h_ga.resize(L); G.h_gs.resize(L); G.h_Epp.resize(L); G.h_na.resize(L); G.h_mu.resize(L);
     G.h_iso.resize(L); G.h_gid.resize(L);
+    bool all_da = true;
+    for (int sl : slots) all_da = all_da && !ctx->gas[sl].h_da.empty();
+    if (all_da) G.h_da.resize(L);   // (shifts only where every member has them: a flagged group refuses a table without)
     for (int64_t i = 0; i < L; i++) {
         const Src q = order[i];
         const GasTable &g = ctx->gas[slots[q.m]];
@@ -1884,6 +1956,7 @@ static int merged_table(cs_ctx *ctx, const std::vector<int> &slots, std::shared_
         G.h_Epp[i] = g.h_Epp[q.j]; G.h_na[i] = g.h_na[q.j]; G.h_mu[i] = g.h_mu[q.j];
         G.h_iso[i] = (int16_t)(g.h_iso[q.j] + iso_off[q.m]);
         G.h_gid[i] = q.m;
+        if (all_da) G.h_da[i] = g.h_da[q.j];
     }
     int rc;
     if ((rc = table_to_device(G, ctx->stream))) return rc;
@@ -1984,23 +2057,29 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
 {
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (slot < 0 || slot >= CS_MAX_GAS || !ctx->gas[slot].present) return fail(CS_EINVAL, "gas slot %d is empty", slot);
-    if (shape < 0 || shape > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", shape);
+    bool pshift;
+    int rc;
+    if ((rc = decode_shape(shape, shape, pshift))) return rc;
     if (K < 1 || ld_state < nnu) return fail(CS_EINVAL, "bad K/ld_state");
     const bool ped = shape == SH_VOIGT_CKD || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum, then the pedestal behind it
     const bool vvh = shape == SH_VOIGT_VVH || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
     if (ped || vvh) shape = SH_VOIGT;
-    int rc;
     if ((rc = check_ascending(nu, nnu))) return rc;
     GasTable &G = ctx->gas[slot];
+    double ds = 0.0;   // CS_SHAPE_PSHIFT: every window and the line range widened by the largest shift of these states
+    if (pshift && (rc = shift_width(G, P, K, ds))) return rc;
     if ((rc = check_gas_states(G, K, T))) return rc;
-    if (shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, dnu_cut))) return rc;
+    if (shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, dnu_cut, ds))) return rc;
     ph_set_grid(ctx, ctx->ph, nu, nnu, ++g_grid_counter);
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
+    if (pshift && (rc = ensure_shifts(G, s))) return rc;
     int64_t g0, g1, pairs, inr;
-    included_range(G.h_nu, nu[0], nu[nnu - 1], dnu_cut, strict, g0, g1);
+    included_range(G.h_nu, nu[0], nu[nnu - 1], dnu_cut + ds, strict, g0, g1);
     std::vector<int32_t> J0, J1;
-    tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(shape, G, nu[nnu - 1], dnu_cut), J0, J1, pairs, inr);
+    tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(shape, G, nu[nnu - 1] + ds, dnu_cut) + ds, J0, J1, pairs, inr);
+    // (the strict pre-filter of a shifted line is its own state's: prep_body parks the lines whose shifted centre fails it)
+    const double flo = strict ? nu[0] - dnu_cut : -INFINITY, fhi = strict ? nu[nnu - 1] + dnu_cut : INFINITY;
     const int ntile = (int)J0.size();
     DevBuf dnu, dT, dP, dPp, dJ0, dJ1, hot, cold, dsig, dwin, dzones, dgmax, dranges, dlrt, dqref;
     {
@@ -2010,7 +2089,7 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
         HIPCHK(hipStreamSynchronize(s));
     }
     std::vector<WaveWin> win;
-    const int xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, dnu_cut, win);
+    const int xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, dnu_cut, win, 64, ds);
     if ((rc = upload(dnu, nu, nnu, s)) || (rc = upload(dT, T, K, s)) || (rc = upload(dP, P, K, s)) ||
         (rc = upload(dPp, Pp, K, s)) || (rc = upload(dJ0, J0.data(), ntile, s)) || (rc = upload(dJ1, J1.data(), ntile, s)) ||
         (rc = upload(dwin, win.data(), win.size(), s)))
@@ -2027,7 +2106,7 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
     HIPCHK(dzones.reserve((size_t)kc * win.size() * sizeof(Zone)));
     HIPCHK(dgmax.reserve((size_t)K * sizeof(double)));
     LineF32 *mix32 = nullptr;
-    if (ctx->mixed && shape == SH_VOIGT) {
+    if (ctx->mixed && shape == SH_VOIGT && !pshift) {
         HIPCHK(ctx->hot32.reserve(((size_t)kc * G.L + 4) * sizeof(LineF32)));
         mix32 = ctx->hot32.as<LineF32>();
     }
@@ -2041,7 +2120,7 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
     Interp itp;
     if (ctx->interp && (shape == SH_VOIGT || shape == SH_LORENTZ)) {
         if ((rc = cheb_build(ctx, cheb, nu, dnu.as<double>(), nnu, dnu_cut, s)) ||
-            (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, g0, g1, nu, nnu, dnu_cut, kc, s)))
+            (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, g0, g1, nu, nnu, dnu_cut, kc, s, true, ds)))
             return rc;
         itp = interp_view(cheb, ginterp, kc);
         if (!ctx->matrix_nodes) itp.sep = nullptr, itp.edge = nullptr;
@@ -2054,7 +2133,7 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
         launch_gas(s, vvh ? SH_VOIGT_VVH : shape, G, J0.front(), J1.back(), kn, dT.as<double>() + k0, dP.as<double>() + k0, dPp.as<double>() + k0, nullptr, 0,
                    dlrt.as<double>() + k0, dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(),
                    dwin.as<WaveWin>(), xtiles, dzones.as<Zone>(), dranges.as<int2>(), dgmax.as<double>() + k0, dnu_cut, 0.0, nullptr, dsig.as<double>(), 0, nullptr,
-                   mix32, ctx->far_s, itp, nullptr, &ctx->ph);
+                   mix32, ctx->far_s, itp, nullptr, &ctx->ph, nullptr, false, pshift, flo, fhi, ds);
         if (ped && !vvh)
             launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
                             hot.as<LineHot>(), cold.as<LineCold>(),
@@ -2083,12 +2162,13 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (gas_slot < 0 || gas_slot >= CS_MAX_GAS || !ctx->gas[gas_slot].present) return fail(CS_EINVAL, "gas slot %d is empty", gas_slot);
     if (table_slot < 0 || table_slot >= CS_MAX_TABLE) return fail(CS_EINVAL, "table slot %d out of range", table_slot);
-    if (shape < 0 || shape > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", shape);
+    bool pshift;
+    int rc;
+    if ((rc = decode_shape(shape, shape, pshift))) return rc;
     if (nT < 2 || nP < 2) return fail(CS_EINVAL, "need at least 2 x 2 grid points");
     const bool ped = shape == SH_VOIGT_CKD || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum, then the pedestal behind it (clamped before k_table_log)
     const bool vvh = shape == SH_VOIGT_VVH || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
     if (ped || vvh) shape = SH_VOIGT;
-    int rc;
     if ((rc = check_ascending(nu, nnu))) return rc;
     for (int64_t i = 0; i < nnu; i++)
         if (!(nu[i] >= 0)) return fail(CS_EINVAL, "wavenumbers must be positive");
@@ -2103,19 +2183,23 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
             Pp[i + nT * j] = C * P[j];
         }
     GasTable &G = ctx->gas[gas_slot];
+    double ds = 0.0;   // CS_SHAPE_PSHIFT: as in shape_impl
+    if (pshift && (rc = shift_width(G, Ps.data(), M, ds))) return rc;
     if ((rc = check_gas_states(G, M, Ts.data()))) return rc;
-    if (shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, dnu_cut))) return rc;
+    if (shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, dnu_cut, ds))) return rc;
     ph_set_grid(ctx, ctx->ph, nu, nnu, ++g_grid_counter);
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     TableDev &tb = ctx->tab[table_slot];
     tb.present = false;
+    if (pshift && (rc = ensure_shifts(G, s))) return rc;
     int64_t g0, g1, pairs, inr;
-    included_range(G.h_nu, nu[0], nu[nnu - 1], dnu_cut, true, g0, g1);
+    included_range(G.h_nu, nu[0], nu[nnu - 1], dnu_cut + ds, true, g0, g1);
     std::vector<int32_t> J0, J1;
-    tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(shape, G, nu[nnu - 1], dnu_cut), J0, J1, pairs, inr);
+    tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(shape, G, nu[nnu - 1] + ds, dnu_cut) + ds, J0, J1, pairs, inr);
+    const double flo = nu[0] - dnu_cut, fhi = nu[nnu - 1] + dnu_cut;   // (bake uses the vector method: strict pre-filter, per state when shifted)
     std::vector<WaveWin> win;
-    const int xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, dnu_cut, win);
+    const int xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, dnu_cut, win, 64, ds);
     const int ntile = (int)J0.size();
     DevBuf dnu, dT, dP, dPp, dJ0, dJ1, hot, cold, dwin, dzones, dgb, dranges, dlrt, dqref;
     {
@@ -2139,7 +2223,7 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
     HIPCHK(dzones.reserve((size_t)kc * win.size() * sizeof(Zone)));
     HIPCHK(dranges.reserve((size_t)kc * nnu * sizeof(int2) + (size_t)2 * kc * ((nnu + 63) / 64) * sizeof(int)));   // + per-(tile, state) flags
     LineF32 *mix32 = nullptr;
-    if (ctx->mixed && shape == SH_VOIGT) {
+    if (ctx->mixed && shape == SH_VOIGT && !pshift) {
         HIPCHK(ctx->hot32.reserve(((size_t)kc * G.L + 4) * sizeof(LineF32)));
         mix32 = ctx->hot32.as<LineF32>();
     }
@@ -2148,7 +2232,7 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
     Interp itp;
     if (ctx->interp && (shape == SH_VOIGT || shape == SH_LORENTZ)) {
         if ((rc = cheb_build(ctx, cheb, nu, dnu.as<double>(), nnu, dnu_cut, s)) ||
-            (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, g0, g1, nu, nnu, dnu_cut, kc, s)))
+            (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, g0, g1, nu, nnu, dnu_cut, kc, s, true, ds)))
             return rc;
         itp = interp_view(cheb, ginterp, kc);
         if (!ctx->matrix_nodes) itp.sep = nullptr, itp.edge = nullptr;
@@ -2161,7 +2245,7 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
         launch_gas(s, vvh ? SH_VOIGT_VVH : shape, G, J0.front(), J1.back(), kn, dT.as<double>() + k0, dP.as<double>() + k0, dPp.as<double>() + k0, nullptr, 0, dlrt.as<double>() + k0,
                    dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(), dwin.as<WaveWin>(), xtiles,
                    dzones.as<Zone>(), dranges.as<int2>(), dgb.as<double>() + k0, dnu_cut, 0.0, nullptr, tb.Z.as<double>() + (size_t)k0 * nnu, 0, nullptr,
-                   mix32, ctx->far_s, itp, nullptr, &ctx->ph);
+                   mix32, ctx->far_s, itp, nullptr, &ctx->ph, nullptr, false, pshift, flo, fhi, ds);
         if (ped && !vvh)
             launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
                             hot.as<LineHot>(), cold.as<LineCold>(),
@@ -2670,13 +2754,14 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     c.cheb.nlev = 0;
     if (ctx->interp) {   // interval sizes from the narrowest Voigt cut-off of the column
         double cmin = 0.0;
-        for (int gi = 0; gi < ngas; gi++)
-            if ((shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT || (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_LORENTZ ||
-                (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_CKD || (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_VVH ||
-                (shapes ? shapes[gi] : CS_SHAPE_VOIGT) == SH_VOIGT_CKD_VVH) {
+        for (int gi = 0; gi < ngas; gi++) {
+            int sh = shapes ? shapes[gi] : CS_SHAPE_VOIGT;
+            if (sh >= 0 && (sh & CS_SHAPE_PSHIFT)) sh &= ~CS_SHAPE_PSHIFT;   // (a flagged Voigt / Lorentz gas interpolates its far wings too)
+            if (sh == SH_VOIGT || sh == SH_LORENTZ || sh == SH_VOIGT_CKD || sh == SH_VOIGT_VVH || sh == SH_VOIGT_CKD_VVH) {
                 const double cu = dnu_cuts ? dnu_cuts[gi] : 25.0;
                 cmin = cmin > 0.0 ? std::min(cmin, cu) : cu;
             }
+        }
         if (cmin > 0.0 && (rc = cheb_build(ctx, c.cheb, nu, c.nu.as<double>(), nnu, cmin, s))) return rc;
     }
     std::vector<std::vector<int>> groups;
@@ -2688,17 +2773,21 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         if (ug.slot < 0 || ug.slot >= CS_MAX_GAS || !ctx->gas[ug.slot].present)
             return fail(CS_EINVAL, "gas slot %d is empty", ug.slot);
         ug.generation = ctx->gas[ug.slot].generation;
-        if (ug.shape < 0 || ug.shape > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", ug.shape);
+        int base;
+        bool psh;
+        if ((rc = decode_shape(ug.shape, base, psh))) return rc;
         const GasTable &G = ctx->gas[ug.slot];
+        double ds_unused;
+        if (psh && (rc = shift_width(G, P, np, ds_unused))) return rc;
         ug.pairs_per_state = -1;   // counted on demand (cs_column_counts): O(nnu log L) on the host
         ug.lines_in_range = std::upper_bound(G.h_nu.begin(), G.h_nu.end(), nu[nnu - 1] + ug.cut) -
                             std::lower_bound(G.h_nu.begin(), G.h_nu.end(), nu[0] - ug.cut);   // (the reference's count: inside the cut-off)
         // Voigt (Lorentz, pedestal-removed Voigt, Van Vleck-Huber Voigt, both) gases with the same shape and cut-off go into one group --
         // never codes 4, 5, 6 with code 0 or with each other: the pedestal, or R(nu, T) and the mirror term, act on every line of a group; a
-        // slot named twice stays apart (a merged table tags a line with ONE member)
+        // slot named twice stays apart (a merged table tags a line with ONE member).  ug.shape is the caller's code, CS_SHAPE_PSHIFT included:
+        // a flagged group merges only with flagged gases of the same base code and cut-off
         bool placed = false;
-        if (ctx->merge && (ug.shape == SH_VOIGT || ug.shape == SH_LORENTZ || ug.shape == SH_VOIGT_CKD || ug.shape == SH_VOIGT_VVH ||
-                           ug.shape == SH_VOIGT_CKD_VVH))
+        if (ctx->merge && (base == SH_VOIGT || base == SH_LORENTZ || base == SH_VOIGT_CKD || base == SH_VOIGT_VVH || base == SH_VOIGT_CKD_VVH))
             for (auto &grp : groups) {
                 const UserGas &h = c.ugas[grp[0]];
                 bool dup = false;
@@ -2718,6 +2807,8 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         ColGas &cg = c.gas[qi];
         cg.mem = groups[qi];
         cg.shape = c.ugas[cg.mem[0]].shape;
+        cg.pshift = (cg.shape & CS_SHAPE_PSHIFT) != 0;
+        if (cg.pshift) cg.shape &= ~CS_SHAPE_PSHIFT;
         cg.ped = cg.shape == SH_VOIGT_CKD || cg.shape == SH_VOIGT_CKD_VVH;
         cg.vvh = cg.shape == SH_VOIGT_VVH || cg.shape == SH_VOIGT_CKD_VVH;
         if (cg.ped || cg.vvh) cg.shape = SH_VOIGT;   // every kernel of a Voigt group, then the pedestal and / or R(nu, T) and the mirror term
@@ -2731,25 +2822,27 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
             cg.tab = cg.hold.get();
         }
         const GasTable &G = *cg.tab;
-        if (cg.shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, cg.cut))) return rc;
+        cg.ds = 0.0;   // CS_SHAPE_PSHIFT: windows and line range widened by the group's largest shift at the node pressures
+        if (cg.pshift && ((rc = shift_width(G, c.h_Pk.data(), K, cg.ds)) || (rc = ensure_shifts(G, s)))) return rc;
+        if (cg.shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, cg.cut, cg.ds))) return rc;
         int64_t g0, g1, pairs_unused, inr_unused;
         included_range(G.h_nu, nu[0], nu[nnu - 1], cg.cut, false, g0, g1);
         std::vector<int32_t> J0, J1;
-        tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(cg.shape, G, nu[nnu - 1], cg.cut), J0, J1, pairs_unused, inr_unused);
+        tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(cg.shape, G, nu[nnu - 1] + cg.ds, cg.cut) + cg.ds, J0, J1, pairs_unused, inr_unused);
         cg.jlo = J0.front();
         cg.jhi = J1.back();
         cg.pa = std::max(g0, cg.jlo);
         cg.pb = std::min(g1, cg.jhi);
         cg.mb = cg.vvh ? vvh_mirror_end(G.h_nu, cg.pa, cg.pb, nu[0], cg.cut) : cg.pa;
         std::vector<WaveWin> win;
-        cg.xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, cg.cut, win);
+        cg.xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, cg.cut, win, 64, cg.ds);
         if ((rc = upload(cg.J0, J0.data(), J0.size(), s)) || (rc = upload(cg.J1, J1.data(), J1.size(), s)) ||
             (rc = upload(cg.win, win.data(), win.size(), s)))
             return rc;
         HIPCHK(cg.zones.reserve((size_t)c.K * win.size() * sizeof(Zone)));
         HIPCHK(cg.gmax.reserve((size_t)c.K * sizeof(double)));
         if (c.cheb.nlev > 0 && (cg.shape == SH_VOIGT || cg.shape == SH_LORENTZ) &&
-            (rc = gas_interp_build(ctx, cg.itp, c.cheb, G.h_nu, g0, g1, nu, nnu, cg.cut, c.K, s, false)))
+            (rc = gas_interp_build(ctx, cg.itp, c.cheb, G.h_nu, g0, g1, nu, nnu, cg.cut, c.K, s, false, cg.ds)))
             return rc;
         HIPCHK(hipStreamSynchronize(s));   // J0, J1, win are locals
         maxL = std::max(maxL, (size_t)G.L);
@@ -2966,7 +3059,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
                        dconc.as<double>() + k0, (int)BK, dlrt.as<double>() + k0, dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, c.ntile,
                        cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), cg.win.as<WaveWin>(), cg.xtiles, dzones.as<Zone>(), dranges.as<int2>(),
                        dgb.as<double>() + k0, cg.cut, cg.vvh ? 0.0 : c.sigma_gray, nullptr, dst, cg.vvh ? 0 : qi > 0, nullptr,
-                       (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, nullptr, &ctx->ph);
+                       (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, nullptr, &ctx->ph, nullptr, false, cg.pshift, -INFINITY, INFINITY, cg.ds);
             if (cg.vvh && cg.ped)
                 launch_vvh_ped(s, G, cg.pa, cg.pb, cg.mb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), kn, dTk.as<double>() + k0, hot.as<LineHot>(),
                                cold.as<LineCold>(), c.h_nu.data(), c.nu.as<double>(), c.nnu, cg.cut, dst, c.sigma_gray, nullptr, sk, qi > 0, false, dped.as<double>());
@@ -3105,7 +3198,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
                    cg.vvh ? 0.0 : c.sigma_gray, cg.vvh ? nullptr : extra, dst, cg.vvh ? 0 : gi > 0,
                    ev ? ev + e : nullptr,
                    (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, cg.vvh ? nullptr : &apply, &ctx->ph,
-                   (use_fork && !cg.vvh) ? &fk : nullptr);
+                   (use_fork && !cg.vvh) ? &fk : nullptr, false, cg.pshift, -INFINITY, INFINITY, cg.ds);
         if (cg.vvh && cg.ped)
             launch_vvh_ped(s, G, cg.pa, cg.pb, cg.mb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), K, c.Tk.as<double>(), c.hot.as<LineHot>(),
                            c.cold.as<LineCold>(), c.h_nu.data(), c.nu.as<double>(), c.nnu, cg.cut, dst, c.sigma_gray, extra, sig, gi > 0, false, c.ped.as<double>());
@@ -3456,9 +3549,23 @@ int cs_column_counts(cs_ctx *ctx, int64_t *pair_evals, int64_t *lines_in_range)
     Column &c = ctx->col;
     int64_t p = 0, l = 0;
     for (auto &g : c.ugas) {
+        l += g.lines_in_range;
+        if (g.shape & CS_SHAPE_PSHIFT) {   // pairs inside the cut-off of the shifted centres, state by state
+            if (g.pairs_all < 0) {
+                const GasTable &G = ctx->gas[g.slot];
+                std::vector<double> sh(G.h_nu.size());
+                g.pairs_all = 0;
+                for (int k = 0; k < c.K; k++) {
+                    for (size_t j = 0; j < sh.size(); j++) sh[j] = G.h_nu[j] + G.h_da[j] * c.h_Pk[k] / kAtm;
+                    std::sort(sh.begin(), sh.end());
+                    g.pairs_all += count_pairs(sh, c.h_nu.data(), c.nnu, g.cut);
+                }
+            }
+            p += g.pairs_all;
+            continue;
+        }
         if (g.pairs_per_state < 0) g.pairs_per_state = count_pairs(ctx->gas[g.slot].h_nu, c.h_nu.data(), c.nnu, g.cut);
         p += g.pairs_per_state * c.K;
-        l += g.lines_in_range;
     }
     if (pair_evals) *pair_evals = p;
     if (lines_in_range) *lines_in_range = l;
@@ -3549,7 +3656,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
             iz.resize((size_t)K * nItot);
             HIPCHK(hipMemcpy(iz.data(), g.itp.iz.p, iz.size() * sizeof(IZone), hipMemcpyDeviceToHost));
             const int q0 = c.cheb.ioff[g.itp.l0];
-            const bool use_sep = sep_in_use(ctx->matrix_nodes != 0, ctx->matrix_nodes == 2, nItot - q0, K, g.shape != SH_VOIGT, ctx->mixed != 0, ctx->tune[1] != 0);
+            const bool use_sep = !g.pshift && sep_in_use(ctx->matrix_nodes != 0, ctx->matrix_nodes == 2, nItot - q0, K, g.shape != SH_VOIGT, ctx->mixed != 0, ctx->tune[1] != 0);
             std::vector<SepZone> sz;
             if (use_sep) {
                 sz.resize((size_t)((K + 15) / 16) * nItot);
@@ -3588,7 +3695,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
         }
         if (nlev > 0) {
             const int q0 = c.cheb.ioff[g.itp.l0];
-            if (sep_in_use(ctx->matrix_nodes != 0, ctx->matrix_nodes == 2, nItot - q0, K, g.shape != SH_VOIGT, ctx->mixed != 0, ctx->tune[1] != 0)) {
+            if (!g.pshift && sep_in_use(ctx->matrix_nodes != 0, ctx->matrix_nodes == 2, nItot - q0, K, g.shape != SH_VOIGT, ctx->mixed != 0, ctx->tune[1] != 0)) {
                 std::vector<SepZone> sz((size_t)((K + 15) / 16) * nItot);
                 HIPCHK(hipMemcpy(sz.data(), g.itp.sep.p, sz.size() * sizeof(SepZone), hipMemcpyDeviceToHost));
                 for (int gq = 0; gq < (K + 15) / 16; gq++) {
@@ -3608,7 +3715,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
         }
         int ishift = 0;
         if (nlev > 0) for (int r = c.cheb.itv[nlev - 1] / 64; r > 1; r >>= 1) ishift++;
-        const bool use_edge = nlev > 0 && edge_in_use(ctx->matrix_nodes != 0, ctx->matrix_nodes == 2, nt64, K, g.shape != SH_VOIGT, ctx->mixed != 0,
+        const bool use_edge = nlev > 0 && !g.pshift && edge_in_use(ctx->matrix_nodes != 0, ctx->matrix_nodes == 2, nt64, K, g.shape != SH_VOIGT, ctx->mixed != 0,
                                                       std::max<int64_t>(g.jhi - g.jlo, 0), ctx->tune[1] != 0);
         std::vector<EdgeZone> ez;
         if (use_edge) {
@@ -4136,7 +4243,7 @@ int cs_gas_upload_par(cs_ctx *ctx, int slot, const char *filename, double numin,
     }
     std::stable_sort(keep.begin(), keep.end(), [&](int64_t a, int64_t b) { return nu[a] < nu[b]; });   // par.jl:188-191
     const int64_t L = (int64_t)keep.size();
-    std::vector<double> o_nu(L), o_S(L), o_ga(L), o_gs(L), o_E(L), o_na(L), o_mu(L);
+    std::vector<double> o_nu(L), o_S(L), o_ga(L), o_gs(L), o_E(L), o_na(L), o_mu(L), o_da(L);
     std::vector<int16_t> o_iso(L);
     for (int64_t j = 0; j < L; j++) {
         const int64_t i = keep[j];
@@ -4145,13 +4252,15 @@ int cs_gas_upload_par(cs_ctx *ctx, int slot, const char *filename, double numin,
                         (long long)i, (int)M[i], M_expected);
         const int ii = iso_index(I[i]);
         if (ii < 1 || ii > niso) return fail(CS_EINVAL, "isotopologue '%c' of record %lld has no MOLPARAM row (%d rows)", I[i], (long long)i, niso);
-        o_nu[j] = nu[i]; o_S[j] = S[i]; o_ga[j] = ga[i]; o_gs[j] = gs[i]; o_E[j] = Epp[i]; o_na[j] = na[i];
+        o_nu[j] = nu[i]; o_S[j] = S[i]; o_ga[j] = ga[i]; o_gs[j] = gs[i]; o_E[j] = Epp[i]; o_na[j] = na[i]; o_da[j] = da[i];
         o_iso[j] = (int16_t)ii;
         o_mu[j] = mu_table[ii - 1];
     }
     if (L_out) *L_out = L;
-    return cs_gas_upload(ctx, slot, L, o_nu.data(), o_S.data(), o_ga.data(), o_gs.data(), o_E.data(), o_na.data(), o_mu.data(), o_iso.data(),
-                         niso, ncheb, cheb);
+    if ((rc = cs_gas_upload(ctx, slot, L, o_nu.data(), o_S.data(), o_ga.data(), o_gs.data(), o_E.data(), o_na.data(), o_mu.data(), o_iso.data(),
+                            niso, ncheb, cheb)))
+        return rc;
+    return attach_shift(ctx, slot, L, o_da.data());   // the file's own air pressure shifts (CS_SHAPE_PSHIFT)
 }
 
 int cs_gas_fetch(cs_ctx *ctx, int slot, int64_t L, double *nu, double *S, double *gamma_a, double *gamma_s, double *Epp, double *na,

@@ -66,6 +66,7 @@ struct GasDev {
     const double *cheb;  // [niso][16]
     const uint8_t *gid;  // merged table of several gases of a column: member index of each line (NULL: one gas) -- selects the
                          // member's partial pressure and concentration in k_gas_setup; everything else of a record is per line
+    const double *da;    // HITRAN's air pressure shift delta_a [cm^-1/atm] of each line (kept by cs_gas_upload_par; NULL: none)
 };
 
 // line_shapes.jl:27-48
@@ -103,7 +104,12 @@ struct PrepArgs {
     LineF32 *hot32;
     double *phfac;    // PHCO2 fast path: [6][K][L] line factors exp(+-b_r(T) (nul - nu_c)), r = 1..3 (NULL: not needed)
     double nu_c;      // reference wavenumber of those factors (centre of the grid)
+    int pshift;       // CS_SHAPE_PSHIFT: the record's centre is nul + delta_a P / P0 (g.da); S, alpha, gamma stay those of nul
+    double flo, fhi;  // ... and a line whose shifted centre is not strictly inside (flo, fhi) is left out (the strict end-point pre-filter of
+                      // includedlines, per state): its record is parked at kParked, beyond every cut-off, with zero strength (every body
+                      // then adds an exact 0: finite squares, no 0 x inf)
 };
+constexpr double kParked = 1e100;
 // VVH: shape code 5 -- the Voigt records carry S / R(nul, T) instead of S (k_gas_setup_vvh, k_gas_setup_mx_vvh)
 template <bool VVH = false>
 __device__ __forceinline__ void prep_body(unsigned bid, const PrepArgs &pa)
@@ -141,6 +147,12 @@ __device__ __forceinline__ void prep_body(unsigned bid, const PrepArgs &pa)
         LineHot h;
         LineCold c;
         h.nul = nul;
+        bool parked = false;
+        if (pa.pshift) {   // ν_l + δ_l P / P0 (HAPI's convention: only the centre moves)
+            h.nul = nul + g.da[j] * P / kAtm;
+            parked = !(h.nul > pa.flo && h.nul < pa.fhi);
+            if (parked) h.nul = kParked;
+        }
         if (shape == SH_LORENTZ) {
             h.p1 = gamma * gamma; h.p2 = C * S * gamma / kPi; h.p3 = 0.0;
             c.y = gamma; c.A = C * S;
@@ -155,6 +167,10 @@ __device__ __forceinline__ void prep_body(unsigned bid, const PrepArgs &pa)
             const double y2 = y * y;
             h.p1 = dd; h.p2 = y2; h.p3 = A * y * kIsqPi;
             c.y = y; c.A = A;
+        }
+        if (parked) {
+            if (shape == SH_LORENTZ || shape == SH_DOPPLER) h.p2 = 0.0; else h.p3 = 0.0;
+            c.A = 0.0;
         }
         hot[idx] = h;
         cold[idx] = c;
@@ -305,6 +321,7 @@ struct ZoneArgs {
     int ntile, K, lorentz;   // lorentz: pure Lorentz profile -- one body everywhere, no Doppler core, no near zone
     double mu_min, mu_max, cut, far_s;
     double margin;           // an interval's interpolated set stays max(dA, margin x its half-width) away from it (kChebMargin)
+    double ds;               // CS_SHAPE_PSHIFT: the group's largest line shift -- every span searched against table positions is widened by it
 };
 // the zones of (state k, tile t)
 __device__ __forceinline__ Zone zone_compute(const ZoneArgs &a, int k, int t)
@@ -314,7 +331,8 @@ __device__ __forceinline__ Zone zone_compute(const ZoneArgs &a, int k, int t)
     const int64_t nnu = a.nnu;
     const double mu_min = a.mu_min, mu_max = a.mu_max, cut = a.cut, far_s = a.far_s;
     const int64_t i0 = (int64_t)t * 64, i1 = (i0 + 63 < nnu ? i0 + 63 : nnu - 1);
-    const double vlo = nu[i0], vhi = nu[i1];
+    // (a shifted line sits within ds of its table position: a tile widened by ds on both sides makes every bound below hold for it)
+    const double vlo = nu[i0] - a.ds, vhi = nu[i1] + a.ds;
     const WaveWin w = win[t];
     if (a.lorentz) {
         // every line takes the (exact) Lorentz body, so the zones only say where the cut-off predicate is needed: the window is
@@ -622,12 +640,12 @@ struct IzParams {
 // point, dZ = how far the interpolated set stays from the interval; false if the set is empty
 __device__ __forceinline__ bool izone_frame(const IzParams &P, int l, int T, const double *__restrict__ nu, int64_t nnu, double vth,
                                             double mu_min, double cut, double &vlo, double &vhi, double &dA, double &dZ, int &E0, int &E1,
-                                            bool lorentz, double margin)
+                                            bool lorentz, double margin, double ds = 0.0)
 {
     const int itv = P.itv[l];
     const int64_t i0 = (int64_t)T * itv, i1 = (i0 + itv - 1 < nnu ? i0 + itv - 1 : nnu - 1);
-    vlo = nu[i0];
-    vhi = nu[i1];
+    vlo = nu[i0] - ds;   // (ds: the interval widened by the group's largest line shift, as in zone_compute)
+    vhi = nu[i1] + ds;
     const WaveWin w = P.iwin[l][T];   // E0..E1: lines inside the cut-off of every point of the interval
     E0 = w.E0; E1 = w.E1;
     if (w.E1 <= w.E0) { E0 = E1 = w.E0; return false; }   // (then the parent has nothing either: the sets are nested)
@@ -649,7 +667,7 @@ __device__ __forceinline__ IZone izone_compute(const IzParams &P, const ZoneArgs
     const double vth = sqrt(2.0 * kRgas * Tk[k]);
     double vlo, vhi, dA, dZ;
     IZone z;
-    if (!izone_frame(P, l, T, nu, nnu, vth, mu_min, cut, vlo, vhi, dA, dZ, z.E0, z.E1, a.lorentz, a.margin)) {
+    if (!izone_frame(P, l, T, nu, nnu, vth, mu_min, cut, vlo, vhi, dA, dZ, z.E0, z.E1, a.lorentz, a.margin, a.ds)) {
         z.Z0 = z.Z1 = z.Q0 = z.M0 = z.M1 = z.Q1 = z.P0 = z.P1 = z.P2 = z.P3 = z.S0 = z.S1 = z.E0;
         z.pad0 = z.pad1 = 0;
         return z;
@@ -671,7 +689,7 @@ __device__ __forceinline__ IZone izone_compute(const IzParams &P, const ZoneArgs
     if (l > P.l0) {
         int pshift = 0;
         for (int r = P.itv[l - 1] / P.itv[l]; r > 1; r >>= 1) pshift++;
-        par = izone_frame(P, l - 1, T >> pshift, nu, nnu, vth, mu_min, cut, pvlo, pvhi, pdA, pdZ, qE0, qE1, a.lorentz, a.margin);
+        par = izone_frame(P, l - 1, T >> pshift, nu, nnu, vth, mu_min, cut, pvlo, pvhi, pdA, pdZ, qE0, qE1, a.lorentz, a.margin, a.ds);
     }
     // this state's radius of the 4-term series in 1/dnu^2 (sepzones_body takes the group's pieces from these)
     const double R4 = [&] {

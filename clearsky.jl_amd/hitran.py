@@ -143,11 +143,13 @@ class SpectralLines:
 
     Fields (reference names in brackets): name, formula, N, M, I [I], mu [mu], A [A], nu [nu], S, gamma_a [gamma_a],
     gamma_s [gamma_s], Epp, na.  `SpectralLines(filename, **kw)` reads a .par file; `SpectralLines(par_dict)` wraps
-    the output of readpar.  The pressure-shift column is parsed but dropped, as in the reference (quirk 2).
+    the output of readpar.  The pressure-shift column is kept as delta_a (the reference drops it, quirk 2): the shapes take it with
+    pressure_shift=True, through the native parser (Context.load_par, or the file a SpectralLines was read from).
     """
 
     def __init__(self, src, **kwargs):
         par = readpar(src, **kwargs) if isinstance(src, str) else src
+        self.source = (src, dict(kwargs)) if isinstance(src, str) else None   # (a use with pressure_shift=True loads the file natively)
         nu = np.asarray(par["nu"], float)
         N = len(nu)
         Ms = np.unique(par["M"])
@@ -168,6 +170,8 @@ class SpectralLines:
         self.gamma_s = np.ascontiguousarray(np.asarray(par["gamma_s"], float)[idx])
         self.Epp = np.ascontiguousarray(np.asarray(par["Epp"], float)[idx])
         self.na = np.ascontiguousarray(np.asarray(par["na"], float)[idx])
+        # air pressure shift [cm^-1/atm] (par.jl:80,140), used by shapes called with pressure_shift=True; None where the source has none
+        self.delta_a = np.ascontiguousarray(np.asarray(par["delta_a"], float)[idx]) if "delta_a" in par else None
         self.ncheb = mp.ncheb_table()
         self.cheb = mp.cheb_table()
 

@@ -68,6 +68,22 @@ enum {
  * cut-off: 25 cm^-1.  Accepted wherever a shape code is; merged only with code 6 of the same cut-off. */
 enum { CS_SHAPE_VOIGT = 0, CS_SHAPE_LORENTZ = 1, CS_SHAPE_DOPPLER = 2, CS_SHAPE_PHCO2 = 3, CS_SHAPE_VOIGT_CKD = 4, CS_SHAPE_VOIGT_VVH = 5,
        CS_SHAPE_VOIGT_CKD_VVH = 6 };
+/* CS_SHAPE_PSHIFT, ORed onto codes 0, 1, 2: HITRAN's air pressure shift of the line centres (LBLRTM, HAPI, ARTS).  For every state
+ * (T, P, Pp), with delta_l the slot's shifts (from its .par file) and P0 = 1 atm = 101325 Pa,
+ *     sigma(nu) = sum_l S_l(T) f_l(nu - nul - s_l),    s_l = delta_l P / P0,
+ * f_l the line's profile under its base code, S_l, alpha_l and gamma_l computed exactly as without the flag, from the UNSHIFTED nul
+ * (HAPI's convention).  P is the state's total pressure; the 160-column format carries the air shift only (no self shift, no temperature
+ * exponent).  The inclusive cut-off |nu - nul - s_l| <= dnu_cut and the strict end-point pre-filter of the vector methods
+ * (nu_1 - cut < nul + s_l < nu_N + cut) are measured from the SHIFTED centre: line l's term is the unflagged term on the grid nu - s_l.
+ * The shifts come from the file: cs_gas_upload_par keeps each record's delta_a (HITRAN columns 60-67, par.jl:80,140) with the slot;
+ * cs_gas_upload and cs_gas_clear drop them.
+ * Accepted wherever a shape code is (B1, cs_bake, the Mode D calls, resident columns in every flux form, cs_column_sigma_run,
+ * cs_column_batch, cs_accel_store, nu-shards); on codes 3-6, or with any other bit set, CS_EINVAL.  A flagged gas on a slot without
+ * shifts (one filled by cs_gas_upload) is CS_EINVAL -- never a shift of zero.  Flagged gases merge only with flagged gases of the same
+ * base code and cut-off.  A flagged Voigt / Lorentz group keeps the vector-unit path (interpolated far wings, near-line pairs) with every
+ * window and zone widened by its largest shift; it takes no matrix-core pieces and no fp32 wings under cs_set_precision mode 1 (both
+ * are formed from table positions): it runs in fp64.  Codes without the flag run exactly as before. */
+#define CS_SHAPE_PSHIFT 16
 
 #define CS_MAX_GAS 16
 #define CS_MAX_TABLE 16
