@@ -707,6 +707,7 @@ class Gas(AbstractGas):
         self.mu = float(np.sum(sl.A * sl.mu) / np.sum(sl.A))      # gases.jl:233
         self.nu, self.Omega, self.shape, self.dnu_cut = nu, Omega, shape, float(dnu_cut)
         self.fC = fC if callable(fC) else (lambda T, P, _c=float(fC): _c)
+        self.fC_bake = self.fC     # the concentration the tables carry (self-broadening); reconcentrate() copies it unchanged (gases.jl fCbake)
         conc = np.zeros((Omega.nT, Omega.nP), order="F")
         for i, T in enumerate(Omega.T):
             for j, P in enumerate(Omega.P):
@@ -776,7 +777,8 @@ def reconcentrate(g: Gas, fC):
 
 def opacityerror(g: Gas, i: int, N: int = 50, shape=None, pressure_shift=None):
     """opacityerror(Π, Ω, sl, ν, C, shape=voigt, N=50) (gases.jl:152-175) for the table of wavenumber index i (0-based) of a baked Gas
-    -- Π = that wavenumber's OpacityTable, Ω = g.Omega, sl = g.sl, ν = g.nu[i], C = the concentration the gas was baked with.
+    -- Π = that wavenumber's OpacityTable, Ω = g.Omega, sl = g.sl, ν = g.nu[i], C = the concentration the gas was baked with (g.fC_bake:
+    a reconcentrate()d gas keeps the tables, and with them the self-broadening, of the gas it came from).
     Returns (T, P, aerr, rerr) on the reference's N x N grid (T linear over [Tmin, Tmax], P logarithmic over [Pmin, Pmax]):
     interpolated minus exact cross-section and that over the exact one.  The N*N exact values come from ONE cs_shape_points call
     (the scalar-wavenumber `shape(ν, sl, T, P, C(T,P)*P)` at N*N states), the interpolated ones from cs_table_eval.  pressure_shift:
@@ -787,7 +789,7 @@ def opacityerror(g: Gas, i: int, N: int = 50, shape=None, pressure_shift=None):
     T = np.linspace(Om.Tmin, Om.Tmax, N)
     P = 10.0 ** np.linspace(math.log10(Om.Pmin), math.log10(Om.Pmax), N)
     TT, PP = np.meshgrid(T, P, indexing="ij")
-    Pp = np.array([g.fC(t, p) * p for t, p in zip(TT.ravel(), PP.ravel())])
+    Pp = np.array([g.fC_bake(t, p) * p for t, p in zip(TT.ravel(), PP.ravel())])
     sex = shape_points(g.sl, shape or g.shape, [g.nu[int(i)]], TT.ravel(), PP.ravel(), Pp, g.dnu_cut, g.ctx, psh)[:, 0].reshape(N, N)
     sop = np.array([[g.rawsigma(t, p, int(i)) for p in P] for t in T])
     aerr = sop - sex

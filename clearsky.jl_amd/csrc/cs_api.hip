@@ -4037,6 +4037,16 @@ int cs_fluxes_discretized_members(cs_ctx *ctx, int64_t nnu, const double *nu, in
 }
 
 // ---- host-held reference objects handed over as they are ---------------------------------------------------------------------
+// x[0..n) = chebygrid(x[0], x[n-1], n) (Chebyshev extrema, ascending) to 1e-9 of the range
+static bool cheb_extrema(const double *x, int n)
+{
+    const double a = x[0], b = x[n - 1];
+    for (int i = 0; i < n; i++) {
+        const double e = (std::cos(M_PI * (n - 1 - i) / (n - 1)) + 1.0) * (b - a) / 2.0 + a;
+        if (!(std::fabs(x[i] - e) <= 1e-9 * (b - a))) return false;
+    }
+    return true;
+}
 int cs_table_upload(cs_ctx *ctx, int table_slot, int64_t nnu, const double *nu, int nT, const double *T, int nP, const double *P,
                     const double *lnsigma)
 {
@@ -4049,6 +4059,14 @@ int cs_table_upload(cs_ctx *ctx, int table_slot, int64_t nnu, const double *nu, 
         if (!(T[i] > T[i - 1])) return fail(CS_EORDER, "table temperatures must be ascending");
     for (int j = 0; j < nP; j++)
         if (!(P[j] > 0) || (j > 0 && !(P[j] > P[j - 1]))) return fail(CS_EORDER, "table pressures must be positive and ascending");
+    // the interpolant's barycentric weights (cheb_basis) are those of Chebyshev extrema: on any other grid the result would not be the
+    // interpolating polynomial.  Omega.T and Omega.P are chebygrid(Tmin, Tmax, nT) and exp.(chebygrid(ln Pmin, ln Pmax, nP)), gases.jl:57-58
+    {
+        std::vector<double> lnP(nP);
+        for (int j = 0; j < nP; j++) lnP[j] = std::log(P[j]);
+        if (!cheb_extrema(T, nT)) return fail(CS_EINVAL, "table temperatures are not the Chebyshev extrema of [%g, %g] (Omega.T, gases.jl:57)", T[0], T[nT - 1]);
+        if (!cheb_extrema(lnP.data(), nP)) return fail(CS_EINVAL, "table pressures are not the Chebyshev extrema in ln P of [%g, %g] (Omega.P, gases.jl:58)", P[0], P[nP - 1]);
+    }
     const size_t n = (size_t)nT * nP * nnu;
     for (size_t i = 0; i < n; i++)
         if (!std::isfinite(lnsigma[i])) return fail(CS_EINVAL, "ln sigma must be finite (OpacityTable stores ln(floatmin) for empty rows, gases.jl:76-80)");

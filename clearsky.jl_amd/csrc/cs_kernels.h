@@ -3000,7 +3000,7 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p, const double *__restrict
             const double bn = p.C * (sgv / muk[ke]);
             ti += (dP * p.ws[nlob - 1]) * bn;
             b1 = bn;
-            const double t = ti > 1e-6 ? ti : 1e-6;  // floor, discretized.jl:147,174
+            const double t = ti < 1e-6 ? 1e-6 : ti;  // floor, discretized.jl:147,174 (max(tau, taumin): a NaN depth stays NaN, as Julia's max keeps it)
             if (tau && live) tau[(size_t)i * nnu + j] = t;
             const double Bnext = planck(v, Tlev[i + 1]);
             Md = 0.0;
@@ -3060,7 +3060,7 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p, const double *__restrict
                 for (int n = 1; n < nlob - 1; n++) ti += (dP * p.ws[n]) * (p.C * (sg((size_t)(kl + n) * nnu + jj) / muk[kl + n]));
                 ti += (dP * p.ws[nlob - 1]) * b_hi;
                 b_hi = b_lo;
-                t = ti > 1e-6 ? ti : 1e-6;
+                t = ti < 1e-6 ? 1e-6 : ti;
             } else {
                 t = t_next;
                 if (i > 0) t_next = live ? tau[(size_t)(i - 1) * nnu + j] : 1.0;   // one layer ahead
@@ -3142,7 +3142,7 @@ __global__ __launch_bounds__(2 * NS * 64) void k_rt_streams(RtParams p, const do
             double ti = (dP * p.ws[0]) * (p.C * (sg((size_t)kl * nnu + jj) / muk[kl]));
             for (int n = 1; n < nlob - 1; n++) ti += (dP * p.ws[n]) * (p.C * (sg((size_t)(kl + n) * nnu + jj) / muk[kl + n]));
             ti += (dP * p.ws[nlob - 1]) * (p.C * (sg((size_t)(kl + nlob - 1) * nnu + jj) / muk[kl + nlob - 1]));
-            const double t = ti > 1e-6 ? ti : 1e-6;
+            const double t = ti < 1e-6 ? 1e-6 : ti;
             tl[(size_t)i * 64 + lane] = t;
             if (tau && live) tau[(size_t)i * nnu + j] = t;
         }
@@ -3745,7 +3745,7 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
             double ti = (dP * p.ws[0]) * (p.C * (sg(kl) / muk[kl]));
             for (int n = 1; n < nlob - 1; n++) ti += (dP * p.ws[n]) * (p.C * (sg(kl + n) / muk[kl + n]));
             ti += (dP * p.ws[nlob - 1]) * (p.C * (sg(kl + nlob - 1) / muk[kl + nlob - 1]));
-            const double t = ti > 1e-6 ? ti : 1e-6;
+            const double t = ti < 1e-6 ? 1e-6 : ti;
             tl[(size_t)i * 64 + lane] = t;
             if (tau && live) tau[(size_t)i * nnu + j] = t;
         }
@@ -4078,7 +4078,7 @@ __device__ __forceinline__ void flux_chunk_body(const RtParams &p, const double 
         const double bn = p.C * (sg(ke) / muk[ke]);
         ti += (dP * p.ws[nlob - 1]) * bn;
         b1 = bn;
-        const double t = ti > 1e-6 ? ti : 1e-6;  // floor, discretized.jl:147,174
+        const double t = ti < 1e-6 ? 1e-6 : ti;  // floor, discretized.jl:147,174
         if (live) tau[(size_t)i * nnu + j] = t;
         const double Bnext = planck(v, Tlev[i + 1]);
         Md = 0.0;

@@ -171,7 +171,9 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
 int cs_table_clear(cs_ctx *ctx, int table_slot);
 /* A table the HOST baked -- the reference's own Gas object (gases.jl:205-249), whatever shape! filled it: lnsigma[nnu, nT, nP]
  * column-major (nu fastest) = the knot values ln sigma of its OpacityTables (gases.jl:75-82; finite: ln(floatmin) for empty rows) on
- * T[nT] x P[nP] = Omega.T, Omega.P.  The slot then behaves exactly as one filled by cs_bake. */
+ * T[nT] x P[nP] = Omega.T, Omega.P.  The slot then behaves exactly as one filled by cs_bake.  The grid is part of the contract: the
+ * interpolant is evaluated with the barycentric weights of Chebyshev extrema, so T must be chebygrid(T[0], T[nT-1], nT) and ln P must be
+ * chebygrid(ln P[0], ln P[nP-1], nP) (gases.jl:57-58) to 1e-9 of their ranges; any other ascending grid is CS_EINVAL. */
 int cs_table_upload(cs_ctx *ctx, int table_slot, int64_t nnu, const double *nu, int nT, const double *T, int nP, const double *P,
                     const double *lnsigma);
 /* sigma(nu[i0..i0+n), T, P) of a baked table WITHOUT the concentration factor: rawsigma(g, T, P) gases.jl:256-263 */

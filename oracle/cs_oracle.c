@@ -454,7 +454,7 @@ void cso_depth_bang(double *tau, int np, const double *P, const double *beta, in
         double bn = beta[(i + 1) * (nlobatto - 1)];
         ti += (dP * ws[nlobatto - 1]) * bn;
         b1 = bn;
-        tau[i] = ti > taumin ? ti : taumin;
+        tau[i] = ti < taumin ? taumin : ti;   /* max(tau_i, taumin), :174: Julia's max keeps a NaN */
     }
 }
 

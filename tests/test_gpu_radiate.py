@@ -128,6 +128,24 @@ def test_opacityerror_vs_definition(cs, lines, ctx):
     assert np.max(np.abs(rerr)) < 0.1       # "about 1 %" with a production grid (gases.jl:7); this one is coarse
 
 
+def test_opacityerror_of_a_reconcentrated_gas(cs, lines, ctx):
+    """opacityerror's exact values take the concentration the table was baked with (its self-broadening), not the view's new one: for a
+    reconcentrate()d gas it reports the same interpolation error as for the gas it came from"""
+    nu = np.linspace(660.0, 680.0, 65)
+    Om = cs.AtmosphericDomain((180.0, 320.0), 5, (10.0, 1e5), 6)
+    g = cs.Gas(lines("CO2"), 0.3, nu, Om, ctx=ctx)
+    g2 = g.reconcentrate(0.01)
+    a, b = cs.opacityerror(g, 30, 5), cs.opacityerror(g2, 30, 5)
+    assert g2.fC(250.0, 1e4) == 0.01 and g2.fC_bake(250.0, 1e4) == 0.3
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    T, P = a[0], a[1]
+    ex = cs.voigt(float(nu[30]), lines("CO2"), T[2], P[3], 0.3 * P[3], ctx=ctx)
+    assert abs(b[2][2, 3] - (g2.rawsigma(T[2], P[3], 30) - ex)) <= 1e-13 * abs(ex)
+    other = cs.voigt(float(nu[30]), lines("CO2"), T[2], P[3], 0.01 * P[3], ctx=ctx)
+    assert abs(other - ex) > 1e-3 * abs(ex)                             # (the self-broadening matters at this point)
+
+
 def test_band_fluxes_written_into_caller_memory(cs, lines, ctx):
     """cs_column_set_flux_dst: the flux kernel's last blocks (or k_freduce) write [Fup; Fdn] straight into caller-owned device memory --
     the tensor a collective reduces in place -- bitwise what the column's own buffer gets, for every later run until the column is set up
