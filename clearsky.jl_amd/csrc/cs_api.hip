@@ -777,8 +777,11 @@ struct Interp {
                               // (0: always the 8-term one -- measured at C3 with 0.75 / 0.3 / 0: 2.61 / 2.55 / 2.52 ms)
 };
 
-static void interp_settings(const cs_ctx *ctx, Interp &itp)   // the cs_set_tuning keys an Interp view carries
+static void interp_settings(const cs_ctx *ctx, Interp &itp)   // what cs_set_matrix_cores says, and the cs_set_tuning keys an Interp view carries
 {
+    if (!ctx->matrix_nodes) itp.sep = nullptr, itp.edge = nullptr;
+    itp.sep_always = ctx->matrix_nodes == 2;
+    itp.core = ctx->matrix_core != 0;
     itp.small_mx = ctx->tune[1] != 0;
     itp.margin = ctx->tune[3] > 0 ? 0.01 * ctx->tune[3] : kChebMargin;
     itp.nsplit_levels = ctx->tune[6] > 0 ? ctx->tune[6] : 1;
@@ -1200,479 +1203,553 @@ static void fork_join(Fork *f, hipStream_t s, bool nodes = true, bool near = tru
     if (f && near && f->pending3) { (void)hipStreamWaitEvent(s, f->ev_join3, 0); f->pending3 = false; }
 }
 
-// K1 + K2 for one gas on `s`: parameters for `kn` states, then the line sum into sigma ([kn][nnu])
-void launch_gas(hipStream_t s, int shape, const GasTable &G, int64_t jrange0, int64_t jrange1, int kn, const double *Tk, const double *Pk, const double *Ppk,
-                const double *scale, int mstride /* members of a merged table: element (m, k) of Ppk / scale at m * mstride + k */,
-                const double *lrt, const double *qrefq /* state_tables(): [kn], [kn][niso] */, LineHot *hot, LineCold *cold, const double *dnu, int64_t nnu, int ntile256,
-                const int32_t *J0, const int32_t *J1, const WaveWin *win, int xtiles, Zone *zones, int2 *ranges, const double *gbound, double cut, double base,
-                const double *extra, double *sigma, int accumulate, hipEvent_t *evg,   // NULL or 6 events: after K1 (+ zones), nodes (vector unit), nodes (matrix cores), far (vector unit), sub-tile cores, far (matrix cores)
-                LineF32 *hot32 = nullptr, double far_s = 1e6, Interp itp = Interp(), ChebApply *defer = nullptr, PhScratch *ph = nullptr,
-                Fork *fork = nullptr, bool records_ready = false /* hot / cold already hold this gas at these states: zones and sums only */,
-                bool pshift = false, double flo = -INFINITY, double fhi = INFINITY, double ds = 0.0)
-{
-    fork_join(fork, s);   // (an earlier group's node kernels may still read the records this launch overwrites)
-    const bool vvh = shape == SH_VOIGT_VVH;   // shape code 5: every Voigt kernel, over records of S / R(nul, T) (k_gas_setup*_vvh); the caller runs launch_vvh
-    if (vvh) shape = SH_VOIGT;
+// One pass of one launch group over kn states: K1 (parameters), K2 (the line sum into sigma [kn][nnu]) and the step that finishes shape
+// codes 4, 5 and 6 behind it (launch_gas).  A caller states facts -- the group's final plane, whether it accumulates, base, extra,
+// clamp, the spare plane -- and launch_gas decides what the line sum of such a group is given and what follows it.  Views only: nothing
+// here owns memory.
+struct GasPass {
+    // the table, its record range and the shape
+    const GasTable *G = nullptr;
+    int shape = SH_VOIGT;           // of the line sum: codes 4, 5, 6 are SH_VOIGT with ped / vvh
+    int64_t jlo = 0, jhi = 0;       // only the lines some window can reach (windows are sorted: first tile's start .. last tile's end)
+    double cut = 25.0;
+    bool ped = false;               // shape codes 4, 6: the pedestals of the included lines [pa, pb) come off behind the line sum
+    bool vvh = false;               // shape codes 5, 6: every Voigt kernel, over records of S / R(nul, T) (k_gas_setup*_vvh); then R(nu, T) and
+    int64_t pa = 0, pb = 0, mb = 0; // the mirror term of the lines [pa, mb) (vvh_mirror_end)
     // CS_SHAPE_PSHIFT (codes 0-2): records centred at nul + delta_a P / P0, lines whose shifted centre fails the strict pre-filter (flo, fhi)
     // parked.  Every kernel reads the record's centre for the values and the cut-off tests; what is decided from TABLE positions -- the
     // windows and zones of the tiles, the interval zones of the interpolated wings, J0 / J1 and the record range -- was (caller) or is
     // (zones: ZoneArgs::ds) widened by the group's largest shift ds.  Off for such groups: the fp32 wings (far_term32 reads the table
     // position) and the matrix-core pieces (their 1/dnu^2 operand is formed from table positions, state-independent)
-    if (pshift) hot32 = nullptr;
-    // only the lines some window can reach (windows are sorted: first tile's start .. last tile's end)
-    const int64_t jlo = jrange0, jhi = std::max(jrange1, jrange0);
+    bool pshift = false;
+    double flo = -INFINITY, fhi = INFINITY, ds = 0.0;
+    // the states
+    int kn = 0;
+    const double *Tk = nullptr, *Pk = nullptr, *Ppk = nullptr, *scale = nullptr;
+    int mstride = 0;                // members of a merged table: element (m, k) of Ppk / scale at m * mstride + k
+    const double *lrt = nullptr, *qrefq = nullptr;   // state_tables(): [kn], [kn][niso]
+    const double *gbound = nullptr; // [kn] largest Lorentz width (gamma_bound)
+    // the grid and its windows
+    const double *dnu = nullptr, *nu = nullptr;      // on the device, on the host
+    int64_t nnu = 0;
+    int ntile256 = 0;
+    const int32_t *J0 = nullptr, *J1 = nullptr;      // the line kernels' windows of the 256-point tiles (tile_windows)
+    const WaveWin *win = nullptr;
+    int xtiles = 0;                 // longest XCD stretch of the far kernel's tile order, in tiles (wave_windows)
+    // the workspace
+    LineHot *hot = nullptr;
+    LineCold *cold = nullptr;
+    LineF32 *hot32 = nullptr;       // fp32 records of the far wings beyond far_s (mixed precision); NULL: fp64 throughout
+    Zone *zones = nullptr;
+    int2 *ranges = nullptr;
+    double *ped_ws = nullptr;       // ped_bytes(kn, G->L) where ped
+    // the output: sigma = (accumulate ? sigma : base + extra) + this group, then max(0, .) if clamp (codes 4, 6 where the gas's own sigma
+    // is complete: B1, bake)
+    double base = 0.0;
+    const double *extra = nullptr;
+    double *sigma = nullptr;        // the group's final plane
+    int accumulate = 0;
+    bool clamp = false;
+    double *spare = nullptr;        // the line sum of a code-5/6 group that accumulates goes here first (one that does not: sigma itself)
+    // how to run
+    double far_s = 1e6;
+    Interp itp;
+    ChebApply *defer = nullptr;
+    PhScratch *ph = nullptr;
+    Fork *fork = nullptr;
+    hipEvent_t *evg = nullptr;      // NULL or 6 events: after K1 (+ zones), nodes (vector unit), nodes (matrix cores), far (vector unit), sub-tile cores, far (matrix cores)
+    bool records_ready = false;     // hot / cold already hold this gas at these states: zones and sums only
+};
+
+static ZoneArgs zone_args(const GasPass &p, bool lor, double margin, double ds)
+{
+    ZoneArgs za;
+    za.nu = p.dnu; za.nul = p.G->nu.as<double>(); za.Tk = p.Tk; za.gbound = p.gbound; za.win = p.win; za.zones = p.zones; za.nnu = p.nnu;
+    za.lorentz = lor ? 1 : 0;
+    za.ntile = (int)((p.nnu + 63) / 64); za.K = p.kn; za.mu_min = p.G->mu_min; za.mu_max = p.G->mu_max; za.cut = p.cut; za.far_s = p.far_s;
+    za.margin = margin;
+    za.ds = ds;
+    return za;
+}
+
+// k_voigt_far as launched: fp32 wings or not, 1 / 2 / 4 waves per tile, and the Lorentz body, or the window ends left to k_voigt_edge_mx, or neither
+using FarKernel = decltype(&k_voigt_far<false, 1, false, false>);
+template <bool MIX, bool LOR, bool EDGE> static FarKernel far_kernel_split(int split)
+{
+    return split == 1 ? k_voigt_far<MIX, 1, LOR, EDGE> : (split == 2 ? k_voigt_far<MIX, 2, LOR, EDGE> : k_voigt_far<MIX, 4, LOR, EDGE>);
+}
+static FarKernel far_kernel(bool mixed, int split, bool lor, bool edge)
+{
+    if (lor) return far_kernel_split<false, true, false>(split);
+    if (mixed) return edge ? far_kernel_split<true, false, true>(split) : far_kernel_split<true, false, false>(split);
+    return edge ? far_kernel_split<false, false, true>(split) : far_kernel_split<false, false, false>(split);
+}
+
+// K2 on the far-wing machinery (Voigt, and lorentz! with its own exact body): zones, interpolated wings, k_voigt_far, window cores and ends, near-line tiers
+static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, unsigned nb_prep)
+{
+    const GasTable &G = *p.G;
+    const Interp &itp = p.itp;
+    const int kn = p.kn;
+    const int64_t nnu = p.nnu, jlo = pa.jlo, jhi = pa.jhi;
+    const bool lor = p.shape == SH_LORENTZ;
+    LineF32 *const hot32 = pa.hot32;   // (none under CS_SHAPE_PSHIFT, and no fp32 variant of the Lorentz body)
+    int accumulate = p.accumulate;
+    const int nt64 = (int)((nnu + 63) / 64);
+    // wave priority of the near-line stream's kernels (wave_prio): long grids only
+    const int near_prio = (itp.near_prio == 2 || (itp.near_prio == 0 && nt64 >= 512)) ? 3 : 0;
+    const ZoneArgs za = zone_args(p, lor, itp.margin, p.pshift ? p.ds : 0.0);
+    const unsigned nb_zones = (unsigned)(((int64_t)nt64 * kn + 255) / 256);
+    IzParams P;
+    memset(&P, 0, sizeof P);
+    unsigned nb_iz = 0;
+    const IZone *iz = nullptr;
+    int ishift = 0;
+    bool forked_here = false;   // ev_fork was recorded on the main stream after the zone launches: the near-line side stream can wait on it too
+    bool use_edge = false;   // window ends of the per-point sum on the matrix cores (k_voigt_edge_mx; with the far wings interpolated only)
+    bool fuse = false;       // ... which then also applies the interpolated wings (no k_cheb_apply launch for this group)
+    ChebApply Afuse;
+    memset(&Afuse, 0, sizeof Afuse);
+    if (itp.nlev > 0) {
+        P.nlev = itp.nlev;
+        P.nItot = itp.nItot;
+        P.l0 = itp.l0;
+        for (int l = 0; l < itp.nlev; l++) { P.itv[l] = itp.itv[l]; P.nI[l] = itp.nI[l]; P.ioff[l] = itp.ioff[l]; P.iwin[l] = itp.iwin[l]; }
+        nb_iz = (unsigned)(((int64_t)(itp.nItot - itp.ioff[itp.l0]) * kn + 255) / 256);
+    }
+    // what the matrix cores take of the interpolated sets and of the window ends: piece tables per (interval | tile, state group).  They
+    // need the zones -- which their sixteen-lanes-per-item form computes itself, as blocks of the SAME launch (k_gas_setup_mx); the
+    // one-thread-per-item form (from ~50 000 items on: BASELINE configs[4]) reads them, a launch of its own behind k_gas_setup
+    const int q0s = itp.nlev > 0 ? itp.ioff[itp.l0] : 0, ngrp_s = (kn + 15) / 16;
+    const bool use_sep_s = itp.nlev > 0 && !p.pshift && sep_in_use(itp.sep != nullptr, itp.sep_always, itp.nItot - q0s, kn, lor, hot32 != nullptr, itp.small_mx);
+    if (itp.nlev > 0 && !p.pshift) use_edge = edge_in_use(itp.edge != nullptr, itp.sep_always, nt64, kn, lor, hot32 != nullptr, jhi - jlo, itp.small_mx);
+    SepArgs sa;
+    EdgeArgs ea;
+    memset(&sa, 0, sizeof sa);
+    memset(&ea, 0, sizeof ea);
+    bool mx_one_thread = false, mx_merged = false;
+    if (use_sep_s || use_edge) {
+        sa.nodes = itp.nodes; sa.nul = G.nu.as<double>(); sa.gbound = p.gbound; sa.Tk = p.Tk; sa.iz = itp.iz; sa.out = itp.sep;
+        sa.nItot = itp.nItot; sa.q0 = q0s; sa.K = kn; sa.ngrp = ngrp_s; sa.mu_min = G.mu_min; sa.cut = p.cut; sa.min_states = itp.mx_min_states;
+        ea.nu = p.dnu; ea.nul = G.nu.as<double>(); ea.gbound = p.gbound; ea.Tk = p.Tk; ea.win = p.win; ea.zones = p.zones;
+        ea.iz = itp.iz + itp.ioff[itp.nlev - 1]; ea.out = itp.edge; ea.nnu = nnu; ea.ntile = nt64; ea.K = kn; ea.ngrp = ngrp_s;
+        ea.nI = itp.nItot; ea.ishift = 0;
+        for (int r = itp.itv[itp.nlev - 1] / 64; r > 1; r >>= 1) ea.ishift++;
+        ea.mu_min = G.mu_min; ea.cut = p.cut;
+        ea.core = (use_edge && itp.core) ? 1 : 0;
+        ea.core4 = itp.core4;
+        // sixteen lanes per item shorten the chain where the items are few (a nu-shard: 21 -> 8 us; the bench column 27 -> 9); from
+        // ~50 000 items on one thread per item has parallelism enough and sixteen times fewer threads (BASELINE configs[4]: 0.256 vs 0.276 ms)
+        const int64_t nitems = (use_sep_s ? (int64_t)(itp.nItot - q0s) * ngrp_s : 0) + (use_edge ? (int64_t)nt64 * ngrp_s : 0);
+        mx_one_thread = itp.mxzones_one_thread || nitems > 50000;   // (cs_set_tuning key 15 | 16: always)
+        // merged on short grids, where the head of the step is a chain of launch tails (1/8 of the bench column: 0.347 -> 0.340 ms);
+        // at full size the second set of searches beside 300 MB of record stores costs more than the launch it saves (1.900 -> 1.908)
+        // (cs_set_tuning key 21: 1 = never, 2 = always, A/B)
+        mx_merged = !mx_one_thread && itp.mxzones_merge != 1 && (itp.mxzones_merge == 2 || nt64 < 1024);
+    }
+    g_disp.far_split = 0; g_disp.tables = 0; g_disp.near_prio = near_prio; g_disp.streams = 0; g_disp.nodes_split = 0;
+    if (use_sep_s || use_edge) g_disp.tables = mx_merged ? 1 : (mx_one_thread ? 3 : 2);
+    if (mx_merged) {
+        const unsigned nb_sep = use_sep_s ? (unsigned)(((int64_t)(itp.nItot - q0s) * ngrp_s + 15) / 16) : 0u;
+        const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp_s + 15) / 16) : 0u;
+        CS_LAUNCH(p.vvh ? k_gas_setup_mx_vvh : k_gas_setup_mx, dim3(nb_prep + nb_zones + nb_iz + nb_sep + nb_edge), dim3(256), 0, s, nb_prep, nb_zones, nb_iz, nb_sep, pa, za, P, itp.iz, sa, ea);
+    } else {
+        CS_LAUNCH(p.vvh ? k_gas_setup_vvh : k_gas_setup, dim3(nb_prep + nb_zones + nb_iz), dim3(256), 0, s, nb_prep, nb_zones, pa, za, P, itp.iz);
+    }
+    if (p.evg && itp.nlev == 0) (void)hipEventRecord(p.evg[0], s);
+    if (itp.nlev > 0) {   // sigma = base + extra + interpolated far wings; the per-point kernels add the rest
+        const int q0 = itp.ioff[itp.l0];
+        // deferred apply: the gases of a column add their node sums into ONE F (levels an earlier gas has written accumulate)
+        const int q_acc = (p.defer && p.defer->ngas > 0 && p.defer->l0[0] < itp.nlev) ? itp.ioff[p.defer->l0[0]] : itp.nItot;
+        // short grids: four waves per (interval, state) (cs_set_tuning key 13: 0 = below 16384 waves, 1 = always, 2 = never)
+        const bool nsplit4 = itp.nodes_split == 1 || (itp.nodes_split == 0 && (int64_t)(itp.nItot - q0) * kn < 16384);
+        g_disp.nodes_split = nsplit4 ? 1 : 0;
+        const dim3 gridn(nsplit4 ? (unsigned)kn * (unsigned)(itp.nItot - q0) : (unsigned)((kn + 3) / 4) * (unsigned)(itp.nItot - q0));
+        const int ngrp = ngrp_s;
+        const bool use_sep = use_sep_s;
+        if ((use_sep || use_edge) && !mx_merged) {
+            if (mx_one_thread) {
+                const unsigned nb_sep = use_sep ? (unsigned)(((int64_t)(itp.nItot - q0) * ngrp + 255) / 256) : 0u;
+                const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp + 255) / 256) : 0u;
+                CS_LAUNCH(k_mxzones, dim3(nb_sep + nb_edge), dim3(256), 0, s, nb_sep, sa, ea);
+            } else {                        // sixteen lanes per item
+                const unsigned nb_sep = use_sep ? (unsigned)(((int64_t)(itp.nItot - q0) * ngrp + 15) / 16) : 0u;
+                const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp + 15) / 16) : 0u;
+                CS_LAUNCH(k_mxzones16, dim3(nb_sep + nb_edge), dim3(256), 0, s, nb_sep, sa, ea);
+            }
+        }
+        if (p.evg) (void)hipEventRecord(p.evg[0], s);
+        const SepZone *sepz = use_sep ? itp.sep : nullptr;
+        hipStream_t sm = s;   // main stream
+        if (p.fork && p.fork->use_nodes && p.defer && !p.evg) {
+            (void)hipEventRecord(p.fork->ev_fork, s);
+            (void)hipStreamWaitEvent(p.fork->s2, p.fork->ev_fork, 0);
+            forked_here = true;
+            g_disp.streams |= 1;
+            s = p.fork->s2;     // the two node kernels below run beside what follows them on the main stream
+        }
+#define NODES_LAUNCH(M, L_, M4, L4, S4) do { if (nsplit4) CS_LAUNCH((k_cheb_nodes<M4, L4, S4>), gridn, dim3(256), 0, s, itp.nodes, G.L, p.hot, hot32, G.nu.as<double>(), itp.iz, \
+                               itp.nItot, q0, q_acc, kn, itp.Kpad, p.cut, itp.F, sepz); \
+        else CS_LAUNCH((k_cheb_nodes<M, L_>), gridn, dim3(256), 0, s, itp.nodes, G.L, p.hot, hot32, G.nu.as<double>(), itp.iz, \
+                               itp.nItot, q0, q_acc, kn, itp.Kpad, p.cut, itp.F, sepz); } while (0)
+        if (lor)
+            NODES_LAUNCH(false, true, false, true, 4);
+        else if (hot32)
+            NODES_LAUNCH(true, false, true, false, 4);
+        else
+            NODES_LAUNCH(false, false, false, false, 4);
+        if (p.evg) (void)hipEventRecord(p.evg[1], s);
+        if (use_sep) {
+            const int nq = itp.nItot - q0;
+            // the largest interval sizes in use are shared by the four waves of a block -- itp.nsplit_levels of them (all sizes on a
+            // grid too short to fill the chip with one (interval, group) per wave)
+            int nsplit = 0;
+            for (int l = itp.l0; l < std::min(itp.nlev, itp.l0 + itp.nsplit_levels); l++) nsplit += itp.nI[l];
+            if (!mx_big(nq, kn, 2048) || nsplit > nq) nsplit = nq;
+            const unsigned nblk_mx = (unsigned)(nsplit * ngrp) + (unsigned)(((int64_t)(nq - nsplit) * ngrp + 3) / 4);
+            MxFar mf;
+            memset(&mf, 0, sizeof mf);
+            mf.nlev = itp.nlev;
+            for (int l = 0; l < itp.nlev; l++) { mf.ioff[l] = itp.ioff[l]; mf.nfar[l] = itp.nfar[l] > 0 ? itp.nfar[l] : CS_NC; }
+            mf.ioff[itp.nlev] = itp.nItot;
+            mf.R = (itp.far_shared_full && nsplit == nq) ? nullptr : itp.R;
+            if (itp.R && !mf.R) g_disp.flags |= CS_DF_FAR64_SHARED;
+            CS_LAUNCH(k_cheb_nodes_mx, dim3(nblk_mx), dim3(256), 0, s, itp.nodes, G.L, p.hot, itp.sep, itp.nItot, q0, nsplit, kn,
+                               itp.Kpad, ngrp, itp.F, itp.iz, mf);
+        }
+        if (s != sm) {
+            (void)hipEventRecord(p.fork->ev_join, s);
+            p.fork->pending = true;
+            s = sm;
+        }
+        if (p.evg) (void)hipEventRecord(p.evg[2], s);
+        ChebApply A0;
+        ChebApply &A = p.defer ? *p.defer : A0;
+        if (!p.defer) A.ngas = 0;
+        A.nlev = itp.nlev;
+        for (int l = 0; l < itp.nlev; l++) {
+            A.shift[l] = 0;
+            for (int r = itp.itv[l] / 64; r > 1; r >>= 1) A.shift[l]++;
+            A.ioff[l] = itp.ioff[l];
+            A.nc[l] = CS_NC;
+            A.noff[l] = itp.ioff[l] * CS_NC;
+            A.Cm[l] = itp.Cm[l];
+        }
+        fuse = p.defer && itp.fuse_apply && use_edge && p.defer->ngas == 0;   // (then k_voigt_edge_mx below carries this group's node sums to the grid)
+        if (fuse) {
+            Afuse = A;
+            Afuse.ngas = 1;
+            Afuse.l0[0] = itp.l0;
+            Afuse.F[0] = itp.F;
+        } else if (p.defer && A.ngas > 0) {
+            A.l0[0] = std::min(A.l0[0], itp.l0);   // same F: the sum over the gases so far
+        } else {
+            A.l0[A.ngas] = itp.l0;
+            A.F[A.ngas++] = itp.F;
+        }
+        if (!p.defer) {   // sigma = base + extra + interpolated far wings now; the per-point kernels add the rest
+            launch_apply_cascade(s, A, itp.Rc, itp.itv, itp.nI, itp.cascade, itp.Kpad, nnu, kn, p.base, p.extra, p.sigma, accumulate);
+            accumulate = 1;
+        }               // (deferred: the caller applies the node sums of all its gases in one launch, after the last gas)
+        const int low = itp.nlev - 1;
+        iz = itp.iz + itp.ioff[low];
+        ishift = A.shift[low];
+    } else if (p.evg) {
+        (void)hipEventRecord(p.evg[1], s);
+        (void)hipEventRecord(p.evg[2], s);
+    }
+    g_line_kernel = 0;
+
+    // waves per tile: enough waves to fill 256 CUs x 32 wave slots about 4 times over
+    const int64_t nwave = (int64_t)nt64 * kn;
+    int split = nwave >= 16384 ? 1 : (nwave >= 4096 ? 2 : 4);   // (re-tuned with the far wings interpolated: waves are 3x shorter)
+    if (itp.far_split == 1 || itp.far_split == 2 || itp.far_split == 4) split = itp.far_split;   // (cs_set_tuning key 22, A/B)
+    g_disp.far_split = split;
+    const int nblk_s = (nt64 * split + 3) / 4;
+    // 8 x (blocks of the longest XCD stretch): XCD-aware tile mapping (tile_block); xtiles is a multiple of 4 tiles
+    const dim3 grid_s((unsigned)(8 * (p.xtiles * split / 4)), kn);
+    const EdgeZone *edgez = use_edge ? itp.edge : nullptr;
+    // near-line kernels and the sub-tile cores on a side stream, into their own plane (Voigt only; not while profiling)
+    const bool near_fork = !lor && p.fork && p.fork->use_near && p.fork->sigma2 && p.defer && !p.evg;
+    double *zero2 = nullptr;   // (the far kernel can clear the plane itself: unused since k_voigt_sub adds to it beside k_voigt_far)
+    if (near_fork) {   // zones, records and piece tables are written: the side stream may start
+        if (forked_here) {   // (nothing was enqueued on the main stream since that record: one event serves both side streams)
+            (void)hipStreamWaitEvent(p.fork->s3, p.fork->ev_fork, 0);
+        } else {
+            (void)hipEventRecord(p.fork->ev_fork3, s);
+            (void)hipStreamWaitEvent(p.fork->s3, p.fork->ev_fork3, 0);
+        }
+        // the plane's first writer of the step defines all of it: k_voigt_sub where it runs (sums where a tile has a core, zeros
+        // elsewhere: cs_set_tuning key 19 = 1 keeps the memset for A/B), else a memset
+        const bool sub_here = use_edge && itp.core;
+        const bool sub_assigns = sub_here && !p.fork->zeroed && !itp.near_memset;
+        if (!p.fork->zeroed && !sub_assigns) {
+            (void)hipMemsetAsync(p.fork->sigma2, 0, (size_t)kn * nnu * sizeof(double), p.fork->s3);
+            g_disp.flags |= CS_DF_NEAR_MEMSET;
+        }
+        g_disp.streams |= 2;
+        p.fork->zeroed = true;
+        if (sub_here)
+            CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, p.fork->s3, p.dnu, nnu, G.L, p.hot,
+                      G.nu.as<double>(), p.zones, itp.edge, nt64, kn, p.cut, p.fork->sigma2, reinterpret_cast<unsigned *>(p.ranges), near_prio, sub_assigns ? 1 : 0);
+    }
+    CS_LAUNCH(far_kernel(hot32 != nullptr, split, lor, use_edge), grid_s, dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, hot32, G.nu.as<double>(), p.win, p.zones,
+              nt64, nblk_s, p.cut, p.base, p.extra, p.sigma, accumulate, p.ranges, iz, itp.nItot, ishift, edgez, zero2);
+    if (p.evg) (void)hipEventRecord(p.evg[3], s);
+    if (use_edge && itp.core && !near_fork)   // the window cores of the groups whose series radius is short: pairs inside it (the rest: k_voigt_edge_mx)
+        CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, s, p.dnu, nnu, G.L, p.hot, G.nu.as<double>(), p.zones,
+                           itp.edge, nt64, kn, p.cut, p.sigma, reinterpret_cast<unsigned *>(p.ranges), near_prio, 0);
+    auto launch_near = [&](hipStream_t sn, double *out) {
+        const int ngrpn = (nt64 + CS_NEAR_R - 1) / CS_NEAR_R;   // near kernels: one wave = CS_NEAR_R consecutive tiles ...
+        // ... times nrep, one after the other: where the table is sparse against the grid (few tiles have candidates at all) and the
+        // grid long enough to keep the chip full with an eighth of the waves, and on every grid of half a million (tile, state) waves
+        // and more -- there the launch of the waves is what a near-line kernel costs first (BASELINE configs[4]: 7.9e5 waves per
+        // tier, step 7.06 -> 6.85 ms with eight tiles per wave; the bench column, 9.5e4 waves: a tie with two, a loss with four)
+        const int64_t nwaves_near = (int64_t)ngrpn * kn;
+        const int nrep = (nwaves_near >= 524288 || (jhi - jlo < (int64_t)nt64 * 2 && nwaves_near >= 262144)) ? 8 : 1;
+        const dim3 gridq((unsigned)(((ngrpn + nrep - 1) / nrep + 3) / 4), kn);
+        if (nrep == 1 && itp.near_both) {   // both tiers in one launch (one tile per wave; cs_set_tuning key 16 | 4: two launches, A/B)
+            CS_LAUNCH(k_voigt_near_both, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, p.cut, out, p.ranges, near_prio);
+            g_near_launches += 1;
+            return;
+        }
+        g_near_launches += 2;
+        CS_LAUNCH(k_voigt_near<0>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, ngrpn, nrep, p.cut, out, p.ranges, near_prio);
+        CS_LAUNCH(k_voigt_near<1>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, ngrpn, nrep, p.cut, out, p.ranges, near_prio);
+    };
+    if (near_fork) {   // the near kernels need the hand-off words of both k_voigt_far (main stream) and k_voigt_sub (theirs)
+        (void)hipEventRecord(p.fork->ev_far3, s);
+        (void)hipStreamWaitEvent(p.fork->s3, p.fork->ev_far3, 0);
+        launch_near(p.fork->s3, p.fork->sigma2);
+        (void)hipEventRecord(p.fork->ev_join3, p.fork->s3);
+        p.fork->pending3 = true;
+        p.fork->live = true;
+    }
+    if (p.evg) (void)hipEventRecord(p.evg[4], s);
+    if (use_edge)
+    {
+        if (fuse) fork_join(p.fork, s);   // (it reads F)
+        if (mx_big(nt64, kn, 1024) && itp.edge_phases && itp.tnodes) g_disp.flags |= CS_DF_TNODES;
+        if (mx_big(nt64, kn, 1024))
+            CS_LAUNCH(k_voigt_edge_mx<1>, dim3((unsigned)((nt64 + 3) / 4), (unsigned)((kn + 15) / 16)), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.win,
+                      itp.edge, nt64, kn, p.cut, p.sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), itp.edge_phases,
+                      itp.edge_phases ? itp.tnodes : nullptr, itp.tC);
+        else   // short grid: four waves per (tile, group)
+            CS_LAUNCH(k_voigt_edge_mx<4>, dim3((unsigned)nt64, (unsigned)((kn + 15) / 16)), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.win,
+                      itp.edge, nt64, kn, p.cut, p.sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), itp.edge_phases,
+                      (const double *)nullptr, (const double *)nullptr);   // (the 16-node path in the shared form: 16 more matrix steps per WAVE, no gain measured)
+    }
+    if (p.evg) (void)hipEventRecord(p.evg[5], s);
+    if (!lor && !near_fork) launch_near(s, p.sigma);
+}
+
+static void launch_line_sum(hipStream_t s, const GasPass &p);
+
+// PHCO2 fast path (k_phco2): region-uniform far lines with factorised chi; needs the cut-off edges inside region 3 and the
+// near zone inside the chi = 1 core (phco2_fast_ok), else the generic kernel
+static void line_sum_phco2(hipStream_t s, const GasPass &p, PrepArgs pa, unsigned nb_prep)
+{
+    const GasTable &G = *p.G;
+    const int kn = p.kn;
+    const int64_t nnu = p.nnu, jlo = pa.jlo, jhi = pa.jhi;
+    int accumulate = p.accumulate;
+    const int nt64 = (int)((nnu + 63) / 64);
+    pa.phfac = p.ph->fac.as<double>();
+    pa.nu_c = p.ph->nu_c;
+    const ZoneArgs za = zone_args(p, false, kChebMargin, 0.0);
+    const unsigned nb_zones = (unsigned)(((int64_t)nt64 * kn + 255) / 256);
+    IzParams P;
+    memset(&P, 0, sizeof P);
+    CS_LAUNCH(k_gas_setup, dim3(nb_prep + nb_zones), dim3(256), 0, s, nb_prep, nb_zones, pa, za, P, (IZone *)nullptr);
+    const bool use_itp = ph_interp_ready(p.ph, p.dnu, nnu, p.cut, kn, s);
+    const PhScratch::Grid &pg = p.ph->grid;
+    PhArgs pw;
+    pw.nu = p.dnu; pw.nul = G.nu.as<double>(); pw.nnu = nnu; pw.ntile = nt64; pw.J0 = (int32_t)jlo; pw.J1 = (int32_t)jhi; pw.cut = p.cut;
+    pw.tol = 1e-9 * (std::max(std::fabs(p.ph->nu_lo), std::fabs(p.ph->nu_hi)) + p.cut + 1.0);
+    pw.out = p.ph->win.as<PhWin>();
+    PhIArgs ia;
+    memset(&ia, 0, sizeof ia);
+    if (use_itp) {
+        ia.nu = p.dnu; ia.nul = pw.nul; ia.nnu = nnu; ia.J0 = pw.J0; ia.J1 = pw.J1; ia.cut = p.cut; ia.tol = pw.tol; ia.margin = p.ph->margin;
+        ia.lv = pg.lv;
+        ia.out = p.ph->piw.as<PhIWin>();
+    }
+    // the pairs within 3 cm^-1 (chi = 1: plain Voigt, every near-line pair among them) through the Voigt kernels, where their
+    // near-line hand-off takes this table (check_near_density; else k_phco2's own core loop)
+    bool inner = false;
+    if (p.ranges && !p.ph->own_core) {
+        const PhScratch::Dens *hit = nullptr;
+        for (auto &d : p.ph->dens) if (d.tab == (const void *)&G && d.gen == G.generation && d.grid == p.ph->grid_id) hit = &d;
+        if (!hit) {
+            if (p.ph->dens.size() >= 8) p.ph->dens.erase(p.ph->dens.begin());
+            p.ph->dens.push_back({(const void *)&G, G.generation, p.ph->grid_id, check_near_density(G, p.ph->nu_hi, p.ph->max_span, 3.0) == CS_OK});
+            hit = &p.ph->dens.back();
+        }
+        inner = hit->ok && p.ph->win3.reserve((size_t)(nt64 + 3) * sizeof(WaveWin)) == hipSuccess &&
+                p.ph->zones3.reserve((size_t)kn * nt64 * sizeof(Zone)) == hipSuccess;
+    }
+    WwArgs wa;
+    memset(&wa, 0, sizeof wa);
+    if (inner) {
+        wa.nu = p.dnu; wa.nul = pw.nul; wa.nnu = nnu; wa.ntile = nt64; wa.J0 = pw.J0; wa.J1 = pw.J1; wa.cut = 3.0;
+        wa.sparse = (jhi - jlo) * 8 < nnu ? 1 : 0;
+        wa.out = p.ph->win3.as<WaveWin>();
+    }
+    const unsigned nb_tiles = (unsigned)((nt64 + 255) / 256), nb_itv = (unsigned)((ia.lv.nItot + 255) / 256);
+    CS_LAUNCH(k_phwin, dim3(nb_tiles + nb_itv + (inner ? nb_tiles : 0u)), dim3(256), 0, s, nb_tiles, nb_itv, pw, ia, wa);
+    if (p.evg) (void)hipEventRecord(p.evg[0], s);
+    const PhIWin *piw = nullptr;
+    PhFine fine;
+    memset(&fine, 0, sizeof fine);
+    if (use_itp) {   // far wings of the region-uniform lines: node sums, carried to the grid (sigma = base + extra + them)
+        const int Kpad = cheb_kpad(kn);
+        CS_LAUNCH(k_phco2_nodes, dim3((unsigned)pg.nslots * (unsigned)((kn + 3) / 4)), dim3(256), 0, s, pg.nodes.as<double>(), G.L, p.hot,
+                  p.ph->fac.as<double>(), p.ph->nu_c, p.ph->piw.as<PhIWin>(), pg.lv, pg.vl, kn, Kpad, p.Tk, p.cut, p.gbound, G.mu_min, G.mu_max, p.far_s,
+                  p.ph->F.as<double>());
+        if (p.evg) (void)hipEventRecord(p.evg[1], s);
+        ChebApply A;
+        memset(&A, 0, sizeof A);
+        A.nlev = pg.vl.nv; A.ngas = 1; A.F[0] = p.ph->F.as<double>(); A.l0[0] = 0;
+        for (int v = 0; v < pg.vl.nv; v++) {
+            for (int r = pg.lv.itv[pg.vl.rl[v]] / 64; r > 1; r >>= 1) A.shift[v]++;
+            A.ioff[v] = pg.vl.boff[v];
+            A.nc[v] = pg.vl.nc[v];
+            A.noff[v] = pg.vl.noff[v];
+            A.Cm[v] = pg.Cm[v].as<double>();
+        }
+        launch_apply(s, A, Kpad, nnu, kn, p.base, p.extra, p.sigma, accumulate, true);
+        accumulate = 1;
+        if (p.evg) (void)hipEventRecord(p.evg[2], s);
+        piw = p.ph->piw.as<PhIWin>();
+        fine = pg.fine;
+    } else if (p.evg) { (void)hipEventRecord(p.evg[1], s); (void)hipEventRecord(p.evg[2], s); }
+    g_line_kernel = 2;
+    CS_LAUNCH(k_phco2, dim3((unsigned)((nt64 + 3) / 4), kn), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.cold, p.ph->fac.as<double>(), p.ph->nu_c,
+                       p.ph->win.as<PhWin>(), p.zones, nt64, p.cut, p.Tk, kn, p.base, p.extra, p.sigma, accumulate, piw, fine, inner ? 1 : 0);
+    if (p.evg) (void)hipEventRecord(p.evg[3], s);
+    if (inner) {
+        const int nt4 = (nt64 + 3) / 4 * 4, per = ((nt4 / 4 + 7) / 8) * 4;   // (wave_windows' stretch length)
+        GasPass in = p;   // same table, record range, states, records, grid, ranges and plane: the zones and sums of a Voigt pass with its own windows
+        in.shape = SH_VOIGT; in.cut = 3.0; in.win = p.ph->win3.as<WaveWin>(); in.xtiles = per; in.zones = p.ph->zones3.as<Zone>();
+        in.base = 0.0; in.extra = nullptr; in.accumulate = 1; in.evg = nullptr; in.hot32 = nullptr; in.itp = Interp();
+        in.defer = nullptr; in.ph = nullptr; in.fork = nullptr; in.records_ready = true;
+        in.flo = -INFINITY; in.fhi = INFINITY;   // (no K1 in this pass: nothing reads them)
+        launch_line_sum(s, in);
+        g_line_kernel = 2;   // (the group's far lines were k_phco2's; the inner pass only took the pairs within 3 cm^-1)
+    }
+    if (p.evg) { (void)hipEventRecord(p.evg[4], s); (void)hipEventRecord(p.evg[5], s); }
+}
+
+// every other shape, CS_SHAPE_PSHIFT Doppler and PHCO2 off its fast path: k_linesum over the windows of the 256-point tiles
+static void line_sum_generic(hipStream_t s, const GasPass &p, const PrepArgs &pa, unsigned nb_prep)
+{
+    if (nb_prep > 0) {
+        ZoneArgs za;
+        IzParams P;
+        memset(&za, 0, sizeof za);
+        memset(&P, 0, sizeof P);
+        CS_LAUNCH(k_gas_setup, dim3(nb_prep), dim3(256), 0, s, nb_prep, 0u, pa, za, P, (IZone *)nullptr);
+    }
+    if (p.evg) { (void)hipEventRecord(p.evg[0], s); (void)hipEventRecord(p.evg[1], s); (void)hipEventRecord(p.evg[2], s); }
+    g_line_kernel = 1;
+    launch_linesum_shape(p.shape, dim3(p.ntile256, p.kn), s, p.dnu, p.nnu, p.G->L, p.hot, p.cold, p.J0, p.J1, p.cut, p.Tk, p.base, p.extra, p.sigma,
+                         p.accumulate);
+    if (p.evg) { (void)hipEventRecord(p.evg[3], s); (void)hipEventRecord(p.evg[4], s); (void)hipEventRecord(p.evg[5], s); }
+}
+
+// K1 + K2 for one gas on `s`: parameters for `kn` states, then the line sum into sigma ([kn][nnu])
+static void launch_line_sum(hipStream_t s, const GasPass &p)
+{
+    fork_join(p.fork, s);   // (an earlier group's node kernels may still read the records this launch overwrites)
+    const GasTable &G = *p.G;
+    const int64_t jlo = p.jlo, jhi = std::max(p.jhi, p.jlo);
     PrepArgs pa;
-    pa.shape = shape; pa.K = kn; pa.g = G.dev(); pa.jlo = jlo; pa.jhi = jhi;
-    pa.Tk = Tk; pa.Pk = Pk; pa.Ppk = Ppk; pa.scale = scale; pa.mstride = mstride; pa.lrt = lrt; pa.qrefq = qrefq; pa.niso = G.niso; pa.hot = hot; pa.cold = cold; pa.hot32 = shape == SH_VOIGT ? hot32 : nullptr;
+    pa.shape = p.shape; pa.K = p.kn; pa.g = G.dev(); pa.jlo = jlo; pa.jhi = jhi;
+    pa.Tk = p.Tk; pa.Pk = p.Pk; pa.Ppk = p.Ppk; pa.scale = p.scale; pa.mstride = p.mstride; pa.lrt = p.lrt; pa.qrefq = p.qrefq; pa.niso = G.niso; pa.hot = p.hot; pa.cold = p.cold;
+    pa.hot32 = (p.shape == SH_VOIGT && !p.pshift) ? p.hot32 : nullptr;   // (far_term32 reads the table position: no fp32 wings for shifted lines)
     pa.phfac = nullptr;
     pa.nu_c = 0.0;
-    pa.pshift = pshift ? 1 : 0; pa.flo = flo; pa.fhi = fhi;
-    const unsigned nb_prep = records_ready ? 0u : (unsigned)((jhi - jlo + 255) / 256) * (unsigned)((kn + CS_PREP_KC - 1) / CS_PREP_KC);   // (line block, chunk of states)
-    const bool lor = shape == SH_LORENTZ;   // lorentz! runs on the same far-wing machinery with its own (exact) body
-    if (shape == SH_VOIGT || lor) {
-        if (lor) hot32 = nullptr;           // (no fp32 variant of the Lorentz body)
-        const int nt64 = (int)((nnu + 63) / 64);
-        // wave priority of the near-line stream's kernels (wave_prio): long grids only
-        const int near_prio = (itp.near_prio == 2 || (itp.near_prio == 0 && nt64 >= 512)) ? 3 : 0;
-        ZoneArgs za;
-        za.nu = dnu; za.nul = G.nu.as<double>(); za.Tk = Tk; za.gbound = gbound; za.win = win; za.zones = zones; za.nnu = nnu;
-        za.lorentz = lor ? 1 : 0;
-        za.ntile = nt64; za.K = kn; za.mu_min = G.mu_min; za.mu_max = G.mu_max; za.cut = cut; za.far_s = far_s;
-        za.margin = itp.margin;
-        za.ds = pshift ? ds : 0.0;
-        const unsigned nb_zones = (unsigned)(((int64_t)nt64 * kn + 255) / 256);
-        IzParams P;
-        memset(&P, 0, sizeof P);
-        unsigned nb_iz = 0;
-        const IZone *iz = nullptr;
-        int ishift = 0;
-        bool forked_here = false;   // ev_fork was recorded on the main stream after the zone launches: the near-line side stream can wait on it too
-        bool use_edge = false;   // window ends of the per-point sum on the matrix cores (k_voigt_edge_mx; with the far wings interpolated only)
-        bool fuse = false;       // ... which then also applies the interpolated wings (no k_cheb_apply launch for this group)
-        ChebApply Afuse;
-        memset(&Afuse, 0, sizeof Afuse);
-        if (itp.nlev > 0) {
-            P.nlev = itp.nlev;
-            P.nItot = itp.nItot;
-            P.l0 = itp.l0;
-            for (int l = 0; l < itp.nlev; l++) { P.itv[l] = itp.itv[l]; P.nI[l] = itp.nI[l]; P.ioff[l] = itp.ioff[l]; P.iwin[l] = itp.iwin[l]; }
-            nb_iz = (unsigned)(((int64_t)(itp.nItot - itp.ioff[itp.l0]) * kn + 255) / 256);
-        }
-        // what the matrix cores take of the interpolated sets and of the window ends: piece tables per (interval | tile, state group).  They
-        // need the zones -- which their sixteen-lanes-per-item form computes itself, as blocks of the SAME launch (k_gas_setup_mx); the
-        // one-thread-per-item form (from ~50 000 items on: BASELINE configs[4]) reads them, a launch of its own behind k_gas_setup
-        const int q0s = itp.nlev > 0 ? itp.ioff[itp.l0] : 0, ngrp_s = (kn + 15) / 16;
-        const bool use_sep_s = itp.nlev > 0 && !pshift && sep_in_use(itp.sep != nullptr, itp.sep_always, itp.nItot - q0s, kn, lor, hot32 != nullptr, itp.small_mx);
-        if (itp.nlev > 0 && !pshift) use_edge = edge_in_use(itp.edge != nullptr, itp.sep_always, nt64, kn, lor, hot32 != nullptr, jhi - jlo, itp.small_mx);
-        SepArgs sa;
-        EdgeArgs ea;
-        memset(&sa, 0, sizeof sa);
-        memset(&ea, 0, sizeof ea);
-        bool mx_one_thread = false, mx_merged = false;
-        if (use_sep_s || use_edge) {
-            sa.nodes = itp.nodes; sa.nul = G.nu.as<double>(); sa.gbound = gbound; sa.Tk = Tk; sa.iz = itp.iz; sa.out = itp.sep;
-            sa.nItot = itp.nItot; sa.q0 = q0s; sa.K = kn; sa.ngrp = ngrp_s; sa.mu_min = G.mu_min; sa.cut = cut; sa.min_states = itp.mx_min_states;
-            ea.nu = dnu; ea.nul = G.nu.as<double>(); ea.gbound = gbound; ea.Tk = Tk; ea.win = win; ea.zones = zones;
-            ea.iz = itp.iz + itp.ioff[itp.nlev - 1]; ea.out = itp.edge; ea.nnu = nnu; ea.ntile = nt64; ea.K = kn; ea.ngrp = ngrp_s;
-            ea.nI = itp.nItot; ea.ishift = 0;
-            for (int r = itp.itv[itp.nlev - 1] / 64; r > 1; r >>= 1) ea.ishift++;
-            ea.mu_min = G.mu_min; ea.cut = cut;
-            ea.core = (use_edge && itp.core) ? 1 : 0;
-            ea.core4 = itp.core4;
-            // sixteen lanes per item shorten the chain where the items are few (a nu-shard: 21 -> 8 us; the bench column 27 -> 9); from
-            // ~50 000 items on one thread per item has parallelism enough and sixteen times fewer threads (BASELINE configs[4]: 0.256 vs 0.276 ms)
-            const int64_t nitems = (use_sep_s ? (int64_t)(itp.nItot - q0s) * ngrp_s : 0) + (use_edge ? (int64_t)nt64 * ngrp_s : 0);
-            mx_one_thread = itp.mxzones_one_thread || nitems > 50000;   // (cs_set_tuning key 15 | 16: always)
-            // merged on short grids, where the head of the step is a chain of launch tails (1/8 of the bench column: 0.347 -> 0.340 ms);
-            // at full size the second set of searches beside 300 MB of record stores costs more than the launch it saves (1.900 -> 1.908)
-            // (cs_set_tuning key 21: 1 = never, 2 = always, A/B)
-            mx_merged = !mx_one_thread && itp.mxzones_merge != 1 && (itp.mxzones_merge == 2 || nt64 < 1024);
-        }
-        g_disp.far_split = 0; g_disp.tables = 0; g_disp.near_prio = near_prio; g_disp.streams = 0; g_disp.nodes_split = 0;
-        if (use_sep_s || use_edge) g_disp.tables = mx_merged ? 1 : (mx_one_thread ? 3 : 2);
-        if (mx_merged) {
-            const unsigned nb_sep = use_sep_s ? (unsigned)(((int64_t)(itp.nItot - q0s) * ngrp_s + 15) / 16) : 0u;
-            const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp_s + 15) / 16) : 0u;
-            CS_LAUNCH(vvh ? k_gas_setup_mx_vvh : k_gas_setup_mx, dim3(nb_prep + nb_zones + nb_iz + nb_sep + nb_edge), dim3(256), 0, s, nb_prep, nb_zones, nb_iz, nb_sep, pa, za, P, itp.iz, sa, ea);
-        } else {
-            CS_LAUNCH(vvh ? k_gas_setup_vvh : k_gas_setup, dim3(nb_prep + nb_zones + nb_iz), dim3(256), 0, s, nb_prep, nb_zones, pa, za, P, itp.iz);
-        }
-        if (evg && itp.nlev == 0) (void)hipEventRecord(evg[0], s);
-        if (itp.nlev > 0) {   // sigma = base + extra + interpolated far wings; the per-point kernels add the rest
-            const int q0 = itp.ioff[itp.l0];
-            // deferred apply: the gases of a column add their node sums into ONE F (levels an earlier gas has written accumulate)
-            const int q_acc = (defer && defer->ngas > 0 && defer->l0[0] < itp.nlev) ? itp.ioff[defer->l0[0]] : itp.nItot;
-            // short grids: four waves per (interval, state) (cs_set_tuning key 13: 0 = below 16384 waves, 1 = always, 2 = never)
-            const bool nsplit4 = itp.nodes_split == 1 || (itp.nodes_split == 0 && (int64_t)(itp.nItot - q0) * kn < 16384);
-            g_disp.nodes_split = nsplit4 ? 1 : 0;
-            const dim3 gridn(nsplit4 ? (unsigned)kn * (unsigned)(itp.nItot - q0) : (unsigned)((kn + 3) / 4) * (unsigned)(itp.nItot - q0));
-            const int ngrp = ngrp_s;
-            const bool use_sep = use_sep_s;
-            if ((use_sep || use_edge) && !mx_merged) {
-                if (mx_one_thread) {
-                    const unsigned nb_sep = use_sep ? (unsigned)(((int64_t)(itp.nItot - q0) * ngrp + 255) / 256) : 0u;
-                    const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp + 255) / 256) : 0u;
-                    CS_LAUNCH(k_mxzones, dim3(nb_sep + nb_edge), dim3(256), 0, s, nb_sep, sa, ea);
-                } else {                        // sixteen lanes per item
-                    const unsigned nb_sep = use_sep ? (unsigned)(((int64_t)(itp.nItot - q0) * ngrp + 15) / 16) : 0u;
-                    const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp + 15) / 16) : 0u;
-                    CS_LAUNCH(k_mxzones16, dim3(nb_sep + nb_edge), dim3(256), 0, s, nb_sep, sa, ea);
-                }
-            }
-            if (evg) (void)hipEventRecord(evg[0], s);
-            const SepZone *sepz = use_sep ? itp.sep : nullptr;
-            hipStream_t sm = s;   // main stream
-            if (fork && fork->use_nodes && defer && !evg) {
-                (void)hipEventRecord(fork->ev_fork, s);
-                (void)hipStreamWaitEvent(fork->s2, fork->ev_fork, 0);
-                forked_here = true;
-                g_disp.streams |= 1;
-                s = fork->s2;     // the two node kernels below run beside what follows them on the main stream
-            }
-#define NODES_LAUNCH(M, L_, M4, L4, S4) do { if (nsplit4) CS_LAUNCH((k_cheb_nodes<M4, L4, S4>), gridn, dim3(256), 0, s, itp.nodes, G.L, hot, hot32, G.nu.as<double>(), itp.iz, \
-                                   itp.nItot, q0, q_acc, kn, itp.Kpad, cut, itp.F, sepz); \
-            else CS_LAUNCH((k_cheb_nodes<M, L_>), gridn, dim3(256), 0, s, itp.nodes, G.L, hot, hot32, G.nu.as<double>(), itp.iz, \
-                                   itp.nItot, q0, q_acc, kn, itp.Kpad, cut, itp.F, sepz); } while (0)
-            if (lor)
-                NODES_LAUNCH(false, true, false, true, 4);
-            else if (hot32)
-                NODES_LAUNCH(true, false, true, false, 4);
-            else
-                NODES_LAUNCH(false, false, false, false, 4);
-            if (evg) (void)hipEventRecord(evg[1], s);
-            if (use_sep) {
-                const int nq = itp.nItot - q0;
-                // the largest interval sizes in use are shared by the four waves of a block -- itp.nsplit_levels of them (all sizes on a
-                // grid too short to fill the chip with one (interval, group) per wave)
-                int nsplit = 0;
-                for (int l = itp.l0; l < std::min(itp.nlev, itp.l0 + itp.nsplit_levels); l++) nsplit += itp.nI[l];
-                if (!mx_big(nq, kn, 2048) || nsplit > nq) nsplit = nq;
-                const unsigned nblk_mx = (unsigned)(nsplit * ngrp) + (unsigned)(((int64_t)(nq - nsplit) * ngrp + 3) / 4);
-                MxFar mf;
-                memset(&mf, 0, sizeof mf);
-                mf.nlev = itp.nlev;
-                for (int l = 0; l < itp.nlev; l++) { mf.ioff[l] = itp.ioff[l]; mf.nfar[l] = itp.nfar[l] > 0 ? itp.nfar[l] : CS_NC; }
-                mf.ioff[itp.nlev] = itp.nItot;
-                mf.R = (itp.far_shared_full && nsplit == nq) ? nullptr : itp.R;
-                if (itp.R && !mf.R) g_disp.flags |= CS_DF_FAR64_SHARED;
-                CS_LAUNCH(k_cheb_nodes_mx, dim3(nblk_mx), dim3(256), 0, s, itp.nodes, G.L, hot, itp.sep, itp.nItot, q0, nsplit, kn,
-                                   itp.Kpad, ngrp, itp.F, itp.iz, mf);
-            }
-            if (s != sm) {
-                (void)hipEventRecord(fork->ev_join, s);
-                fork->pending = true;
-                s = sm;
-            }
-            if (evg) (void)hipEventRecord(evg[2], s);
-            ChebApply A0;
-            ChebApply &A = defer ? *defer : A0;
-            if (!defer) A.ngas = 0;
-            A.nlev = itp.nlev;
-            for (int l = 0; l < itp.nlev; l++) {
-                A.shift[l] = 0;
-                for (int r = itp.itv[l] / 64; r > 1; r >>= 1) A.shift[l]++;
-                A.ioff[l] = itp.ioff[l];
-                A.nc[l] = CS_NC;
-                A.noff[l] = itp.ioff[l] * CS_NC;
-                A.Cm[l] = itp.Cm[l];
-            }
-            fuse = defer && itp.fuse_apply && use_edge && defer->ngas == 0;   // (then k_voigt_edge_mx below carries this group's node sums to the grid)
-            if (fuse) {
-                Afuse = A;
-                Afuse.ngas = 1;
-                Afuse.l0[0] = itp.l0;
-                Afuse.F[0] = itp.F;
-            } else if (defer && A.ngas > 0) {
-                A.l0[0] = std::min(A.l0[0], itp.l0);   // same F: the sum over the gases so far
-            } else {
-                A.l0[A.ngas] = itp.l0;
-                A.F[A.ngas++] = itp.F;
-            }
-            if (!defer) {   // sigma = base + extra + interpolated far wings now; the per-point kernels add the rest
-                launch_apply_cascade(s, A, itp.Rc, itp.itv, itp.nI, itp.cascade, itp.Kpad, nnu, kn, base, extra, sigma, accumulate);
-                accumulate = 1;
-            }               // (deferred: the caller applies the node sums of all its gases in one launch, after the last gas)
-            const int low = itp.nlev - 1;
-            iz = itp.iz + itp.ioff[low];
-            ishift = A.shift[low];
-        } else if (evg) {
-            (void)hipEventRecord(evg[1], s);
-            (void)hipEventRecord(evg[2], s);
-        }
-        const int nblk = (nt64 + 3) / 4;
-        g_line_kernel = 0;
-
-        // waves per tile: enough waves to fill 256 CUs x 32 wave slots about 4 times over
-        const int64_t nwave = (int64_t)nt64 * kn;
-        int split = nwave >= 16384 ? 1 : (nwave >= 4096 ? 2 : 4);   // (re-tuned with the far wings interpolated: waves are 3x shorter)
-        if (itp.far_split == 1 || itp.far_split == 2 || itp.far_split == 4) split = itp.far_split;   // (cs_set_tuning key 22, A/B)
-        g_disp.far_split = split;
-        const int nblk_s = (nt64 * split + 3) / 4;
-        // 8 x (blocks of the longest XCD stretch): XCD-aware tile mapping (tile_block); xtiles is a multiple of 4 tiles
-        const dim3 grid_s((unsigned)(8 * (xtiles * split / 4)), kn);
-#define CS_FAR_LAUNCH(MIX, SP) CS_LAUNCH((k_voigt_far<MIX, SP, false>), grid_s, dim3(256), 0, s, dnu, nnu, G.L, hot, hot32, G.nu.as<double>(), \
-                                                  win, zones, nt64, nblk_s, cut, base, extra, sigma, accumulate, ranges, iz, itp.nItot, ishift, edgez, zero2)
-#define CS_LOR_LAUNCH(SP) CS_LAUNCH((k_voigt_far<false, SP, true>), grid_s, dim3(256), 0, s, dnu, nnu, G.L, hot, hot32, G.nu.as<double>(), \
-                                                  win, zones, nt64, nblk_s, cut, base, extra, sigma, accumulate, ranges, iz, itp.nItot, ishift, edgez)
-        const EdgeZone *edgez = use_edge ? itp.edge : nullptr;
-        // near-line kernels and the sub-tile cores on a side stream, into their own plane (Voigt only; not while profiling)
-        const bool near_fork = !lor && fork && fork->use_near && fork->sigma2 && defer && !evg;
-        double *zero2 = nullptr;   // (the far kernel can clear the plane itself: unused since k_voigt_sub adds to it beside k_voigt_far)
-        if (near_fork) {   // zones, records and piece tables are written: the side stream may start
-            if (forked_here) {   // (nothing was enqueued on the main stream since that record: one event serves both side streams)
-                (void)hipStreamWaitEvent(fork->s3, fork->ev_fork, 0);
-            } else {
-                (void)hipEventRecord(fork->ev_fork3, s);
-                (void)hipStreamWaitEvent(fork->s3, fork->ev_fork3, 0);
-            }
-            // the plane's first writer of the step defines all of it: k_voigt_sub where it runs (sums where a tile has a core, zeros
-            // elsewhere: cs_set_tuning key 19 = 1 keeps the memset for A/B), else a memset
-            const bool sub_here = use_edge && itp.core;
-            const bool sub_assigns = sub_here && !fork->zeroed && !itp.near_memset;
-            if (!fork->zeroed && !sub_assigns) {
-                (void)hipMemsetAsync(fork->sigma2, 0, (size_t)kn * nnu * sizeof(double), fork->s3);
-                g_disp.flags |= CS_DF_NEAR_MEMSET;
-            }
-            g_disp.streams |= 2;
-            fork->zeroed = true;
-            if (sub_here)
-                CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, fork->s3, dnu, nnu, G.L, hot,
-                          G.nu.as<double>(), zones, itp.edge, nt64, kn, cut, fork->sigma2, reinterpret_cast<unsigned *>(ranges), near_prio, sub_assigns ? 1 : 0);
-        }
-        if (lor) {
-            if (split == 1) CS_LOR_LAUNCH(1); else if (split == 2) CS_LOR_LAUNCH(2); else CS_LOR_LAUNCH(4);
-        } else if (hot32 && use_edge) {
-#define CS_EDGE32_LAUNCH(SP) CS_LAUNCH((k_voigt_far<true, SP, false, true>), grid_s, dim3(256), 0, s, dnu, nnu, G.L, hot, hot32, G.nu.as<double>(), \
-                                                  win, zones, nt64, nblk_s, cut, base, extra, sigma, accumulate, ranges, iz, itp.nItot, ishift, edgez, zero2)
-            if (split == 1) CS_EDGE32_LAUNCH(1); else if (split == 2) CS_EDGE32_LAUNCH(2); else CS_EDGE32_LAUNCH(4);
-#undef CS_EDGE32_LAUNCH
-        } else if (hot32) {
-            if (split == 1) CS_FAR_LAUNCH(true, 1); else if (split == 2) CS_FAR_LAUNCH(true, 2); else CS_FAR_LAUNCH(true, 4);
-        } else if (use_edge) {
-#define CS_EDGE_LAUNCH(SP) CS_LAUNCH((k_voigt_far<false, SP, false, true>), grid_s, dim3(256), 0, s, dnu, nnu, G.L, hot, hot32, G.nu.as<double>(), \
-                                                  win, zones, nt64, nblk_s, cut, base, extra, sigma, accumulate, ranges, iz, itp.nItot, ishift, edgez, zero2)
-            if (split == 1) CS_EDGE_LAUNCH(1); else if (split == 2) CS_EDGE_LAUNCH(2); else CS_EDGE_LAUNCH(4);
-#undef CS_EDGE_LAUNCH
-        } else {
-            if (split == 1) CS_FAR_LAUNCH(false, 1); else if (split == 2) CS_FAR_LAUNCH(false, 2); else CS_FAR_LAUNCH(false, 4);
-        }
-#undef CS_FAR_LAUNCH
-#undef CS_LOR_LAUNCH
-        if (evg) (void)hipEventRecord(evg[3], s);
-        if (use_edge && itp.core && !near_fork)   // the window cores of the groups whose series radius is short: pairs inside it (the rest: k_voigt_edge_mx)
-            CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, s, dnu, nnu, G.L, hot, G.nu.as<double>(), zones,
-                               itp.edge, nt64, kn, cut, sigma, reinterpret_cast<unsigned *>(ranges), near_prio, 0);
-        auto launch_near = [&](hipStream_t sn, double *out) {
-            const int ngrpn = (nt64 + CS_NEAR_R - 1) / CS_NEAR_R;   // near kernels: one wave = CS_NEAR_R consecutive tiles ...
-            // ... times nrep, one after the other: where the table is sparse against the grid (few tiles have candidates at all) and the
-            // grid long enough to keep the chip full with an eighth of the waves, and on every grid of half a million (tile, state) waves
-            // and more -- there the launch of the waves is what a near-line kernel costs first (BASELINE configs[4]: 7.9e5 waves per
-            // tier, step 7.06 -> 6.85 ms with eight tiles per wave; the bench column, 9.5e4 waves: a tie with two, a loss with four)
-            const int64_t nwaves_near = (int64_t)ngrpn * kn;
-            const int nrep = (nwaves_near >= 524288 || (jhi - jlo < (int64_t)nt64 * 2 && nwaves_near >= 262144)) ? 8 : 1;
-            const dim3 gridq((unsigned)(((ngrpn + nrep - 1) / nrep + 3) / 4), kn);
-            if (nrep == 1 && itp.near_both) {   // both tiers in one launch (one tile per wave; cs_set_tuning key 16 | 4: two launches, A/B)
-                CS_LAUNCH(k_voigt_near_both, gridq, dim3(256), 0, sn, dnu, nnu, G.L, hot, cold, zones, nt64, cut, out, ranges, near_prio);
-                g_near_launches += 1;
-                return;
-            }
-            g_near_launches += 2;
-            CS_LAUNCH(k_voigt_near<0>, gridq, dim3(256), 0, sn, dnu, nnu, G.L, hot, cold, zones, nt64, ngrpn, nrep, cut, out, ranges, near_prio);
-            CS_LAUNCH(k_voigt_near<1>, gridq, dim3(256), 0, sn, dnu, nnu, G.L, hot, cold, zones, nt64, ngrpn, nrep, cut, out, ranges, near_prio);
-        };
-        if (near_fork) {   // the near kernels need the hand-off words of both k_voigt_far (main stream) and k_voigt_sub (theirs)
-            (void)hipEventRecord(fork->ev_far3, s);
-            (void)hipStreamWaitEvent(fork->s3, fork->ev_far3, 0);
-            launch_near(fork->s3, fork->sigma2);
-            (void)hipEventRecord(fork->ev_join3, fork->s3);
-            fork->pending3 = true;
-            fork->live = true;
-        }
-        if (evg) (void)hipEventRecord(evg[4], s);
-        if (use_edge)
-        {
-            if (fuse) fork_join(fork, s);   // (it reads F)
-            if (mx_big(nt64, kn, 1024) && itp.edge_phases && itp.tnodes) g_disp.flags |= CS_DF_TNODES;
-            if (mx_big(nt64, kn, 1024))
-                CS_LAUNCH(k_voigt_edge_mx<1>, dim3((unsigned)((nt64 + 3) / 4), (unsigned)((kn + 15) / 16)), dim3(256), 0, s, dnu, nnu, G.L, hot, win,
-                          itp.edge, nt64, kn, cut, sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), itp.edge_phases,
-                          itp.edge_phases ? itp.tnodes : nullptr, itp.tC);
-            else   // short grid: four waves per (tile, group)
-                CS_LAUNCH(k_voigt_edge_mx<4>, dim3((unsigned)nt64, (unsigned)((kn + 15) / 16)), dim3(256), 0, s, dnu, nnu, G.L, hot, win,
-                          itp.edge, nt64, kn, cut, sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), itp.edge_phases,
-                          (const double *)nullptr, (const double *)nullptr);   // (the 16-node path in the shared form: 16 more matrix steps per WAVE, no gain measured)
-        }
-        if (evg) (void)hipEventRecord(evg[5], s);
-        if (!lor && !near_fork) launch_near(s, sigma);
-    } else if (shape == SH_PHCO2 && !pshift && ph && phco2_fast_ok(G, nnu, cut, kn, ph)) {
-        // PHCO2 fast path (k_phco2): region-uniform far lines with factorised chi; needs the cut-off edges inside region 3 and the
-        // near zone inside the chi = 1 core (phco2_fast_ok), else the generic kernel below
-        const int nt64 = (int)((nnu + 63) / 64);
-        pa.phfac = ph->fac.as<double>();
-        pa.nu_c = ph->nu_c;
-        ZoneArgs za;
-        za.nu = dnu; za.nul = G.nu.as<double>(); za.Tk = Tk; za.gbound = gbound; za.win = win; za.zones = zones; za.nnu = nnu;
-        za.lorentz = 0;
-        za.ntile = nt64; za.K = kn; za.mu_min = G.mu_min; za.mu_max = G.mu_max; za.cut = cut; za.far_s = far_s;
-        za.margin = kChebMargin;
-        za.ds = 0.0;
-        const unsigned nb_zones = (unsigned)(((int64_t)nt64 * kn + 255) / 256);
-        IzParams P;
-        memset(&P, 0, sizeof P);
-        CS_LAUNCH(k_gas_setup, dim3(nb_prep + nb_zones), dim3(256), 0, s, nb_prep, nb_zones, pa, za, P, (IZone *)nullptr);
-        const bool use_itp = ph_interp_ready(ph, dnu, nnu, cut, kn, s);
-        const PhScratch::Grid &pg = ph->grid;
-        PhArgs pw;
-        pw.nu = dnu; pw.nul = G.nu.as<double>(); pw.nnu = nnu; pw.ntile = nt64; pw.J0 = (int32_t)jlo; pw.J1 = (int32_t)jhi; pw.cut = cut;
-        pw.tol = 1e-9 * (std::max(std::fabs(ph->nu_lo), std::fabs(ph->nu_hi)) + cut + 1.0);
-        pw.out = ph->win.as<PhWin>();
-        PhIArgs ia;
-        memset(&ia, 0, sizeof ia);
-        if (use_itp) {
-            ia.nu = dnu; ia.nul = pw.nul; ia.nnu = nnu; ia.J0 = pw.J0; ia.J1 = pw.J1; ia.cut = cut; ia.tol = pw.tol; ia.margin = ph->margin;
-            ia.lv = pg.lv;
-            ia.out = ph->piw.as<PhIWin>();
-        }
-        // the pairs within 3 cm^-1 (chi = 1: plain Voigt, every near-line pair among them) through the Voigt kernels, where their
-        // near-line hand-off takes this table (check_near_density; else k_phco2's own core loop)
-        bool inner = false;
-        if (ranges && !ph->own_core) {
-            const PhScratch::Dens *hit = nullptr;
-            for (auto &d : ph->dens) if (d.tab == (const void *)&G && d.gen == G.generation && d.grid == ph->grid_id) hit = &d;
-            if (!hit) {
-                if (ph->dens.size() >= 8) ph->dens.erase(ph->dens.begin());
-                ph->dens.push_back({(const void *)&G, G.generation, ph->grid_id, check_near_density(G, ph->nu_hi, ph->max_span, 3.0) == CS_OK});
-                hit = &ph->dens.back();
-            }
-            inner = hit->ok && ph->win3.reserve((size_t)(nt64 + 3) * sizeof(WaveWin)) == hipSuccess &&
-                    ph->zones3.reserve((size_t)kn * nt64 * sizeof(Zone)) == hipSuccess;
-        }
-        WwArgs wa;
-        memset(&wa, 0, sizeof wa);
-        if (inner) {
-            wa.nu = dnu; wa.nul = pw.nul; wa.nnu = nnu; wa.ntile = nt64; wa.J0 = pw.J0; wa.J1 = pw.J1; wa.cut = 3.0;
-            wa.sparse = (jhi - jlo) * 8 < nnu ? 1 : 0;
-            wa.out = ph->win3.as<WaveWin>();
-        }
-        const unsigned nb_tiles = (unsigned)((nt64 + 255) / 256), nb_itv = (unsigned)((ia.lv.nItot + 255) / 256);
-        CS_LAUNCH(k_phwin, dim3(nb_tiles + nb_itv + (inner ? nb_tiles : 0u)), dim3(256), 0, s, nb_tiles, nb_itv, pw, ia, wa);
-        if (evg) (void)hipEventRecord(evg[0], s);
-        const PhIWin *piw = nullptr;
-        PhFine fine;
-        memset(&fine, 0, sizeof fine);
-        if (use_itp) {   // far wings of the region-uniform lines: node sums, carried to the grid (sigma = base + extra + them)
-            const int Kpad = cheb_kpad(kn);
-            CS_LAUNCH(k_phco2_nodes, dim3((unsigned)pg.nslots * (unsigned)((kn + 3) / 4)), dim3(256), 0, s, pg.nodes.as<double>(), G.L, hot,
-                      ph->fac.as<double>(), ph->nu_c, ph->piw.as<PhIWin>(), pg.lv, pg.vl, kn, Kpad, Tk, cut, gbound, G.mu_min, G.mu_max, far_s,
-                      ph->F.as<double>());
-            if (evg) (void)hipEventRecord(evg[1], s);
-            ChebApply A;
-            memset(&A, 0, sizeof A);
-            A.nlev = pg.vl.nv; A.ngas = 1; A.F[0] = ph->F.as<double>(); A.l0[0] = 0;
-            for (int v = 0; v < pg.vl.nv; v++) {
-                for (int r = pg.lv.itv[pg.vl.rl[v]] / 64; r > 1; r >>= 1) A.shift[v]++;
-                A.ioff[v] = pg.vl.boff[v];
-                A.nc[v] = pg.vl.nc[v];
-                A.noff[v] = pg.vl.noff[v];
-                A.Cm[v] = pg.Cm[v].as<double>();
-            }
-            launch_apply(s, A, Kpad, nnu, kn, base, extra, sigma, accumulate, true);
-            accumulate = 1;
-            if (evg) (void)hipEventRecord(evg[2], s);
-            piw = ph->piw.as<PhIWin>();
-            fine = pg.fine;
-        } else if (evg) { (void)hipEventRecord(evg[1], s); (void)hipEventRecord(evg[2], s); }
-        g_line_kernel = 2;
-        CS_LAUNCH(k_phco2, dim3((unsigned)((nt64 + 3) / 4), kn), dim3(256), 0, s, dnu, nnu, G.L, hot, cold, ph->fac.as<double>(), ph->nu_c,
-                           ph->win.as<PhWin>(), zones, nt64, cut, Tk, kn, base, extra, sigma, accumulate, piw, fine, inner ? 1 : 0);
-        if (evg) (void)hipEventRecord(evg[3], s);
-        if (inner) {
-            const int nt4 = (nt64 + 3) / 4 * 4, per = ((nt4 / 4 + 7) / 8) * 4;   // (wave_windows' stretch length)
-            launch_gas(s, SH_VOIGT, G, jrange0, jrange1, kn, Tk, Pk, Ppk, scale, mstride, lrt, qrefq, hot, cold, dnu, nnu, ntile256, J0, J1,
-                       ph->win3.as<WaveWin>(), per, ph->zones3.as<Zone>(), ranges, gbound, 3.0, 0.0, nullptr, sigma, 1, nullptr, nullptr, far_s,
-                       Interp(), nullptr, nullptr, nullptr, true);
-            g_line_kernel = 2;   // (the group's far lines were k_phco2's; the inner pass only took the pairs within 3 cm^-1)
-        }
-        if (evg) { (void)hipEventRecord(evg[4], s); (void)hipEventRecord(evg[5], s); }
-    } else {
-        if (nb_prep > 0) {
-            ZoneArgs za;
-            IzParams P;
-            memset(&za, 0, sizeof za);
-            memset(&P, 0, sizeof P);
-            CS_LAUNCH(k_gas_setup, dim3(nb_prep), dim3(256), 0, s, nb_prep, 0u, pa, za, P, (IZone *)nullptr);
-        }
-        if (evg) { (void)hipEventRecord(evg[0], s); (void)hipEventRecord(evg[1], s); (void)hipEventRecord(evg[2], s); }
-        g_line_kernel = 1;
-        launch_linesum_shape(shape, dim3(ntile256, kn), s, dnu, nnu, G.L, hot, cold, J0, J1, cut, Tk, base, extra, sigma,
-                             accumulate);
-        if (evg) { (void)hipEventRecord(evg[3], s); (void)hipEventRecord(evg[4], s); (void)hipEventRecord(evg[5], s); }
-    }
+    pa.pshift = p.pshift ? 1 : 0; pa.flo = p.flo; pa.fhi = p.fhi;
+    const unsigned nb_prep = p.records_ready ? 0u : (unsigned)((jhi - jlo + 255) / 256) * (unsigned)((p.kn + CS_PREP_KC - 1) / CS_PREP_KC);   // (line block, chunk of states)
+    if (p.shape == SH_VOIGT || p.shape == SH_LORENTZ) line_sum_voigt(s, p, pa, nb_prep);
+    else if (p.shape == SH_PHCO2 && !p.pshift && p.ph && phco2_fast_ok(G, p.nnu, p.cut, p.kn, p.ph)) line_sum_phco2(s, p, pa, nb_prep);
+    else line_sum_generic(s, p, pa, nb_prep);
 }
 
 // workspace of launch_pedestal for kn states of a table of L lines: p, in-block prefix and suffix sums [3][kn][L], block sums [kn][ceil(L / CS_PED_B)]
 static size_t ped_bytes(int64_t kn, int64_t L) { return (size_t)kn * ((size_t)3 * L + (L + CS_PED_B - 1) / CS_PED_B) * sizeof(double); }
 
-// shape code 4 behind a code-0 launch_gas on the same stream (whose K1 left the Voigt records of these kn states in hot / cold):
-// sigma[k][i] -= sum of p[k][l] over the lines l of [a, b) with |nu_i - nul_l| <= cut; clamp: then max(0, .) (sigma complete).
-// [a, b) = the lines the line sum included (the strict end-point pre-filter of the vector method, or every line) within the records'
-// range; J0, J1: the line kernels' windows of the 256-point tiles (tile_windows).  ws: ped_bytes(kn, G.L).  Runs before the next group's K1 overwrites the records (stream order).
-static void launch_pedestal(hipStream_t s, const GasTable &G, int64_t a, int64_t b, const int32_t *J0, const int32_t *J1, int kn,
-                            const LineHot *hot, const LineCold *cold, const double *dnu, int64_t nnu, double cut, double *sigma, bool clamp,
-                            double *ws)
+// shape code 4 behind the group's line sum on the same stream (whose K1 left the Voigt records of these kn states in hot / cold):
+// sigma[k][i] -= sum of p[k][l] over the lines l of [pa, pb) with |nu_i - nul_l| <= cut; clamp: then max(0, .) (sigma complete).
+// [pa, pb) = the lines the line sum included (the strict end-point pre-filter of the vector method, or every line) within the records'
+// range.  ped_ws: ped_bytes(kn, G.L).  Runs before the next group's K1 overwrites the records (stream order).
+static void launch_pedestal(hipStream_t s, const GasPass &g)
 {
-    const int64_t nqt = (G.L + CS_PED_B - 1) / CS_PED_B;
-    const size_t kl = (size_t)kn * G.L;
-    double *p = ws, *pre = ws + kl, *suf = ws + 2 * kl, *bsum = ws + 3 * kl;
-    b = std::max(a, b);
+    const GasTable &G = *g.G;
+    const int64_t nqt = (G.L + CS_PED_B - 1) / CS_PED_B, a = g.pa, b = std::max(a, g.pb);
+    const size_t kl = (size_t)g.kn * G.L;
+    double *p = g.ped_ws, *pre = p + kl, *suf = p + 2 * kl, *bsum = p + 3 * kl;
     if (b > a) {
         const int64_t q0 = a / CS_PED_B, q1 = (b - 1) / CS_PED_B + 1;
-        CS_LAUNCH(k_ped_values, dim3((unsigned)((q1 - q0 + 3) / 4), (unsigned)kn), dim3(256), 0, s, hot, cold, G.L, a, b, cut, q0, q1 - q0,
+        CS_LAUNCH(k_ped_values, dim3((unsigned)((q1 - q0 + 3) / 4), (unsigned)g.kn), dim3(256), 0, s, g.hot, g.cold, G.L, a, b, g.cut, q0, q1 - q0,
                   nqt, p, pre, suf, bsum);
     }
-    CS_LAUNCH(k_ped_sub, dim3((unsigned)((nnu + 255) / 256), (unsigned)((kn + CS_PED_KC - 1) / CS_PED_KC)), dim3(256), 0, s, dnu, nnu,
-              G.nu.as<double>(), G.L, a, b, J0, J1, cut, kn, p, pre, suf, bsum, nqt, sigma, clamp ? 1 : 0);
+    CS_LAUNCH(k_ped_sub, dim3((unsigned)((g.nnu + 255) / 256), (unsigned)((g.kn + CS_PED_KC - 1) / CS_PED_KC)), dim3(256), 0, s, g.dnu, g.nnu,
+              G.nu.as<double>(), G.L, a, b, g.J0, g.J1, g.cut, g.kn, p, pre, suf, bsum, nqt, g.sigma, g.clamp ? 1 : 0);
 }
 
-// shape code 5 behind a launch_gas(SH_VOIGT_VVH) on the same stream, whose line sum of these kn states is in src (base 0, nothing
-// else added; src may be sigma): sigma = (accumulate ? sigma : base + extra) + R(nu, T) (src + mirror term of the lines [a, m)).
+// shape code 5 behind the group's line sum on the same stream, which is in src (base 0, nothing else added; src may be sigma):
+// sigma = (accumulate ? sigma : base + extra) + R(nu, T) (src + mirror term of the lines [pa, mb)).
 // Reads the records the line sum used: runs before the next group's K1 overwrites them (stream order).
-static void launch_vvh(hipStream_t s, const GasTable &G, int64_t a, int64_t m, int kn, const double *Tk, const LineHot *hot,
-                       const LineCold *cold, const double *dnu, int64_t nnu, double cut, const double *src, double base, const double *extra,
-                       double *sigma, int accumulate)
+static void launch_vvh(hipStream_t s, const GasPass &g, const double *src)
 {
-    CS_LAUNCH(k_vvh_finish, dim3((unsigned)((nnu + 255) / 256), (unsigned)kn), dim3(256), 0, s, dnu, nnu, Tk, hot, cold, G.L, a,
-              std::max(a, m), cut, src, base, extra, sigma, accumulate);
+    CS_LAUNCH(k_vvh_finish, dim3((unsigned)((g.nnu + 255) / 256), (unsigned)g.kn), dim3(256), 0, s, g.dnu, g.nnu, g.Tk, g.hot, g.cold, g.G->L, g.pa,
+              std::max(g.pa, g.mb), g.cut, src, g.base, g.extra, g.sigma, g.accumulate);
 }
 
-// shape code 6 in place of launch_vvh, behind the same launch_gas(SH_VOIGT_VVH): k_ped_values over the included lines [a, b) of the
-// S~ records, then ONE pass k_vvh_ped_finish that subtracts each point's direct pedestals, adds the mirror pairs of [a, m) minus theirs,
-// multiplies by R(nu, T) and writes sigma = (accumulate ? sigma : base + extra) + r, then max(0, .) if clamp (the gas's own sigma
-// complete: B1, bake).  J0, J1, ws: as launch_pedestal's; nu: the grid on the host (dnu on the device).
-static void launch_vvh_ped(hipStream_t s, const GasTable &G, int64_t a, int64_t b, int64_t m, const int32_t *J0, const int32_t *J1, int kn,
-                           const double *Tk, const LineHot *hot, const LineCold *cold, const double *nu, const double *dnu, int64_t nnu,
-                           double cut, const double *src, double base, const double *extra, double *sigma, int accumulate, bool clamp, double *ws)
+// shape code 6 in place of launch_vvh: k_ped_values over the included lines [pa, pb) of the S~ records, then ONE pass k_vvh_ped_finish
+// that subtracts each point's direct pedestals, adds the mirror pairs of [pa, mb) minus theirs, multiplies by R(nu, T) and writes
+// sigma = (accumulate ? sigma : base + extra) + r, then max(0, .) if clamp.  ped_ws: as launch_pedestal's.
+static void launch_vvh_ped(hipStream_t s, const GasPass &g, const double *src)
 {
-    const int64_t nqt = (G.L + CS_PED_B - 1) / CS_PED_B;
-    const size_t kl = (size_t)kn * G.L;
-    double *p = ws, *pre = ws + kl, *suf = ws + 2 * kl, *bsum = ws + 3 * kl;
-    b = std::max(a, b);
-    m = std::min(std::max(a, m), b);
+    const GasTable &G = *g.G;
+    const int64_t nqt = (G.L + CS_PED_B - 1) / CS_PED_B, a = g.pa, b = std::max(a, g.pb), m = std::min(std::max(a, g.mb), b);
+    const size_t kl = (size_t)g.kn * G.L;
+    double *p = g.ped_ws, *pre = p + kl, *suf = p + 2 * kl, *bsum = p + 3 * kl;
     if (b > a) {
         const int64_t q0 = a / CS_PED_B, q1 = (b - 1) / CS_PED_B + 1;
-        CS_LAUNCH(k_ped_values, dim3((unsigned)((q1 - q0 + 3) / 4), (unsigned)kn), dim3(256), 0, s, hot, cold, G.L, a, b, cut, q0, q1 - q0,
+        CS_LAUNCH(k_ped_values, dim3((unsigned)((q1 - q0 + 3) / 4), (unsigned)g.kn), dim3(256), 0, s, g.hot, g.cold, G.L, a, b, g.cut, q0, q1 - q0,
                   nqt, p, pre, suf, bsum);
     }
     // the tiles [0, tm) whose first point can reach a mirror line (nu + nul_a <= cut) get one state per block
-    const int64_t ntile = (nnu + 255) / 256;
+    const int64_t ntile = (g.nnu + 255) / 256;
     int64_t tm = 0;
     if (m > a) {
-        const double lim = cut - G.h_nu[a];
-        while (tm < ntile && nu[tm * 256] <= lim) tm++;
+        const double lim = g.cut - G.h_nu[a];
+        while (tm < ntile && g.nu[tm * 256] <= lim) tm++;
     }
-    const int64_t nblk = tm * kn + (ntile - tm) * ((kn + CS_PED_KC - 1) / CS_PED_KC);
-    CS_LAUNCH(k_vvh_ped_finish, dim3((unsigned)nblk), dim3(256), 0, s, dnu, nnu, Tk, G.nu.as<double>(), hot, cold, G.L, a, b, a, m, J0, J1, cut,
-              kn, p, pre, suf, bsum, nqt, src, base, extra, sigma, accumulate, clamp ? 1 : 0, (int)tm);
+    const int64_t nblk = tm * g.kn + (ntile - tm) * ((g.kn + CS_PED_KC - 1) / CS_PED_KC);
+    CS_LAUNCH(k_vvh_ped_finish, dim3((unsigned)nblk), dim3(256), 0, s, g.dnu, g.nnu, g.Tk, G.nu.as<double>(), g.hot, g.cold, G.L, a, b, a, m, g.J0, g.J1,
+              g.cut, g.kn, p, pre, suf, bsum, nqt, src, g.base, g.extra, g.sigma, g.accumulate, g.clamp ? 1 : 0, (int)tm);
+}
+
+// One launch group on `s`, finishing step included.  Codes 0-3: the line sum as the pass states it; code 4: launch_pedestal behind it.
+// Codes 5, 6: the bare line sum of the S / R(nul, T) records -- base 0, no extra, applied at once (no deferred apply) and without side
+// streams, into sigma itself for a group that does not accumulate, else into the spare plane -- then launch_vvh (5) or launch_vvh_ped
+// (6), which write sigma as the pass states it.
+static void launch_gas(hipStream_t s, const GasPass &p)
+{
+    if (!p.vvh) {
+        launch_line_sum(s, p);
+        if (p.ped) launch_pedestal(s, p);
+        return;
+    }
+    GasPass bare = p;
+    bare.base = 0.0; bare.extra = nullptr; bare.sigma = p.accumulate ? p.spare : p.sigma; bare.accumulate = 0;
+    bare.defer = nullptr; bare.fork = nullptr;
+    launch_line_sum(s, bare);
+    if (p.ped) launch_vvh_ped(s, p, bare.sigma);
+    else launch_vvh(s, p, bare.sigma);
 }
 
 // end of the mirror lines of shape code 5 among the included lines [a, b) whose records exist: nu + nul <= cut can hold for some point
@@ -2037,8 +2114,115 @@ int cs_gas_clear(cs_ctx *ctx, int slot)
     return CS_OK;
 }
 
+// where gas_states puts sigma [K][nnu]: host rows of pitch ld (it owns the buffer of a chunk and copies each chunk out), or a device plane
+// written in place, which plane() hands out once the call has passed its checks (cs_bake: only then is the table in the slot given up)
+struct StatesOut {
+    double *host = nullptr;
+    int64_t ld = 0;
+    std::function<int(double *&)> plane;
+};
+
+// sigma of one gas at K states on the grid nu, behind cs_shape_batch / cs_shape_points / cs_bake (which have checked the slot, the shape
+// code -- base code `shape`, CS_SHAPE_PSHIFT as `pshift` -- their sizes and the grid): the states in chunks that bound the workspace
+static int gas_states(cs_ctx *ctx, GasTable &G, int shape, bool pshift, double dnu_cut, int64_t nnu, const double *nu, int K,
+                      const double *T, const double *P, const double *Pp, bool strict, const StatesOut &out)
+{
+    int rc;
+    const bool ped = shape == SH_VOIGT_CKD || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum, then the pedestal behind it
+    const bool vvh = shape == SH_VOIGT_VVH || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
+    if (ped || vvh) shape = SH_VOIGT;
+    double ds = 0.0;   // CS_SHAPE_PSHIFT: every window and the line range widened by the largest shift of these states
+    if (pshift && (rc = shift_width(G, P, K, ds))) return rc;
+    if ((rc = check_gas_states(G, K, T))) return rc;
+    if (shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, dnu_cut, ds))) return rc;
+    ph_set_grid(ctx, ctx->ph, nu, nnu, ++g_grid_counter);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    double *Z = nullptr;   // the caller's plane; NULL: a chunk buffer of our own, copied to out.host
+    if (out.plane && (rc = out.plane(Z))) return rc;
+    if (pshift && (rc = ensure_shifts(G, s))) return rc;
+    int64_t g0, g1, pairs, inr;
+    included_range(G.h_nu, nu[0], nu[nnu - 1], dnu_cut + ds, strict, g0, g1);
+    std::vector<int32_t> J0, J1;
+    tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(shape, G, nu[nnu - 1] + ds, dnu_cut) + ds, J0, J1, pairs, inr);
+    const int ntile = (int)J0.size();
+    DevBuf dnu, dT, dP, dPp, dJ0, dJ1, hot, cold, dsig, dwin, dzones, dgmax, dranges, dlrt, dqref, dped;
+    {
+        std::vector<double> lrt, qr;
+        state_tables(G, K, T, lrt, qr);
+        if ((rc = upload(dlrt, lrt.data(), lrt.size(), s)) || (rc = upload(dqref, qr.data(), qr.size(), s))) return rc;
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    std::vector<WaveWin> win;
+    const int xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, dnu_cut, win, 64, ds);
+    const std::vector<double> gb = gamma_bound(G, K, T, P, Pp);
+    if ((rc = upload(dnu, nu, nnu, s)) || (rc = upload(dT, T, K, s)) || (rc = upload(dP, P, K, s)) ||
+        (rc = upload(dPp, Pp, K, s)) || (rc = upload(dJ0, J0.data(), ntile, s)) || (rc = upload(dJ1, J1.data(), ntile, s)) ||
+        (rc = upload(dwin, win.data(), win.size(), s)) || (rc = upload(dgmax, gb.data(), K, s)))
+        return rc;
+    // bound the workspace: process the states in chunks
+    const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) +
+                             (Z ? (size_t)nnu * sizeof(int2) : (size_t)nnu * (sizeof(double) + sizeof(int2))) + (ped ? ped_bytes(1, G.L) : 0);
+    const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));   // gridDim.y limit
+    if (ped) HIPCHK(dped.reserve(ped_bytes(kc, G.L)));
+    HIPCHK(hot.reserve(((size_t)kc * G.L + 4) * sizeof(LineHot)));
+    HIPCHK(cold.reserve((size_t)kc * G.L * sizeof(LineCold)));
+    if (!Z) HIPCHK(dsig.reserve((size_t)kc * nnu * sizeof(double)));
+    HIPCHK(dzones.reserve((size_t)kc * win.size() * sizeof(Zone)));
+    HIPCHK(dranges.reserve((size_t)kc * nnu * sizeof(int2) + (size_t)2 * kc * ((nnu + 63) / 64) * sizeof(int)));   // + per-(tile, state) flags
+    GasPass p;
+    p.G = &G; p.shape = shape; p.jlo = J0.front(); p.jhi = J1.back(); p.cut = dnu_cut; p.ped = ped; p.vvh = vvh;
+    p.pa = std::max<int64_t>(g0, J0.front()); p.pb = std::min<int64_t>(g1, J1.back());   // the included lines whose records exist
+    if (vvh) p.mb = vvh_mirror_end(G.h_nu, p.pa, p.pb, nu[0], dnu_cut);
+    // (the strict pre-filter of a shifted line is its own state's: prep_body parks the lines whose shifted centre fails it)
+    p.pshift = pshift; p.ds = ds; p.flo = strict ? nu[0] - dnu_cut : -INFINITY; p.fhi = strict ? nu[nnu - 1] + dnu_cut : INFINITY;
+    p.dnu = dnu.as<double>(); p.nu = nu; p.nnu = nnu; p.ntile256 = ntile; p.J0 = dJ0.as<int32_t>(); p.J1 = dJ1.as<int32_t>();
+    p.win = dwin.as<WaveWin>(); p.xtiles = xtiles;
+    p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<int2>(); p.ped_ws = dped.as<double>();
+    if (ctx->mixed && shape == SH_VOIGT && !pshift) {
+        HIPCHK(ctx->hot32.reserve(((size_t)kc * G.L + 4) * sizeof(LineF32)));
+        p.hot32 = ctx->hot32.as<LineF32>();
+    }
+    p.clamp = true;   // the gas's own sigma, complete
+    p.far_s = ctx->far_s; p.ph = &ctx->ph;
+    ChebGrid cheb;
+    GasInterp ginterp;
+    if (ctx->interp && (shape == SH_VOIGT || shape == SH_LORENTZ)) {
+        if ((rc = cheb_build(ctx, cheb, nu, dnu.as<double>(), nnu, dnu_cut, s)) ||
+            (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, g0, g1, nu, nnu, dnu_cut, kc, s, true, ds)))
+            return rc;
+        p.itp = interp_view(cheb, ginterp, kc);
+        interp_settings(ctx, p.itp);
+    }
+    for (int k0 = 0; k0 < K; k0 += kc) {
+        p.kn = std::min(kc, K - k0);
+        p.Tk = dT.as<double>() + k0; p.Pk = dP.as<double>() + k0; p.Ppk = dPp.as<double>() + k0; p.gbound = dgmax.as<double>() + k0;
+        p.lrt = dlrt.as<double>() + k0; p.qrefq = dqref.as<double>() + (size_t)k0 * G.niso;
+        p.sigma = Z ? Z + (size_t)k0 * nnu : dsig.as<double>();
+        launch_gas(s, p);
+        HIPCHK(hipGetLastError());
+        if (!Z)
+            HIPCHK(hipMemcpy2DAsync(out.host + (size_t)k0 * out.ld, out.ld * sizeof(double), dsig.p, nnu * sizeof(double), nnu * sizeof(double), p.kn,
+                                    hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return CS_OK;
+}
+
 static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t nnu, const double *nu, int K,
-                      const double *T, const double *P, const double *Pp, double *sigma, int64_t ld_state, bool strict);
+                      const double *T, const double *P, const double *Pp, double *sigma, int64_t ld_state, bool strict)
+{
+    if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
+    if (slot < 0 || slot >= CS_MAX_GAS || !ctx->gas[slot].present) return fail(CS_EINVAL, "gas slot %d is empty", slot);
+    bool pshift;
+    int rc;
+    if ((rc = decode_shape(shape, shape, pshift))) return rc;
+    if (K < 1 || ld_state < nnu) return fail(CS_EINVAL, "bad K/ld_state");
+    if ((rc = check_ascending(nu, nnu))) return rc;
+    StatesOut out;
+    out.host = sigma; out.ld = ld_state;   // no plane: gas_states owns the chunk buffer
+    return gas_states(ctx, ctx->gas[slot], shape, pshift, dnu_cut, nnu, nu, K, T, P, Pp, strict, out);
+}
 
 int cs_shape_batch(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t nnu, const double *nu, int K,
                    const double *T, const double *P, const double *Pp, double *sigma, int64_t ld_state)
@@ -2052,110 +2236,6 @@ int cs_shape_points(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t nn
     return shape_impl(ctx, slot, shape, dnu_cut, nnu, nu, K, T, P, Pp, sigma, ld_state, false);
 }
 
-static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t nnu, const double *nu, int K,
-                      const double *T, const double *P, const double *Pp, double *sigma, int64_t ld_state, bool strict)
-{
-    if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
-    if (slot < 0 || slot >= CS_MAX_GAS || !ctx->gas[slot].present) return fail(CS_EINVAL, "gas slot %d is empty", slot);
-    bool pshift;
-    int rc;
-    if ((rc = decode_shape(shape, shape, pshift))) return rc;
-    if (K < 1 || ld_state < nnu) return fail(CS_EINVAL, "bad K/ld_state");
-    const bool ped = shape == SH_VOIGT_CKD || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum, then the pedestal behind it
-    const bool vvh = shape == SH_VOIGT_VVH || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
-    if (ped || vvh) shape = SH_VOIGT;
-    if ((rc = check_ascending(nu, nnu))) return rc;
-    GasTable &G = ctx->gas[slot];
-    double ds = 0.0;   // CS_SHAPE_PSHIFT: every window and the line range widened by the largest shift of these states
-    if (pshift && (rc = shift_width(G, P, K, ds))) return rc;
-    if ((rc = check_gas_states(G, K, T))) return rc;
-    if (shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, dnu_cut, ds))) return rc;
-    ph_set_grid(ctx, ctx->ph, nu, nnu, ++g_grid_counter);
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    if (pshift && (rc = ensure_shifts(G, s))) return rc;
-    int64_t g0, g1, pairs, inr;
-    included_range(G.h_nu, nu[0], nu[nnu - 1], dnu_cut + ds, strict, g0, g1);
-    std::vector<int32_t> J0, J1;
-    tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(shape, G, nu[nnu - 1] + ds, dnu_cut) + ds, J0, J1, pairs, inr);
-    // (the strict pre-filter of a shifted line is its own state's: prep_body parks the lines whose shifted centre fails it)
-    const double flo = strict ? nu[0] - dnu_cut : -INFINITY, fhi = strict ? nu[nnu - 1] + dnu_cut : INFINITY;
-    const int ntile = (int)J0.size();
-    DevBuf dnu, dT, dP, dPp, dJ0, dJ1, hot, cold, dsig, dwin, dzones, dgmax, dranges, dlrt, dqref;
-    {
-        std::vector<double> lrt, qr;
-        state_tables(G, K, T, lrt, qr);
-        if ((rc = upload(dlrt, lrt.data(), lrt.size(), s)) || (rc = upload(dqref, qr.data(), qr.size(), s))) return rc;
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    std::vector<WaveWin> win;
-    const int xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, dnu_cut, win, 64, ds);
-    if ((rc = upload(dnu, nu, nnu, s)) || (rc = upload(dT, T, K, s)) || (rc = upload(dP, P, K, s)) ||
-        (rc = upload(dPp, Pp, K, s)) || (rc = upload(dJ0, J0.data(), ntile, s)) || (rc = upload(dJ1, J1.data(), ntile, s)) ||
-        (rc = upload(dwin, win.data(), win.size(), s)))
-        return rc;
-    // bound the workspace: process the states in chunks
-    const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * (sizeof(double) + sizeof(int2)) +
-                             (ped ? ped_bytes(1, G.L) : 0);
-    int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));   // gridDim.y limit
-    DevBuf dped;
-    if (ped) HIPCHK(dped.reserve(ped_bytes(kc, G.L)));
-    HIPCHK(hot.reserve(((size_t)kc * G.L + 4) * sizeof(LineHot)));
-    HIPCHK(cold.reserve((size_t)kc * G.L * sizeof(LineCold)));
-    HIPCHK(dsig.reserve((size_t)kc * nnu * sizeof(double)));
-    HIPCHK(dzones.reserve((size_t)kc * win.size() * sizeof(Zone)));
-    HIPCHK(dgmax.reserve((size_t)K * sizeof(double)));
-    LineF32 *mix32 = nullptr;
-    if (ctx->mixed && shape == SH_VOIGT && !pshift) {
-        HIPCHK(ctx->hot32.reserve(((size_t)kc * G.L + 4) * sizeof(LineF32)));
-        mix32 = ctx->hot32.as<LineF32>();
-    }
-    HIPCHK(dranges.reserve((size_t)kc * nnu * sizeof(int2) + (size_t)2 * kc * ((nnu + 63) / 64) * sizeof(int)));   // + per-(tile, state) flags
-    {
-        std::vector<double> gb = gamma_bound(G, K, T, P, Pp);
-        if ((rc = upload(dgmax, gb.data(), K, s))) return rc;
-    }
-    ChebGrid cheb;
-    GasInterp ginterp;
-    Interp itp;
-    if (ctx->interp && (shape == SH_VOIGT || shape == SH_LORENTZ)) {
-        if ((rc = cheb_build(ctx, cheb, nu, dnu.as<double>(), nnu, dnu_cut, s)) ||
-            (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, g0, g1, nu, nnu, dnu_cut, kc, s, true, ds)))
-            return rc;
-        itp = interp_view(cheb, ginterp, kc);
-        if (!ctx->matrix_nodes) itp.sep = nullptr, itp.edge = nullptr;
-        itp.sep_always = ctx->matrix_nodes == 2;
-        interp_settings(ctx, itp);
-        itp.core = ctx->matrix_core != 0;
-    }
-    for (int k0 = 0; k0 < K; k0 += kc) {
-        const int kn = std::min(kc, K - k0);
-        launch_gas(s, vvh ? SH_VOIGT_VVH : shape, G, J0.front(), J1.back(), kn, dT.as<double>() + k0, dP.as<double>() + k0, dPp.as<double>() + k0, nullptr, 0,
-                   dlrt.as<double>() + k0, dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(),
-                   dwin.as<WaveWin>(), xtiles, dzones.as<Zone>(), dranges.as<int2>(), dgmax.as<double>() + k0, dnu_cut, 0.0, nullptr, dsig.as<double>(), 0, nullptr,
-                   mix32, ctx->far_s, itp, nullptr, &ctx->ph, nullptr, false, pshift, flo, fhi, ds);
-        if (ped && !vvh)
-            launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
-                            hot.as<LineHot>(), cold.as<LineCold>(),
-                            dnu.as<double>(), nnu, dnu_cut, dsig.as<double>(), true, dped.as<double>());
-        if (vvh) {
-            const int64_t a = std::max<int64_t>(g0, J0.front()), b = std::min<int64_t>(g1, J1.back());
-            const int64_t m = vvh_mirror_end(G.h_nu, a, b, nu[0], dnu_cut);
-            if (ped)
-                launch_vvh_ped(s, G, a, b, m, dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn, dT.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(),
-                               nu, dnu.as<double>(), nnu, dnu_cut, dsig.as<double>(), 0.0, nullptr, dsig.as<double>(), 0, true, dped.as<double>());
-            else
-                launch_vvh(s, G, a, m, kn, dT.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, dnu_cut,
-                           dsig.as<double>(), 0.0, nullptr, dsig.as<double>(), 0);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy2DAsync(sigma + (size_t)k0 * ld_state, ld_state * sizeof(double), dsig.p, nnu * sizeof(double),
-                                nnu * sizeof(double), kn, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return CS_OK;
-}
-
 int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut, int64_t nnu, const double *nu, int nT,
             const double *T, int nP, const double *P, const double *conc, double *lnsigma_out)
 {
@@ -2166,9 +2246,6 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
     int rc;
     if ((rc = decode_shape(shape, shape, pshift))) return rc;
     if (nT < 2 || nP < 2) return fail(CS_EINVAL, "need at least 2 x 2 grid points");
-    const bool ped = shape == SH_VOIGT_CKD || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum, then the pedestal behind it (clamped before k_table_log)
-    const bool vvh = shape == SH_VOIGT_VVH || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
-    if (ped || vvh) shape = SH_VOIGT;
     if ((rc = check_ascending(nu, nnu))) return rc;
     for (int64_t i = 0; i < nnu; i++)
         if (!(nu[i] >= 0)) return fail(CS_EINVAL, "wavenumbers must be positive");
@@ -2182,88 +2259,17 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
             Ps[i + nT * j] = P[j];
             Pp[i + nT * j] = C * P[j];
         }
-    GasTable &G = ctx->gas[gas_slot];
-    double ds = 0.0;   // CS_SHAPE_PSHIFT: as in shape_impl
-    if (pshift && (rc = shift_width(G, Ps.data(), M, ds))) return rc;
-    if ((rc = check_gas_states(G, M, Ts.data()))) return rc;
-    if (shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, dnu_cut, ds))) return rc;
-    ph_set_grid(ctx, ctx->ph, nu, nnu, ++g_grid_counter);
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     TableDev &tb = ctx->tab[table_slot];
-    tb.present = false;
-    if (pshift && (rc = ensure_shifts(G, s))) return rc;
-    int64_t g0, g1, pairs, inr;
-    included_range(G.h_nu, nu[0], nu[nnu - 1], dnu_cut + ds, true, g0, g1);
-    std::vector<int32_t> J0, J1;
-    tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(shape, G, nu[nnu - 1] + ds, dnu_cut) + ds, J0, J1, pairs, inr);
-    const double flo = nu[0] - dnu_cut, fhi = nu[nnu - 1] + dnu_cut;   // (bake uses the vector method: strict pre-filter, per state when shifted)
-    std::vector<WaveWin> win;
-    const int xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, dnu_cut, win, 64, ds);
-    const int ntile = (int)J0.size();
-    DevBuf dnu, dT, dP, dPp, dJ0, dJ1, hot, cold, dwin, dzones, dgb, dranges, dlrt, dqref;
-    {
-        std::vector<double> lrt, qr;
-        state_tables(G, M, Ts.data(), lrt, qr);
-        if ((rc = upload(dlrt, lrt.data(), lrt.size(), s)) || (rc = upload(dqref, qr.data(), qr.size(), s))) return rc;
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    std::vector<double> gb = gamma_bound(G, M, Ts.data(), Ps.data(), Pp.data());
-    if ((rc = upload(dnu, nu, nnu, s)) || (rc = upload(dT, Ts.data(), M, s)) || (rc = upload(dP, Ps.data(), M, s)) ||
-        (rc = upload(dPp, Pp.data(), M, s)) || (rc = upload(dJ0, J0.data(), ntile, s)) || (rc = upload(dJ1, J1.data(), ntile, s)) ||
-        (rc = upload(dwin, win.data(), win.size(), s)) || (rc = upload(dgb, gb.data(), M, s)))
-        return rc;
-    HIPCHK(tb.Z.reserve((size_t)M * nnu * sizeof(double)));
-    const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * sizeof(int2) + (ped ? ped_bytes(1, G.L) : 0);
-    const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)M, ((size_t)4 << 30) / per_state, (size_t)65535}));
-    DevBuf dped;
-    if (ped) HIPCHK(dped.reserve(ped_bytes(kc, G.L)));
-    HIPCHK(hot.reserve(((size_t)kc * G.L + 4) * sizeof(LineHot)));
-    HIPCHK(cold.reserve((size_t)kc * G.L * sizeof(LineCold)));
-    HIPCHK(dzones.reserve((size_t)kc * win.size() * sizeof(Zone)));
-    HIPCHK(dranges.reserve((size_t)kc * nnu * sizeof(int2) + (size_t)2 * kc * ((nnu + 63) / 64) * sizeof(int)));   // + per-(tile, state) flags
-    LineF32 *mix32 = nullptr;
-    if (ctx->mixed && shape == SH_VOIGT && !pshift) {
-        HIPCHK(ctx->hot32.reserve(((size_t)kc * G.L + 4) * sizeof(LineF32)));
-        mix32 = ctx->hot32.as<LineF32>();
-    }
-    ChebGrid cheb;
-    GasInterp ginterp;
-    Interp itp;
-    if (ctx->interp && (shape == SH_VOIGT || shape == SH_LORENTZ)) {
-        if ((rc = cheb_build(ctx, cheb, nu, dnu.as<double>(), nnu, dnu_cut, s)) ||
-            (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, g0, g1, nu, nnu, dnu_cut, kc, s, true, ds)))
-            return rc;
-        itp = interp_view(cheb, ginterp, kc);
-        if (!ctx->matrix_nodes) itp.sep = nullptr, itp.edge = nullptr;
-        itp.sep_always = ctx->matrix_nodes == 2;
-        interp_settings(ctx, itp);
-        itp.core = ctx->matrix_core != 0;
-    }
-    for (int k0 = 0; k0 < M; k0 += kc) {
-        const int kn = std::min(kc, M - k0);
-        launch_gas(s, vvh ? SH_VOIGT_VVH : shape, G, J0.front(), J1.back(), kn, dT.as<double>() + k0, dP.as<double>() + k0, dPp.as<double>() + k0, nullptr, 0, dlrt.as<double>() + k0,
-                   dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, ntile, dJ0.as<int32_t>(), dJ1.as<int32_t>(), dwin.as<WaveWin>(), xtiles,
-                   dzones.as<Zone>(), dranges.as<int2>(), dgb.as<double>() + k0, dnu_cut, 0.0, nullptr, tb.Z.as<double>() + (size_t)k0 * nnu, 0, nullptr,
-                   mix32, ctx->far_s, itp, nullptr, &ctx->ph, nullptr, false, pshift, flo, fhi, ds);
-        if (ped && !vvh)
-            launch_pedestal(s, G, std::max<int64_t>(g0, J0.front()), std::min<int64_t>(g1, J1.back()), dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn,
-                            hot.as<LineHot>(), cold.as<LineCold>(),
-                            dnu.as<double>(), nnu, dnu_cut, tb.Z.as<double>() + (size_t)k0 * nnu, true, dped.as<double>());
-        if (vvh) {
-            const int64_t a = std::max<int64_t>(g0, J0.front()), b = std::min<int64_t>(g1, J1.back());
-            const int64_t m = vvh_mirror_end(G.h_nu, a, b, nu[0], dnu_cut);
-            double *z = tb.Z.as<double>() + (size_t)k0 * nnu;
-            if (ped)
-                launch_vvh_ped(s, G, a, b, m, dJ0.as<int32_t>(), dJ1.as<int32_t>(), kn, dT.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(),
-                               nu, dnu.as<double>(), nnu, dnu_cut, z, 0.0, nullptr, z, 0, true, dped.as<double>());
-            else
-                launch_vvh(s, G, a, m, kn, dT.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(), dnu.as<double>(), nnu, dnu_cut, z, 0.0,
-                           nullptr, z, 0);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-    }
+    StatesOut out;   // straight into the table's Z; a call refused before this leaves a table already in the slot usable
+    out.plane = [&](double *&Z) {
+        tb.present = false;
+        HIPCHK(tb.Z.reserve((size_t)M * nnu * sizeof(double)));
+        Z = tb.Z.as<double>();
+        return (int)CS_OK;
+    };
+    // (bake uses the vector method: strict pre-filter, per state when shifted; codes 4, 6 clamped before k_table_log)
+    if ((rc = gas_states(ctx, ctx->gas[gas_slot], shape, pshift, dnu_cut, nnu, nu, M, Ts.data(), Ps.data(), Pp.data(), true, out))) return rc;
+    hipStream_t s = ctx->stream;
     CS_LAUNCH(k_table_log, dim3((unsigned)((nnu + 255) / 256)), dim3(256), 0, s, tb.Z.as<double>(), M, nnu);
     HIPCHK(hipGetLastError());
     if (lnsigma_out) HIPCHK(hipMemcpyAsync(lnsigma_out, tb.Z.p, (size_t)M * nnu * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2937,6 +2943,22 @@ int cs_column_update_state(cs_ctx *ctx, const double *T_nodes, const double *mu_
     return CS_OK;
 }
 
+// what a launch group of the resident column fixes at setup: its table, record range and shape, the grid and its windows, and how the
+// context runs it; the callers add the states, the workspace and the output (one state set of the column | a chunk of a batch)
+static GasPass column_pass(cs_ctx *ctx, const ColGas &cg)
+{
+    const Column &c = ctx->col;
+    GasPass p;
+    p.G = cg.tab; p.shape = cg.shape; p.jlo = cg.jlo; p.jhi = cg.jhi; p.cut = cg.cut;
+    p.ped = cg.ped; p.vvh = cg.vvh; p.pa = cg.pa; p.pb = cg.pb; p.mb = cg.mb; p.pshift = cg.pshift; p.ds = cg.ds;
+    p.dnu = c.nu.as<double>(); p.nu = c.h_nu.data(); p.nnu = c.nnu; p.ntile256 = c.ntile;
+    p.J0 = cg.J0.as<int32_t>(); p.J1 = cg.J1.as<int32_t>(); p.win = cg.win.as<WaveWin>(); p.xtiles = cg.xtiles;
+    p.hot32 = (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr;
+    p.base = c.sigma_gray;   // (clamp stays off: the column's sigma is complete only after its last absorber)
+    p.far_s = ctx->far_s; p.ph = &ctx->ph;
+    return p;
+}
+
 int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_nodes, const double *T_levels,
                     const double *conc, const double *conc_tab, const double *cia_P1, const double *cia_P2, double *Fup, double *Fdn)
 {
@@ -3033,7 +3055,11 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
             (rc = upload(dlrt, lrt.data(), lrt.size(), s)) || (rc = upload(dqref, qr.data(), qr.size(), s)))
             return rc;
         HIPCHK(dzones.reserve((size_t)kc * nt64 * sizeof(Zone)));
-        Interp itp;
+        GasPass p = column_pass(ctx, cg);
+        p.mstride = (int)BK;
+        p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<int2>(); p.ped_ws = dped.as<double>();
+        p.accumulate = qi > 0; p.spare = dvvh.as<double>();   // (a second code-5/6 group: its bare line sum goes there first)
+        Interp &itp = p.itp;
         if (cg.itp.nlev > 0) {
             HIPCHK(dizones.reserve((size_t)kc * c.cheb.nItot * sizeof(IZone)));
             const size_t fb = (size_t)c.cheb.nItot * CS_NC * cheb_kpad(kc) * sizeof(double);
@@ -3045,30 +3071,16 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
             itp.F = dF2.as<double>();
             HIPCHK(dsep.reserve((size_t)((kc + 15) / 16) * c.cheb.nItot * sizeof(SepZone)));   // (the column's own buffer is sized for K states)
             HIPCHK(dedge.reserve((size_t)((kc + 15) / 16) * nt64 * sizeof(EdgeZone)));
-            itp.sep = ctx->matrix_nodes ? dsep.as<SepZone>() : nullptr;
-            itp.edge = ctx->matrix_nodes ? dedge.as<EdgeZone>() : nullptr;
-            itp.sep_always = ctx->matrix_nodes == 2;
+            itp.sep = dsep.as<SepZone>();
+            itp.edge = dedge.as<EdgeZone>();
             interp_settings(ctx, itp);
-            itp.core = ctx->matrix_core != 0;
         }
         for (int64_t k0 = 0; k0 < BK; k0 += kc) {
-            const int kn = (int)std::min<int64_t>(kc, BK - k0);
-            double *sk = sig + (size_t)k0 * c.nnu;
-            double *dst = (cg.vvh && qi > 0) ? dvvh.as<double>() : sk;   // code 5: the bare line sum (base 0), then launch_vvh
-            launch_gas(s, cg.vvh ? SH_VOIGT_VVH : cg.shape, G, cg.jlo, cg.jhi, kn, dTk.as<double>() + k0, dPk.as<double>() + k0, dPp.as<double>() + k0,
-                       dconc.as<double>() + k0, (int)BK, dlrt.as<double>() + k0, dqref.as<double>() + (size_t)k0 * G.niso, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, c.ntile,
-                       cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), cg.win.as<WaveWin>(), cg.xtiles, dzones.as<Zone>(), dranges.as<int2>(),
-                       dgb.as<double>() + k0, cg.cut, cg.vvh ? 0.0 : c.sigma_gray, nullptr, dst, cg.vvh ? 0 : qi > 0, nullptr,
-                       (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, nullptr, &ctx->ph, nullptr, false, cg.pshift, -INFINITY, INFINITY, cg.ds);
-            if (cg.vvh && cg.ped)
-                launch_vvh_ped(s, G, cg.pa, cg.pb, cg.mb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), kn, dTk.as<double>() + k0, hot.as<LineHot>(),
-                               cold.as<LineCold>(), c.h_nu.data(), c.nu.as<double>(), c.nnu, cg.cut, dst, c.sigma_gray, nullptr, sk, qi > 0, false, dped.as<double>());
-            else if (cg.vvh)
-                launch_vvh(s, G, cg.pa, cg.mb, kn, dTk.as<double>() + k0, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, dst,
-                           c.sigma_gray, nullptr, sk, qi > 0);
-            if (cg.ped && !cg.vvh)
-                launch_pedestal(s, G, cg.pa, cg.pb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), kn, hot.as<LineHot>(), cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut,
-                                sig + (size_t)k0 * c.nnu, false, dped.as<double>());
+            p.kn = (int)std::min<int64_t>(kc, BK - k0);
+            p.Tk = dTk.as<double>() + k0; p.Pk = dPk.as<double>() + k0; p.Ppk = dPp.as<double>() + k0; p.scale = dconc.as<double>() + k0;
+            p.lrt = dlrt.as<double>() + k0; p.qrefq = dqref.as<double>() + (size_t)k0 * G.niso; p.gbound = dgb.as<double>() + k0;
+            p.sigma = sig + (size_t)k0 * c.nnu;
+            launch_gas(s, p);
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipStreamSynchronize(s));   // cc/pp/gb are locals; the device buffers are reused by the next group
@@ -3181,33 +3193,19 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
     const bool use_fork = fk.use_nodes || fk.use_near;
     for (int gi = 0; gi < (int)c.gas.size(); gi++) {
         ColGas &cg = c.gas[gi];
-        const GasTable &G = *cg.tab;
-        Interp itp = cg.itp.nlev > 0 ? interp_view(c.cheb, cg.itp, K) : Interp();
-        itp.F = c.chebF.as<double>();
-        if (!ctx->matrix_nodes) itp.sep = nullptr, itp.edge = nullptr;
-        itp.sep_always = ctx->matrix_nodes == 2;
-        interp_settings(ctx, itp);
-        itp.core = ctx->matrix_core != 0;
-        itp.fuse_apply = ctx->tune[0] != 0 && n_itp == 1;
-        // code 5 (first in the column): the bare line sum, applied at once and without side streams -- into sigma itself for the first
-        // group, else into a plane of its own -- then launch_vvh; the other groups as they were
-        double *dst = (cg.vvh && gi > 0) ? c.vvh.as<double>() : sig;
-        launch_gas(s, cg.vvh ? SH_VOIGT_VVH : cg.shape, G, cg.jlo, cg.jhi, K, c.Tk.as<double>(), c.Pk.as<double>(), cg.Pp.as<double>(), cg.conc.as<double>(), K,
-                   cg.lrt.as<double>(), cg.qref.as<double>(), c.hot.as<LineHot>(), c.cold.as<LineCold>(), c.nu.as<double>(), c.nnu, c.ntile, cg.J0.as<int32_t>(),
-                   cg.J1.as<int32_t>(), cg.win.as<WaveWin>(), cg.xtiles, cg.zones.as<Zone>(), c.ranges.as<int2>(), cg.gmax.as<double>(), cg.cut,
-                   cg.vvh ? 0.0 : c.sigma_gray, cg.vvh ? nullptr : extra, dst, cg.vvh ? 0 : gi > 0,
-                   ev ? ev + e : nullptr,
-                   (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr, ctx->far_s, itp, cg.vvh ? nullptr : &apply, &ctx->ph,
-                   (use_fork && !cg.vvh) ? &fk : nullptr, false, cg.pshift, -INFINITY, INFINITY, cg.ds);
-        if (cg.vvh && cg.ped)
-            launch_vvh_ped(s, G, cg.pa, cg.pb, cg.mb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), K, c.Tk.as<double>(), c.hot.as<LineHot>(),
-                           c.cold.as<LineCold>(), c.h_nu.data(), c.nu.as<double>(), c.nnu, cg.cut, dst, c.sigma_gray, extra, sig, gi > 0, false, c.ped.as<double>());
-        else if (cg.vvh)
-            launch_vvh(s, G, cg.pa, cg.mb, K, c.Tk.as<double>(), c.hot.as<LineHot>(), c.cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, dst,
-                       c.sigma_gray, extra, sig, gi > 0);
-        if (cg.ped && !cg.vvh)   // (into the plane the group's first kernel initialised; the near-line plane and the wings still to come only add)
-            launch_pedestal(s, G, cg.pa, cg.pb, cg.J0.as<int32_t>(), cg.J1.as<int32_t>(), K, c.hot.as<LineHot>(), c.cold.as<LineCold>(), c.nu.as<double>(), c.nnu, cg.cut, sig, false,
-                            c.ped.as<double>());
+        GasPass p = column_pass(ctx, cg);
+        p.kn = K;
+        p.Tk = c.Tk.as<double>(); p.Pk = c.Pk.as<double>(); p.Ppk = cg.Pp.as<double>(); p.scale = cg.conc.as<double>(); p.mstride = K;
+        p.lrt = cg.lrt.as<double>(); p.qrefq = cg.qref.as<double>(); p.gbound = cg.gmax.as<double>();
+        p.hot = c.hot.as<LineHot>(); p.cold = c.cold.as<LineCold>(); p.zones = cg.zones.as<Zone>(); p.ranges = c.ranges.as<int2>(); p.ped_ws = c.ped.as<double>();
+        // (code 4: the pedestal comes off the plane the group's first kernel initialised; the near-line plane and the wings still to come only add)
+        p.extra = extra; p.sigma = sig; p.accumulate = gi > 0; p.spare = c.vvh.as<double>();
+        if (cg.itp.nlev > 0) p.itp = interp_view(c.cheb, cg.itp, K);
+        p.itp.F = c.chebF.as<double>();
+        interp_settings(ctx, p.itp);
+        p.itp.fuse_apply = ctx->tune[0] != 0 && n_itp == 1;
+        p.defer = &apply; p.fork = use_fork ? &fk : nullptr; p.evg = ev ? ev + e : nullptr;
+        launch_gas(s, p);
         if (ev) { e += 6; HIPCHK(hipEventRecord(ev[e++], s)); }
     }
     if (fuse) { fuse->apply = 0; fuse->ncia = 0; fuse->Kpad = cheb_kpad(K); }

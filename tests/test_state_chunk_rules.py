@@ -1,6 +1,7 @@
 """The chunk rules of tests/test_gpu_state_chunks.py (RULES) against clearsky.jl_amd/csrc/cs_api.hip: the per-state bytes and the kc
-expressions of cs_shape_batch / cs_shape_points (shape_impl), cs_bake and cs_column_batch, the pedestal workspace and the record sizes they
-count.  If one of them changes, the GPU tests may no longer cross a chunk boundary; this fails first.  No GPU needed."""
+expressions of gas_states -- the state-chunked driver behind cs_shape_batch / cs_shape_points (shape_impl), which have it own the chunk's
+sigma, and cs_bake, which has it write the table's plane in place -- and of cs_column_batch, the pedestal workspace and the record sizes
+they count.  If one of them changes, the GPU tests may no longer cross a chunk boundary; this fails first.  No GPU needed."""
 import os
 import re
 
@@ -9,17 +10,16 @@ import test_gpu_state_chunks as SC
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "clearsky.jl_amd", "csrc")
 
-# function -> (per-state bytes, kc) as written in the source, whitespace collapsed
+# the two sides of the driver's per-state bytes: Z is the caller's device plane (NULL: the driver owns the chunk's sigma)
+OWNED = "(size_t)nnu * (sizeof(double) + sizeof(int2))"     # rule "shape"
+IN_PLACE = "(size_t)nnu * sizeof(int2)"                     # rule "bake"
+# function -> (rules, per-state bytes, kc) as written in the source, whitespace collapsed
 SOURCE = {
-    "static int shape_impl(": ("shape",
-        "const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * (sizeof(double) + sizeof(int2)) + "
-        "(ped ? ped_bytes(1, G.L) : 0);",
-        "int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));"),
-    "int cs_bake(": ("bake",
-        "const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + (size_t)nnu * sizeof(int2) + "
-        "(ped ? ped_bytes(1, G.L) : 0);",
-        "const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)M, ((size_t)4 << 30) / per_state, (size_t)65535}));"),
-    "int cs_column_batch(": ("column",
+    "static int gas_states(": (("shape", "bake"),
+        "const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) + "
+        "(Z ? " + IN_PLACE + " : " + OWNED + ") + (ped ? ped_bytes(1, G.L) : 0);",
+        "const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));"),
+    "int cs_column_batch(": (("column",),
         "const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + "
         "(size_t)c.nnu * sizeof(int2) + (any_ped ? ped_bytes(1, (int64_t)maxL) : 0) + (vvh2 ? (size_t)c.nnu * sizeof(double) : 0);",
         "const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BK, ((size_t)8 << 30) / std::max<size_t>(per_state, 1), "
@@ -52,6 +52,24 @@ def test_kc_expressions_match_the_rule_table():
         assert _norm(per_state) in body, (rule, "per-state bytes")
         assert _norm(kc) in body, (rule, "kc")
         assert re.search(r"for \(int(64_t)? k0 = 0; k0 < (K|M|BK); k0 \+= kc\)", body), (rule, "chunk loop")
+    assert {r for rules, _, _ in SOURCE.values() for r in rules} == set(SC.RULES)
+    # which side of the driver's conditional term an entry point takes: Z is what out.plane hands out, and only cs_bake sets one
+    drv = _body(src, "static int gas_states(")
+    assert "double *Z = nullptr;" in drv and "if (out.plane && (rc = out.plane(Z))) return rc;" in drv
+    assert drv.count("Z = ") == 1 and "dsig.reserve((size_t)kc * nnu * sizeof(double))" in drv
+    shape = _body(src, "static int shape_impl(")
+    assert "out.host = sigma; out.ld = ld_state;" in shape and "plane =" not in shape and "gas_states(ctx, ctx->gas[slot]," in shape
+    for head in ("int cs_shape_batch(", "int cs_shape_points("):
+        assert "return shape_impl(ctx, slot, shape," in _body(src, head), head
+    bake = _body(src, "int cs_bake(")
+    assert "out.plane = [&](double *&Z) {" in bake and "Z = tb.Z.as<double>();" in bake and "out.host" not in bake
+    assert "gas_states(ctx, ctx->gas[gas_slot]," in bake
+    # ... and the two sides are the rules' own terms, on top of the same record and pedestal bytes
+    L, n = SC.NLINES, 400
+    for ped in (False, True):
+        common = L * (SC.HOT + SC.COLD) + (SC.ped_bytes(1, L) if ped else 0)
+        assert SC.RULES["shape"][1](L, n, ped=ped) == common + n * (SC.DBL + SC.INT2)
+        assert SC.RULES["bake"][1](L, n, ped=ped) == common + n * SC.INT2
     budgets = {r: b for r, (b, _) in SC.RULES.items()}
     assert budgets == {"shape": 4 << 30, "bake": 4 << 30, "column": 8 << 30}
     assert SC.GRID_Y == 65535
