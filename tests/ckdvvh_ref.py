@@ -30,13 +30,15 @@ class _Tab:
     pass
 
 
-def tilde(cs, sl, T, a=0, b=None):
-    """the lines [a, b) of sl with S scaled so that the oracle's S_l(T) becomes S_l(T) / R(nul, T)"""
+def tilde(cs, sl, T, a=0, b=None, scale=True):
+    """the lines [a, b) of sl with S scaled so that the oracle's S_l(T) becomes S_l(T) / R(nul, T) (scale=False: the plain slice)"""
     b = len(sl.nu) if b is None else b
     o = _Tab()
     for n in ("nu", "S", "gamma_a", "gamma_s", "Epp", "na", "mu", "I"):
         setattr(o, n, np.ascontiguousarray(getattr(sl, n)[a:b]))
     o.ncheb, o.cheb = sl.ncheb, sl.cheb
+    if not scale:
+        return o
     k2 = c2(cs)
     f = []
     for nl in o.nu:
