@@ -18,7 +18,7 @@ from . import constants as K
 from ._lib import (CHEB_LD, CS_MAX_ACCEL, CS_MAX_CIA, CS_MAX_GAS, CS_MAX_TABLE, CS_SHAPE_PSHIFT, SHAPES, ClearSkyHIPError, as_f64, check,
                    dptr, lib)
 from .hitran import TMAX, TMIN, SpectralLines
-from .cia import CIATables, cia, readcia
+from .cia import CIATables, Continuum, cia, readcia
 
 # ----------------------------------------------------------------------------------------------------------------
 # small numerical helpers (host)
@@ -807,14 +807,18 @@ class UnifiedAbsorber:
         assert len(absorbers) > 0, "no absorbers... nothing to group"
         assert len(absorbers) == len(set(map(id, absorbers))), "duplicate absorbers"
         for a in absorbers:
-            if isinstance(a, (UnifiedAbsorber, AcceleratedAbsorber)) or not (isinstance(a, (AbstractGas, CIATables)) or callable(a)):
+            if isinstance(a, (UnifiedAbsorber, AcceleratedAbsorber)) or not (isinstance(a, (AbstractGas, CIATables, Continuum)) or callable(a)):
                 raise TypeError("absorbers must only be gases (<: Gas), CIA objects, or functions in the form σ(ν, T, P)")
         self.gas = tuple(a for a in absorbers if isinstance(a, AbstractGas))
         if not self.gas:
             raise ValueError("must have at least one Gas object, which specifies wavenumber samples")
         realgas = [g_ for g_ in self.gas if isinstance(g_, (Gas, DirectGas))]     # "real gases, ignoring Gray" absorbers.jl:67
-        self.cia = tuple(CIA(x, realgas) for x in absorbers if isinstance(x, CIATables))   # absorbers.jl:69
-        self.fun = tuple(a for a in absorbers if not isinstance(a, (AbstractGas, CIATables)))
+        # (a Continuum is its own pairing: .x, .g1, .g2 as a CIA has them)
+        self.cia = tuple(x if isinstance(x, Continuum) else CIA(x, realgas) for x in absorbers if isinstance(x, (CIATables, Continuum)))   # absorbers.jl:69
+        for x in self.cia:
+            if isinstance(x, Continuum):
+                assert any(x.gas is g_ for g_ in realgas), f"{x!r}: its gas is not among the absorbers"
+        self.fun = tuple(a for a in absorbers if not isinstance(a, (AbstractGas, CIATables, Continuum)))
         nu0 = self.gas[0].nu
         assert all(len(g.nu) == len(nu0) and np.array_equal(g.nu, nu0) for g in self.gas), \
             "gases must have identical wavenumber vectors"
@@ -1155,6 +1159,8 @@ class Column:
         self.cia_P1 = np.zeros((nc, self.K), order="F")
         self.cia_P2 = np.zeros((nc, self.K), order="F")
         for ci, x in enumerate(self.U.cia):
+            if isinstance(x, Continuum):
+                x.check_temperatures(self.Tk)
             for k in range(self.K):
                 self.cia_P1[ci, k] = self.Pk[k] * x.g1.concentration(self.Tk[k], self.Pk[k])   # cia…jl:378-382
                 self.cia_P2[ci, k] = self.Pk[k] * x.g2.concentration(self.Tk[k], self.Pk[k])
@@ -1198,7 +1204,7 @@ class Column:
         if not self.U.cia:
             return
         slots = np.array([self.ctx.cia_slot(x.x) for x in self.U.cia], dtype=np.int32)
-        flags = np.array([int(x.x.extrapolate) | (int(x.x.singles) << 1) for x in self.U.cia], dtype=np.int32)
+        flags = np.array([int(x.x.extrapolate) | (int(x.x.singles) << 1) | (int(x.x.radiation) << 2) for x in self.U.cia], dtype=np.int32)
         check(lib().cs_column_set_cia(self.ctx.handle, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int)),
                                       flags.ctypes.data_as(C.POINTER(C.c_int)), dptr(self.cia_P1.ravel(order="F").copy()),
                                       dptr(self.cia_P2.ravel(order="F").copy())))
@@ -1265,6 +1271,8 @@ class Column:
             if nc:
                 p1, p2 = np.zeros((nc, self.K), order="F"), np.zeros((nc, self.K), order="F")
                 for ci, x in enumerate(self.U.cia):
+                    if isinstance(x, Continuum):
+                        x.check_temperatures(Tk)
                     for k in range(self.K):
                         p1[ci, k] = self.Pk[k] * x.g1.concentration(Tk[k], self.Pk[k])      # cia…jl:378-382
                         p2[ci, k] = self.Pk[k] * x.g2.concentration(Tk[k], self.Pk[k])
@@ -1403,7 +1411,7 @@ def _fluxes_discretized(col: "Column", tau, Mup, Mdn):
     # members beyond the line-by-line gases go by slot (cs_fluxes_discretized_members; without any it is cs_fluxes_discretized)
     tslots = np.array([g_.slot for g_ in col.baked], dtype=np.int32)
     cslots = np.array([col.ctx.cia_slot(x.x) for x in col.U.cia], dtype=np.int32)
-    cflags = np.array([int(x.x.extrapolate) | (int(x.x.singles) << 1) for x in col.U.cia], dtype=np.int32)
+    cflags = np.array([int(x.x.extrapolate) | (int(x.x.singles) << 1) | (int(x.x.radiation) << 2) for x in col.U.cia], dtype=np.int32)
     args = (col.ctx.handle, col.nnu, dptr(col.nu), col.np, dptr(col.P), col.g, col.core.nlobatto,
             dptr(np.asfortranarray(col.Tn).ravel(order="F").copy()), dptr(np.asfortranarray(col.mun).ravel(order="F").copy()),
             dptr(col.Tlev), len(col.gases), ip(col.slots), ip(col.shapes), dptr(col.cuts) if len(col.cuts) else None,

@@ -173,6 +173,7 @@ struct CiaDev {
 struct ColCia {
     int slot = 0, flags = 0;
     DevBuf bands, st, rho1, rho2, rhoa;
+    DevBuf Tr;            // CS_CIA_RADIATION: [K] node temperatures, where R(nu, T_k) is formed (upload_cia_states)
     DevBuf fac;           // k_cia_tab: [K] Lo^2 rho1 rho2 / rhoa
     DevBuf tab, toff;     // k_cia_tab: ln k of every band at the temperature of every node state, [toff[b] + k * nb + c]
     DevBuf tband, cell, fx;   // k_flux: per 64-point tile the bands that reach it [ntile][CS_CIA_ACT] (-1: none), and per (slot, wavenumber)
@@ -564,7 +565,8 @@ int flux_form(const cs_ctx *ctx, const Column &c, size_t *shmem, int *nblk, int 
     return 2;
 }
 
-template <int NS>
+// RAD: the column holds a CIA object flagged CS_CIA_RADIATION (kernels that can form R(nu, T_k); every other column runs the ones it always ran)
+template <int NS, bool RAD>
 void launch_flux_ns(int form, size_t shmem, int nblk, int threads, hipStream_t s, const RtParams &p, const double *nu, const double *wts,
                            int64_t nnu, const double *sigma, const double *muk, const double *P, const double *Tlev, const double *S,
                            const double *alb, double *tau, double *Mup, double *Mdn, double *partial, const FluxFuse &f, bool three_waves = true, bool scan_recompute = false)
@@ -576,23 +578,23 @@ void launch_flux_ns(int form, size_t shmem, int nblk, int threads, hipStream_t s
             bool in_regs = false;
             if constexpr (NS <= 6) {   // (seven streams and up: the 5 x NS values no longer fit beside the rest at three waves per SIMD)
                 if (per <= 5 && !scan_recompute) {
-                    if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_scan<NS, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                    CS_LAUNCH((k_flux_scan<NS, 5>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f);
+                    if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_scan<NS, 5, RAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+                    CS_LAUNCH((k_flux_scan<NS, 5, RAD>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f);
                     in_regs = true;
                 }
             }
             if (!in_regs) {
-                if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_scan<NS, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                CS_LAUNCH((k_flux_scan<NS, 0>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f);
+                if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_scan<NS, 0, RAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+                CS_LAUNCH((k_flux_scan<NS, 0, RAD>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f);
             }
         }
     } else if (three_waves) {
-        if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_chunk3<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        CS_LAUNCH((k_flux_chunk3<NS>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f,
+        if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_chunk3<NS, RAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        CS_LAUNCH((k_flux_chunk3<NS, RAD>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f,
                   (int)((nnu + 63) / 64));
     } else {
-        if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_chunk<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        CS_LAUNCH((k_flux_chunk<NS>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f,
+        if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_chunk<NS, RAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        CS_LAUNCH((k_flux_chunk<NS, RAD>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f,
                   (int)((nnu + 63) / 64));
     }
 }
@@ -2432,13 +2434,14 @@ int cs_cia_clear(cs_ctx *ctx, int cia_slot)
 
 // per-state inputs of a CIA pair: temperature cells of every band + number densities (cia(k,T,Pa,P1,P2), :295-303).
 // Kn states with temperatures T, air pressures Pa and partial pressures P1/P2 (element k at P[idx + stride*k]); results go to the
-// given device buffers (a column's own, or a batch's)
+// given device buffers (a column's own, or a batch's).  An object flagged CS_CIA_RADIATION also gets the temperatures themselves (dT):
+// R(nu, T_k) follows the node states like everything else here
 static int upload_cia_states(cs_ctx *ctx, int slot, int flags, int Kn, const double *T, const double *Pa, const double *P1,
-                             const double *P2, int stride, int idx, DevBuf &dst, DevBuf &d1, DevBuf &d2, DevBuf &da)
+                             const double *P2, int stride, int idx, DevBuf &dst, DevBuf &d1, DevBuf &d2, DevBuf &da, DevBuf &dT)
 {
     CiaDev &cd = ctx->cia[slot];
     const int K = Kn, nband = (int)cd.bands.size();
-    const bool extrap = flags & 1, singles = flags & 2;
+    const bool extrap = flags & CS_CIA_EXTRAPOLATE, singles = flags & CS_CIA_SINGLES;
     std::vector<CiaState> st((size_t)nband * K);
     for (int b = 0; b < nband; b++) {
         const std::vector<double> &Tg = cd.bands[b].T;
@@ -2472,15 +2475,26 @@ static int upload_cia_states(cs_ctx *ctx, int slot, int flags, int Kn, const dou
     hipStream_t s = ctx->stream;
     int rc;
     if ((rc = upload(dst, st.data(), st.size(), s)) || (rc = upload(d1, r1.data(), K, s)) ||
-        (rc = upload(d2, r2.data(), K, s)) || (rc = upload(da, ra.data(), K, s)))
+        (rc = upload(d2, r2.data(), K, s)) || (rc = upload(da, ra.data(), K, s)) ||
+        ((flags & CS_CIA_RADIATION) && (rc = upload(dT, T, K, s))))
         return rc;
     HIPCHK(hipStreamSynchronize(s));   // the host vectors are locals
     return CS_OK;
 }
+// k_cia over Kn states with the given per-state inputs (a column's own, or a batch's); an object flagged CS_CIA_RADIATION runs k_cia<true>
+static void launch_cia(hipStream_t s, Column &c, ColCia &cc, DevBuf &st, DevBuf &d1, DevBuf &d2, DevBuf &da, DevBuf &dT, int Kn, double *sig)
+{
+    if (cc.flags & CS_CIA_RADIATION)
+        CS_LAUNCH(k_cia<true>, dim3((unsigned)c.ntile), dim3(256), 0, s, cc.nband, cc.bands.as<CiaBand>(), st.as<CiaState>(), c.nu.as<double>(),
+                  c.nnu, Kn, d1.as<double>(), d2.as<double>(), da.as<double>(), dT.as<double>(), sig);
+    else
+        CS_LAUNCH(k_cia<false>, dim3((unsigned)c.ntile), dim3(256), 0, s, cc.nband, cc.bands.as<CiaBand>(), st.as<CiaState>(), c.nu.as<double>(),
+                  c.nnu, Kn, d1.as<double>(), d2.as<double>(), da.as<double>(), (const double *)nullptr, sig);
+}
 static int upload_cia_state(cs_ctx *ctx, ColCia &cc, const double *P1, const double *P2, int stride, int idx)
 {
     Column &c = ctx->col;
-    return upload_cia_states(ctx, cc.slot, cc.flags, c.K, c.h_Tk.data(), c.h_Pk.data(), P1, P2, stride, idx, cc.st, cc.rho1, cc.rho2, cc.rhoa);
+    return upload_cia_states(ctx, cc.slot, cc.flags, c.K, c.h_Tk.data(), c.h_Pk.data(), P1, P2, stride, idx, cc.st, cc.rho1, cc.rho2, cc.rhoa, cc.Tr);
 }
 
 int cs_column_set_cia(cs_ctx *ctx, int ncia, const int *cia_slots, const int *flags, const double *P1, const double *P2)
@@ -2493,6 +2507,11 @@ int cs_column_set_cia(cs_ctx *ctx, int ncia, const int *cia_slots, const int *fl
         if (cia_slots[t] < 0 || cia_slots[t] >= CS_MAX_CIA || !ctx->cia[cia_slots[t]].present) {
             c.cia.clear();
             return fail(CS_EINVAL, "CIA slot %d is empty", cia_slots[t]);
+        }
+    for (int t = 0; t < ncia && flags; t++)
+        if (flags[t] & ~(CS_CIA_EXTRAPOLATE | CS_CIA_SINGLES | CS_CIA_RADIATION)) {
+            c.cia.clear();
+            return fail(CS_EINVAL, "CIA flags %d: only CS_CIA_EXTRAPOLATE, CS_CIA_SINGLES and CS_CIA_RADIATION are defined", flags[t]);
         }
     // what depends on the grid and the tables alone (band descriptors, sample cells of every wavenumber) is kept while the pairs named
     // are the ones the column already holds: an RCM loop re-sets its pairs on every call for the partial pressures only
@@ -2509,7 +2528,9 @@ int cs_column_set_cia(cs_ctx *ctx, int ncia, const int *cia_slots, const int *fl
     for (int t = 0; t < ncia; t++) {
         ColCia &cc = c.cia[t];
         cc.slot = cia_slots[t];
-        cc.flags = flags ? flags[t] : 0;
+        const int fl = flags ? flags[t] : 0;
+        if (same && ((fl ^ cc.flags) & CS_CIA_RADIATION)) drop_graph(c);   // (the captured launches name the kernels of the other kind)
+        cc.flags = fl;
         CiaDev &cd = ctx->cia[cc.slot];
         if (!same) {
             cc.generation = cd.generation;
@@ -3109,7 +3130,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     }
     if (!shared_sigma && !c.cia.empty()) {
         const int nc = (int)c.cia.size();
-        DevBuf dst, d1, d2, da;
+        DevBuf dst, d1, d2, da, dT;
         std::vector<double> p1(BK), p2(BK);
         for (int t = 0; t < nc; t++) {
             ColCia &ci = c.cia[t];
@@ -3118,9 +3139,8 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
                     p1[(size_t)b * K + k] = cia_P1[(size_t)b * nc * K + t + (size_t)nc * k];
                     p2[(size_t)b * K + k] = cia_P2[(size_t)b * nc * K + t + (size_t)nc * k];
                 }
-            if ((rc = upload_cia_states(ctx, ci.slot, ci.flags, (int)BK, Tk.data(), Pk.data(), p1.data(), p2.data(), 1, 0, dst, d1, d2, da))) return rc;
-            CS_LAUNCH(k_cia, dim3((unsigned)c.ntile), dim3(256), 0, s, ci.nband, ci.bands.as<CiaBand>(), dst.as<CiaState>(),
-                               c.nu.as<double>(), c.nnu, (int)BK, d1.as<double>(), d2.as<double>(), da.as<double>(), sig);
+            if ((rc = upload_cia_states(ctx, ci.slot, ci.flags, (int)BK, Tk.data(), Pk.data(), p1.data(), p2.data(), 1, 0, dst, d1, d2, da, dT))) return rc;
+            launch_cia(s, c, ci, dst, d1, d2, da, dT, (int)BK, sig);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(s));
         }
@@ -3255,13 +3275,13 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
             pd.tband = cc.tband.as<int32_t>(); pd.cell = cc.cell.as<int32_t>(); pd.fx = cc.fx.as<double>();
             pd.nslot = std::min(std::max(cc.max_overlap, 1), (int)CS_CIA_ACT);
             pd.fac = cc.fac.as<double>();
+            pd.Tr = (cc.flags & CS_CIA_RADIATION) ? cc.Tr.as<double>() : nullptr;
             int maxnb = 0;
             for (auto &b : ctx->cia[cc.slot].bands) maxnb = std::max(maxnb, (int)b.nu.size());
             CS_LAUNCH(k_cia_tab, dim3((unsigned)((maxnb + 255) / 256), (unsigned)K, (unsigned)cc.nband), dim3(256), 0, s, pd, K);
             continue;
         }
-        CS_LAUNCH(k_cia, dim3((unsigned)c.ntile), dim3(256), 0, s, cc.nband, cc.bands.as<CiaBand>(), cc.st.as<CiaState>(),
-                           c.nu.as<double>(), c.nnu, K, cc.rho1.as<double>(), cc.rho2.as<double>(), cc.rhoa.as<double>(), sig);
+        launch_cia(s, c, cc, cc.st, cc.rho1, cc.rho2, cc.rhoa, cc.Tr, K, sig);
     }
     fork_join(&fk, s);
     c.near_live = false;
@@ -3339,13 +3359,17 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
         if ((ctx->tune[15] & 128) && c.fluxdbg.reserve((8 + 2 * (size_t)fblk + 32) * sizeof(unsigned long long)) == hipSuccess) fuse.dbg = c.fluxdbg.as<unsigned long long>();
         // the chunked form always writes the layer optical depths (its upward sweep reads them back): into the caller's plane or scratch
         double *dtau = (c.want_tau || form == 2) ? c.tau.as<double>() : nullptr;   // (forms 1 and 3 keep the optical depths in LDS)
-#define CS_FLUX_CASE(N) case N: launch_flux_ns<N>(form, fsh, fblk, fthr, s, c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, sig, c.muk.as<double>(), \
-                                                  c.P.as<double>(), c.Tlev.as<double>(), dS, dA, dtau, dMu, dMd, c.partial.as<double>(), fuse, (ctx->tune[15] & 8) == 0, (ctx->tune[15] & 2048) != 0); break;
+        bool rad = false;
+        for (int t = 0; t < fuse.ncia; t++) rad = rad || fuse.cia[t].Tr != nullptr;
+#define CS_FLUX_ARGS form, fsh, fblk, fthr, s, c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, sig, c.muk.as<double>(), c.P.as<double>(), \
+                     c.Tlev.as<double>(), dS, dA, dtau, dMu, dMd, c.partial.as<double>(), fuse, (ctx->tune[15] & 8) == 0, (ctx->tune[15] & 2048) != 0
+#define CS_FLUX_CASE(N) case N: if (rad) launch_flux_ns<N, true>(CS_FLUX_ARGS); else launch_flux_ns<N, false>(CS_FLUX_ARGS); break;
         switch (c.nstream) {
             CS_FLUX_CASE(1) CS_FLUX_CASE(2) CS_FLUX_CASE(3) CS_FLUX_CASE(4) CS_FLUX_CASE(5) CS_FLUX_CASE(6) CS_FLUX_CASE(7) CS_FLUX_CASE(8)
             CS_FLUX_CASE(9) CS_FLUX_CASE(10) CS_FLUX_CASE(11) CS_FLUX_CASE(12) CS_FLUX_CASE(13) CS_FLUX_CASE(14) CS_FLUX_CASE(15) CS_FLUX_CASE(16)
         }
 #undef CS_FLUX_CASE
+#undef CS_FLUX_ARGS
     } else {
         if (c.rtg.streams) g_disp.flags |= CS_DF_RT_STREAMS;
         launch_rt(c.nstream, c.rtg, 1, s, c.rt, c.nu.as<double>(), c.wts.as<double>(),

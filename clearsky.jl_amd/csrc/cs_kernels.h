@@ -34,6 +34,10 @@ constexpr double kSqLn2 = 0.8325546111576977;     // sqrt(ln 2)            line_
 constexpr double kOSqPiLn2 = 0.46971863934982566;  // 1/sqrt(pi/ln 2)       line_shapes.jl:3
 constexpr double kC2 = 100.0 * kHp * kC / kKb;     // 100 h c / k           line_shapes.jl:5
 
+// the radiation term R(nu, T) = nu tanh(c2 nu / 2T): of the Van Vleck-Huber shapes (k_vvh_finish, k_vvh_ped_finish) and of CIA objects
+// flagged CS_CIA_RADIATION (k_cia, cia_add).  Formed as nu tanh(.), which is exact to rounding for small arguments (nu -> 0: R -> 0).
+__device__ __forceinline__ double radiation_term(double v, double T) { return v * tanh(kC2 * v / (2.0 * T)); }
+
 enum { SH_VOIGT = 0, SH_LORENTZ = 1, SH_DOPPLER = 2, SH_PHCO2 = 3 };
 // shape code 4 (pedestal-removed Voigt) never reaches a line kernel: its groups run as SH_VOIGT, then k_ped_values / k_ped_sub
 constexpr int SH_VOIGT_CKD = 4;
@@ -3385,10 +3389,12 @@ struct CiaState {       // per (band, node): temperature cell of the band's T gr
 #define CS_MAX_CIA_BAND 24
 
 // sigma[k][nu] += (ktot*Lo^2)*rho1*rho2/rhoa   (cia(k,T,Pa,P1,P2), :295-303)
+// RAD (an object flagged CS_CIA_RADIATION, a continuum in MT_CKD form): ktot is multiplied by R(nu, T_k) first, Tr[k] = T_k
+template <bool RAD>
 __global__ __launch_bounds__(256) void k_cia(int nband, const CiaBand *__restrict__ bands, const CiaState *__restrict__ st,
                                               const double *__restrict__ nu, int64_t nnu, int K,
                                               const double *__restrict__ rho1, const double *__restrict__ rho2,
-                                              const double *__restrict__ rhoa, double *__restrict__ sigma)
+                                              const double *__restrict__ rhoa, const double *__restrict__ Tr, double *__restrict__ sigma)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nnu) return;
@@ -3426,6 +3432,7 @@ __global__ __launch_bounds__(256) void k_cia(int nband, const CiaBand *__restric
             }
             ktot += exp(lnk);
         }
+        if (RAD) ktot *= radiation_term(v, Tr[k]);
         if (ktot != 0.0) sigma[(size_t)k * nnu + i] += (ktot * Lo2) * rho1[k] * rho2[k] / rhoa[k];
     }
 }
@@ -3447,6 +3454,7 @@ struct CiaPairDev {
     const int64_t *toff;       // [nband]
     const double *rho1, *rho2, *rhoa;   // [K]
     double *fac;               // [K] Lo^2 rho1 rho2 / rhoa of cia(k, T, Pa, P1, P2), :295-303 (k_cia_tab)
+    const double *Tr;          // [K] node temperatures of an object flagged CS_CIA_RADIATION (NULL: not flagged)
     // per grid (built once at cs_column_set_cia): the bands reaching each 64-point tile, [ntile][CS_CIA_ACT] (-1: none); the sample cell
     // of wavenumber i in the band of slot q, cell[q * nnu + i] (-1: outside the band), and its position in the cell, fx[q * nnu + i]
     const int32_t *tband, *cell;
@@ -3508,6 +3516,10 @@ __global__ __launch_bounds__(256) void k_cia_tab(CiaPairDev p, int K)
 // the linear interpolation in nu of the band's samples at the state's temperature (tab).  Written for memory-level parallelism: what
 // depends on the band alone is loaded once, the two samples of eight states are requested together, nothing in the state loop waits
 // for a load that depends on another load.  (Where two bands overlap their terms are added one after the other.)
+// RAD (the flux kernels of a column that holds an object flagged CS_CIA_RADIATION; every other column runs the <false> kernels, whose
+// instructions are what they always were): the terms of an object with p.Tr != NULL are multiplied by R(nu, T_k) at the lane's wavenumber
+// -- one tanh per (point, state, band on the tile), behind a wave-uniform test, so an unflagged object beside a flagged one pays no tanh.
+template <bool RAD>
 __device__ __forceinline__ void cia_add(const CiaPairDev &p, int tile, int64_t ii, int64_t nnu, double v, int K, int k0, int kstep, int n,
                                         double *__restrict__ dst, int R)
 {
@@ -3542,6 +3554,7 @@ __device__ __forceinline__ void cia_add(const CiaPairDev &p, int tile, int64_t i
                 } else {             // finite samples (floatmin-clamped, :205): the flux kernel's own exponential (<= 2 ulp, tests/test_gpu_kat.py)
                     e = exp_rt((1.0 - x) * t0[s] + x * t1[s]);
                 }
+                if (RAD && p.Tr) e *= radiation_term(v, p.Tr[k]);      // (wave-uniform)
                 if (cc >= 0) dst[(size_t)(k % R) * 64] += e * p.fac[k];
             }
         }
@@ -3550,6 +3563,7 @@ __device__ __forceinline__ void cia_add(const CiaPairDev &p, int tile, int64_t i
 
 // phase A: sig[k][lane] = Sigma(U, i, T_k, P_k) of the block's tile for every node state k, in the order the separate kernels add
 // it up: ((sigma + interpolated wings) + CIA pairs, one after the other) + sigma2
+template <bool RAD>
 __device__ __forceinline__ void flux_sigma_tile(const FluxFuse &f, int K, int64_t nnu, int tile, const double *__restrict__ sigma,
                                                 const double *__restrict__ nu, double *__restrict__ sig, int wave, int nwaves, int lane)
 {
@@ -3618,7 +3632,7 @@ __device__ __forceinline__ void flux_sigma_tile(const FluxFuse &f, int K, int64_
     const double v = nu[ii];
     for (int pq = 0; pq < f.ncia; pq++)
         for (int k0 = wave; k0 < K; k0 += 16 * nwaves)        // this wave's states k0, k0 + nwaves, ..., sixteen at a time
-            cia_add(f.cia[pq], tile, ii, nnu, v, K, k0, nwaves, 16, sig + lane, K);
+            cia_add<RAD>(f.cia[pq], tile, ii, nnu, v, K, k0, nwaves, 16, sig + lane, K);
     if (f.sigma2)
         for (int k = wave; k < K; k += nwaves) sig[(size_t)k * 64 + lane] += f.sigma2[(size_t)k * nnu + ii];
 }
@@ -3710,7 +3724,8 @@ __device__ __forceinline__ void flux_last_block_reduce(const FluxFuse &f, const 
 //   phase 3     every wave runs its chunk again from its true incoming intensity and forms what radiate! returns at its levels.
 // Inside a chunk the operations and their order are discretized.jl:282-322's; across chunk boundaries the incoming intensity was
 // formed as A I + B instead of layer by layer: the same numbers to a few units in the last place (tests: 1e-13 against k_rt_streams).
-template <int NS, int PER>
+// (RAD: the column holds a CIA object flagged CS_CIA_RADIATION, cia_add)
+template <int NS, int PER, bool RAD>
 __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__restrict__ nu, const double *__restrict__ wts, int64_t nnu,
                                                     const double *__restrict__ sigma, const double *__restrict__ muk, const double *__restrict__ P,
                                                     const double *__restrict__ Tlev, const double *__restrict__ S_toa,
@@ -3728,7 +3743,7 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
     const int64_t jj = live ? j : nnu - 1;
     flux_stamp(f, 0);
     flux_stamp_block(f, 0);
-    flux_sigma_tile(f, K, nnu, (int)blockIdx.x, sigma, nu, sig, wave, NW, lane);
+    flux_sigma_tile<RAD>(f, K, nnu, (int)blockIdx.x, sigma, nu, sig, wave, NW, lane);
     __syncthreads();
     flux_stamp(f, 1);
     const double v = nu[jj];
@@ -3978,7 +3993,7 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
 // rows of LDS per wave, just ahead of the downward sweep that consumes them: the interpolation product of the chunk (4 matrix
 // instructions per 4-node step: one F operand, four C operands), sigma and sigma2 of the chunk, its CIA terms.  The layer optical
 // depths go to `tau` (the caller's output, or scratch) for the upward sweep, as in k_rt.  LDS: 8.7 KB per wave with nlobatto = 2.
-template <int NS>
+template <int NS, bool RAD>
 __device__ __forceinline__ void flux_chunk_body(const RtParams &p, const double *__restrict__ nu, const double *__restrict__ wts, int64_t nnu,
                                                 const double *__restrict__ sigma, const double *__restrict__ muk, const double *__restrict__ P,
                                                 const double *__restrict__ Tlev, const double *__restrict__ S_toa,
@@ -4046,7 +4061,7 @@ __device__ __forceinline__ void flux_chunk_body(const RtParams &p, const double 
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        for (int pq = 0; pq < f.ncia; pq++) cia_add(f.cia[pq], tl_, jj, nnu, v, K, k0, 1, 16, ring + lane, R);
+        for (int pq = 0; pq < f.ncia; pq++) cia_add<RAD>(f.cia[pq], tl_, jj, nnu, v, K, k0, 1, 16, ring + lane, R);
         if (f.sigma2)
             for (int k = k0; k < min(k0 + 16, K); k++) ring[(size_t)(k % R) * 64 + lane] += f.sigma2[(size_t)k * nnu + jj];
         chunk_next = k0 + 16;
@@ -4145,14 +4160,14 @@ __device__ __forceinline__ void flux_chunk_body(const RtParams &p, const double 
 // (the register budget decides how many waves a SIMD holds: 168 registers = 3 waves, nothing spilled -- the default; 128 = 4 waves with a
 //  few values in scratch: BASELINE configs[4] 1.59 vs 2.58 ms (profiles/r04_notes.md).  Both are kept for A/B, cs_set_tuning key 15 | 8)
 #define CS_FLUX_CHUNK_KERNEL(NAME, WAVES)                                                                                                       \
-    template <int NS>                                                                                                                           \
+    template <int NS, bool RAD>                                                                                                                 \
     __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void NAME(                                              \
         RtParams p, const double *__restrict__ nu, const double *__restrict__ wts, int64_t nnu, const double *__restrict__ sigma,               \
         const double *__restrict__ muk, const double *__restrict__ P, const double *__restrict__ Tlev, const double *__restrict__ S_toa,         \
         const double *__restrict__ albedo, double *__restrict__ tau, double *__restrict__ Mup, double *__restrict__ Mdn,                         \
         double *__restrict__ partial, FluxFuse f, int ntile)                                                                                    \
     {                                                                                                                                           \
-        flux_chunk_body<NS>(p, nu, wts, nnu, sigma, muk, P, Tlev, S_toa, albedo, tau, Mup, Mdn, partial, f, ntile);                             \
+        flux_chunk_body<NS, RAD>(p, nu, wts, nnu, sigma, muk, P, Tlev, S_toa, albedo, tau, Mup, Mdn, partial, f, ntile);                        \
     }
 CS_FLUX_CHUNK_KERNEL(k_flux_chunk, 4)
 CS_FLUX_CHUNK_KERNEL(k_flux_chunk3, 3)
@@ -4320,7 +4335,7 @@ __global__ __launch_bounds__(256) void k_vvh_finish(const double *__restrict__ n
         const LineCold c = cold[idx];
         s += c.A * fad_re(x * hot[idx].p1, c.y);
     }
-    const double r = v * tanh(kC2 * v / (2.0 * Tk[k])) * s;
+    const double r = radiation_term(v, Tk[k]) * s;
     sigma[o] = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
 }
 
@@ -4395,7 +4410,7 @@ __global__ __launch_bounds__(256) void k_vvh_ped_finish(const double *__restrict
             const LineCold c = cold[idx];
             s += c.A * fad_re(x * hot[idx].p1, c.y) - p[idx];
         }
-        const double r = v * tanh(kC2 * v / (2.0 * Tk[k])) * s;
+        const double r = radiation_term(v, Tk[k]) * s;
         const double out = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
         sigma[o] = clamp ? fmax(out, 0.0) : out;
     }

@@ -185,7 +185,22 @@ int cs_table_eval(cs_ctx *ctx, int table_slot, double T, double P, int64_t i0, i
  * evaluated bilinearly inside the grid (BilinearInterpolator of ln k, :207); nt == 1 marks a single-temperature range
  * (LinearInterpolator in nu, :188), used only when `singles` is set.  k <= 0 must already be replaced as the reference
  * does (floatmin for grids :205, 0 -> ln 0 = -inf for singles :187).
+ *
+ * The flags a column gives with each object (cs_column_set_cia, cs_fluxes_discretized_members); any other bit is CS_EINVAL:
+ *   CS_CIA_EXTRAPOLATE  beyond a band's temperature range ln k is taken at the nearest end (:261-263); off: the band adds nothing there
+ *   CS_CIA_SINGLES      single-temperature ranges are used (:267)
+ *   CS_CIA_RADIATION    a continuum in MT_CKD form: the object's contribution at wavenumber nu_i and node k becomes
+ *                         R(nu_i, T_k) (sum over bands of exp(ln k_b)) Lo^2 rho1 rho2 / rhoa,   R(nu, T) = nu tanh(c2 nu / 2T) [cm^-1],
+ *                       with R the radiation term of CS_SHAPE_VOIGT_VVH, formed the same way (exact to rounding as nu -> 0) at the exact
+ *                       wavenumber and node temperature -- it is neither log-linear in T nor linear in nu between samples, so it cannot
+ *                       be folded into the tables.  A flagged table holds ln(C / n_ref): C the continuum coefficient [cm^2 molecule^-1
+ *                       per cm^-1], n_ref = P_ref / (k T_ref) [molecule cm^-3], so ln k is in cm^5 molecule^-2 per cm^-1 and R supplies
+ *                       the missing cm^-1; with P1, P2 the partial pressures of the absorber and its partner the term is
+ *                       x1 R C n2 / n_ref per molecule of air.  The flag is per object: R multiplies the flagged object's band sum only.
  */
+#define CS_CIA_EXTRAPOLATE 1
+#define CS_CIA_SINGLES 2
+#define CS_CIA_RADIATION 4
 int cs_cia_begin(cs_ctx *ctx, int cia_slot, int nband);
 int cs_cia_band(cs_ctx *ctx, int cia_slot, int band, int nb, const double *nu_b, int nt, const double *T_b, const double *lnk);
 int cs_cia_clear(cs_ctx *ctx, int cia_slot);
@@ -234,7 +249,8 @@ int cs_fluxes_discretized_multi(cs_ctx *const *ctxs, int nctx, int64_t nnu, cons
  * absorbers...) fluxes.jl:238-279 + intF! shared.jl:125-137 with the sigma-chain of absorbers.jl:84-95 on the device -- line-by-line
  * gases (gas_slots, as cs_fluxes_discretized), baked Gas objects (gases.jl:205-281: table_slots of cs_bake / cs_table_upload with
  * conc_tab[ntab, K] = fC_t(T_k, P_k)), CIA pairs (collision_induced_absorption.jl:431-465: cia_slots of cs_cia_begin / cs_cia_band,
- * cia_flags bit 0 = extrapolate, bit 1 = singles, cia_P1 / cia_P2 [ncia, K] = P_k * concentration(g1 / g2, T_k, P_k), :378-382), the
+ * cia_flags = CS_CIA_EXTRAPOLATE | CS_CIA_SINGLES | CS_CIA_RADIATION (above: with the last one the object's band sum is multiplied by
+ * R(nu_i, T_k) = nu tanh(c2 nu / 2T) and its tables hold ln(C / n_ref), a continuum in MT_CKD form), cia_P1 / cia_P2 [ncia, K] = P_k * concentration(g1 / g2, T_k, P_k), :378-382), the
  * gray term and host-evaluated functions (sigma_gray, sigma_extra) -- or, instead of all of these, an AcceleratedAbsorber
  * (absorbers.jl:114-203, what heating! hands radiate!, radiative_convective.jl:112-113): accel_slot >= 0 with ngas = ntab = ncia = 0;
  * accel_slot = -1 otherwise.  Everything else as cs_fluxes_discretized, which is this call without tables, CIA pairs and accelerated
@@ -288,7 +304,10 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
 int cs_column_set_tables(cs_ctx *ctx, int ntab, const int *table_slots, const double *conc_tab);
 /* add CIA pairs to the resident column: sigma += cia(nu, tables, T, P, P1, P2) (collision_induced_absorption.jl:295-303,
  * :318-323, the CIA functor :465).  P1, P2: [ncia, K] column-major partial pressures of the two gases at the nodes
- * (= P*concentration(g, T, P), :378-382); flags[c] bit 0 = extrapolate, bit 1 = singles (:163). */
+ * (= P*concentration(g, T, P), :378-382); flags[c] = CS_CIA_EXTRAPOLATE (bit 0) | CS_CIA_SINGLES (bit 1) (:163) | CS_CIA_RADIATION
+ * (bit 2: sigma += R(nu_i, T_k) (sum over bands of exp(ln k_b)) Lo^2 rho1 rho2 / rhoa with R(nu, T) = nu tanh(c2 nu / 2T) and ln k =
+ * ln(C / n_ref) in cm^5 molecule^-2 per cm^-1, see cs_cia_begin); any other bit is CS_EINVAL.  Called again after
+ * cs_column_update_state it re-forms the per-node inputs, R's temperatures among them. */
 int cs_column_set_cia(cs_ctx *ctx, int ncia, const int *cia_slots, const int *flags, const double *P1, const double *P2);
 int cs_column_run(cs_ctx *ctx, void *stream);
 /* only the cross-section stage of cs_column_run: sigma[K][nnu] = Sigma(absorbers, i, T_k, P_k) for every wavenumber and node

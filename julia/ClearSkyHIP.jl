@@ -18,6 +18,7 @@
 #       - `GrayGas`     [gases.jl:342-360]                                        -> sigma_gray
 #       - `SemiGrayGas` [gases.jl:366-386]                                        -> a per-ν vector in sigma_extra
 #       - `CIATables`   paired with any of the gases above by formula [cia...jl:431-465] -> cs_cia_begin / cs_cia_band
+#       - `Continuum`   a continuum in MT_CKD form, x₁ R(ν,T) C(ν,T) n₂/n_ref: CIA tables flagged CS_CIA_RADIATION -> cs_cia_begin / cs_cia_band
 #       - functions σ(ν,T,P) [absorbers.jl:24,71]                                 -> evaluated here, sigma_extra
 #       - `AcceleratedAbsorber` [absorbers.jl:114-203], what `RCM` holds and `heating!` passes -> cs_accel_upload, or
 #         kept on the device by the `update!` method below                        -> cs_accel_store
@@ -39,6 +40,7 @@ const CS_MAX_GAS = 16        # gas slots per context (include/clearsky_hip.h)
 const CS_MAX_TABLE = 16      # opacity-table slots
 const CS_MAX_CIA = 8         # CIA slots
 const CS_MAX_ACCEL = 4       # accelerated-absorber slots
+const CS_CIA_EXTRAPOLATE, CS_CIA_SINGLES, CS_CIA_RADIATION = Cint(1), Cint(2), Cint(4)   # cia_flags (include/clearsky_hip.h)
 const SHAPES = Dict(:voigt=>0, :lorentz=>1, :doppler=>2, :PHCO2=>3, :voigtCKD=>4, :voigtVVH=>5, :voigtCKDVVH=>6)   # 4: pedestal-removed Voigt (CS_SHAPE_VOIGT_CKD), 5: Van Vleck-Huber Voigt (CS_SHAPE_VOIGT_VVH), 6: both (CS_SHAPE_VOIGT_CKD_VVH)
 
 lasterror() = unsafe_string(ccall((:cs_last_error, LIB), Cstring, ()))
@@ -425,7 +427,9 @@ struct HIPCIA{T,U}
     x::CIATables
     g₁::T
     g₂::U
+    radiation::Bool      # CS_CIA_RADIATION: the tables' k is multiplied by R(ν, T) = ν tanh(c₂ν/2T) (a Continuum)
 end
+HIPCIA(name, formulae, x::CIATables, g₁, g₂) = HIPCIA(name, formulae, x, g₁, g₂, false)
 
 function findpairgas(f::String, cianame::String, gases::Tuple)
     idx = findall(g -> g.formula == f, gases)
@@ -440,20 +444,73 @@ function HIPCIA(x::CIATables, gases::Tuple)
     HIPCIA(x.name, x.formulae, x, findpairgas(f₁, x.name, gases), findpairgas(f₂, x.name, gases))
 end
 
-(χ::HIPCIA)(ν, T, P) = cia(ν, χ.x, T, P, P*concentration(χ.g₁, T, P), P*concentration(χ.g₂, T, P))
+const C₂ = 100.0*ClearSky.𝐡*ClearSky.𝐜/ClearSky.𝐤       # 100 h c / k [cm K], line_shapes.jl:5
+radiationterm(ν, T) = ν*tanh(C₂*ν/(2.0*T))                # R(ν, T) [cm⁻¹], as the device forms it (exact to rounding as ν → 0)
+
+(χ::HIPCIA)(ν, T, P) = (χ.radiation ? radiationterm(ν, T) : 1.0)*cia(ν, χ.x, T, P, P*concentration(χ.g₁, T, P), P*concentration(χ.g₂, T, P))
+
+#-------------------------------------------------------------------------------
+# A continuum in MT_CKD form, per molecule of air:  σ(ν; T, P) = x₁ R(ν, T) C(ν, T) n₂ / n_ref,  n_ref = P_ref/(k T_ref).
+# That is the CIA functor σ = k Lo² ρ₁ρ₂/ρₐ with k = R C / n_ref; R is neither log-linear in T nor linear in ν between samples, so the
+# tables hold k = C / n_ref and the device multiplies by R at the exact wavenumber and node temperature (CS_CIA_RADIATION).
+#   data  Vector of Dict("ν"=>..., "T"=>..., "C"=>...) on the same samples, C [cm² molecule⁻¹ per cm⁻¹]: one temperature (C does not
+#         depend on T) or several (ln C bilinear; temperatures outside the table are refused, never clamped)
+#   gas   the absorber (molecule 1); kind = :self pairs it with itself (P₂ = P C_gas), :foreign with everything else (P₂ = P (1 - C_gas))
+
+struct ForeignPartner{G}
+    gas::G
+end
+concentration(p::ForeignPartner, T, P) = 1.0 - concentration(p.gas, T, P)
+
+struct Continuum{G}
+    name::String
+    kind::Symbol
+    x::CIATables
+    gas::G
+    T::Vector{Float64}
+end
+
+function Continuum(data::Vector, gas; kind::Symbol=:self, P_ref=101325.0, T_ref=296.0)
+    kind in (:self, :foreign) || error("kind must be :self or :foreign, not $kind")
+    isempty(data) && error("no continuum coefficients given")
+    n_ref = 1e-6*P_ref/(ClearSky.𝐤*T_ref)                                    # molecule cm⁻³
+    name = string(gas.formula, "-", kind == :self ? gas.formula : "air")
+    rows = Dict{String,Any}[]
+    for d in data
+        ν, C = collect(Float64, d["ν"]), collect(Float64, d["C"])
+        (all(isfinite, C) && all(>(0), C)) || error("continuum coefficients must be finite and positive (the tables hold ln C)")
+        push!(rows, Dict{String,Any}("symbol"=>name, "νmin"=>ν[1], "νmax"=>ν[end], "T"=>Float64(d["T"]), "ν"=>ν, "k"=>C./n_ref))
+    end
+    x = CIATables(rows; extrapolate=false, singles=length(rows) == 1, verbose=false)
+    Continuum(name, kind, x, gas, sort(Float64[d["T"] for d in data]))
+end
+
+function checktemperatures(c::Continuum, T)
+    length(c.T) < 2 && return nothing
+    for t in T
+        (c.T[1] <= t <= c.T[end]) || error("$(c.kind) continuum $(c.name): temperature $t K is outside the table's range [$(c.T[1]), $(c.T[end])] K (extend the table: the continuum is never extrapolated)")
+    end
+    nothing
+end
+
+HIPCIA(c::Continuum) = HIPCIA(c.name, c.x.formulae, c.x, c.gas, c.kind == :self ? c.gas : ForeignPartner(c.gas), true)
+(c::Continuum)(ν, T, P) = (checktemperatures(c, T); HIPCIA(c)(ν, T, P))
 
 # UnifiedAbsorber(absorbers) [absorbers.jl:50-77] for line-ups that hold DirectGas / HIPGas members: the same checks and the same
 # struct (its type parameters are open), with the CIA pairs formed over ALL real gases.  Line-ups without such members fall through
 # to the reference's method untouched.
-const HIPInput = Union{AbstractGas, CIATables, Function}
+const HIPInput = Union{AbstractGas, CIATables, Continuum, Function}
 function ClearSky.UnifiedAbsorber(absorbers::Tuple{Vararg{HIPInput}})
     any(a -> a isa HIPLineGas, absorbers) || return invoke(UnifiedAbsorber, Tuple{Tuple}, absorbers)
     @assert length(absorbers) > 0 "no absorbers... nothing to group"
     @assert length(absorbers) == length(unique(absorbers)) "duplicate absorbers"
     gas = Tuple(a for a in absorbers if a isa AbstractGas)
     realgas = Tuple(g for g in gas if g isa PairGas)                              # "real gases, ignoring Gray", absorbers.jl:67
-    ciax = Tuple(HIPCIA(x, realgas) for x in absorbers if x isa CIATables)
-    fun = Tuple(a for a in absorbers if !(a isa AbstractGas) && !(a isa CIATables))
+    ciax = Tuple(x isa Continuum ? HIPCIA(x) : HIPCIA(x, realgas) for x in absorbers if x isa Union{CIATables,Continuum})
+    for x in absorbers
+        x isa Continuum && @assert any(g -> g === x.gas, realgas) "continuum $(x.name): its gas is not among the absorbers"
+    end
+    fun = Tuple(a for a in absorbers if !(a isa AbstractGas) && !(a isa Union{CIATables,Continuum}))
     ν = getwavenumbers(gas...)
     UnifiedAbsorber(gas, ciax, fun, ν, length(ν))
 end
@@ -512,7 +569,13 @@ function members(ctx::Context, U::UnifiedAbsorber, Tk::Vector{Float64}, Pk::Vect
     conctab = Float64[concentration(baked[t], Tk[k], Pk[k]) for t in 1:length(baked), k in 1:K]    # gases.jl:270,278
     xs     = [χ.x for χ in U.cia]
     cslots = Cint[ciaslot!(ctx, χ.x; keep=xs) for χ in U.cia]
-    cflags = Cint[(χ.x.extrapolate ? 1 : 0) | (χ.x.singles ? 2 : 0) for χ in U.cia]
+    cflags = Cint[(χ.x.extrapolate ? CS_CIA_EXTRAPOLATE : Cint(0)) | (χ.x.singles ? CS_CIA_SINGLES : Cint(0)) |
+                  ((χ isa HIPCIA && χ.radiation) ? CS_CIA_RADIATION : Cint(0)) for χ in U.cia]
+    for χ in U.cia      # a continuum table of several temperatures covers its own range only
+        (χ isa HIPCIA && χ.radiation && length(χ.x.Φ) > 0) && for Φ in χ.x.Φ, t in Tk
+            (Φ.G.ya <= t <= Φ.G.yb) || error("continuum $(χ.name): node temperature $t K is outside the table's range [$(Φ.G.ya), $(Φ.G.yb)] K")
+        end
+    end
     P₁ = Float64[Pk[k]*concentration(U.cia[c].g₁, Tk[k], Pk[k]) for c in 1:length(U.cia), k in 1:K]   # cia...jl:378-382
     P₂ = Float64[Pk[k]*concentration(U.cia[c].g₂, Tk[k], Pk[k]) for c in 1:length(U.cia), k in 1:K]
     σgray = isempty(gray) ? 0.0 : Float64(sum(g.σ for g in gray))
@@ -815,7 +878,7 @@ function batchfluxes(core::HIPDiscretized, P::AbstractVector{<:Real}, Ts::Abstra
     return F⁺, F⁻
 end
 
-export HIPDiscretized, DirectGas, HIPGas, HIPCIA, hipvoigt!, hiplorentz!, hipdoppler!, hipPHCO2!, hipvoigtCKD!, hipvoigtVVH!, hipvoigtCKDVVH!, hipbake!, hipshapepoints, batchfluxes,
+export HIPDiscretized, DirectGas, HIPGas, HIPCIA, Continuum, hipvoigt!, hiplorentz!, hipdoppler!, hipPHCO2!, hipvoigtCKD!, hipvoigtVVH!, hipvoigtCKDVVH!, hipbake!, hipshapepoints, batchfluxes,
        hipfluxes, hipnetfluxes
 
 end # module
