@@ -1342,12 +1342,12 @@ class Column:
         """Evaluations the last run issued for its Voigt gases: per-point, at interpolation nodes; levels in use.  `dispatch`: the
         kernel forms the last run (or batch) chose (cs_column_work out[34..39], include/clearsky_hip_dev.h)."""
         self._require_resident("work")
-        out = (C.c_int64 * 40)()
+        out = (C.c_int64 * 41)()
         check(lib().cs_column_work(self.ctx.handle, out))
         return dict(direct_evals=out[0], node_evals=out[1], levels=out[2], intervals=out[3],
                     direct_by_body=dict(zip(("t2", "t2_cut", "t3", "t3_cut", "t4_cut", "near_zone"), [out[4 + q] for q in range(6)])),
                     node_by_body=dict(zip(("t2", "t3", "t4"), [out[10 + q] for q in range(3)])), node_evals_matrix=out[13],
-                    direct_evals_matrix=out[14], matrix_evals_3term=out[15], sub_evals=out[16], core_tile_states=out[17], matrix_evals_8term=out[18], node_evals_matrix_3term=out[19],
+                    direct_evals_matrix=out[14], matrix_evals_3term=out[15], sub_evals=out[16], sub_lean_evals=out[40], core_tile_states=out[17], matrix_evals_8term=out[18], node_evals_matrix_3term=out[19],
                     near_pairs_tier0=out[20], near_pairs_tier1=out[21], edge_mx_flops_useful=out[22], edge_mx_flops_issued=out[23],
                     nodes_mx_flops_useful=out[24], nodes_mx_flops_issued=out[25], apply_flops=out[26],
                     flux_scan_ns=[out[27 + q] for q in range(5)],

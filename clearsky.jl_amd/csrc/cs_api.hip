@@ -774,6 +774,7 @@ struct Interp {
     bool near_both = true;             // both tiers of the near-line pairs in one launch where a wave takes one tile (cs_set_tuning key 16 | 4: off)
     int near_prio = 0;                 // cs_set_tuning key 16: issue priority for k_voigt_sub / k_voigt_near (0 = from 512 tiles on, 1 = never, 2 = always)
     bool fuse_apply = false;  // the column's only interpolating group: k_voigt_edge_mx may carry the node sums to the grid itself
+    int sub_lean = 0;         // cs_set_tuning key 18: k_voigt_sub's range-only pass -- 0 = where the piece tables predict no series pair, 1 = never, 2 = first in every wave
     bool near_memset = false; // cs_set_tuning key 19: the near-line plane cleared by a memset in front of k_voigt_sub (1) instead of written by it (0, default)
     double core4 = 0.0;       // the core takes the 4-term series where its radius is below core4 x the tile's span, else the 8-term one
                               // (0: always the 8-term one -- measured at C3 with 0.75 / 0.3 / 0: 2.61 / 2.55 / 2.52 ms)
@@ -795,6 +796,7 @@ static void interp_settings(const cs_ctx *ctx, Interp &itp)   // what cs_set_mat
     itp.mxzones_one_thread = (ctx->tune[15] & 16) != 0;
     itp.near_prio = ctx->tune[16] & 3;
     itp.near_both = (ctx->tune[16] & 4) == 0;
+    itp.sub_lean = ctx->tune[18];
     itp.near_memset = ctx->tune[19] != 0;
     itp.mxzones_merge = ctx->tune[21];
     itp.far_split = ctx->tune[22];
@@ -1337,7 +1339,7 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
         ea.iz = itp.iz + itp.ioff[itp.nlev - 1]; ea.out = itp.edge; ea.nnu = nnu; ea.ntile = nt64; ea.K = kn; ea.ngrp = ngrp_s;
         ea.nI = itp.nItot; ea.ishift = 0;
         for (int r = itp.itv[itp.nlev - 1] / 64; r > 1; r >>= 1) ea.ishift++;
-        ea.mu_min = G.mu_min; ea.cut = p.cut;
+        ea.mu_min = G.mu_min; ea.mu_max = G.mu_max; ea.cut = p.cut;
         ea.core = (use_edge && itp.core) ? 1 : 0;
         ea.core4 = itp.core4;
         // sixteen lanes per item shorten the chain where the items are few (a nu-shard: 21 -> 8 us; the bench column 27 -> 9); from
@@ -1493,14 +1495,14 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
         p.fork->zeroed = true;
         if (sub_here)
             CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, p.fork->s3, p.dnu, nnu, G.L, p.hot,
-                      G.nu.as<double>(), p.zones, itp.edge, nt64, kn, p.cut, p.fork->sigma2, reinterpret_cast<unsigned *>(p.ranges), near_prio, sub_assigns ? 1 : 0);
+                      G.nu.as<double>(), p.zones, itp.edge, nt64, kn, p.cut, p.fork->sigma2, reinterpret_cast<unsigned *>(p.ranges), near_prio, sub_assigns ? 1 : 0, itp.sub_lean);
     }
     CS_LAUNCH(far_kernel(hot32 != nullptr, split, lor, use_edge), grid_s, dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, hot32, G.nu.as<double>(), p.win, p.zones,
               nt64, nblk_s, p.cut, p.base, p.extra, p.sigma, accumulate, p.ranges, iz, itp.nItot, ishift, edgez, zero2);
     if (p.evg) (void)hipEventRecord(p.evg[3], s);
     if (use_edge && itp.core && !near_fork)   // the window cores of the groups whose series radius is short: pairs inside it (the rest: k_voigt_edge_mx)
         CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, s, p.dnu, nnu, G.L, p.hot, G.nu.as<double>(), p.zones,
-                           itp.edge, nt64, kn, p.cut, p.sigma, reinterpret_cast<unsigned *>(p.ranges), near_prio, 0);
+                           itp.edge, nt64, kn, p.cut, p.sigma, reinterpret_cast<unsigned *>(p.ranges), near_prio, 0, itp.sub_lean);
     auto launch_near = [&](hipStream_t sn, double *out) {
         const int ngrpn = (nt64 + CS_NEAR_R - 1) / CS_NEAR_R;   // near kernels: one wave = CS_NEAR_R consecutive tiles ...
         // ... times nrep, one after the other: where the table is sparse against the grid (few tiles have candidates at all) and the
@@ -2102,6 +2104,7 @@ int cs_set_tuning(cs_ctx *ctx, int key, int value)
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (key < 0 || key >= CS_NTUNE) return fail(CS_EINVAL, "tuning key %d out of range", key);
     if (key == 3 && value != 0 && (value < 15 || value > 100)) return fail(CS_EINVAL, "interpolation margin must be 15..100 per cent of the half-width");
+    if (key == 18 && (value < 0 || value > 2)) return fail(CS_EINVAL, "range-only pass of k_voigt_sub: 0 (by the tables), 1 (never) or 2 (always first)");
     ctx->tune[key] = value;
     drop_graph(ctx->col);
     return CS_OK;
@@ -3638,7 +3641,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
     HIPCHK(hipDeviceSynchronize());
     const int K = c.K;
     const int nt64 = (int)((c.nnu + 63) / 64);
-    int64_t direct = 0, nodes = 0, sepn = 0, edgen = 0, mx3 = 0, subn = 0, ncore = 0, mx8 = 0, mx3n = 0;   // subn: (lane, line) evaluations of k_voigt_sub
+    int64_t direct = 0, nodes = 0, sepn = 0, edgen = 0, mx3 = 0, subn = 0, subn_lean = 0, ncore = 0, mx8 = 0, mx3n = 0;   // subn: (lane, line) evaluations of k_voigt_sub, subn_lean: those of waves that start range-only
     //   // sepn, edgen: (node | point, line, state) triples summed on the matrix cores; mx3: those with 3 terms
     // flops of the two matrix-core kernels: issued = every matrix instruction's 2048; useful = 2 x terms per (column, line, state) with
     // the column inside the cut-off, outside the core radius, and the state a real one (a group's tail rows are padding)
@@ -3851,6 +3854,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
                             const int ja = (int)(std::lower_bound(nl + e.cL, nl + e.cR, v0) - nl);
                             const int jb = (int)(std::upper_bound(nl + ja, nl + e.cR, v1) - nl);
                             subn += CS_SUBW * (int64_t)(jb - ja);
+                            if (ctx->tune[18] != 1 && ((e.lean >> ((k >> 3) & 1)) & 1)) subn_lean += CS_SUBW * (int64_t)(jb - ja);
                         }
                     }
                 }
@@ -3966,6 +3970,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
     out[17] = ncore;
     out[18] = mx8;
     out[19] = mx3n;
+    out[40] = subn_lean;
     return CS_OK;
 }
 

@@ -780,7 +780,7 @@ struct __attribute__((aligned(16))) SepZone { int32_t a[4], b[4], m[4]; };   // 
 // [cL, cR) (empty: cR <= cL): the core of the window -- everything between the matrix-core pieces, near zone included -- when the
 // series radius R of the group is shorter than the tile: there k_voigt_sub sums the pairs with |dnu| < R on 16-point sub-tiles
 // and k_voigt_edge_mx the pairs with |dnu| >= R (a second mask), and k_voigt_far leaves the core alone
-struct __attribute__((aligned(16))) EdgeZone { int32_t eL, mL0, mL1, mR0, mR1, eR, mL3, mR3, far3, cL, cR, pad0; double R, pad1; };
+struct __attribute__((aligned(16))) EdgeZone { int32_t eL, mL0, mL1, mR0, mR1, eR, mL3, mR3, far3, cL, cR, lean; double R, pad1; };   // lean: sub_series_free, bit per octet of states
 
 // vector-unit node sum of one (interval, state) at the lane's node v: own set minus the parent's -- [E0,P0) U [P1,Z0) left of the
 // interval, [Z1,P2) U [P3,E1) right of it -- each minus the piece [sa[p], sb[p]) the matrix cores take.  Both sides are summed from
@@ -1625,7 +1625,20 @@ struct EdgeArgs {
     int64_t nnu;
     int ntile, K, ngrp, nI, ishift, core;   // core: sub-tile treatment of the window core where it pays (k_voigt_sub)
     double mu_min, cut, core4;              // core4: the core takes the 4-term series where its radius is below core4 x the tile's span
+    double mu_max;                          // heaviest molecule of the table (sub_series_free)
 };
+// true where NO pair of (state, tile) inside the core radius Rc can reach the six-term series of k_voigt_sub (s = x^2 + y^2 >= kSerS):
+// x^2 <= ln2 Rc^2 / amin^2 and y^2 <= (gbound sqrt(ln2) / amin)^2 with amin the smallest Doppler width a line of the window can have at
+// this temperature (as zone_compute).  A hint only -- k_voigt_sub checks what it finds -- but the same bits from every table builder:
+// products, quotients, roots and one explicit fma, nothing the compiler may contract one way here and another way there
+__device__ __forceinline__ bool sub_series_free(double vlo, double cut, double nulW0, bool lines, double T, double gb, double mu_max, double Rc)
+{
+    const double vmin = vlo - cut;
+    if (!(vmin > 0.0) || !lines) return false;
+    const double amin = (fmax(vmin, nulW0) / kC) * sqrt(2.0 * kRgas * T) / sqrt(mu_max);
+    const double xb = Rc * kSqLn2 / amin, yb = gb * kSqLn2 / amin;
+    return __builtin_fma(xb, xb, yb * yb) < kSerS;
+}
 // per (state group, tile): the pieces common to the group's states -- the window ends left of every state's first interpolated or
 // near-zone line and right of the last; between every state's interpolated sets and near zone -- clipped to the distance at which
 // the 4-term series holds for the widest line of the group
@@ -1691,7 +1704,14 @@ __device__ __forceinline__ void edgezones_body(unsigned bid, const EdgeArgs &a)
     if (!core_ok) e.cL = e.cR = 0;
     else if (core8) e.far3 |= 4;
     e.R = Rc;
-    e.pad0 = 0;
+    // bit o: none of the states 8 o .. 8 o + 7 of the group can reach the series inside Rc -- k_voigt_sub's range-only pass
+    int lean = 0;
+    if (core_ok) {
+        lean = 3;
+        for (int k = g * 16; k < min(g * 16 + 16, a.K); k++)
+            if (!sub_series_free(vlo, a.cut, a.nul[w.W0 < w.W1 ? w.W0 : 0], w.W1 > w.W0, a.Tk[k], a.gbound[k], a.mu_max, Rc)) lean &= ~(1 << ((k >> 3) & 1));
+    }
+    e.lean = lean;
     e.pad1 = 0.0;
     a.out[idx] = e;
 }
@@ -1817,6 +1837,11 @@ __device__ __forceinline__ void edgezones_body16(unsigned bid, const EdgeArgs &a
         const double sv[4] = {vlo - R, vlo - R3, vhi + R, vhi + R3};
         search4(a.nul, sv, w.W0, w.W1, sr);
     }
+    const bool core8 = !(R < a.core4 * (vhi - vlo));
+    const double Rc = core8 ? R8 : R;
+    // (every lane its own state against the group's radius; the octets that hold a state which can reach the series, OR-ed to lane 0)
+    const bool reach = have && !sub_series_free(vlo, a.cut, a.nul[w.W0 < w.W1 ? w.W0 : 0], w.W1 > w.W0, a.Tk[have ? k : 0], a.gbound[have ? k : 0], a.mu_max, Rc);
+    const int lean = 3 & ~red16(reach ? 1 << (kk >> 3) : 0, [](int x, int y) { return x | y; });
     if (kk != 0) return;
     const int S0 = sr[0], S1 = max(sr[2], S0);            // the series holds in [W0, S0) and [S1, W1)
     const int T0 = min(sr[1], S0), T1 = max(sr[3], S1);   // ... with three terms in [W0, T0) and [T1, W1)
@@ -1836,14 +1861,12 @@ __device__ __forceinline__ void edgezones_body16(unsigned bid, const EdgeArgs &a
     if (e.mR1 - e.mR3 < 8) e.mR3 = e.mR1;
     e.cL = e.mL1 > e.mL0 ? e.mL1 : mL0;
     e.cR = e.mR1 > e.mR0 ? e.mR0 : mR1;
-    const bool core8 = !(R < a.core4 * (vhi - vlo));
-    const double Rc = core8 ? R8 : R;
     const bool core_ok = a.core && a.iz && i0 + 63 < a.nnu && mL0 <= mL1 && mR0 <= mR1 && e.cL <= mL1 && e.cR >= mR0 && e.cR > e.cL &&
                          Rc < (core8 ? 0.3 : 0.75) * (vhi - vlo);
     if (!core_ok) e.cL = e.cR = 0;
     else if (core8) e.far3 |= 4;
     e.R = Rc;
-    e.pad0 = 0;
+    e.lean = core_ok ? lean : 0;
     e.pad1 = 0.0;
     a.out[item] = e;
 }
@@ -2114,7 +2137,7 @@ template <int SW>
 __global__ __launch_bounds__(4096 / SW) void k_voigt_sub(const double *__restrict__ nu, int64_t nnu, int64_t L, const LineHot *__restrict__ hot,
                                                          const double *__restrict__ gnul, const Zone *__restrict__ zones,
                                                          const EdgeZone *__restrict__ edge, int ntile, int K, double cut,
-                                                         double *__restrict__ sigma, unsigned *__restrict__ rp, int prio, int assign)
+                                                         double *__restrict__ sigma, unsigned *__restrict__ rp, int prio, int assign, int lean_mode)
 {
     // assign != 0: `sigma` is the near-line plane of the step (its first writer on the side stream): every (state, point) of it is
     // WRITTEN here -- the sum where the tile has a core, a zero where it has not (and for the points of a ragged last tile) -- instead
@@ -2195,14 +2218,54 @@ __global__ __launch_bounds__(4096 / SW) void k_voigt_sub(const double *__restric
         if (in && s < kSerS) { bl = min(bl, j); bh = j; }
         if (in && s < kMidS) { cl = min(cl, j); ch = j; }
     };
+    // Range-only pass first where the piece tables say that no pair inside Rg can reach the series (EdgeZone::lean: the Doppler-dominated
+    // state groups, where Rg is ~22 Doppler widths and s = 1e3 starts at ~38): the same x, s, `in` and hand-off ranges, no reciprocal and
+    // no polynomial -- every term would be added as an exact 0.  The pass watches for a pair that does reach the series; if any lane of the
+    // wave saw one, the full loop below runs from ja as if nothing had happened, so the result never depends on the prediction.
+    // lean_mode (cs_set_tuning key 18): 0 = by the tables, 1 = full loop everywhere, 2 = range-only pass first in every wave
+    bool full = true;
+    if (lean_mode == 2 || (lean_mode == 0 && ((e.lean >> (((kq * NSW) >> 3) & 1)) & 1))) {   // (wave-uniform)
+        bool any_series = false;
+        auto ranges = [&](double nul, double p1, double p2, int j) {
+            const double dv = v - nul;
+            const double x = dv * p1;
+            const double s = __builtin_fma(x, x, p2);
+            const bool in = fabs(dv) < Rg && !(fabs(dv) > cut);
+            any_series |= in && s >= kSerS;
+            if (in && s < kSerS) { bl = min(bl, j); bh = j; }
+            if (in && s < kMidS) { cl = min(cl, j); ch = j; }
+        };
+        // (two lines per trip, the two record buffers swapping roles: the record of the line after next is in flight during a line, no copy)
+        const LineHot *h0 = hk + (ja < jb ? ja : 0);
+        double an = h0->nul, a1 = h0->p1, a2 = h0->p2;
+        int j = ja;
+        for (; j + 1 < jb; j += 2) {
+            const double bn = hk[j + 1].nul, b1 = hk[j + 1].p1, b2 = hk[j + 1].p2;
+            __builtin_amdgcn_sched_barrier(0);
+            ranges(an, a1, a2, j);
+            __builtin_amdgcn_sched_barrier(0);
+            const LineHot *hn = hk + min(j + 2, jb - 1);
+            an = hn->nul; a1 = hn->p1; a2 = hn->p2;
+            __builtin_amdgcn_sched_barrier(0);
+            ranges(bn, b1, b2, j + 1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (j < jb) ranges(an, a1, a2, j);
+        full = __builtin_amdgcn_ballot_w64(any_series) != 0;
+        if (full) { bl = 0x3fffffff; bh = -1; cl = 0x3fffffff; ch = -1; }
+    }
     // (the records of the next TWO lines in flight, three buffers in rotation: k_voigt_sub alone 0.196 -> 0.184 ms, the step unchanged: round 5)
-    LineHot cur = hk[ja < jb ? ja : 0];
-    for (int j = ja; j < jb; j++) {
-        const LineHot nxt = hk[min(j + 1, jb - 1)];   // in flight while this line is evaluated
-        __builtin_amdgcn_sched_barrier(0);
-        eval(cur, j);
-        __builtin_amdgcn_sched_barrier(0);
-        cur = nxt;
+    // (two lines per trip here too, without the record copy: 51 -> 47 instructions per line, alone 0.158 -> 0.150 ms, the step lower in five of
+    //  seven interleaved pairs only: measured and removed, round 7)
+    if (full) {
+        LineHot cur = hk[ja < jb ? ja : 0];
+        for (int j = ja; j < jb; j++) {
+            const LineHot nxt = hk[min(j + 1, jb - 1)];   // in flight while this line is evaluated
+            __builtin_amdgcn_sched_barrier(0);
+            eval(cur, j);
+            __builtin_amdgcn_sched_barrier(0);
+            cur = nxt;
+        }
     }
     const int N0 = zones[(size_t)(kin ? k : K - 1) * ntile + tile].N0;
     const unsigned r0 = (kin && bh >= bl) ? ((unsigned)(bl - N0) << 12) | (unsigned)(bh + 1 - bl) : 0u;

@@ -95,7 +95,10 @@ int cs_set_merge(cs_ctx *ctx, int on);
  *          instead of on 16 Chebyshev nodes of the tile (0, default, where the grid allows: cut-off far beyond tile + smallest interval) (A/B).
  *   key 17: where the four waves of a block share every item of k_cheb_nodes_mx (short grids), the far pieces of an interval on all 64
  *          nodes (1) instead of on its level's 16 or 32, a quarter of the lines per wave (0, default) (A/B).
- *   (keys 18, 20 are unused.)
+ *   key 18: the range-only pass of k_voigt_sub -- hand-off ranges only, no series -- 0 (default) in the waves whose octet of states the piece
+ *          tables mark as unable to reach the series inside the core radius (EdgeZone::lean), 1 never (the full loop everywhere), 2 first
+ *          in every wave; a wave that meets a series pair on that pass runs the full loop afterwards (A/B; same results).
+ *   (key 20 is unused.)
  * Applies to every later cs_column_setup / cs_column_run of the context. */
 int cs_set_tuning(cs_ctx *ctx, int key, int value);
 
@@ -140,7 +143,8 @@ int cs_column_info(cs_ctx *ctx, int64_t *out);
  * 1 window ends on the 16 tile nodes in k_voigt_edge_mx (key 23), 2 near-line plane cleared by a memset (key 19), 4 k_rt_streams
  * (key 5), 8 band sum inside the flux kernel (key 15 | 4), 16 far pieces of shared items on 64 nodes (key 17), 32 k_flux_chunk with
  * four waves per SIMD (key 15 | 8), 64 levels folded on the node-sum side stream (key 15 | 256).  out[0..26] and out[32..33] describe
- * the column's own last cross-section stage: zero while only cs_column_batch has run since cs_column_setup.  `out` holds 40 values.
+ * the column's own last cross-section stage: zero while only cs_column_batch has run since cs_column_setup; so does out[40] = the part
+ * of out[16] in waves that start with the range-only pass by the piece tables (0 with key 18 = 1).  `out` holds 41 values.
  * cs_column_counts is the reference's count. */
 int cs_column_work(cs_ctx *ctx, int64_t *out);
 
