@@ -21,6 +21,10 @@ CS_MAX_ACCEL = 4
 CHEB_LD = 16
 CS_SHAPE_PSHIFT = 16   # include/clearsky_hip.h: ORed onto shape codes 0-2, line centres at nul + delta_a P / P0
 CS_CIA_EXTRAPOLATE, CS_CIA_SINGLES, CS_CIA_RADIATION = 1, 2, 4   # include/clearsky_hip.h: cia_flags (4: the object's band sum times R(nu, T))
+# include/clearsky_hip_dev.h (tests/test_host.py holds both against the header): values cs_column_work writes, and the CS_DF_* bits of its
+# CS_WORK_FLAGS -- Column.work()["dispatch"]["flags"]
+WORK_COUNT = 41
+DISPATCH_FLAGS = {"TNODES": 1, "NEAR_MEMSET": 2, "RT_STREAMS": 4, "BAND_SUM": 8, "FAR64_SHARED": 16, "CHUNK4": 32, "CASCADE_ASIDE": 64}
 SHAPES = {"voigt": 0, "lorentz": 1, "doppler": 2, "PHCO2": 3, "phco2": 3, "voigtCKD": 4, "voigtVVH": 5,
           "voigtCKDVVH": 6}   # 4: CS_SHAPE_VOIGT_CKD, pedestal-removed Voigt; 5: CS_SHAPE_VOIGT_VVH, Van Vleck-Huber Voigt; 6: CS_SHAPE_VOIGT_CKD_VVH, both
 

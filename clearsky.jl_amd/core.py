@@ -15,7 +15,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import constants as K
-from ._lib import (CHEB_LD, CS_MAX_ACCEL, CS_MAX_CIA, CS_MAX_GAS, CS_MAX_TABLE, CS_SHAPE_PSHIFT, SHAPES, ClearSkyHIPError, as_f64, check,
+from ._lib import (CHEB_LD, CS_MAX_ACCEL, CS_MAX_CIA, CS_MAX_GAS, CS_MAX_TABLE, CS_SHAPE_PSHIFT, SHAPES, WORK_COUNT, ClearSkyHIPError, as_f64, check,
                    dptr, lib)
 from .hitran import TMAX, TMIN, SpectralLines
 from .cia import CIATables, Continuum, cia, readcia
@@ -1340,9 +1340,10 @@ class Column:
 
     def work(self):
         """Evaluations the last run issued for its Voigt gases: per-point, at interpolation nodes; levels in use.  `dispatch`: the
-        kernel forms the last run (or batch) chose (cs_column_work out[34..39], include/clearsky_hip_dev.h)."""
+        kernel forms the last run (or batch) chose (CS_WORK_FAR_SPLIT .. CS_WORK_FLAGS of include/clearsky_hip_dev.h; bits of `flags`:
+        DISPATCH_FLAGS).  Every value describes the run as it was dispatched, whatever the settings are now."""
         self._require_resident("work")
-        out = (C.c_int64 * 41)()
+        out = (C.c_int64 * WORK_COUNT)()
         check(lib().cs_column_work(self.ctx.handle, out))
         return dict(direct_evals=out[0], node_evals=out[1], levels=out[2], intervals=out[3],
                     direct_by_body=dict(zip(("t2", "t2_cut", "t3", "t3_cut", "t4_cut", "near_zone"), [out[4 + q] for q in range(6)])),

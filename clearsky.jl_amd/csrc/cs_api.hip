@@ -43,14 +43,54 @@ int fail(int code, const char *fmt, ...)
 }
 
 thread_local int g_nlaunch = 0;   // kernel launches since the last reset (cs_column_run reports its count)
-thread_local int g_near_launches = 0, g_line_kernel = 0;   // of the step being enqueued: near-line launches (all groups), and what summed the per-point
-                                                           // far lines of its last group: 0 = k_voigt_far, 1 = k_linesum<shape>, 2 = k_phco2
-// which forms the step being enqueued dispatched (cs_column_work out[34..39]): the fields of its last Voigt group, the flags of the whole step
-struct Dispatch { int far_split, tables, near_prio, streams, nodes_split, flags; };
-enum { CS_DF_TNODES = 1, CS_DF_NEAR_MEMSET = 2, CS_DF_RT_STREAMS = 4, CS_DF_BAND_SUM = 8, CS_DF_FAR64_SHARED = 16, CS_DF_CHUNK4 = 32,
-       CS_DF_CASCADE_ASIDE = 64 };
-thread_local Dispatch g_disp = {};
 #define CS_LAUNCH(...) do { g_nlaunch++; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+
+// How one Voigt / Lorentz launch group is run: everything that follows from sizes, settings and which buffers exist (voigt_plan, the one
+// place that holds the rules).  line_sum_voigt launches by it, a column keeps the plan of its last run and cs_column_work counts from it.
+// What depends on the state of the step -- the side streams, who clears the near-line plane, the fused apply -- is not in here.
+struct VoigtPlan {
+    bool lor;                   // the Lorentz body (no near-line tiers, no matrix cores)
+    int nt64, ngrp;             // 64-point tiles; groups of 16 states
+    int q0, ishift;             // first interval in use; tile -> interval of the smallest size (both 0 without interpolated wings)
+    int near_prio;              // wave priority of k_voigt_sub / k_voigt_near (0, 3)
+    bool use_sep, use_edge;     // node sums (k_cheb_nodes_mx) / window ends (k_voigt_edge_mx) on the matrix cores
+    bool core;                  // ... and the window cores on sub-tiles (k_voigt_sub)
+    bool mx_one_thread, mx_merged;   // the piece tables: k_mxzones, blocks of k_gas_setup_mx (neither: k_mxzones16)
+    int tables;                 // ... as cs_column_work reports them: 0 none, 1 k_gas_setup_mx, 2 k_mxzones16, 3 k_mxzones
+    bool nsplit4;               // k_cheb_nodes with four waves per (interval, state)
+    int nsplit;                 // k_cheb_nodes_mx: intervals (from q0 on) the four waves of a block share ...
+    unsigned nblk_mx;           // ... and its blocks
+    bool far_R;                 // ... its far pieces on their level's nfar nodes (re-interpolation matrices in use), else on all 64
+    bool far64_shared;          // ... on all 64 because every item is shared (key 17), not for want of the matrices
+    int nfar[CS_MAX_LEVEL];
+    int far_split;              // waves per tile of k_voigt_far
+    bool edge_big;              // k_voigt_edge_mx<1>: one wave per (tile, group); else <4>
+    int edge_phases;            // ... cuts a cut-off edge by the sub-tiles its lines reach (<1> only)
+    bool tnodes;                // ... and sums the lines inside every point's cut-off on the 16 tile nodes
+    int ngrpn, nrep;            // near-line kernels: CS_NEAR_R-tile stretches, and how many of them a wave takes in turn
+    bool near_both;             // ... both tiers in one launch
+    int sub_lean;               // k_voigt_sub's range-only pass (cs_set_tuning key 18)
+    unsigned nb_zones, nb_iz, nb_sep, nb_edge;   // blocks of the zone, interval-zone and piece-table parts of the setup launches
+};
+
+// which forms a step dispatched (cs_column_work CS_WORK_FAR_SPLIT ..): the fields of its last Voigt group, the flags (CS_DF_*) of the whole step
+struct Dispatch { int far_split, tables, near_prio, streams, nodes_split, flags; };
+// What the step being enqueued did, kept by the caller that enqueues it (run_impl, cs_column_batch) and reached by the launchers through
+// GasPass::log (NULL: nobody asks)
+struct StepLog {
+    Dispatch disp = {};
+    int near_launches = 0;      // near-line launches, all groups
+    int line_kernel = 0;        // what summed the per-point far lines of the last group: 0 = k_voigt_far, 1 = k_linesum<shape>, 2 = k_phco2
+    // a Voigt group as planned; streams: 1 node sums, 2 near-line kernels on their side streams
+    void voigt_group(const VoigtPlan &pl, int streams, bool near_memset)
+    {
+        disp.far_split = pl.far_split; disp.tables = pl.tables; disp.near_prio = pl.near_prio; disp.streams = streams;
+        disp.nodes_split = pl.nsplit4 ? 1 : 0;
+        disp.flags |= (pl.tnodes ? CS_DF_TNODES : 0) | (pl.far64_shared ? CS_DF_FAR64_SHARED : 0) | (near_memset ? CS_DF_NEAR_MEMSET : 0);
+        if (!pl.lor) near_launches += pl.near_both ? 1 : 2;
+        line_kernel = 0;
+    }
+};
 
 #define HIPCHK(expr)                                                                                   \
     do {                                                                                               \
@@ -230,6 +270,11 @@ struct ColGas {
     int64_t mb = 0;           // ... with the mirror lines [pa, mb) (vvh_mirror_end)
     bool pshift = false;      // CS_SHAPE_PSHIFT: records centred at nul + delta_a P / P0, summed by k_linesum<shape> over windows widened by ds
     double ds = 0.0;          // ... the largest shift of the group at the column's node pressures (shift_width)
+    // Voigt / Lorentz groups: how the column's own cross-section stage last ran the group (sigma_impl; a batch's chunked passes run on
+    // buffers of their own and leave it alone).  planned: it has, since setup -- the group's windows and zones are written, and
+    // cs_column_work counts them by this plan
+    VoigtPlan plan;
+    bool planned = false;
 };
 
 // k_rt launch geometry (rt_geometry)
@@ -239,7 +284,6 @@ struct Column {
     double *F_dst = nullptr;   // cs_column_set_flux_dst: caller-owned device memory the band fluxes [2 np] are written to (NULL: the column's own F)
     double *flux_out() { return F_dst ? F_dst : F.as<double>(); }
     bool ready = false;
-    bool swept = false;        // the column's own cross-section stage has run since setup: its windows / zones (cs_column_work reads them) are written
     int64_t nnu = 0;
     int np = 0, nl = 0, nlob = 0, K = 0, nstream = 0, ngas = 0, ntile = 0;
     RtGeom rtg = {};
@@ -274,11 +318,10 @@ struct Column {
     DevBuf hot, cold, sigma, sigma2, tau, Mup, Mdn, partial, F, stage, ranges;   // sigma2: the near-line plane (k_voigt_near on a side stream)
     DevBuf ped;                // launch_pedestal's workspace for K states (columns with a code-4 group)
     DevBuf vvh;                // the line sum of a code-5 group that is not the column's first, before launch_vvh (K x nnu)
-    DevBuf fluxdbg;            // k_flux_scan: phase time stamps of block 0 (cs_set_tuning key 15 | 128; cs_column_work out[27..])
+    DevBuf fluxdbg;            // k_flux_scan: phase time stamps of block 0 (cs_set_tuning key 15 | 128; cs_column_work CS_WORK_FLUX_SCAN_NS ..)
     DevBuf ticket;             // k_flux: blocks finished (the last one adds the block partials up)
     int flux_form_last = 0;      // which flux kernel the last run used (flux_form)
-    int near_launches_last = 0, line_kernel_last = 0;   // cs_column_info out[6], out[7]
-    Dispatch disp_last = {};     // cs_column_work out[34..39]
+    StepLog log_last;            // of the last cs_column_run (cs_column_info out[6], out[7]); its disp also of the last cs_column_batch
     bool sigma_partial = false;  // the last run finished the cross-sections on chip (k_flux): cs_column_sigma_fetch evaluates them again, in HBM
     ChebGrid cheb;             // interpolation levels of the nu grid (nlev = 0: off)
     DevBuf chebF;              // node sums F [nItot][64][Kpad], summed over the column's gases (k_cheb_nodes accumulates)
@@ -1263,6 +1306,9 @@ struct GasPass {
     Fork *fork = nullptr;
     hipEvent_t *evg = nullptr;      // NULL or 6 events: after K1 (+ zones), nodes (vector unit), nodes (matrix cores), far (vector unit), sub-tile cores, far (matrix cores)
     bool records_ready = false;     // hot / cold already hold this gas at these states: zones and sums only
+    // what the caller wants to know afterwards
+    StepLog *log = nullptr;         // the record of the step this pass belongs to (NULL: none kept)
+    VoigtPlan *keep = nullptr;      // where the plan of a Voigt / Lorentz group is kept (NULL: nowhere)
 };
 
 static ZoneArgs zone_args(const GasPass &p, bool lor, double margin, double ds)
@@ -1289,114 +1335,159 @@ static FarKernel far_kernel(bool mixed, int split, bool lor, bool edge)
     return edge ? far_kernel_split<false, false, true>(split) : far_kernel_split<false, false, false>(split);
 }
 
+// How a Voigt / Lorentz group of this pass is run.  Host arithmetic only: launches nothing, reads no device data.
+static VoigtPlan voigt_plan(const GasPass &p)
+{
+    const Interp &itp = p.itp;
+    const int kn = p.kn;
+    const int64_t nlines = std::max(p.jhi, p.jlo) - p.jlo;   // the lines some window can reach
+    const bool mixed = p.shape == SH_VOIGT && !p.pshift && p.hot32 != nullptr;   // (no fp32 wings for shifted lines, nor a Lorentz variant)
+    VoigtPlan pl;
+    memset(&pl, 0, sizeof pl);
+    pl.lor = p.shape == SH_LORENTZ;
+    pl.nt64 = (int)((p.nnu + 63) / 64);
+    pl.ngrp = (kn + 15) / 16;
+    // wave priority of the near-line stream's kernels (wave_prio): long grids only
+    pl.near_prio = (itp.near_prio == 2 || (itp.near_prio == 0 && pl.nt64 >= 512)) ? 3 : 0;
+    pl.sub_lean = itp.sub_lean;
+    pl.nb_zones = (unsigned)(((int64_t)pl.nt64 * kn + 255) / 256);
+    if (itp.nlev > 0) {
+        pl.q0 = itp.ioff[itp.l0];
+        for (int r = itp.itv[itp.nlev - 1] / 64; r > 1; r >>= 1) pl.ishift++;
+        const int nq = itp.nItot - pl.q0;
+        pl.nb_iz = (unsigned)(((int64_t)nq * kn + 255) / 256);
+        // what the matrix cores take of the interpolated sets and of the window ends (not of a shifted group: GasPass::pshift)
+        if (!p.pshift) {
+            pl.use_sep = sep_in_use(itp.sep != nullptr, itp.sep_always, nq, kn, pl.lor, mixed, itp.small_mx);
+            pl.use_edge = edge_in_use(itp.edge != nullptr, itp.sep_always, pl.nt64, kn, pl.lor, mixed, nlines, itp.small_mx);
+        }
+        // short grids: four waves per (interval, state) (cs_set_tuning key 13: 0 = below 16384 waves, 1 = always, 2 = never)
+        pl.nsplit4 = itp.nodes_split == 1 || (itp.nodes_split == 0 && (int64_t)nq * kn < 16384);
+        if (pl.use_sep) {
+            // the largest interval sizes in use are shared by the four waves of a block -- itp.nsplit_levels of them (all sizes on a
+            // grid too short to fill the chip with one (interval, group) per wave)
+            for (int l = itp.l0; l < std::min(itp.nlev, itp.l0 + itp.nsplit_levels); l++) pl.nsplit += itp.nI[l];
+            if (!mx_big(nq, kn, 2048) || pl.nsplit > nq) pl.nsplit = nq;
+            pl.nblk_mx = (unsigned)(pl.nsplit * pl.ngrp) + (unsigned)(((int64_t)(nq - pl.nsplit) * pl.ngrp + 3) / 4);
+            pl.far_R = itp.R != nullptr && !(itp.far_shared_full && pl.nsplit == nq);
+            pl.far64_shared = itp.R != nullptr && !pl.far_R;
+            for (int l = 0; l < itp.nlev; l++) pl.nfar[l] = itp.nfar[l] > 0 ? itp.nfar[l] : CS_NC;
+        }
+    }
+    pl.core = pl.use_edge && itp.core;
+    // The piece tables per (interval | tile, state group) need the zones -- which their sixteen-lanes-per-item form computes itself, as
+    // blocks of the SAME launch (k_gas_setup_mx); the one-thread-per-item form reads them, a launch of its own behind k_gas_setup
+    if (pl.use_sep || pl.use_edge) {
+        const int64_t nsep = pl.use_sep ? (int64_t)(itp.nItot - pl.q0) * pl.ngrp : 0, nedge = pl.use_edge ? (int64_t)pl.nt64 * pl.ngrp : 0;
+        // sixteen lanes per item shorten the chain where the items are few (a nu-shard: 21 -> 8 us; the bench column 27 -> 9); from
+        // ~50 000 items on one thread per item has parallelism enough and sixteen times fewer threads (BASELINE configs[4]: 0.256 vs 0.276 ms)
+        pl.mx_one_thread = itp.mxzones_one_thread || nsep + nedge > 50000;   // (cs_set_tuning key 15 | 16: always)
+        // merged on short grids, where the head of the step is a chain of launch tails (1/8 of the bench column: 0.347 -> 0.340 ms);
+        // at full size the second set of searches beside 300 MB of record stores costs more than the launch it saves (1.900 -> 1.908)
+        // (cs_set_tuning key 21: 1 = never, 2 = always, A/B)
+        pl.mx_merged = !pl.mx_one_thread && itp.mxzones_merge != 1 && (itp.mxzones_merge == 2 || pl.nt64 < 1024);
+        pl.tables = pl.mx_merged ? 1 : (pl.mx_one_thread ? 3 : 2);
+        const int per = pl.mx_one_thread ? 256 : 16;   // items per block
+        pl.nb_sep = (unsigned)((nsep + per - 1) / per);
+        pl.nb_edge = (unsigned)((nedge + per - 1) / per);
+    }
+    // k_voigt_far, waves per tile: enough waves to fill 256 CUs x 32 wave slots about 4 times over
+    const int64_t nwave = (int64_t)pl.nt64 * kn;
+    pl.far_split = nwave >= 16384 ? 1 : (nwave >= 4096 ? 2 : 4);   // (re-tuned with the far wings interpolated: waves are 3x shorter)
+    if (itp.far_split == 1 || itp.far_split == 2 || itp.far_split == 4) pl.far_split = itp.far_split;   // (cs_set_tuning key 22, A/B)
+    // k_voigt_edge_mx: one wave per (tile, state group) where those fill the chip, else four (short grid) -- and no tile nodes in that
+    // shared form (the 16-node path there: 16 more matrix steps per WAVE, no gain measured)
+    pl.edge_big = mx_big(pl.nt64, kn, 1024);
+    pl.edge_phases = itp.edge_phases;
+    pl.tnodes = pl.use_edge && pl.edge_big && itp.edge_phases && itp.tnodes != nullptr;
+    pl.ngrpn = (pl.nt64 + CS_NEAR_R - 1) / CS_NEAR_R;   // near kernels: one wave = CS_NEAR_R consecutive tiles ...
+    // ... times nrep, one after the other: where the table is sparse against the grid (few tiles have candidates at all) and the
+    // grid long enough to keep the chip full with an eighth of the waves, and on every grid of half a million (tile, state) waves
+    // and more -- there the launch of the waves is what a near-line kernel costs first (BASELINE configs[4]: 7.9e5 waves per
+    // tier, step 7.06 -> 6.85 ms with eight tiles per wave; the bench column, 9.5e4 waves: a tie with two, a loss with four)
+    const int64_t nwaves_near = (int64_t)pl.ngrpn * kn;
+    pl.nrep = (nwaves_near >= 524288 || (nlines < (int64_t)pl.nt64 * 2 && nwaves_near >= 262144)) ? 8 : 1;
+    pl.near_both = pl.nrep == 1 && itp.near_both;   // (one tile per wave; cs_set_tuning key 16 | 4: two launches, A/B)
+    return pl;
+}
+
 // K2 on the far-wing machinery (Voigt, and lorentz! with its own exact body): zones, interpolated wings, k_voigt_far, window cores and ends, near-line tiers
 static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, unsigned nb_prep)
 {
     const GasTable &G = *p.G;
     const Interp &itp = p.itp;
     const int kn = p.kn;
-    const int64_t nnu = p.nnu, jlo = pa.jlo, jhi = pa.jhi;
-    const bool lor = p.shape == SH_LORENTZ;
+    const int64_t nnu = p.nnu;
     LineF32 *const hot32 = pa.hot32;   // (none under CS_SHAPE_PSHIFT, and no fp32 variant of the Lorentz body)
     int accumulate = p.accumulate;
-    const int nt64 = (int)((nnu + 63) / 64);
-    // wave priority of the near-line stream's kernels (wave_prio): long grids only
-    const int near_prio = (itp.near_prio == 2 || (itp.near_prio == 0 && nt64 >= 512)) ? 3 : 0;
-    const ZoneArgs za = zone_args(p, lor, itp.margin, p.pshift ? p.ds : 0.0);
-    const unsigned nb_zones = (unsigned)(((int64_t)nt64 * kn + 255) / 256);
+    const VoigtPlan pl = voigt_plan(p);
+    if (p.keep) *p.keep = pl;
+    const int nt64 = pl.nt64;
+    const bool use_sep = pl.use_sep, use_edge = pl.use_edge;
+    // the side streams (not while profiling): the node kernels beside what follows them on the main stream; the near-line kernels and
+    // the sub-tile cores into their own plane (Voigt only) -- whose first writer of the step defines all of it: k_voigt_sub where it
+    // runs (sums where a tile has a core, zeros elsewhere: cs_set_tuning key 19 = 1 keeps the memset for A/B), else a memset
+    const bool nodes_fork = itp.nlev > 0 && p.fork && p.fork->use_nodes && p.defer && !p.evg;
+    const bool near_fork = !pl.lor && p.fork && p.fork->use_near && p.fork->sigma2 && p.defer && !p.evg;
+    const bool sub_assigns = near_fork && pl.core && !p.fork->zeroed && !itp.near_memset;
+    const bool near_memset = near_fork && !p.fork->zeroed && !sub_assigns;
+    if (p.log) p.log->voigt_group(pl, (nodes_fork ? 1 : 0) | (near_fork ? 2 : 0), near_memset);
+
+    const ZoneArgs za = zone_args(p, pl.lor, itp.margin, p.pshift ? p.ds : 0.0);
     IzParams P;
     memset(&P, 0, sizeof P);
-    unsigned nb_iz = 0;
-    const IZone *iz = nullptr;
-    int ishift = 0;
-    bool forked_here = false;   // ev_fork was recorded on the main stream after the zone launches: the near-line side stream can wait on it too
-    bool use_edge = false;   // window ends of the per-point sum on the matrix cores (k_voigt_edge_mx; with the far wings interpolated only)
-    bool fuse = false;       // ... which then also applies the interpolated wings (no k_cheb_apply launch for this group)
-    ChebApply Afuse;
-    memset(&Afuse, 0, sizeof Afuse);
     if (itp.nlev > 0) {
         P.nlev = itp.nlev;
         P.nItot = itp.nItot;
         P.l0 = itp.l0;
         for (int l = 0; l < itp.nlev; l++) { P.itv[l] = itp.itv[l]; P.nI[l] = itp.nI[l]; P.ioff[l] = itp.ioff[l]; P.iwin[l] = itp.iwin[l]; }
-        nb_iz = (unsigned)(((int64_t)(itp.nItot - itp.ioff[itp.l0]) * kn + 255) / 256);
     }
-    // what the matrix cores take of the interpolated sets and of the window ends: piece tables per (interval | tile, state group).  They
-    // need the zones -- which their sixteen-lanes-per-item form computes itself, as blocks of the SAME launch (k_gas_setup_mx); the
-    // one-thread-per-item form (from ~50 000 items on: BASELINE configs[4]) reads them, a launch of its own behind k_gas_setup
-    const int q0s = itp.nlev > 0 ? itp.ioff[itp.l0] : 0, ngrp_s = (kn + 15) / 16;
-    const bool use_sep_s = itp.nlev > 0 && !p.pshift && sep_in_use(itp.sep != nullptr, itp.sep_always, itp.nItot - q0s, kn, lor, hot32 != nullptr, itp.small_mx);
-    if (itp.nlev > 0 && !p.pshift) use_edge = edge_in_use(itp.edge != nullptr, itp.sep_always, nt64, kn, lor, hot32 != nullptr, jhi - jlo, itp.small_mx);
     SepArgs sa;
     EdgeArgs ea;
     memset(&sa, 0, sizeof sa);
     memset(&ea, 0, sizeof ea);
-    bool mx_one_thread = false, mx_merged = false;
-    if (use_sep_s || use_edge) {
+    if (pl.tables) {
         sa.nodes = itp.nodes; sa.nul = G.nu.as<double>(); sa.gbound = p.gbound; sa.Tk = p.Tk; sa.iz = itp.iz; sa.out = itp.sep;
-        sa.nItot = itp.nItot; sa.q0 = q0s; sa.K = kn; sa.ngrp = ngrp_s; sa.mu_min = G.mu_min; sa.cut = p.cut; sa.min_states = itp.mx_min_states;
+        sa.nItot = itp.nItot; sa.q0 = pl.q0; sa.K = kn; sa.ngrp = pl.ngrp; sa.mu_min = G.mu_min; sa.cut = p.cut; sa.min_states = itp.mx_min_states;
         ea.nu = p.dnu; ea.nul = G.nu.as<double>(); ea.gbound = p.gbound; ea.Tk = p.Tk; ea.win = p.win; ea.zones = p.zones;
-        ea.iz = itp.iz + itp.ioff[itp.nlev - 1]; ea.out = itp.edge; ea.nnu = nnu; ea.ntile = nt64; ea.K = kn; ea.ngrp = ngrp_s;
-        ea.nI = itp.nItot; ea.ishift = 0;
-        for (int r = itp.itv[itp.nlev - 1] / 64; r > 1; r >>= 1) ea.ishift++;
+        ea.iz = itp.iz + itp.ioff[itp.nlev - 1]; ea.out = itp.edge; ea.nnu = nnu; ea.ntile = nt64; ea.K = kn; ea.ngrp = pl.ngrp;
+        ea.nI = itp.nItot; ea.ishift = pl.ishift;
         ea.mu_min = G.mu_min; ea.mu_max = G.mu_max; ea.cut = p.cut;
-        ea.core = (use_edge && itp.core) ? 1 : 0;
+        ea.core = pl.core ? 1 : 0;
         ea.core4 = itp.core4;
-        // sixteen lanes per item shorten the chain where the items are few (a nu-shard: 21 -> 8 us; the bench column 27 -> 9); from
-        // ~50 000 items on one thread per item has parallelism enough and sixteen times fewer threads (BASELINE configs[4]: 0.256 vs 0.276 ms)
-        const int64_t nitems = (use_sep_s ? (int64_t)(itp.nItot - q0s) * ngrp_s : 0) + (use_edge ? (int64_t)nt64 * ngrp_s : 0);
-        mx_one_thread = itp.mxzones_one_thread || nitems > 50000;   // (cs_set_tuning key 15 | 16: always)
-        // merged on short grids, where the head of the step is a chain of launch tails (1/8 of the bench column: 0.347 -> 0.340 ms);
-        // at full size the second set of searches beside 300 MB of record stores costs more than the launch it saves (1.900 -> 1.908)
-        // (cs_set_tuning key 21: 1 = never, 2 = always, A/B)
-        mx_merged = !mx_one_thread && itp.mxzones_merge != 1 && (itp.mxzones_merge == 2 || nt64 < 1024);
     }
-    g_disp.far_split = 0; g_disp.tables = 0; g_disp.near_prio = near_prio; g_disp.streams = 0; g_disp.nodes_split = 0;
-    if (use_sep_s || use_edge) g_disp.tables = mx_merged ? 1 : (mx_one_thread ? 3 : 2);
-    if (mx_merged) {
-        const unsigned nb_sep = use_sep_s ? (unsigned)(((int64_t)(itp.nItot - q0s) * ngrp_s + 15) / 16) : 0u;
-        const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp_s + 15) / 16) : 0u;
-        CS_LAUNCH(p.vvh ? k_gas_setup_mx_vvh : k_gas_setup_mx, dim3(nb_prep + nb_zones + nb_iz + nb_sep + nb_edge), dim3(256), 0, s, nb_prep, nb_zones, nb_iz, nb_sep, pa, za, P, itp.iz, sa, ea);
-    } else {
-        CS_LAUNCH(p.vvh ? k_gas_setup_vvh : k_gas_setup, dim3(nb_prep + nb_zones + nb_iz), dim3(256), 0, s, nb_prep, nb_zones, pa, za, P, itp.iz);
-    }
+    if (pl.mx_merged)
+        CS_LAUNCH(p.vvh ? k_gas_setup_mx_vvh : k_gas_setup_mx, dim3(nb_prep + pl.nb_zones + pl.nb_iz + pl.nb_sep + pl.nb_edge), dim3(256), 0, s, nb_prep, pl.nb_zones, pl.nb_iz, pl.nb_sep, pa, za, P, itp.iz, sa, ea);
+    else
+        CS_LAUNCH(p.vvh ? k_gas_setup_vvh : k_gas_setup, dim3(nb_prep + pl.nb_zones + pl.nb_iz), dim3(256), 0, s, nb_prep, pl.nb_zones, pa, za, P, itp.iz);
     if (p.evg && itp.nlev == 0) (void)hipEventRecord(p.evg[0], s);
+    const IZone *iz = nullptr;
+    bool fuse = false;       // k_voigt_edge_mx also applies the interpolated wings (no k_cheb_apply launch for this group)
+    ChebApply Afuse;
+    memset(&Afuse, 0, sizeof Afuse);
     if (itp.nlev > 0) {   // sigma = base + extra + interpolated far wings; the per-point kernels add the rest
-        const int q0 = itp.ioff[itp.l0];
+        const int q0 = pl.q0;
         // deferred apply: the gases of a column add their node sums into ONE F (levels an earlier gas has written accumulate)
         const int q_acc = (p.defer && p.defer->ngas > 0 && p.defer->l0[0] < itp.nlev) ? itp.ioff[p.defer->l0[0]] : itp.nItot;
-        // short grids: four waves per (interval, state) (cs_set_tuning key 13: 0 = below 16384 waves, 1 = always, 2 = never)
-        const bool nsplit4 = itp.nodes_split == 1 || (itp.nodes_split == 0 && (int64_t)(itp.nItot - q0) * kn < 16384);
-        g_disp.nodes_split = nsplit4 ? 1 : 0;
+        const bool nsplit4 = pl.nsplit4;
         const dim3 gridn(nsplit4 ? (unsigned)kn * (unsigned)(itp.nItot - q0) : (unsigned)((kn + 3) / 4) * (unsigned)(itp.nItot - q0));
-        const int ngrp = ngrp_s;
-        const bool use_sep = use_sep_s;
-        if ((use_sep || use_edge) && !mx_merged) {
-            if (mx_one_thread) {
-                const unsigned nb_sep = use_sep ? (unsigned)(((int64_t)(itp.nItot - q0) * ngrp + 255) / 256) : 0u;
-                const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp + 255) / 256) : 0u;
-                CS_LAUNCH(k_mxzones, dim3(nb_sep + nb_edge), dim3(256), 0, s, nb_sep, sa, ea);
-            } else {                        // sixteen lanes per item
-                const unsigned nb_sep = use_sep ? (unsigned)(((int64_t)(itp.nItot - q0) * ngrp + 15) / 16) : 0u;
-                const unsigned nb_edge = use_edge ? (unsigned)(((int64_t)nt64 * ngrp + 15) / 16) : 0u;
-                CS_LAUNCH(k_mxzones16, dim3(nb_sep + nb_edge), dim3(256), 0, s, nb_sep, sa, ea);
-            }
+        if (pl.tables && !pl.mx_merged) {
+            if (pl.mx_one_thread) CS_LAUNCH(k_mxzones, dim3(pl.nb_sep + pl.nb_edge), dim3(256), 0, s, pl.nb_sep, sa, ea);
+            else CS_LAUNCH(k_mxzones16, dim3(pl.nb_sep + pl.nb_edge), dim3(256), 0, s, pl.nb_sep, sa, ea);   // sixteen lanes per item
         }
         if (p.evg) (void)hipEventRecord(p.evg[0], s);
         const SepZone *sepz = use_sep ? itp.sep : nullptr;
         hipStream_t sm = s;   // main stream
-        if (p.fork && p.fork->use_nodes && p.defer && !p.evg) {
+        if (nodes_fork) {
             (void)hipEventRecord(p.fork->ev_fork, s);
             (void)hipStreamWaitEvent(p.fork->s2, p.fork->ev_fork, 0);
-            forked_here = true;
-            g_disp.streams |= 1;
             s = p.fork->s2;     // the two node kernels below run beside what follows them on the main stream
         }
 #define NODES_LAUNCH(M, L_, M4, L4, S4) do { if (nsplit4) CS_LAUNCH((k_cheb_nodes<M4, L4, S4>), gridn, dim3(256), 0, s, itp.nodes, G.L, p.hot, hot32, G.nu.as<double>(), itp.iz, \
                                itp.nItot, q0, q_acc, kn, itp.Kpad, p.cut, itp.F, sepz); \
         else CS_LAUNCH((k_cheb_nodes<M, L_>), gridn, dim3(256), 0, s, itp.nodes, G.L, p.hot, hot32, G.nu.as<double>(), itp.iz, \
                                itp.nItot, q0, q_acc, kn, itp.Kpad, p.cut, itp.F, sepz); } while (0)
-        if (lor)
+        if (pl.lor)
             NODES_LAUNCH(false, true, false, true, 4);
         else if (hot32)
             NODES_LAUNCH(true, false, true, false, 4);
@@ -1404,22 +1495,14 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
             NODES_LAUNCH(false, false, false, false, 4);
         if (p.evg) (void)hipEventRecord(p.evg[1], s);
         if (use_sep) {
-            const int nq = itp.nItot - q0;
-            // the largest interval sizes in use are shared by the four waves of a block -- itp.nsplit_levels of them (all sizes on a
-            // grid too short to fill the chip with one (interval, group) per wave)
-            int nsplit = 0;
-            for (int l = itp.l0; l < std::min(itp.nlev, itp.l0 + itp.nsplit_levels); l++) nsplit += itp.nI[l];
-            if (!mx_big(nq, kn, 2048) || nsplit > nq) nsplit = nq;
-            const unsigned nblk_mx = (unsigned)(nsplit * ngrp) + (unsigned)(((int64_t)(nq - nsplit) * ngrp + 3) / 4);
             MxFar mf;
             memset(&mf, 0, sizeof mf);
             mf.nlev = itp.nlev;
-            for (int l = 0; l < itp.nlev; l++) { mf.ioff[l] = itp.ioff[l]; mf.nfar[l] = itp.nfar[l] > 0 ? itp.nfar[l] : CS_NC; }
+            for (int l = 0; l < itp.nlev; l++) { mf.ioff[l] = itp.ioff[l]; mf.nfar[l] = pl.nfar[l]; }
             mf.ioff[itp.nlev] = itp.nItot;
-            mf.R = (itp.far_shared_full && nsplit == nq) ? nullptr : itp.R;
-            if (itp.R && !mf.R) g_disp.flags |= CS_DF_FAR64_SHARED;
-            CS_LAUNCH(k_cheb_nodes_mx, dim3(nblk_mx), dim3(256), 0, s, itp.nodes, G.L, p.hot, itp.sep, itp.nItot, q0, nsplit, kn,
-                               itp.Kpad, ngrp, itp.F, itp.iz, mf);
+            mf.R = pl.far_R ? itp.R : nullptr;
+            CS_LAUNCH(k_cheb_nodes_mx, dim3(pl.nblk_mx), dim3(256), 0, s, itp.nodes, G.L, p.hot, itp.sep, itp.nItot, q0, pl.nsplit, kn,
+                               itp.Kpad, pl.ngrp, itp.F, itp.iz, mf);
         }
         if (s != sm) {
             (void)hipEventRecord(p.fork->ev_join, s);
@@ -1455,71 +1538,46 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
             launch_apply_cascade(s, A, itp.Rc, itp.itv, itp.nI, itp.cascade, itp.Kpad, nnu, kn, p.base, p.extra, p.sigma, accumulate);
             accumulate = 1;
         }               // (deferred: the caller applies the node sums of all its gases in one launch, after the last gas)
-        const int low = itp.nlev - 1;
-        iz = itp.iz + itp.ioff[low];
-        ishift = A.shift[low];
+        iz = itp.iz + itp.ioff[itp.nlev - 1];
     } else if (p.evg) {
         (void)hipEventRecord(p.evg[1], s);
         (void)hipEventRecord(p.evg[2], s);
     }
-    g_line_kernel = 0;
 
-    // waves per tile: enough waves to fill 256 CUs x 32 wave slots about 4 times over
-    const int64_t nwave = (int64_t)nt64 * kn;
-    int split = nwave >= 16384 ? 1 : (nwave >= 4096 ? 2 : 4);   // (re-tuned with the far wings interpolated: waves are 3x shorter)
-    if (itp.far_split == 1 || itp.far_split == 2 || itp.far_split == 4) split = itp.far_split;   // (cs_set_tuning key 22, A/B)
-    g_disp.far_split = split;
+    const int split = pl.far_split;
     const int nblk_s = (nt64 * split + 3) / 4;
     // 8 x (blocks of the longest XCD stretch): XCD-aware tile mapping (tile_block); xtiles is a multiple of 4 tiles
     const dim3 grid_s((unsigned)(8 * (p.xtiles * split / 4)), kn);
     const EdgeZone *edgez = use_edge ? itp.edge : nullptr;
-    // near-line kernels and the sub-tile cores on a side stream, into their own plane (Voigt only; not while profiling)
-    const bool near_fork = !lor && p.fork && p.fork->use_near && p.fork->sigma2 && p.defer && !p.evg;
     double *zero2 = nullptr;   // (the far kernel can clear the plane itself: unused since k_voigt_sub adds to it beside k_voigt_far)
+    // the window cores of the groups whose series radius is short: pairs inside it (the rest: k_voigt_edge_mx)
+    auto launch_sub = [&](hipStream_t ss, double *out, bool assigns) {
+        CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, ss, p.dnu, nnu, G.L, p.hot,
+                  G.nu.as<double>(), p.zones, itp.edge, nt64, kn, p.cut, out, reinterpret_cast<unsigned *>(p.ranges), pl.near_prio, assigns ? 1 : 0, pl.sub_lean);
+    };
     if (near_fork) {   // zones, records and piece tables are written: the side stream may start
-        if (forked_here) {   // (nothing was enqueued on the main stream since that record: one event serves both side streams)
+        if (nodes_fork) {   // (nothing was enqueued on the main stream since that record: one event serves both side streams)
             (void)hipStreamWaitEvent(p.fork->s3, p.fork->ev_fork, 0);
         } else {
             (void)hipEventRecord(p.fork->ev_fork3, s);
             (void)hipStreamWaitEvent(p.fork->s3, p.fork->ev_fork3, 0);
         }
-        // the plane's first writer of the step defines all of it: k_voigt_sub where it runs (sums where a tile has a core, zeros
-        // elsewhere: cs_set_tuning key 19 = 1 keeps the memset for A/B), else a memset
-        const bool sub_here = use_edge && itp.core;
-        const bool sub_assigns = sub_here && !p.fork->zeroed && !itp.near_memset;
-        if (!p.fork->zeroed && !sub_assigns) {
-            (void)hipMemsetAsync(p.fork->sigma2, 0, (size_t)kn * nnu * sizeof(double), p.fork->s3);
-            g_disp.flags |= CS_DF_NEAR_MEMSET;
-        }
-        g_disp.streams |= 2;
+        if (near_memset) (void)hipMemsetAsync(p.fork->sigma2, 0, (size_t)kn * nnu * sizeof(double), p.fork->s3);
         p.fork->zeroed = true;
-        if (sub_here)
-            CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, p.fork->s3, p.dnu, nnu, G.L, p.hot,
-                      G.nu.as<double>(), p.zones, itp.edge, nt64, kn, p.cut, p.fork->sigma2, reinterpret_cast<unsigned *>(p.ranges), near_prio, sub_assigns ? 1 : 0, itp.sub_lean);
+        if (pl.core) launch_sub(p.fork->s3, p.fork->sigma2, sub_assigns);   // (it needs the zones only, not k_voigt_far: beside it)
     }
-    CS_LAUNCH(far_kernel(hot32 != nullptr, split, lor, use_edge), grid_s, dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, hot32, G.nu.as<double>(), p.win, p.zones,
-              nt64, nblk_s, p.cut, p.base, p.extra, p.sigma, accumulate, p.ranges, iz, itp.nItot, ishift, edgez, zero2);
+    CS_LAUNCH(far_kernel(hot32 != nullptr, split, pl.lor, use_edge), grid_s, dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, hot32, G.nu.as<double>(), p.win, p.zones,
+              nt64, nblk_s, p.cut, p.base, p.extra, p.sigma, accumulate, p.ranges, iz, itp.nItot, pl.ishift, edgez, zero2);
     if (p.evg) (void)hipEventRecord(p.evg[3], s);
-    if (use_edge && itp.core && !near_fork)   // the window cores of the groups whose series radius is short: pairs inside it (the rest: k_voigt_edge_mx)
-        CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, s, p.dnu, nnu, G.L, p.hot, G.nu.as<double>(), p.zones,
-                           itp.edge, nt64, kn, p.cut, p.sigma, reinterpret_cast<unsigned *>(p.ranges), near_prio, 0, itp.sub_lean);
+    if (pl.core && !near_fork) launch_sub(s, p.sigma, false);
     auto launch_near = [&](hipStream_t sn, double *out) {
-        const int ngrpn = (nt64 + CS_NEAR_R - 1) / CS_NEAR_R;   // near kernels: one wave = CS_NEAR_R consecutive tiles ...
-        // ... times nrep, one after the other: where the table is sparse against the grid (few tiles have candidates at all) and the
-        // grid long enough to keep the chip full with an eighth of the waves, and on every grid of half a million (tile, state) waves
-        // and more -- there the launch of the waves is what a near-line kernel costs first (BASELINE configs[4]: 7.9e5 waves per
-        // tier, step 7.06 -> 6.85 ms with eight tiles per wave; the bench column, 9.5e4 waves: a tie with two, a loss with four)
-        const int64_t nwaves_near = (int64_t)ngrpn * kn;
-        const int nrep = (nwaves_near >= 524288 || (jhi - jlo < (int64_t)nt64 * 2 && nwaves_near >= 262144)) ? 8 : 1;
-        const dim3 gridq((unsigned)(((ngrpn + nrep - 1) / nrep + 3) / 4), kn);
-        if (nrep == 1 && itp.near_both) {   // both tiers in one launch (one tile per wave; cs_set_tuning key 16 | 4: two launches, A/B)
-            CS_LAUNCH(k_voigt_near_both, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, p.cut, out, p.ranges, near_prio);
-            g_near_launches += 1;
+        const dim3 gridq((unsigned)(((pl.ngrpn + pl.nrep - 1) / pl.nrep + 3) / 4), kn);
+        if (pl.near_both) {
+            CS_LAUNCH(k_voigt_near_both, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, p.cut, out, p.ranges, pl.near_prio);
             return;
         }
-        g_near_launches += 2;
-        CS_LAUNCH(k_voigt_near<0>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, ngrpn, nrep, p.cut, out, p.ranges, near_prio);
-        CS_LAUNCH(k_voigt_near<1>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, ngrpn, nrep, p.cut, out, p.ranges, near_prio);
+        CS_LAUNCH(k_voigt_near<0>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, pl.ngrpn, pl.nrep, p.cut, out, p.ranges, pl.near_prio);
+        CS_LAUNCH(k_voigt_near<1>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, pl.ngrpn, pl.nrep, p.cut, out, p.ranges, pl.near_prio);
     };
     if (near_fork) {   // the near kernels need the hand-off words of both k_voigt_far (main stream) and k_voigt_sub (theirs)
         (void)hipEventRecord(p.fork->ev_far3, s);
@@ -1530,21 +1588,15 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
         p.fork->live = true;
     }
     if (p.evg) (void)hipEventRecord(p.evg[4], s);
-    if (use_edge)
-    {
+    if (use_edge) {
         if (fuse) fork_join(p.fork, s);   // (it reads F)
-        if (mx_big(nt64, kn, 1024) && itp.edge_phases && itp.tnodes) g_disp.flags |= CS_DF_TNODES;
-        if (mx_big(nt64, kn, 1024))
-            CS_LAUNCH(k_voigt_edge_mx<1>, dim3((unsigned)((nt64 + 3) / 4), (unsigned)((kn + 15) / 16)), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.win,
-                      itp.edge, nt64, kn, p.cut, p.sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), itp.edge_phases,
-                      itp.edge_phases ? itp.tnodes : nullptr, itp.tC);
-        else   // short grid: four waves per (tile, group)
-            CS_LAUNCH(k_voigt_edge_mx<4>, dim3((unsigned)nt64, (unsigned)((kn + 15) / 16)), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.win,
-                      itp.edge, nt64, kn, p.cut, p.sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), itp.edge_phases,
-                      (const double *)nullptr, (const double *)nullptr);   // (the 16-node path in the shared form: 16 more matrix steps per WAVE, no gain measured)
+        const unsigned ntx = pl.edge_big ? (unsigned)((nt64 + 3) / 4) : (unsigned)nt64;
+        CS_LAUNCH(pl.edge_big ? k_voigt_edge_mx<1> : k_voigt_edge_mx<4>, dim3(ntx, (unsigned)pl.ngrp), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.win,
+                  itp.edge, nt64, kn, p.cut, p.sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), itp.edge_phases,
+                  pl.tnodes ? itp.tnodes : (const double *)nullptr, pl.edge_big ? itp.tC : (const double *)nullptr);
     }
     if (p.evg) (void)hipEventRecord(p.evg[5], s);
-    if (!lor && !near_fork) launch_near(s, p.sigma);
+    if (!pl.lor && !near_fork) launch_near(s, p.sigma);
 }
 
 static void launch_line_sum(hipStream_t s, const GasPass &p);
@@ -1627,7 +1679,7 @@ static void line_sum_phco2(hipStream_t s, const GasPass &p, PrepArgs pa, unsigne
         piw = p.ph->piw.as<PhIWin>();
         fine = pg.fine;
     } else if (p.evg) { (void)hipEventRecord(p.evg[1], s); (void)hipEventRecord(p.evg[2], s); }
-    g_line_kernel = 2;
+    if (p.log) p.log->line_kernel = 2;
     CS_LAUNCH(k_phco2, dim3((unsigned)((nt64 + 3) / 4), kn), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.cold, p.ph->fac.as<double>(), p.ph->nu_c,
                        p.ph->win.as<PhWin>(), p.zones, nt64, p.cut, p.Tk, kn, p.base, p.extra, p.sigma, accumulate, piw, fine, inner ? 1 : 0);
     if (p.evg) (void)hipEventRecord(p.evg[3], s);
@@ -1636,10 +1688,10 @@ static void line_sum_phco2(hipStream_t s, const GasPass &p, PrepArgs pa, unsigne
         GasPass in = p;   // same table, record range, states, records, grid, ranges and plane: the zones and sums of a Voigt pass with its own windows
         in.shape = SH_VOIGT; in.cut = 3.0; in.win = p.ph->win3.as<WaveWin>(); in.xtiles = per; in.zones = p.ph->zones3.as<Zone>();
         in.base = 0.0; in.extra = nullptr; in.accumulate = 1; in.evg = nullptr; in.hot32 = nullptr; in.itp = Interp();
-        in.defer = nullptr; in.ph = nullptr; in.fork = nullptr; in.records_ready = true;
+        in.defer = nullptr; in.ph = nullptr; in.fork = nullptr; in.records_ready = true; in.keep = nullptr;
         in.flo = -INFINITY; in.fhi = INFINITY;   // (no K1 in this pass: nothing reads them)
         launch_line_sum(s, in);
-        g_line_kernel = 2;   // (the group's far lines were k_phco2's; the inner pass only took the pairs within 3 cm^-1)
+        if (p.log) p.log->line_kernel = 2;   // (the group's far lines were k_phco2's; the inner pass only took the pairs within 3 cm^-1)
     }
     if (p.evg) { (void)hipEventRecord(p.evg[4], s); (void)hipEventRecord(p.evg[5], s); }
 }
@@ -1655,7 +1707,7 @@ static void line_sum_generic(hipStream_t s, const GasPass &p, const PrepArgs &pa
         CS_LAUNCH(k_gas_setup, dim3(nb_prep), dim3(256), 0, s, nb_prep, 0u, pa, za, P, (IZone *)nullptr);
     }
     if (p.evg) { (void)hipEventRecord(p.evg[0], s); (void)hipEventRecord(p.evg[1], s); (void)hipEventRecord(p.evg[2], s); }
-    g_line_kernel = 1;
+    if (p.log) p.log->line_kernel = 1;
     launch_linesum_shape(p.shape, dim3(p.ntile256, p.kn), s, p.dnu, p.nnu, p.G->L, p.hot, p.cold, p.J0, p.J1, p.cut, p.Tk, p.base, p.extra, p.sigma,
                          p.accumulate);
     if (p.evg) { (void)hipEventRecord(p.evg[3], s); (void)hipEventRecord(p.evg[4], s); (void)hipEventRecord(p.evg[5], s); }
@@ -2594,7 +2646,7 @@ int cs_column_set_cia(cs_ctx *ctx, int ncia, const int *cia_slots, const int *fl
     return CS_OK;
 }
 
-static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *near_plane_live = nullptr, FluxFuse *fuse = nullptr);
+static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLog *log, bool *near_plane_live = nullptr, FluxFuse *fuse = nullptr);
 static int column_current(cs_ctx *ctx);
 
 // ---- AcceleratedAbsorber (absorbers.jl:114-203) -------------------------------------------------------------------------
@@ -2610,7 +2662,7 @@ int cs_accel_store(cs_ctx *ctx, int accel_slot)
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     int e = 0, rc;
-    if ((rc = sigma_impl(ctx, s, nullptr, e))) return rc;   // Sigma(U, i, T_k, P_k) for every i and knot k (update!, absorbers.jl:173-200)
+    if ((rc = sigma_impl(ctx, s, nullptr, e, nullptr))) return rc;   // Sigma(U, i, T_k, P_k) for every i and knot k (update!, absorbers.jl:173-200)
     AccelDev &ad = ctx->accel[accel_slot];
     const int64_t n = (int64_t)c.K * c.nnu;
     HIPCHK(ad.L.reserve((size_t)n * sizeof(double)));
@@ -2906,7 +2958,6 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     HIPCHK(c.F.reserve((size_t)2 * np * sizeof(double)));
     HIPCHK(hipStreamSynchronize(s));
     c.ready = true;  // state upload below needs the sizes
-    c.swept = false;
     c.tab.clear();
     c.cia.clear();
     c.accel.slot = -1;
@@ -3028,10 +3079,10 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     HIPCHK(dpart.reserve((size_t)B * bg.nblk * 2 * np * sizeof(double)));
     HIPCHK(dF.reserve((size_t)B * 2 * np * sizeof(double)));
     double *sig = shared_sigma ? c.sigma.as<double>() : dsig.as<double>();
-    g_disp = Dispatch();
+    StepLog log;
     if (shared_sigma) {
         int e = 0;
-        if ((rc = sigma_impl(ctx, s, nullptr, e))) return rc;
+        if ((rc = sigma_impl(ctx, s, nullptr, e, &log))) return rc;
     } else if (c.ngas == 0) {
         const int64_t tot = BK * c.nnu;
         CS_LAUNCH(k_fill, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, c.sigma_gray, (const double *)nullptr, sig);
@@ -3083,6 +3134,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
         p.mstride = (int)BK;
         p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<int2>(); p.ped_ws = dped.as<double>();
         p.accumulate = qi > 0; p.spare = dvvh.as<double>();   // (a second code-5/6 group: its bare line sum goes there first)
+        p.log = &log;
         Interp &itp = p.itp;
         if (cg.itp.nlev > 0) {
             HIPCHK(dizones.reserve((size_t)kc * c.cheb.nItot * sizeof(IZone)));
@@ -3148,8 +3200,8 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
             HIPCHK(hipStreamSynchronize(s));
         }
     }
-    if (bg.streams) g_disp.flags |= CS_DF_RT_STREAMS;
-    c.disp_last = g_disp;
+    if (bg.streams) log.disp.flags |= CS_DF_RT_STREAMS;
+    c.log_last.disp = log.disp;
     launch_rt(c.nstream, bg, B, s, c.rt, c.nu.as<double>(),
                     c.wts.as<double>(), c.nnu, sig, dmuk.as<double>(), c.P.as<double>(), dTlev.as<double>(),
                     c.has_S ? c.S_toa.as<double>() : nullptr, c.has_alb ? c.albedo.as<double>() : nullptr, (double *)nullptr, nullptr,
@@ -3167,12 +3219,12 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
 }
 
 // the cross-section stage of one evaluation: sigma[K][nnu] of all absorbers of the resident column at its node states
-// (Sigma(A, i, T, P) of absorbers.jl:95 for every i and node).  ev: see run_impl; e counts the events recorded.
+// (Sigma(A, i, T, P) of absorbers.jl:95 for every i and node).  ev: see run_impl; e counts the events recorded.  log: the step's record, or NULL.
 // near_plane_live: NULL = the cross-sections themselves are the result (the near-line plane is folded into sigma before returning);
 // else the caller (run_impl) hands both planes to k_rt and is told here whether the second one is in use this step
 // fuse != NULL: the interpolated wings are not carried to the grid and the CIA pairs are not added here -- *fuse says what the flux
 // kernel still has to add (k_flux; near_plane_live must be given too: the near-line plane is not folded in either)
-static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *near_plane_live, FluxFuse *fuse)
+static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLog *log, bool *near_plane_live, FluxFuse *fuse)
 {
     Column &c = ctx->col;
     const int K = c.K;
@@ -3228,7 +3280,11 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
         interp_settings(ctx, p.itp);
         p.itp.fuse_apply = ctx->tune[0] != 0 && n_itp == 1;
         p.defer = &apply; p.fork = use_fork ? &fk : nullptr; p.evg = ev ? ev + e : nullptr;
+        p.log = log;
+        const bool voigt = cg.shape == SH_VOIGT || cg.shape == SH_LORENTZ;   // (what line_sum_voigt runs, and plans)
+        p.keep = voigt ? &cg.plan : nullptr;
         launch_gas(s, p);
+        cg.planned = voigt;
         if (ev) { e += 6; HIPCHK(hipEventRecord(ev[e++], s)); }
     }
     if (fuse) { fuse->apply = 0; fuse->ncia = 0; fuse->Kpad = cheb_kpad(K); }
@@ -3251,7 +3307,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
         launch_apply_cascade(fk.s2, apply, Rc, c.cheb.itv, c.cheb.nI, 1, cheb_kpad(K), c.nnu, K, 0.0, nullptr, sig, 1, &carried);
         (void)hipEventRecord(fk.ev_join, fk.s2);   // (the main stream has not waited yet: it will wait for this later record)
         cascaded_aside = true;
-        g_disp.flags |= CS_DF_CASCADE_ASIDE;
+        if (log) log->disp.flags |= CS_DF_CASCADE_ASIDE;
     }
     fork_join(&fk, s, true, false);   // the node sums; the near-line kernels may run on beside what follows (none of it touches their plane)
     // interpolated far wings of all gases: sigma += sum_level C (sum_gas F)  (one pass over C and sigma)
@@ -3301,7 +3357,6 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, bool *
         if (any_ped) CS_LAUNCH(k_clamp0, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, sig);
     }
     HIPCHK(hipGetLastError());
-    c.swept = true;
     return CS_OK;
 }
 
@@ -3331,9 +3386,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
     double *sig = c.sigma.as<double>();
     int e = 0, rc;
     g_nlaunch = 0;
-    g_near_launches = 0;
-    g_line_kernel = 0;
-    g_disp = Dispatch();
+    StepLog log;
     c.last_stream = s;
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
     bool near_live = false;
@@ -3342,7 +3395,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
     const int form = flux_form(ctx, c, &fsh, &fblk, &fthr);
     FluxFuse fuse;
     memset(&fuse, 0, sizeof fuse);
-    if ((rc = sigma_impl(ctx, s, ev, e, &near_live, form ? &fuse : nullptr))) return rc;
+    if ((rc = sigma_impl(ctx, s, ev, e, &log, &near_live, form ? &fuse : nullptr))) return rc;
     c.near_live = near_live;
     c.sigma_partial = form != 0;
     c.flux_form_last = form;
@@ -3357,8 +3410,8 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
         fuse.ticket = (fblk <= 512 && !(ctx->tune[15] & 4) && ctx->gfx950) ? c.ticket.as<unsigned>() : nullptr;   // (| 4: k_freduce always, for A/B)
         fuse.gpartial = c.partial.as<double>() + (size_t)std::max<int64_t>(c.rtg.nblk, (c.nnu + 63) / 64) * 2 * c.np;
         reduced = fuse.ticket != nullptr;
-        if (reduced) g_disp.flags |= CS_DF_BAND_SUM;
-        if (form == 2 && (ctx->tune[15] & 8)) g_disp.flags |= CS_DF_CHUNK4;
+        if (reduced) log.disp.flags |= CS_DF_BAND_SUM;
+        if (form == 2 && (ctx->tune[15] & 8)) log.disp.flags |= CS_DF_CHUNK4;
         if ((ctx->tune[15] & 128) && c.fluxdbg.reserve((8 + 2 * (size_t)fblk + 32) * sizeof(unsigned long long)) == hipSuccess) fuse.dbg = c.fluxdbg.as<unsigned long long>();
         // the chunked form always writes the layer optical depths (its upward sweep reads them back): into the caller's plane or scratch
         double *dtau = (c.want_tau || form == 2) ? c.tau.as<double>() : nullptr;   // (forms 1 and 3 keep the optical depths in LDS)
@@ -3374,7 +3427,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
 #undef CS_FLUX_CASE
 #undef CS_FLUX_ARGS
     } else {
-        if (c.rtg.streams) g_disp.flags |= CS_DF_RT_STREAMS;
+        if (c.rtg.streams) log.disp.flags |= CS_DF_RT_STREAMS;
         launch_rt(c.nstream, c.rtg, 1, s, c.rt, c.nu.as<double>(), c.wts.as<double>(),
                   c.nnu, sig, c.muk.as<double>(), c.P.as<double>(), c.Tlev.as<double>(), dS, dA, c.want_tau ? c.tau.as<double>() : nullptr,
                   dMu, dMd, c.partial.as<double>(), 0, near_live ? c.sigma2.as<double>() : nullptr);
@@ -3384,9 +3437,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
         CS_LAUNCH(k_freduce, dim3(2 * c.np), dim3(256), 0, s, c.partial.as<double>(), form ? fblk : c.rtg.nblk, 2 * c.np, c.flux_out());
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
     c.launches = g_nlaunch;
-    c.near_launches_last = g_near_launches;
-    c.line_kernel_last = g_line_kernel;
-    c.disp_last = g_disp;
+    c.log_last = log;
     HIPCHK(hipGetLastError());
     return CS_OK;
 }
@@ -3396,7 +3447,7 @@ int cs_column_sigma_run(cs_ctx *ctx, void *stream)
     if (!ctx || !ctx->col.ready) return fail(CS_ESTATE, "cs_column_setup has not been called");
     HIPCHK(hipSetDevice(ctx->device));
     int e = 0;
-    return sigma_impl(ctx, stream ? (hipStream_t)stream : ctx->stream, nullptr, e);
+    return sigma_impl(ctx, stream ? (hipStream_t)stream : ctx->stream, nullptr, e, nullptr);
 }
 
 int cs_column_run(cs_ctx *ctx, void *stream)
@@ -3551,7 +3602,7 @@ int cs_column_sigma_fetch(cs_ctx *ctx, int64_t nnu, int K, double *sigma)
     HIPCHK(hipDeviceSynchronize());
     if (c.sigma_partial) {   // the run finished the cross-sections on chip (k_flux): evaluate them once more, all the way into HBM
         int e = 0;
-        const int rc = sigma_impl(ctx, ctx->stream, nullptr, e);
+        const int rc = sigma_impl(ctx, ctx->stream, nullptr, e, nullptr);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(ctx->stream));
         c.sigma_partial = false;
@@ -3607,8 +3658,8 @@ int cs_column_info(cs_ctx *ctx, int64_t *out)
     for (auto &g : c.gas) { out[2] += g.tab->L; out[4] = std::max<int64_t>(out[4], (int64_t)g.mem.size()); }
     out[3] = c.merge;
     out[5] = c.flux_form_last;
-    out[6] = c.near_launches_last;
-    out[7] = c.line_kernel_last;
+    out[6] = c.log_last.near_launches;
+    out[7] = c.log_last.line_kernel;
     return CS_OK;
 }
 
@@ -3633,16 +3684,21 @@ int cs_phco2_plan(int64_t nnu, const double *nu, double dnu_cut, int cap, int *i
     return nv;
 }
 
-int cs_column_work(cs_ctx *ctx, int64_t *out)
-{
-    if (!ctx || !ctx->col.ready || !out) return fail(CS_ESTATE, "no resident column");
-    Column &c = ctx->col;
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipDeviceSynchronize());
-    const int K = c.K;
-    const int nt64 = (int)((c.nnu + 63) / 64);
-    int64_t direct = 0, nodes = 0, sepn = 0, edgen = 0, mx3 = 0, subn = 0, subn_lean = 0, ncore = 0, mx8 = 0, mx3n = 0;   // subn: (lane, line) evaluations of k_voigt_sub, subn_lean: those of waves that start range-only
-    //   // sepn, edgen: (node | point, line, state) triples summed on the matrix cores; mx3: those with 3 terms
+// ---- cs_column_work: one routine per kernel family.  Each counts one Voigt / Lorentz group of the column from the tables its last run
+// left on the device (WorkTables, downloaded once per group) and from the plan that run was dispatched by (ColGas::plan) -- never from
+// the context's settings, which may have changed since.
+struct WorkTables {
+    std::vector<WaveWin> win;   // [tiles]
+    std::vector<Zone> zn;       // [K][tiles]
+    std::vector<IZone> iz;      // [K][nItot] (interpolated wings)
+    std::vector<SepZone> sz;    // [K/16][nItot] (plan.use_sep)
+    std::vector<EdgeZone> ez;   // [K/16][tiles] (plan.use_edge)
+};
+struct Work {
+    int64_t direct = 0, nodes = 0;
+    int64_t sepn = 0, edgen = 0;   // (node | point, line, state) triples summed on the matrix cores; mx3, mx3n: those (of sepn) with 3 terms; mx8: with 8
+    int64_t mx3 = 0, mx3n = 0, mx8 = 0;
+    int64_t subn = 0, subn_lean = 0, ncore = 0;   // (lane, line) evaluations of k_voigt_sub, those of waves that start range-only; (tile, state) cores
     // flops of the two matrix-core kernels: issued = every matrix instruction's 2048; useful = 2 x terms per (column, line, state) with
     // the column inside the cut-off, outside the core radius, and the state a real one (a group's tail rows are padding)
     double fl_edge_useful = 0.0, fl_edge_issued = 0.0, fl_nodes_useful = 0.0, fl_nodes_issued = 0.0, fl_apply = 0.0;
@@ -3651,276 +3707,291 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
     int64_t near0 = 0, near1 = 0;
     int64_t body[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // per-point lines by body: 2-term, 2-term+cut-off, 3-term, 3-term+cut-off, 4-term+cut-off,
                                                      // near-zone pass; node lines: 2-, 3-, 4-term
-    auto seg = [](int lo, int hi, int p0, int p1) { return (int64_t)std::max(0, std::min(hi, p1) - std::max(lo, p0)); };
+};
+static int64_t work_seg(int lo, int hi, int p0, int p1) { return (int64_t)std::max(0, std::min(hi, p1) - std::max(lo, p0)); }
+
+// node sums: k_cheb_nodes on the vector unit, k_cheb_nodes_mx on the matrix cores (useful flops per state, issued and records per group)
+static void work_nodes(const Column &c, const ColGas &g, const WorkTables &T, Work &w)
+{
+    const VoigtPlan &pl = g.plan;
+    const int K = c.K, nlev = g.itp.nlev, nItot = c.cheb.nItot, q0 = pl.q0;
+    // nodes a piece of interval q is summed on in k_cheb_nodes_mx: its level's 16 or 32 for the far pieces (p = 0, 3) where the
+    // re-interpolation matrices are in use, 64 otherwise (the carry to the 64 nodes, 2 x 64 x n per state, is not counted)
+    auto far_nodes = [&](int q, int p) {
+        if (!pl.far_R || (p != 0 && p != 3)) return (int)CS_NC;
+        int l = 0;
+        while (l + 1 < nlev && q >= c.cheb.ioff[l + 1]) l++;
+        return pl.nfar[l];
+    };
+    for (int k = 0; k < K; k++)
+        for (int q = q0; q < nItot; q++) {
+            const IZone &z = T.iz[(size_t)k * nItot + q];
+            w.nodes += (int64_t)CS_NC * ((z.P0 - z.E0) + (z.Z0 - z.P1) + (z.P2 - z.Z1) + (z.E1 - z.P3));
+            // the same segments k_cheb_nodes runs: [E0,P0) U [P1,Z0) left, [Z1,P2) U [P3,E1) right, each minus the piece
+            // the matrix-core kernel takes, cut at Q and M
+            int sa[4] = {z.P0, z.Z0, z.Z1, z.P3}, sb[4] = {z.P0, z.Z0, z.Z1, z.P3};
+            if (pl.use_sep) {
+                const SepZone &s4 = T.sz[(size_t)(k >> 4) * nItot + q];
+                for (int p = 0; p < 4; p++) {   // of the group's piece, this state's part: the lines beyond its own series radius (k_cheb_nodes_mx's mask)
+                    const int pa = p < 2 ? s4.a[p] : std::max(s4.a[p], z.S1), pb = p < 2 ? std::min(s4.b[p], z.S0) : s4.b[p];
+                    if (pb > pa) {
+                        sa[p] = pa; sb[p] = pb; w.sepn += (int64_t)CS_NC * (pb - pa);
+                        const int n3 = p < 2 ? std::max(0, std::min(s4.m[p], pb) - pa) : std::max(0, pb - std::max(s4.m[p], pa));
+                        w.mx3 += (int64_t)CS_NC * n3;
+                        w.mx3n += (int64_t)CS_NC * n3;
+                        w.fl_nodes_useful += 2.0 * far_nodes(q, p) * (3.0 * n3 + 4.0 * ((pb - pa) - n3));
+                    }
+                }
+            }
+            const int lo8[8] = {z.E0, sb[0], z.P1, sb[1], sb[3], z.P3, sb[2], z.Z1}, hi8[8] = {sa[0], z.P0, sa[1], z.Z0, z.E1, sa[3], z.P2, sa[2]};
+            for (int w8 = 0; w8 < 8; w8++) {
+                const int p0 = lo8[w8], p1 = hi8[w8];
+                if (w8 < 4) {
+                    w.body[6] += work_seg(z.E0, z.Q0, p0, p1); w.body[7] += work_seg(z.Q0, z.M0, p0, p1); w.body[8] += work_seg(z.M0, z.Z0, p0, p1);
+                } else {
+                    w.body[6] += work_seg(z.Q1, z.E1, p0, p1); w.body[7] += work_seg(z.M1, z.Q1, p0, p1); w.body[8] += work_seg(z.Z1, z.M1, p0, p1);
+                }
+            }
+        }
+    if (!pl.use_sep) return;
+    for (int gq = 0; gq < pl.ngrp; gq++)
+        for (int q = q0; q < nItot; q++) {
+            const SepZone &z = T.sz[(size_t)gq * nItot + q];
+            for (int p = 0; p < 4; p++) {
+                if (z.b[p] <= z.a[p]) continue;
+                const int n3 = p < 2 ? z.m[p] - z.a[p] : z.b[p] - z.m[p], n4 = (z.b[p] - z.a[p]) - n3;
+                w.rec_nodes += 16 * (int64_t)(n3 + n4);
+                w.fl_nodes_issued += 2.0 * far_nodes(q, p) * 16 * (3.0 * ((n3 + 3) / 4 * 4) + 4.0 * ((n4 + 3) / 4 * 4));
+            }
+        }
+}
+
+// the pieces of k_voigt_edge_mx per (tile, state group): records requested and flops
+static void work_edge(const Column &c, const ColGas &g, const WorkTables &T, Work &w)
+{
+    const VoigtPlan &pl = g.plan;
+    const int K = c.K, nt64 = pl.nt64;
+    const double *nl = g.tab->h_nu.data(), *vv = c.h_nu.data();
+    // the cut-off edges, cut where the next sub-tile comes into reach (k_voigt_edge_mx's phases: one wave per (tile, group) only)
+    const bool phased = pl.edge_phases && pl.edge_big;
+    for (int gq = 0; gq < pl.ngrp; gq++) {
+        const int ns = std::min(16, K - 16 * gq);
+        for (int t = 0; t < nt64; t++) {
+            const WaveWin win = T.win[t];
+            const EdgeZone e = T.ez[(size_t)gq * nt64 + t];
+            const double *v0 = vv + (size_t)t * 64, *v1 = vv + std::min<int64_t>((int64_t)t * 64 + 64, c.nnu);
+            auto piece = [&](int ja, int jb, int nt, int mask) {   // mask 1: the points with |dnu| <= cut count; 2: also |dnu| >= R
+                if (jb <= ja) return;
+                w.rec_edge += 16 * (int64_t)(jb - ja);
+                w.fl_edge_issued += 2.0 * nt * 64.0 * 16.0 * ((jb - ja + 3) / 4 * 4);
+                double cols = 0.0;
+                for (int j = ja; j < jb; j++) {
+                    int n = (int)(std::upper_bound(v0, v1, nl[j] + g.cut) - std::lower_bound(v0, v1, nl[j] - g.cut));
+                    if (mask == 2) n -= (int)(std::lower_bound(v0, v1, nl[j] + e.R) - std::upper_bound(v0, v1, nl[j] - e.R));   // (|dnu| < R: k_voigt_sub's)
+                    cols += std::max(n, 0);
+                }
+                w.fl_edge_useful += 2.0 * nt * cols * ns;
+            };
+            bool tile_carry = false;
+            // a window end: the lines [ja, jb) left or right of the tile
+            auto end_piece = [&](int ja, int jb, int nt, bool left) {
+                if (jb <= ja) return;
+                if (!phased || jb - ja < 48) { piece(ja, jb, nt, 1); return; }
+                const double issued0 = w.fl_edge_issued;
+                piece(ja, jb, nt, 1);              // (for the useful flops)
+                w.fl_edge_issued = issued0;
+                const double tolc = 1e-9 * (std::fabs(v0[0]) + g.cut + 1.0);
+                // the lines inside the cut-off of every point of the tile (those nearest to it): on 16 nodes of the tile (one sub-tile
+                // per step) + the carry to the points, 16 matrix instructions per (tile, group) that has any
+                if (pl.tnodes) {
+                    const int jt = (int)((left ? std::lower_bound(nl + ja, nl + jb, *(v1 - 1) - g.cut + tolc)
+                                               : std::upper_bound(nl + ja, nl + jb, v0[0] + g.cut - tolc)) - nl);
+                    const int nin = left ? jb - jt : jt - ja;
+                    if (nin >= 16) {
+                        w.fl_edge_issued += 2.0 * nt * 16.0 * 16.0 * ((nin + 3) / 4 * 4);
+                        tile_carry = true;
+                        (left ? jb : ja) = jt;
+                    }
+                }
+                // the rest in four parts: part q reaches q + 1 (left) | 4 - q (right) of the tile's four sub-tiles
+                int cutp[5];
+                cutp[0] = ja; cutp[4] = jb;
+                for (int q = 0; q < 3; q++) {
+                    const double col = vv[std::min<int64_t>((int64_t)t * 64 + (left ? 16 * (q + 1) : 16 * q + 15), c.nnu - 1)];
+                    cutp[q + 1] = (int)((left ? std::lower_bound(nl + ja, nl + jb, col - g.cut - tolc)
+                                              : std::upper_bound(nl + ja, nl + jb, col + g.cut + tolc)) - nl);
+                }
+                for (int q = 1; q < 5; q++) cutp[q] = std::max(cutp[q], cutp[q - 1]);
+                for (int q = 0; q < 4; q++) w.fl_edge_issued += 2.0 * nt * 16.0 * (left ? q + 1 : 4 - q) * 16.0 * ((cutp[q + 1] - cutp[q] + 3) / 4 * 4);
+            };
+            end_piece(win.W0, e.eL, (e.far3 & 1) ? 3 : 4, true);
+            end_piece(e.eR, win.W1, (e.far3 & 2) ? 3 : 4, false);
+            if (tile_carry) w.fl_edge_issued += 16.0 * 2048.0;
+            if (e.mL1 > e.mL0) { piece(e.mL0, e.mL3, 3, 1); piece(e.mL3, e.mL1, 4, 1); }
+            if (e.mR1 > e.mR0) { piece(e.mR3, e.mR1, 3, 1); piece(e.mR0, e.mR3, 4, 1); }
+            if (e.cR > e.cL) piece(e.cL, e.cR, (e.far3 & 4) ? 8 : 4, 2);
+        }
+    }
+}
+
+// per (tile, state): the direct bodies of k_voigt_far, what k_voigt_edge_mx takes of the window instead, and k_voigt_sub
+static void work_direct(const Column &c, const ColGas &g, const WorkTables &T, Work &w)
+{
+    const VoigtPlan &pl = g.plan;
+    const int K = c.K, nt64 = pl.nt64, nlev = g.itp.nlev, nItot = c.cheb.nItot;
+    const double *nl = g.tab->h_nu.data();
+    for (int k = 0; k < K; k++)
+        for (int t = 0; t < nt64; t++) {
+            WaveWin win = T.win[t];
+            const Zone &z = T.zn[(size_t)k * nt64 + t];
+            const int W0 = win.W0, W1 = win.W1;
+            int pm[4] = {0, 0, 0, 0};   // [pL0, pL1), [pR0, pR1): the pieces between interpolated sets and near zone on the matrix cores
+            int cc0 = 0, cc1 = 0;       // [cc0, cc1): the core that k_voigt_sub and the second mask of k_voigt_edge_mx share
+            if (pl.use_edge) {   // what k_voigt_edge_mx takes
+                const EdgeZone e = T.ez[(size_t)(k >> 4) * nt64 + t];
+                w.edgen += 64 * (int64_t)((e.eL - W0) + (W1 - e.eR));
+                w.mx3 += 64 * (int64_t)(((e.far3 & 1) ? e.eL - W0 : 0) + ((e.far3 & 2) ? W1 - e.eR : 0));
+                win.W0 = e.eL; win.W1 = e.eR;
+                if (e.mL1 > e.mL0) { pm[0] = e.mL0; pm[1] = e.mL1; w.mx3 += 64 * (int64_t)(e.mL3 - e.mL0); }
+                if (e.mR1 > e.mR0) { pm[2] = e.mR0; pm[3] = e.mR1; w.mx3 += 64 * (int64_t)(e.mR1 - e.mR3); }
+                w.edgen += 64 * (int64_t)((pm[1] - pm[0]) + (pm[3] - pm[2]));
+                if (e.cR > e.cL) {   // the core: every pair visits the matrix cores (masked inside R), k_voigt_sub the lines within R of each sub-tile
+                    cc0 = e.cL; cc1 = e.cR;
+                    w.ncore++;
+                    w.edgen += 64 * (int64_t)(e.cR - e.cL);
+                    if (e.far3 & 4) w.mx8 += 64 * (int64_t)(e.cR - e.cL);
+                    for (int q4 = 0; q4 < 64 / CS_SUBW; q4++) {   // (k_voigt_sub<CS_SUBW>)
+                        const double v0 = c.h_nu[(size_t)t * 64 + CS_SUBW * q4] - e.R, v1 = c.h_nu[(size_t)t * 64 + CS_SUBW * q4 + CS_SUBW - 1] + e.R;
+                        const int ja = (int)(std::lower_bound(nl + e.cL, nl + e.cR, v0) - nl);
+                        const int jb = (int)(std::upper_bound(nl + ja, nl + e.cR, v1) - nl);
+                        w.subn += CS_SUBW * (int64_t)(jb - ja);
+                        if (pl.sub_lean != 1 && ((e.lean >> ((k >> 3) & 1)) & 1)) w.subn_lean += CS_SUBW * (int64_t)(jb - ja);
+                    }
+                }
+            }
+            int64_t n = (win.W1 - win.W0) - (pm[1] - pm[0]) - (pm[3] - pm[2]) - (cc1 - cc0);
+            int sa0 = z.M0, sa1 = z.M0, sb0 = z.M1, sb1 = z.M1;
+            if (nlev > 0) {   // same clamps as k_voigt_far
+                const IZone &zi = T.iz[(size_t)k * nItot + c.cheb.ioff[nlev - 1] + (t >> pl.ishift)];
+                sa0 = std::min(std::max(zi.E0, W0), z.N0); sa1 = std::min(std::max(zi.Z0, sa0), z.N0);
+                sb0 = std::max(std::min(zi.Z1, W1), z.N1); sb1 = std::max(std::min(zi.E1, W1), sb0);
+                n -= (sa1 - sa0) + (sb1 - sb0);
+            }
+            w.direct += 64 * n;
+            // the same segments k_voigt_far runs inside its three clip windows
+            const int a = std::min(std::max(win.E0, W0), z.Q0), a1 = std::min(std::max(win.E0, z.Q0), z.M0);
+            const int b1 = std::max(std::min(win.E1, z.Q1), z.M1), bq = std::max(std::min(win.E1, W1), z.Q1);
+            const int pL0 = pm[1] > pm[0] ? pm[0] : sa1, pL1 = pm[1] > pm[0] ? pm[1] : sa1;
+            const int pR0 = pm[3] > pm[2] ? pm[2] : sb0, pR1 = pm[3] > pm[2] ? pm[3] : sb0;
+            const int cM0 = cc1 > cc0 ? cc0 : pR0, cM1 = cc1 > cc0 ? cc1 : pR0;
+            const int cl[6] = {win.W0, sa1, pL1, cM1, pR1, sb1}, ch[6] = {sa0, pL0, cM0, pR0, sb0, win.W1};
+            for (int cw = 0; cw < 6; cw++) {
+                const int p0 = cl[cw], p1 = ch[cw];
+                if (p0 >= p1) continue;
+                w.body[1] += work_seg(W0, a, p0, p1) + work_seg(bq, W1, p0, p1);
+                w.body[0] += work_seg(a, z.Q0, p0, p1) + work_seg(z.Q1, bq, p0, p1);
+                w.body[3] += work_seg(z.Q0, a1, p0, p1) + work_seg(b1, z.Q1, p0, p1);
+                w.body[2] += work_seg(a1, z.M0, p0, p1) + work_seg(z.M1, b1, p0, p1);
+                w.body[4] += work_seg(z.M0, z.N0, p0, p1) + work_seg(z.N1, z.M1, p0, p1);
+                w.body[5] += work_seg(z.N0, z.N1, p0, p1);
+            }
+        }
+}
+
+// near-line pairs by tier (k_voigt_near<0>: 100 <= s < 1e3, <1>: s < 100), counted from the records of the launch group whose
+// per-(state, line) records are still in HBM -- the last Voigt group of the column (the only one when its gases are merged)
+static int work_near(const Column &c, Work &w)
+{
+    if (c.gas.empty() || c.gas.back().shape != SH_VOIGT || c.gas.back().jhi <= c.gas.back().jlo) return CS_OK;
+    const ColGas &g = c.gas.back();
+    const int64_t L = g.tab->L, nj = g.jhi - g.jlo;
+    std::vector<LineHot> rec((size_t)nj);
+    const double *vv = c.h_nu.data();
+    const int64_t nnu = c.nnu;
+    for (int k = 0; k < c.K; k++) {
+        HIPCHK(hipMemcpy(rec.data(), c.hot.as<LineHot>() + (size_t)k * L + g.jlo, rec.size() * sizeof(LineHot), hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < nj; j++) {
+            const LineHot &h = rec[j];
+            auto within = [&](double smax) -> int64_t {   // points with x^2 + y^2 < smax and |dnu| <= cut
+                if (!(h.p2 < smax)) return 0;
+                const double r = std::min(std::sqrt(smax - h.p2) / h.p1, g.cut);
+                return (std::lower_bound(vv, vv + nnu, h.nul + r) - std::upper_bound(vv, vv + nnu, h.nul - r));
+            };
+            const int64_t n1 = within(kMidS), n0 = within(kSerS);
+            w.near1 += n1;
+            w.near0 += n0 - n1;
+        }
+    }
+    return CS_OK;
+}
+
+int cs_column_work(cs_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !ctx->col.ready || !out) return fail(CS_ESTATE, "no resident column");
+    Column &c = ctx->col;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    const int K = c.K;
+    int rc;
+    Work w;
+    auto download = [](auto &h, const DevBuf &d, size_t n) -> int {
+        h.resize(n);
+        HIPCHK(hipMemcpy(h.data(), d.p, n * sizeof h[0], hipMemcpyDeviceToHost));
+        return CS_OK;
+    };
     for (auto &g : c.gas) {
         // (a batch right after setup writes its windows and zones into buffers of its own: nothing to count, and the column's are unwritten)
-        if (!c.swept || (g.shape != SH_VOIGT && g.shape != SH_LORENTZ)) continue;
-        std::vector<WaveWin> win(nt64);
-        std::vector<Zone> zn((size_t)K * nt64);
-        HIPCHK(hipMemcpy(win.data(), g.win.p, win.size() * sizeof(WaveWin), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(zn.data(), g.zones.p, zn.size() * sizeof(Zone), hipMemcpyDeviceToHost));
-        std::vector<IZone> iz;
+        if (!g.planned) continue;
+        const VoigtPlan &pl = g.plan;
         const int nlev = g.itp.nlev, nItot = c.cheb.nItot;
-        // nodes a piece of interval q is summed on in k_cheb_nodes_mx: 16 or 32 for the far pieces (p = 0, 3) of the intervals that are
-        // not shared by the four waves of a block, 64 otherwise (the carry to the 64 nodes, 2 x 64 x n per state, is not counted)
-        int nsplit_w = 0;
-        if (nlev > 0) {
-            const int q0w = c.cheb.ioff[g.itp.l0], nqw = nItot - q0w;
-            for (int l = g.itp.l0; l < std::min(nlev, g.itp.l0 + (ctx->tune[6] > 0 ? ctx->tune[6] : 1)); l++) nsplit_w += c.cheb.nI[l];
-            if (!mx_big(nqw, K, 2048) || nsplit_w > nqw) nsplit_w = nqw;
-            nsplit_w += q0w;   // intervals below this index are split
-        }
-        auto far_nodes = [&](int q, int p) {
-            // (since round 5 the shared items take their far pieces on fewer nodes as well; key 17: not where every item is shared)
-            if (ctx->tune[11] || (p != 0 && p != 3) || (ctx->tune[17] && nsplit_w >= nItot)) return (int)CS_NC;
-            int l = 0;
-            while (l + 1 < nlev && q >= c.cheb.ioff[l + 1]) l++;
-            return g.itp.nfar[l] > 0 ? g.itp.nfar[l] : (int)CS_NC;
-        };
-        if (nlev > 0) {
-            iz.resize((size_t)K * nItot);
-            HIPCHK(hipMemcpy(iz.data(), g.itp.iz.p, iz.size() * sizeof(IZone), hipMemcpyDeviceToHost));
-            const int q0 = c.cheb.ioff[g.itp.l0];
-            const bool use_sep = !g.pshift && sep_in_use(ctx->matrix_nodes != 0, ctx->matrix_nodes == 2, nItot - q0, K, g.shape != SH_VOIGT, ctx->mixed != 0, ctx->tune[1] != 0);
-            std::vector<SepZone> sz;
-            if (use_sep) {
-                sz.resize((size_t)((K + 15) / 16) * nItot);
-                HIPCHK(hipMemcpy(sz.data(), g.itp.sep.p, sz.size() * sizeof(SepZone), hipMemcpyDeviceToHost));
-            }
-            for (int k = 0; k < K; k++)
-                for (int q = q0; q < nItot; q++) {
-                    const IZone &z = iz[(size_t)k * nItot + q];
-                    nodes += (int64_t)CS_NC * ((z.P0 - z.E0) + (z.Z0 - z.P1) + (z.P2 - z.Z1) + (z.E1 - z.P3));
-                    // the same segments k_cheb_nodes runs: [E0,P0) U [P1,Z0) left, [Z1,P2) U [P3,E1) right, each minus the piece
-                    // the matrix-core kernel takes, cut at Q and M
-                    int sa[4] = {z.P0, z.Z0, z.Z1, z.P3}, sb[4] = {z.P0, z.Z0, z.Z1, z.P3};
-                    if (use_sep) {
-                        const SepZone &s4 = sz[(size_t)(k >> 4) * nItot + q];
-                        for (int p = 0; p < 4; p++) {   // of the group's piece, this state's part: the lines beyond its own series radius (k_cheb_nodes_mx's mask)
-                            const int pa = p < 2 ? s4.a[p] : std::max(s4.a[p], z.S1), pb = p < 2 ? std::min(s4.b[p], z.S0) : s4.b[p];
-                            if (pb > pa) {
-                                sa[p] = pa; sb[p] = pb; sepn += (int64_t)CS_NC * (pb - pa);
-                                const int n3 = p < 2 ? std::max(0, std::min(s4.m[p], pb) - pa) : std::max(0, pb - std::max(s4.m[p], pa));
-                                mx3 += (int64_t)CS_NC * n3;
-                                mx3n += (int64_t)CS_NC * n3;
-                                fl_nodes_useful += 2.0 * far_nodes(q, p) * (3.0 * n3 + 4.0 * ((pb - pa) - n3));
-                            }
-                        }
-                    }
-                    const int lo8[8] = {z.E0, sb[0], z.P1, sb[1], sb[3], z.P3, sb[2], z.Z1}, hi8[8] = {sa[0], z.P0, sa[1], z.Z0, z.E1, sa[3], z.P2, sa[2]};
-                    for (int w8 = 0; w8 < 8; w8++) {
-                        const int p0 = lo8[w8], p1 = hi8[w8];
-                        if (w8 < 4) {
-                            body[6] += seg(z.E0, z.Q0, p0, p1); body[7] += seg(z.Q0, z.M0, p0, p1); body[8] += seg(z.M0, z.Z0, p0, p1);
-                        } else {
-                            body[6] += seg(z.Q1, z.E1, p0, p1); body[7] += seg(z.M1, z.Q1, p0, p1); body[8] += seg(z.Z1, z.M1, p0, p1);
-                        }
-                    }
-                }
-        }
-        if (nlev > 0) {
-            const int q0 = c.cheb.ioff[g.itp.l0];
-            if (!g.pshift && sep_in_use(ctx->matrix_nodes != 0, ctx->matrix_nodes == 2, nItot - q0, K, g.shape != SH_VOIGT, ctx->mixed != 0, ctx->tune[1] != 0)) {
-                std::vector<SepZone> sz((size_t)((K + 15) / 16) * nItot);
-                HIPCHK(hipMemcpy(sz.data(), g.itp.sep.p, sz.size() * sizeof(SepZone), hipMemcpyDeviceToHost));
-                for (int gq = 0; gq < (K + 15) / 16; gq++) {
-                    const int ns = std::min(16, K - 16 * gq);
-                    for (int q = q0; q < nItot; q++) {
-                        const SepZone &z = sz[(size_t)gq * nItot + q];
-                        for (int p = 0; p < 4; p++) {
-                            if (z.b[p] <= z.a[p]) continue;
-                            const int n3 = p < 2 ? z.m[p] - z.a[p] : z.b[p] - z.m[p], n4 = (z.b[p] - z.a[p]) - n3;
-                            (void)ns;   // (useful flops: per state, above -- a state takes part only beyond its own series radius)
-                            rec_nodes += 16 * (int64_t)(n3 + n4);
-                            fl_nodes_issued += 2.0 * far_nodes(q, p) * 16 * (3.0 * ((n3 + 3) / 4 * 4) + 4.0 * ((n4 + 3) / 4 * 4));
-                        }
-                    }
-                }
-            }
-        }
-        int ishift = 0;
-        if (nlev > 0) for (int r = c.cheb.itv[nlev - 1] / 64; r > 1; r >>= 1) ishift++;
-        const bool use_edge = nlev > 0 && !g.pshift && edge_in_use(ctx->matrix_nodes != 0, ctx->matrix_nodes == 2, nt64, K, g.shape != SH_VOIGT, ctx->mixed != 0,
-                                                      std::max<int64_t>(g.jhi - g.jlo, 0), ctx->tune[1] != 0);
-        std::vector<EdgeZone> ez;
-        if (use_edge) {
-            ez.resize((size_t)((K + 15) / 16) * nt64);
-            HIPCHK(hipMemcpy(ez.data(), g.itp.edge.p, ez.size() * sizeof(EdgeZone), hipMemcpyDeviceToHost));
-        }
-        if (use_edge) {
-            const double *nl = g.tab->h_nu.data(), *vv = c.h_nu.data();
-            for (int gq = 0; gq < (K + 15) / 16; gq++) {
-                const int ns = std::min(16, K - 16 * gq);
-                for (int t = 0; t < nt64; t++) {
-                    const WaveWin w = win[t];
-                    const EdgeZone e = ez[(size_t)gq * nt64 + t];
-                    const double *v0 = vv + (size_t)t * 64, *v1 = vv + std::min<int64_t>((int64_t)t * 64 + 64, c.nnu);
-                    auto piece = [&](int ja, int jb, int nt, int mask) {   // mask 0: every point counts; 1: |dnu| <= cut; 2: also |dnu| >= R
-                        if (jb <= ja) return;
-                        rec_edge += 16 * (int64_t)(jb - ja);
-                        fl_edge_issued += 2.0 * nt * 64.0 * 16.0 * ((jb - ja + 3) / 4 * 4);
-                        double cols = 0.0;
-                        for (int j = ja; j < jb; j++) {
-                            if (mask == 0) { cols += (double)(v1 - v0); continue; }
-                            int n = (int)(std::upper_bound(v0, v1, nl[j] + g.cut) - std::lower_bound(v0, v1, nl[j] - g.cut));
-                            if (mask == 2) n -= (int)(std::lower_bound(v0, v1, nl[j] + e.R) - std::upper_bound(v0, v1, nl[j] - e.R));   // (|dnu| < R: k_voigt_sub's)
-                            cols += std::max(n, 0);
-                        }
-                        fl_edge_useful += 2.0 * nt * cols * ns;
-                    };
-                    // the cut-off edges, cut where the next sub-tile comes into reach (k_voigt_edge_mx's phases: one wave per (tile, group) only)
-                    const bool phased = !ctx->tune[14] && mx_big(nt64, K, 1024);
-                    bool tile_carry = false;
-                    auto end_piece = [&](int ja, int jb, int nt, bool left) {
-                        if (jb <= ja) return;
-                        // the lines inside the cut-off of every point of the tile: on 16 nodes of the tile (one sub-tile per step) + the carry
-                        // to the points, 16 matrix instructions per (tile, group) that has any
-                        const bool tnodes_on = c.cheb.tile_nodes_ok && !ctx->tune[23];
-                        if (!phased || jb - ja < 48) { piece(ja, jb, nt, 1); return; }
-                        const double issued0 = fl_edge_issued;
-                        piece(ja, jb, nt, 1);              // (for the useful flops)
-                        fl_edge_issued = issued0;
-                        const double tolc = 1e-9 * (std::fabs(v0[0]) + g.cut + 1.0);
-                        int cutp[5];
-                        if (left) {
-                            if (tnodes_on) {
-                                const int j3 = (int)(std::lower_bound(nl + ja, nl + jb, *(v1 - 1) - g.cut + tolc) - nl);
-                                if (jb - j3 >= 16) {
-                                    fl_edge_issued += 2.0 * nt * 16.0 * 16.0 * ((jb - j3 + 3) / 4 * 4);
-                                    tile_carry = true;
-                                    jb = j3;
-                                }
-                            }
-                            cutp[0] = ja; cutp[4] = jb;
-                            for (int q = 0; q < 3; q++) {
-                                const double *col = vv + std::min<int64_t>((int64_t)t * 64 + 16 * (q + 1), c.nnu - 1);
-                                cutp[q + 1] = (int)(std::lower_bound(nl + ja, nl + jb, *col - g.cut - tolc) - nl);
-                            }
-                            for (int q = 1; q < 5; q++) cutp[q] = std::max(cutp[q], cutp[q - 1]);
-                            for (int q = 0; q < 4; q++) fl_edge_issued += 2.0 * nt * 16.0 * (q + 1) * 16.0 * ((cutp[q + 1] - cutp[q] + 3) / 4 * 4);
-                        } else {
-                            if (tnodes_on) {
-                                const int u3 = (int)(std::upper_bound(nl + ja, nl + jb, v0[0] + g.cut - tolc) - nl);
-                                if (u3 - ja >= 16) {
-                                    fl_edge_issued += 2.0 * nt * 16.0 * 16.0 * ((u3 - ja + 3) / 4 * 4);
-                                    tile_carry = true;
-                                    ja = u3;
-                                }
-                            }
-                            cutp[0] = ja; cutp[4] = jb;
-                            for (int q = 0; q < 3; q++) {
-                                const double *col = vv + std::min<int64_t>((int64_t)t * 64 + 16 * q + 15, c.nnu - 1);
-                                cutp[q + 1] = (int)(std::upper_bound(nl + ja, nl + jb, *col + g.cut + tolc) - nl);
-                            }
-                            for (int q = 1; q < 5; q++) cutp[q] = std::max(cutp[q], cutp[q - 1]);
-                            for (int q = 0; q < 4; q++) fl_edge_issued += 2.0 * nt * 16.0 * (4 - q) * 16.0 * ((cutp[q + 1] - cutp[q] + 3) / 4 * 4);
-                        }
-                    };
-                    tile_carry = false;
-                    end_piece(w.W0, e.eL, (e.far3 & 1) ? 3 : 4, true);
-                    end_piece(e.eR, w.W1, (e.far3 & 2) ? 3 : 4, false);
-                    if (tile_carry) fl_edge_issued += 16.0 * 2048.0;
-                    if (e.mL1 > e.mL0) { piece(e.mL0, e.mL3, 3, 1); piece(e.mL3, e.mL1, 4, 1); }
-                    if (e.mR1 > e.mR0) { piece(e.mR3, e.mR1, 3, 1); piece(e.mR0, e.mR3, 4, 1); }
-                    if (e.cR > e.cL) piece(e.cL, e.cR, (e.far3 & 4) ? 8 : 4, 2);
-                }
-            }
-        }
+        WorkTables T;
+        if ((rc = download(T.win, g.win, (size_t)pl.nt64)) || (rc = download(T.zn, g.zones, (size_t)K * pl.nt64)) ||
+            (nlev > 0 && (rc = download(T.iz, g.itp.iz, (size_t)K * nItot))) ||
+            (pl.use_sep && (rc = download(T.sz, g.itp.sep, (size_t)pl.ngrp * nItot))) ||
+            (pl.use_edge && (rc = download(T.ez, g.itp.edge, (size_t)pl.ngrp * pl.nt64))))
+            return rc;
+        if (nlev > 0) work_nodes(c, g, T, w);
+        if (pl.use_edge) work_edge(c, g, T, w);
         if (nlev > 0)   // the contraction that carries the node sums to the grid (k_cheb_apply_mfma, or fused into k_voigt_edge_mx)
-            fl_apply += 2.0 * CS_NC * 64.0 * 16.0 * ((K + 15) / 16) * (double)nt64 * (nlev - g.itp.l0);   // (per group; with the cascade: cs_column_info)
-        for (int k = 0; k < K; k++)
-            for (int t = 0; t < nt64; t++) {
-                WaveWin w = win[t];
-                const Zone &z = zn[(size_t)k * nt64 + t];
-                const int W0 = w.W0, W1 = w.W1;
-                int pm[4] = {0, 0, 0, 0};   // [pL0, pL1), [pR0, pR1): the pieces between interpolated sets and near zone on the matrix cores
-                int cc0 = 0, cc1 = 0;       // [cc0, cc1): the core that k_voigt_sub and the second mask of k_voigt_edge_mx share
-                if (use_edge) {   // what k_voigt_edge_mx takes
-                    const EdgeZone e = ez[(size_t)(k >> 4) * nt64 + t];
-                    edgen += 64 * (int64_t)((e.eL - W0) + (W1 - e.eR));
-                    mx3 += 64 * (int64_t)(((e.far3 & 1) ? e.eL - W0 : 0) + ((e.far3 & 2) ? W1 - e.eR : 0));
-                    w.W0 = e.eL; w.W1 = e.eR;
-                    if (e.mL1 > e.mL0) { pm[0] = e.mL0; pm[1] = e.mL1; mx3 += 64 * (int64_t)(e.mL3 - e.mL0); }
-                    if (e.mR1 > e.mR0) { pm[2] = e.mR0; pm[3] = e.mR1; mx3 += 64 * (int64_t)(e.mR1 - e.mR3); }
-                    edgen += 64 * (int64_t)((pm[1] - pm[0]) + (pm[3] - pm[2]));
-                    if (e.cR > e.cL) {   // the core: every pair visits the matrix cores (masked inside R), k_voigt_sub the lines within R of each sub-tile
-                        cc0 = e.cL; cc1 = e.cR;
-                        ncore++;
-                        edgen += 64 * (int64_t)(e.cR - e.cL);
-                        if (e.far3 & 4) mx8 += 64 * (int64_t)(e.cR - e.cL);
-                        const double *nl = g.tab->h_nu.data();
-                        for (int q4 = 0; q4 < 64 / CS_SUBW; q4++) {   // (k_voigt_sub<CS_SUBW>)
-                            const double v0 = c.h_nu[(size_t)t * 64 + CS_SUBW * q4] - e.R, v1 = c.h_nu[(size_t)t * 64 + CS_SUBW * q4 + CS_SUBW - 1] + e.R;
-                            const int ja = (int)(std::lower_bound(nl + e.cL, nl + e.cR, v0) - nl);
-                            const int jb = (int)(std::upper_bound(nl + ja, nl + e.cR, v1) - nl);
-                            subn += CS_SUBW * (int64_t)(jb - ja);
-                            if (ctx->tune[18] != 1 && ((e.lean >> ((k >> 3) & 1)) & 1)) subn_lean += CS_SUBW * (int64_t)(jb - ja);
-                        }
-                    }
-                }
-                int64_t n = (w.W1 - w.W0) - (pm[1] - pm[0]) - (pm[3] - pm[2]) - (cc1 - cc0);
-                int sa0 = z.M0, sa1 = z.M0, sb0 = z.M1, sb1 = z.M1;
-                if (nlev > 0) {   // same clamps as k_voigt_far
-                    const IZone &zi = iz[(size_t)k * nItot + c.cheb.ioff[nlev - 1] + (t >> ishift)];
-                    sa0 = std::min(std::max(zi.E0, W0), z.N0); sa1 = std::min(std::max(zi.Z0, sa0), z.N0);
-                    sb0 = std::max(std::min(zi.Z1, W1), z.N1); sb1 = std::max(std::min(zi.E1, W1), sb0);
-                    n -= (sa1 - sa0) + (sb1 - sb0);
-                }
-                direct += 64 * n;
-                // the same segments k_voigt_far runs inside its three clip windows
-                const int a = std::min(std::max(w.E0, W0), z.Q0), a1 = std::min(std::max(w.E0, z.Q0), z.M0);
-                const int b1 = std::max(std::min(w.E1, z.Q1), z.M1), bq = std::max(std::min(w.E1, W1), z.Q1);
-                const int pL0 = pm[1] > pm[0] ? pm[0] : sa1, pL1 = pm[1] > pm[0] ? pm[1] : sa1;
-                const int pR0 = pm[3] > pm[2] ? pm[2] : sb0, pR1 = pm[3] > pm[2] ? pm[3] : sb0;
-                const int cM0 = cc1 > cc0 ? cc0 : pR0, cM1 = cc1 > cc0 ? cc1 : pR0;
-                const int cl[6] = {w.W0, sa1, pL1, cM1, pR1, sb1}, ch[6] = {sa0, pL0, cM0, pR0, sb0, w.W1};
-                for (int cw = 0; cw < 6; cw++) {
-                    const int p0 = cl[cw], p1 = ch[cw];
-                    if (p0 >= p1) continue;
-                    body[1] += seg(W0, a, p0, p1) + seg(bq, W1, p0, p1);
-                    body[0] += seg(a, z.Q0, p0, p1) + seg(z.Q1, bq, p0, p1);
-                    body[3] += seg(z.Q0, a1, p0, p1) + seg(b1, z.Q1, p0, p1);
-                    body[2] += seg(a1, z.M0, p0, p1) + seg(z.M1, b1, p0, p1);
-                    body[4] += seg(z.M0, z.N0, p0, p1) + seg(z.N1, z.M1, p0, p1);
-                    body[5] += seg(z.N0, z.N1, p0, p1);
-                }
-            }
+            w.fl_apply += 2.0 * CS_NC * 64.0 * 16.0 * pl.ngrp * (double)pl.nt64 * (nlev - g.itp.l0);   // (per group; with the cascade: cs_column_info)
+        work_direct(c, g, T, w);
     }
-    // near-line pairs by tier (k_voigt_near<0>: 100 <= s < 1e3, <1>: s < 100), counted from the records of the launch group whose
-    // per-(state, line) records are still in HBM -- the last Voigt group of the column (the only one when its gases are merged)
-    if (!c.gas.empty() && c.gas.back().shape == SH_VOIGT && c.gas.back().jhi > c.gas.back().jlo) {
-        const ColGas &g = c.gas.back();
-        const int64_t L = g.tab->L, nj = g.jhi - g.jlo;
-        std::vector<LineHot> rec((size_t)nj);
-        const double *vv = c.h_nu.data();
-        const int64_t nnu = c.nnu;
-        for (int k = 0; k < K; k++) {
-            HIPCHK(hipMemcpy(rec.data(), c.hot.as<LineHot>() + (size_t)k * L + g.jlo, rec.size() * sizeof(LineHot), hipMemcpyDeviceToHost));
-            for (int64_t j = 0; j < nj; j++) {
-                const LineHot &h = rec[j];
-                auto within = [&](double smax) -> int64_t {   // points with x^2 + y^2 < smax and |dnu| <= cut
-                    if (!(h.p2 < smax)) return 0;
-                    const double r = std::min(std::sqrt(smax - h.p2) / h.p1, g.cut);
-                    return (std::lower_bound(vv, vv + nnu, h.nul + r) - std::upper_bound(vv, vv + nnu, h.nul - r));
-                };
-                const int64_t n1 = within(kMidS), n0 = within(kSerS);
-                near1 += n1;
-                near0 += n0 - n1;
-            }
-        }
-    }
-    out[20] = near0;
-    out[21] = near1;
-    out[22] = (int64_t)fl_edge_useful;
-    out[23] = (int64_t)fl_edge_issued;
-    out[24] = (int64_t)fl_nodes_useful;
-    out[25] = (int64_t)fl_nodes_issued;
-    out[26] = (int64_t)fl_apply;
+    if ((rc = work_near(c, w))) return rc;
+    out[CS_WORK_DIRECT_EVALS] = w.direct;
+    out[CS_WORK_NODE_EVALS] = w.nodes;
+    out[CS_WORK_LEVELS] = c.cheb.nlev;
+    out[CS_WORK_INTERVALS] = c.cheb.nItot;
+    for (int q = 0; q < 6; q++) out[CS_WORK_DIRECT_T2 + q] = 64 * w.body[q];
+    for (int q = 0; q < 3; q++) out[CS_WORK_NODE_T2 + q] = (int64_t)CS_NC * w.body[6 + q];
+    out[CS_WORK_NODE_EVALS_MATRIX] = w.sepn;
+    out[CS_WORK_DIRECT_EVALS_MATRIX] = w.edgen;
+    out[CS_WORK_MATRIX_EVALS_3TERM] = w.mx3;
+    out[CS_WORK_SUB_EVALS] = w.subn;
+    out[CS_WORK_CORE_TILE_STATES] = w.ncore;
+    out[CS_WORK_MATRIX_EVALS_8TERM] = w.mx8;
+    out[CS_WORK_NODE_EVALS_MATRIX_3TERM] = w.mx3n;
+    out[CS_WORK_NEAR_PAIRS_TIER0] = w.near0;
+    out[CS_WORK_NEAR_PAIRS_TIER1] = w.near1;
+    out[CS_WORK_EDGE_MX_FLOPS_USEFUL] = (int64_t)w.fl_edge_useful;
+    out[CS_WORK_EDGE_MX_FLOPS_ISSUED] = (int64_t)w.fl_edge_issued;
+    out[CS_WORK_NODES_MX_FLOPS_USEFUL] = (int64_t)w.fl_nodes_useful;
+    out[CS_WORK_NODES_MX_FLOPS_ISSUED] = (int64_t)w.fl_nodes_issued;
+    out[CS_WORK_APPLY_FLOPS] = (int64_t)w.fl_apply;
+    out[CS_WORK_EDGE_MX_RECORD_BYTES] = w.rec_edge * (int64_t)sizeof(LineHot);
+    out[CS_WORK_NODES_MX_RECORD_BYTES] = w.rec_nodes * (int64_t)sizeof(LineHot);
+    out[CS_WORK_FAR_SPLIT] = c.log_last.disp.far_split;
+    out[CS_WORK_TABLES] = c.log_last.disp.tables;
+    out[CS_WORK_NEAR_PRIO] = c.log_last.disp.near_prio;
+    out[CS_WORK_STREAMS] = c.log_last.disp.streams;
+    out[CS_WORK_NODES_SPLIT] = c.log_last.disp.nodes_split;
+    out[CS_WORK_FLAGS] = c.log_last.disp.flags;
+    out[CS_WORK_SUB_LEAN_EVALS] = w.subn_lean;
+    // (the flux-phase stamps describe the stamp buffer's contents: the only part that looks at a setting)
     if (c.fluxdbg.p && (ctx->tune[15] & 128)) {   // k_flux_scan's phases in block 0, ns: cross-sections, depths + Planck, chunk pass, hand-over, second pass, band sum
         unsigned long long st[8] = {};
         (void)hipMemcpy(st, c.fluxdbg.p, sizeof st, hipMemcpyDeviceToHost);
-        for (int q = 0; q < 4; q++) out[27 + q] = (int64_t)(st[q + 1] - st[q]) * 10;   // (100 MHz clock)
-        out[31] = (int64_t)(st[7] - st[0]) * 10;   // block 0's first instruction to the last block's last word
+        for (int q = 0; q < 4; q++) out[CS_WORK_FLUX_SCAN_NS + q] = (int64_t)(st[q + 1] - st[q]) * 10;   // (100 MHz clock)
+        out[CS_WORK_FLUX_SCAN_TOTAL_NS] = (int64_t)(st[7] - st[0]) * 10;   // block 0's first instruction to the last block's last word
         if (getenv("CS_FLUX_DBG") && c.flux_form_last == 3) {   // every block's start and end (k_flux_scan), relative to the earliest start
             const size_t nb = (size_t)(c.nnu + 63) / 64;
             if (c.fluxdbg.bytes >= (8 + 2 * nb + 32) * sizeof(unsigned long long)) {
@@ -3947,30 +4018,8 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
             }
         }
     } else {
-        for (int q = 27; q < 32; q++) out[q] = 0;
+        for (int q = CS_WORK_FLUX_SCAN_NS; q <= CS_WORK_FLUX_SCAN_TOTAL_NS; q++) out[q] = 0;
     }
-    out[32] = rec_edge * (int64_t)sizeof(LineHot);
-    out[33] = rec_nodes * (int64_t)sizeof(LineHot);
-    out[34] = c.disp_last.far_split;
-    out[35] = c.disp_last.tables;
-    out[36] = c.disp_last.near_prio;
-    out[37] = c.disp_last.streams;
-    out[38] = c.disp_last.nodes_split;
-    out[39] = c.disp_last.flags;
-    out[0] = direct;
-    out[1] = nodes;
-    out[2] = c.cheb.nlev;
-    out[3] = c.cheb.nItot;
-    for (int q = 0; q < 6; q++) out[4 + q] = 64 * body[q];
-    for (int q = 6; q < 9; q++) out[4 + q] = (int64_t)CS_NC * body[q];
-    out[13] = sepn;
-    out[14] = edgen;
-    out[15] = mx3;
-    out[16] = subn;
-    out[17] = ncore;
-    out[18] = mx8;
-    out[19] = mx3n;
-    out[40] = subn_lean;
     return CS_OK;
 }
 

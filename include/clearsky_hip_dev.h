@@ -116,36 +116,65 @@ int cs_column_counts(cs_ctx *ctx, int64_t *pair_evals, int64_t *lines_in_range);
  * summed the per-point far lines of its last group: 0 = k_voigt_far, 1 = k_linesum<shape> (Doppler; PHCO2 without its fast path), 2 = k_phco2 */
 int cs_column_info(cs_ctx *ctx, int64_t *out);
 
-/* line-shape evaluations the last cs_column_run actually issued for its Voigt gases (measurement hook): out[0] = per-point
- * evaluations of k_voigt_far/k_voigt_near (64 lanes x lines per wave), out[1] = node evaluations of k_cheb_nodes,
- * out[2] = interpolation levels in use, out[3] = intervals over all levels; out[4..9] = the per-point evaluations by loop body
- * (2-term, 2-term + cut-off predicate, 3-term, 3-term + predicate, 4-term + predicate, near-zone pass), out[10..12] = the node
- * evaluations by body (2-, 3-, 4-term) on the vector unit -- what bench.py weights with the VALU instruction count of each
- * body -- and out[13], out[14] = the node and the per-point evaluations summed on the matrix cores (cs_set_matrix_cores;
- * out[0] and out[4..9] do not include the latter), out[15] = those of out[13] + out[14] that take three series terms instead of
- * four, out[16] = (lane, line) evaluations of k_voigt_sub (the window core on 16-point sub-tiles; 37 instructions each like the
- * near-zone pass; not in out[0]), out[17] = (tile, state) pairs whose window core is k_voigt_sub's, summed over the gases, out[18] =
- * those of out[14] that take eight series terms (the sub-tile cores), out[19] = the part of out[15] that belongs to out[13];
- * out[20], out[21] = (nu, line, state) pairs of k_voigt_near<0> (100 <= x^2+y^2 < 1e3) and <1> (< 100), counted on the host from the
- * records of the last Voigt launch group; out[22], out[23] = flops of k_voigt_edge_mx: useful (2 x series terms for every (point,
- * line, state) with the point inside the cut-off and outside the core radius, real states only) and issued (2048 per matrix
- * instruction: masked columns, padded states and the fill of the last 4-line step included); out[24], out[25] = the same for
- * k_cheb_nodes_mx; out[26] = flops of the node-sum -> grid contraction (k_cheb_apply_mfma, or inside k_voigt_edge_mx / k_flux_*); with
- * cs_set_tuning key 15 | 128, out[27..30] = nanoseconds block 0 of k_flux_scan spent on cross-sections, optical depths + Planck values,
- * first pass over its layer chunk, hand-over of the incoming intensities, and out[31] = from its first instruction to the last block's
- * store of the band fluxes (100 MHz wall clock; 0 otherwise); out[32], out[33] = bytes of per-(state, line) records k_voigt_edge_mx and
- * k_cheb_nodes_mx REQUEST per launch (lines of every piece x 16 states x 32 B: neighbouring tiles / intervals ask for the same record again --
- * the unique ones are K x lines in range x 32 B); out[34..39] = what the last cs_column_run (or cs_column_batch) dispatched, with
- * out[34..38] for its last Voigt group (0 where it had none): out[34] = waves per 64-point tile of k_voigt_far (1, 2, 4; key 22),
- * out[35] = the matrix-core piece tables: 0 none, 1 blocks of k_gas_setup_mx, 2 k_mxzones16, 3 k_mxzones (one thread per item; key 21,
- * key 15 | 16), out[36] = wave priority of the near-line kernels (0, 3; key 16), out[37] = side streams: 1 node sums, 2 near-line
- * kernels (keys 2, 7), out[38] = 1 where k_cheb_nodes ran four waves per (interval, state) (key 13), out[39] = flags of the whole step:
- * 1 window ends on the 16 tile nodes in k_voigt_edge_mx (key 23), 2 near-line plane cleared by a memset (key 19), 4 k_rt_streams
- * (key 5), 8 band sum inside the flux kernel (key 15 | 4), 16 far pieces of shared items on 64 nodes (key 17), 32 k_flux_chunk with
- * four waves per SIMD (key 15 | 8), 64 levels folded on the node-sum side stream (key 15 | 256).  out[0..26] and out[32..33] describe
- * the column's own last cross-section stage: zero while only cs_column_batch has run since cs_column_setup; so does out[40] = the part
- * of out[16] in waves that start with the range-only pass by the piece tables (0 with key 18 = 1).  `out` holds 41 values.
- * cs_column_counts is the reference's count. */
+/* cs_column_work: what the resident column's last run issued for its Voigt / Lorentz gases, counted on the host from the zone tables that
+ * run left on the device and from the dispatch that run made.  Every counter describes the run AS DISPATCHED: a setting changed since
+ * (cs_set_tuning, cs_set_matrix_cores, cs_set_precision) shows only after the next run.  CS_WORK_DIRECT_EVALS .. CS_WORK_APPLY_FLOPS,
+ * the two *_RECORD_BYTES and CS_WORK_SUB_LEAN_EVALS describe the column's own last cross-section stage and are zero while only
+ * cs_column_batch has run since cs_column_setup.  "Evaluations" are (lane | node, line) pairs: 64 lanes x lines per wave.  `out` holds
+ * CS_WORK_COUNT values.  (cs_column_counts is the reference's count.) */
+enum {
+    CS_WORK_DIRECT_EVALS = 0,       /* per-point evaluations of k_voigt_far / k_voigt_near on the vector unit */
+    CS_WORK_NODE_EVALS = 1,         /* node evaluations of k_cheb_nodes */
+    CS_WORK_LEVELS = 2,             /* interpolation levels in use */
+    CS_WORK_INTERVALS = 3,          /* intervals over all levels */
+    CS_WORK_DIRECT_T2 = 4,          /* [4..9]: CS_WORK_DIRECT_EVALS by loop body -- 2-term, */
+    CS_WORK_DIRECT_T2_CUT = 5,      /* 2-term + cut-off predicate, */
+    CS_WORK_DIRECT_T3 = 6,          /* 3-term, */
+    CS_WORK_DIRECT_T3_CUT = 7,      /* 3-term + predicate, */
+    CS_WORK_DIRECT_T4_CUT = 8,      /* 4-term + predicate, */
+    CS_WORK_DIRECT_NEAR_ZONE = 9,   /* near-zone pass (what bench.py weights with the VALU instruction count of each body) */
+    CS_WORK_NODE_T2 = 10,           /* [10..12]: the node evaluations on the vector unit by body -- 2-, */
+    CS_WORK_NODE_T3 = 11,           /* 3-, */
+    CS_WORK_NODE_T4 = 12,           /* 4-term */
+    CS_WORK_NODE_EVALS_MATRIX = 13,     /* node evaluations summed on the matrix cores (cs_set_matrix_cores) */
+    CS_WORK_DIRECT_EVALS_MATRIX = 14,   /* per-point evaluations summed on the matrix cores (not in [0], [4..9]) */
+    CS_WORK_MATRIX_EVALS_3TERM = 15,    /* those of [13] + [14] that take three series terms instead of four */
+    CS_WORK_SUB_EVALS = 16,         /* (lane, line) evaluations of k_voigt_sub: the window core on sub-tiles, 37 instructions each like the near-zone pass; not in [0] */
+    CS_WORK_CORE_TILE_STATES = 17,  /* (tile, state) pairs whose window core is k_voigt_sub's, summed over the gases */
+    CS_WORK_MATRIX_EVALS_8TERM = 18,    /* those of [14] that take eight series terms (the sub-tile cores) */
+    CS_WORK_NODE_EVALS_MATRIX_3TERM = 19,   /* the part of [15] that belongs to [13] */
+    CS_WORK_NEAR_PAIRS_TIER0 = 20,  /* (nu, line, state) pairs of k_voigt_near<0> (100 <= x^2+y^2 < 1e3), from the records of the last Voigt launch group */
+    CS_WORK_NEAR_PAIRS_TIER1 = 21,  /* ... of k_voigt_near<1> (< 100) */
+    CS_WORK_EDGE_MX_FLOPS_USEFUL = 22,  /* k_voigt_edge_mx: 2 x series terms per (point, line, state), point inside the cut-off and outside the core radius, real states only */
+    CS_WORK_EDGE_MX_FLOPS_ISSUED = 23,  /* ... 2048 per matrix instruction: masked columns, padded states and the fill of the last 4-line step included */
+    CS_WORK_NODES_MX_FLOPS_USEFUL = 24, /* the same for k_cheb_nodes_mx */
+    CS_WORK_NODES_MX_FLOPS_ISSUED = 25,
+    CS_WORK_APPLY_FLOPS = 26,       /* the node-sum -> grid contraction (k_cheb_apply_mfma, or inside k_voigt_edge_mx / k_flux_*) */
+    CS_WORK_FLUX_SCAN_NS = 27,      /* [27..31], with cs_set_tuning key 15 | 128 (0 otherwise; 100 MHz wall clock): ns block 0 of k_flux_scan spent on */
+                                    /* cross-sections, depths + Planck values, first pass over its layer chunk, hand-over of the incoming intensities; */
+    CS_WORK_FLUX_SCAN_TOTAL_NS = 31,    /* and from its first instruction to the last block's store of the band fluxes */
+    CS_WORK_EDGE_MX_RECORD_BYTES = 32,  /* per-(state, line) records k_voigt_edge_mx REQUESTS per launch: lines of every piece x 16 states x 32 B */
+    CS_WORK_NODES_MX_RECORD_BYTES = 33, /* ... k_cheb_nodes_mx (neighbouring tiles / intervals ask for the same record again: the unique ones are K x lines in range x 32 B) */
+    /* [34..39]: what the last cs_column_run (or cs_column_batch) dispatched; [34..38] for its last Voigt group (0 where it had none) */
+    CS_WORK_FAR_SPLIT = 34,         /* waves per 64-point tile of k_voigt_far (1, 2, 4; key 22) */
+    CS_WORK_TABLES = 35,            /* the matrix-core piece tables: 0 none, 1 blocks of k_gas_setup_mx, 2 k_mxzones16, 3 k_mxzones (one thread per item; key 21, key 15 | 16) */
+    CS_WORK_NEAR_PRIO = 36,         /* wave priority of the near-line kernels (0, 3; key 16) */
+    CS_WORK_STREAMS = 37,           /* side streams: 1 node sums, 2 near-line kernels (keys 2, 7) */
+    CS_WORK_NODES_SPLIT = 38,       /* 1 where k_cheb_nodes ran four waves per (interval, state) (key 13) */
+    CS_WORK_FLAGS = 39,             /* CS_DF_* of the whole step */
+    CS_WORK_SUB_LEAN_EVALS = 40,    /* the part of [16] in waves that start with the range-only pass by the piece tables (0 with key 18 = 1) */
+    CS_WORK_COUNT = 41
+};
+/* out[CS_WORK_FLAGS] */
+enum {
+    CS_DF_TNODES = 1,           /* window ends on the 16 tile nodes in k_voigt_edge_mx (key 23) */
+    CS_DF_NEAR_MEMSET = 2,      /* near-line plane cleared by a memset (key 19) */
+    CS_DF_RT_STREAMS = 4,       /* k_rt_streams (key 5) */
+    CS_DF_BAND_SUM = 8,         /* band sum inside the flux kernel (key 15 | 4) */
+    CS_DF_FAR64_SHARED = 16,    /* far pieces of shared items on 64 nodes (key 17) */
+    CS_DF_CHUNK4 = 32,          /* k_flux_chunk with four waves per SIMD (key 15 | 8) */
+    CS_DF_CASCADE_ASIDE = 64    /* levels folded on the node-sum side stream (key 15 | 256) */
+};
 int cs_column_work(cs_ctx *ctx, int64_t *out);
 
 /* interval sizes (descending, <= 5, each 128..2048 points) cs_set_interp(on) would use for this grid and cut-off; returns

@@ -16,13 +16,14 @@ import numpy as np
 import pytest
 
 import tabulated_ref as R
+from clearsky_jl_amd import DISPATCH_FLAGS
 
 pytestmark = pytest.mark.gpu
 
 SCAN, CHUNK, SEP = (), ((15, 2), (5, 0)), ((15, 1),)
 FORMS = (("scan", SCAN, 3), ("chunk", CHUNK, 2), ("separate", SEP, 0))
 G = 9.8
-RT_STREAMS, CHUNK4 = 4, 32                       # cs_column_work out[39] bits (include/clearsky_hip_dev.h)
+RT_STREAMS, CHUNK4 = DISPATCH_FLAGS["RT_STREAMS"], DISPATCH_FLAGS["CHUNK4"]   # Column.work()["dispatch"]["flags"]
 
 
 def _is(r, form, tune):

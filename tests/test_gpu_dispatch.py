@@ -136,8 +136,9 @@ def _streams_near(on):
     return lambda r: bool(_disp(r)["streams"] & 2) == on
 
 
-# out[39] bits (include/clearsky_hip_dev.h, cs_column_work)
-TNODES, NEAR_MEMSET, RT_STREAMS, BAND_SUM, FAR64_SHARED, CHUNK4, CASCADE_ASIDE = 1, 2, 4, 8, 16, 32, 64
+# Column.work()["dispatch"]["flags"] bits (CS_DF_* of include/clearsky_hip_dev.h)
+TNODES, NEAR_MEMSET, RT_STREAMS, BAND_SUM, FAR64_SHARED, CHUNK4, CASCADE_ASIDE = (
+    clearsky_jl_amd.DISPATCH_FLAGS[n] for n in ("TNODES", "NEAR_MEMSET", "RT_STREAMS", "BAND_SUM", "FAR64_SHARED", "CHUNK4", "CASCADE_ASIDE"))
 
 
 def _by_tiles(thr, below_if_less=True):

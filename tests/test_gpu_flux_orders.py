@@ -49,6 +49,7 @@ import pytest
 
 import clearsky_jl_amd
 import workloads as W
+from clearsky_jl_amd import DISPATCH_FLAGS
 from conftest import HITRAN, relerr, source_rounding_bound
 from test_gpu_boundary import _julia_call
 from test_gpu_dispatch import _first_n
@@ -56,7 +57,7 @@ from test_gpu_merge import _close
 
 pytestmark = pytest.mark.gpu
 
-RT_STREAMS, CHUNK4 = 4, 32                       # cs_column_work out[39] bits (include/clearsky_hip_dev.h)
+RT_STREAMS, CHUNK4 = DISPATCH_FLAGS["RT_STREAMS"], DISPATCH_FLAGS["CHUNK4"]   # Column.work()["dispatch"]["flags"]
 LIM = 160 * 1024 - 4096                          # LDS the flux forms may take (flux_form, rt_geometry)
 N_SHORT = 64 * 40 + 17                           # 41 tiles, ragged last tile
 THETA_S, FS, GRAY = 0.6, 0.4, 5e-27

@@ -17,13 +17,14 @@ import numpy as np
 import pytest
 
 import workloads as W
+from clearsky_jl_amd import DISPATCH_FLAGS
 from conftest import HITRAN, relerr
 
 pytestmark = pytest.mark.gpu
 
 CUT = 25.0
 STATES = [(220.0, 50.0, 0.02), (296.0, 101325.0, 40.53), (260.0, 3e3, 30.0)]
-RT_STREAMS = 4   # out[39] bit of cs_column_work (include/clearsky_hip_dev.h)
+RT_STREAMS = DISPATCH_FLAGS["RT_STREAMS"]   # Column.work()["dispatch"]["flags"]
 
 
 def c2(cs):

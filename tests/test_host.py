@@ -25,6 +25,17 @@ def test_library_exports_every_declared_symbol(cs):
     assert cs.lib().cs_version() >= 100
 
 
+def test_work_layout_table_matches_the_header(cs):
+    """The package's copy of cs_column_work's layout -- WORK_COUNT, DISPATCH_FLAGS -- against the enums of include/clearsky_hip_dev.h,
+    whose CS_WORK_* values are the positions 0 .. CS_WORK_COUNT - 1 without a gap where Column.work() reads single values."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "clearsky_hip_dev.h")).read(), flags=re.S)
+    enum = {n: int(v) for n, v in re.findall(r"\b(CS_(?:WORK|DF)_[A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    assert enum["CS_WORK_COUNT"] == cs.WORK_COUNT == 41
+    assert {n[len("CS_DF_"):]: v for n, v in enum.items() if n.startswith("CS_DF_")} == cs.DISPATCH_FLAGS
+    work = sorted(v for n, v in enum.items() if n.startswith("CS_WORK_") and n != "CS_WORK_COUNT")
+    assert work == [q for q in range(cs.WORK_COUNT) if q not in (28, 29, 30)], work     # (CS_WORK_FLUX_SCAN_NS names the first of four)
+
+
 def test_no_oracle_in_product():
     """The shipped path must not import, link or call anything under oracle/."""
     pkg = os.path.join(ROOT, "clearsky.jl_amd")

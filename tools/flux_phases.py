@@ -15,7 +15,7 @@ col = cs.Column(cfg["P"], cfg["g"], cfg["T"], cfg["mu"], cfg["fS"], cfg["fa"], *
 for _ in range(5):
     col.run()
 col.sync()
-out = (C.c_int64 * 41)()   # (cs_column_work writes 41 values)
+out = (C.c_int64 * cs.WORK_COUNT)()
 cs.check(cs.lib().cs_column_work(ctx.handle, out))
 import os
 print(which, "flux form", col.info()["flux_form"], "block 0 [us]: sigma %.1f  depths+planck %.1f  pass1 %.1f  handover %.1f | block 0 start -> band fluxes stored %.1f" % tuple(out[27 + q] / 1e3 for q in range(5)))
