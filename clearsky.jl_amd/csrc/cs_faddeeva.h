@@ -4,7 +4,8 @@
 //              cuts of the same series where they are exact to 1e-15)
 //   s >= 100 : 10-term Laplace continued fraction as the rational  z*PA(z^2)/PB(z^2)
 //   s <  100 : trapezoid rule, h = 1/2, on the integer or half-shifted grid + pole correction when y < 2*pi
-// Max relative error ~1e-14 against 40-digit mpmath (tools/faddeeva_proto.py); the reference's own Faddeeva
+// Max relative error ~1e-14 against 40-digit mpmath (tools/faddeeva_proto.py) for fad_re below, whose far branch divides (1.0 / s);
+// the kernels' far bodies take rcp_fast instead, typically as good and 3.2e-14 at worst (see there).  The reference's own Faddeeva
 // (ACM TOMS Algorithm 985) is only ~4e-5 accurate, so this is strictly closer to the exact profile.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,9 +37,12 @@ __device__ __forceinline__ double rcp_nr1(double s)
     return __builtin_fma(r, e, r);
 }
 
-// 1/s to ~3e-15 for the far-wing series (s >= 1e4): single-precision reciprocal seed (v_cvt_f32_f64, v_rcp_f32,
-// v_cvt_f64_f32 = 1.7 FMA-equivalents, against 3.2 for v_rcp_f64 and 12 for an IEEE division; tools/ubench) + one Newton
-// step.  s beyond the f32 range gives a zero seed and a zero term (the true term is < 1e-38 of the line strength).
+// 1/s to ~3e-15 typically, 3.2e-14 at worst, for the far-wing series (s >= 1e4): single-precision reciprocal seed (v_cvt_f32_f64,
+// v_rcp_f32, v_cvt_f64_f32 = 1.7 FMA-equivalents, against 3.2 for v_rcp_f64 and 12 for an IEEE division; tools/ubench) + one Newton
+// step.  The seed is off by e0 <= 2^-24 (the conversion) + one f32 ulp of 1/s (v_rcp_f32: 2^-23 / m relative, m in [1, 2) the
+// mantissa of 1/s), and the step leaves e0^2, always below 1/s: 1.4e-14 .. 3.2e-14 as a bound, the upper end where 1/s lies just above
+// a power of two (tests/test_gpu_isolated_line.py holds single lines to it; sums of many lines average far below it).
+// s beyond the f32 range gives a zero seed and a zero term (the true term is < 1e-38 of the line strength).
 __device__ __forceinline__ double rcp_fast(double s)
 {
     double r = (double)__builtin_amdgcn_rcpf((float)s);
@@ -92,8 +96,8 @@ __device__ __forceinline__ double fad_near(double x, double y)
         double a = x - t, b = x + t;
         double da = __builtin_fma(a, a, y2), db = __builtin_fma(b, b, y2);
         acc = __builtin_fma(c * (da + db), rcp_fast(da * db), acc);   // (|x -+ t| >= 1/8 by the choice of grid: 2e-4 <= da db <= 2e5, inside the
-                                                                       // f32 range of the seed; 3.6e-15 per term against 1e-16 -- 24 terms of
-                                                                       // one sign -- for 3.5 of the 12 FMA-equivalents a term costs)
+                                                                       // f32 range of the seed; typically 3.6e-15 per term (rcp_fast's bound: 3.2e-14)
+                                                                       // against 1e-16 -- 24 terms of one sign -- for 3.5 of the 12 FMA-equivalents a term costs)
     }
     double res = (0.5 / kPi) * y * acc;
     if (y < 2.0 * kPi) {
