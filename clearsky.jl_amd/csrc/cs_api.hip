@@ -239,6 +239,24 @@ struct ChebGrid {
 struct GasInterp { int nlev = 0, l0 = 0; int nfar[CS_MAX_LEVEL] = {}; DevBuf iwin[CS_MAX_LEVEL], iz, F, sep, edge; };   // nfar: nodes for a level's far pieces (far_node_count)   // levels l0 .. nlev-1 of the grid are in use; sep: SepZone [K/16][nItot]
                                                                                           // (matrix-core node sums), edge: EdgeZone [K/16][tiles] (matrix-core pieces of the per-point sum)
 
+// the windows of one launch group on one grid (build_windows): everything that is decided from the TABLE positions of its lines
+struct GroupWindows {
+    int64_t g0 = 0, g1 = 0;   // the included lines (included_range)
+    int64_t jlo = 0, jhi = 0; // the lines some window can reach: what the records are written for
+    int64_t pa = 0, pb = 0;   // the included lines whose records exist (the pedestals of codes 4, 6 come off over them)
+    int64_t mb = 0;           // codes 5, 6: the mirror lines are [pa, mb) (vvh_mirror_end); = pa for every other code, which never reads it
+    int xtiles = 0;           // longest XCD stretch of the far kernel's tile order, in tiles (wave_windows)
+    double ds = 0.0;          // CS_SHAPE_PSHIFT: the largest shift of the group at the pressures of its states (shift_width), which widens all of the above
+    int ntile256 = 0, nwin = 0;
+    DevBuf J0, J1, win;       // [ntile256], [ntile256] (tile_windows), [nwin] WaveWin: the 64-point tiles and the far kernel's block order (wave_windows)
+};
+// what a launch group needs per state, for N states (upload_group_states)
+struct GroupStates {
+    DevBuf conc, Pp;          // [nmem][N] concentration and partial pressure of every member (conc: groups of a column only)
+    DevBuf gmax;              // [N] max Lorentz width over the members (gamma_bound; Voigt fast path)
+    DevBuf lrt, qref;         // state_tables(): [N], [N][niso]
+};
+
 // a gas of the column as the caller named it (conc is laid out [ngas, K] over these)
 struct UserGas {
     int slot = 0, shape = 0;
@@ -257,19 +275,14 @@ struct ColGas {
     std::shared_ptr<const GasTable> hold;   // ... which the column shares with the context's cache (an eviction there cannot free it)
     int shape = 0;
     double cut = 25.0;
-    DevBuf conc, Pp, J0, J1;  // [nmem][K], [nmem][K], [ntile], [ntile]
-    DevBuf lrt, qref;         // state_tables(): [K], [K][niso]
-    DevBuf win, zones, gmax;  // [ntile64] WaveWin, [K][ntile64] Zone, [K] max Lorentz width (Voigt fast path)
+    GroupWindows w;           // the group's windows on the column's grid, widened by its largest shift at the node pressures (build_windows)
+    GroupStates st;           // what the group needs per node state (upload_group_states; cs_column_update_state)
+    DevBuf zones;             // [K][ntile64] Zone
     GasInterp itp;            // interpolated far wings (nlev = 0: off)
-    int64_t jlo = 0, jhi = 0;
-    int xtiles = 0;           // longest XCD stretch of the far kernel's tile order, in tiles (wave_windows)
-    bool ped = false;         // shape code 4: shape is SH_VOIGT and launch_pedestal follows the line sum over [pa, pb)
-    int64_t pa = 0, pb = 0;
+    bool ped = false;         // shape code 4: shape is SH_VOIGT and launch_pedestal follows the line sum over [w.pa, w.pb)
     bool vvh = false;         // shape code 5: shape is SH_VOIGT, the records carry S / R(nul, T) and launch_vvh follows the line sum
                               // (shape code 6: ped and vvh, and launch_vvh_ped follows it instead of both)
-    int64_t mb = 0;           // ... with the mirror lines [pa, mb) (vvh_mirror_end)
-    bool pshift = false;      // CS_SHAPE_PSHIFT: records centred at nul + delta_a P / P0, summed by k_linesum<shape> over windows widened by ds
-    double ds = 0.0;          // ... the largest shift of the group at the column's node pressures (shift_width)
+    bool pshift = false;      // CS_SHAPE_PSHIFT: records centred at nul + delta_a P / P0, summed by k_linesum<shape> over windows widened by w.ds
     // Voigt / Lorentz groups: how the column's own cross-section stage last ran the group (sigma_impl; a batch's chunked passes run on
     // buffers of their own and leave it alone).  planned: it has, since setup -- the group's windows and zones are written, and
     // cs_column_work counts them by this plan
@@ -297,6 +310,8 @@ struct Column {
     std::vector<double> h_P, h_Pk, h_xs, h_nu;
     std::vector<UserGas> ugas;   // the caller's gases (ngas of them)
     std::vector<ColGas> gas;     // launch groups
+    size_t maxL = 0;             // ... their longest table, whether one of them takes pedestals off (codes 4, 6), whether one is PHCO2 (setup)
+    bool any_ped = false, has_phco2 = false;
     int merge = 1;               // the context's cs_set_merge at setup time
     uint64_t grid_id = 0;        // names this setup's nu grid (what the PHCO2 path keeps per grid: PhScratch)
     int launches = 0;            // kernel launches of the last cs_column_run
@@ -658,7 +673,7 @@ void included_range(const std::vector<double> &nul, double numin, double numax, 
 
 // per-tile union windows (a superset of every lane's |nu - nul| <= cut run; the kernel applies the exact test)
 void tile_windows(const std::vector<double> &nul, int64_t g0, int64_t g1, const double *nu, int64_t nnu, double cut,
-                  std::vector<int32_t> &J0, std::vector<int32_t> &J1, int64_t &pairs, int64_t &inrange)
+                  std::vector<int32_t> &J0, std::vector<int32_t> &J1)
 {
     const int ntile = (int)((nnu + 255) / 256);
     J0.resize(ntile);
@@ -671,8 +686,6 @@ void tile_windows(const std::vector<double> &nul, int64_t g0, int64_t g1, const 
         J0[t] = (int32_t)(std::lower_bound(b, e, lo - tol) - nul.begin());
         J1[t] = (int32_t)(std::upper_bound(b, e, hi + tol) - nul.begin());
     }
-    pairs = -1;  // counted on demand (cs_column_counts): O(nnu log L) on the host
-    inrange = (std::upper_bound(b, e, nu[nnu - 1] + cut) - std::lower_bound(b, e, nu[0] - cut));
 }
 
 // The far kernel hands k_voigt_near the near-line ranges of every (nu, node) as 20-bit offsets into the tile's near zone and
@@ -1819,13 +1832,31 @@ static int64_t vvh_mirror_end(const std::vector<double> &nul, int64_t a, int64_t
     return std::upper_bound(nul.begin() + a, nul.begin() + b, lim + 1e-9 * cut) - nul.begin();
 }
 
-// a shape code as the entry points take it: base code 0..6, and CS_SHAPE_PSHIFT ORed onto codes 0, 1, 2; any other bit is refused
-static int decode_shape(int code, int &base, bool &pshift)
+// a shape code as the entry points take it -- base code 0..6, and CS_SHAPE_PSHIFT ORed onto codes 0, 1, 2 -- taken apart: codes 4, 5, 6 are
+// the Voigt line sum (line_shape), then the pedestal (ped) and / or R(nu, T) and the mirror term (vvh) behind it
+struct ShapeSpec {
+    int base = 0, line_shape = SH_VOIGT;
+    bool pshift = false, ped = false, vvh = false;
+    // Voigt, Lorentz, pedestal-removed Voigt, Van Vleck-Huber Voigt, both: what line_sum_voigt runs.  Its far wings can be interpolated, and
+    // gases of a column with the same code and cut-off can share one merged table
+    bool voigt_family() const { return base == SH_VOIGT || base == SH_LORENTZ || base == SH_VOIGT_CKD || base == SH_VOIGT_VVH || base == SH_VOIGT_CKD_VVH; }
+};
+static ShapeSpec shape_spec(int code)   // (of any integer: decode_shape says which ones are shape codes)
 {
-    pshift = code >= 0 && (code & CS_SHAPE_PSHIFT) != 0;
-    base = pshift ? (code & ~CS_SHAPE_PSHIFT) : code;
-    if (base < 0 || base > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", code);
-    if (pshift && base > SH_DOPPLER) return fail(CS_EINVAL, "CS_SHAPE_PSHIFT applies to shape codes 0, 1 and 2, not to %d", base);
+    ShapeSpec sh;
+    sh.pshift = code >= 0 && (code & CS_SHAPE_PSHIFT) != 0;
+    sh.base = sh.pshift ? (code & ~CS_SHAPE_PSHIFT) : code;
+    sh.ped = sh.base == SH_VOIGT_CKD || sh.base == SH_VOIGT_CKD_VVH;
+    sh.vvh = sh.base == SH_VOIGT_VVH || sh.base == SH_VOIGT_CKD_VVH;
+    sh.line_shape = (sh.ped || sh.vvh) ? SH_VOIGT : sh.base;
+    return sh;
+}
+// ... any other bit, and the flag on another code, is refused
+static int decode_shape(int code, ShapeSpec &sh)
+{
+    sh = shape_spec(code);
+    if (sh.base < 0 || sh.base > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", code);
+    if (sh.pshift && sh.base > SH_DOPPLER) return fail(CS_EINVAL, "CS_SHAPE_PSHIFT applies to shape codes 0, 1 and 2, not to %d", sh.base);
     return CS_OK;
 }
 // the largest pressure shift a line of G can take at pressures P[0..n): max |delta_a| x max P / P0 (every decision made from table positions
@@ -2171,6 +2202,109 @@ int cs_gas_clear(cs_ctx *ctx, int slot)
     return CS_OK;
 }
 
+// The windows of a launch group of table G on the grid nu: the included lines (strict: the end-point pre-filter of the vector method, else every
+// line), the windows of the 256- and 64-point tiles, the record range they span, the far kernel's block order -- all widened by ds, the group's
+// largest shift (the caller's, from shift_width, after check_near_density passed with it).  Uploaded when it returns.
+static int build_windows(GroupWindows &w, const GasTable &G, const ShapeSpec &sh, double cut, double ds, const double *nu, int64_t nnu, bool strict,
+                         hipStream_t s)
+{
+    int rc;
+    w.ds = ds;
+    if (sh.pshift && (rc = ensure_shifts(G, s))) return rc;
+    included_range(G.h_nu, nu[0], nu[nnu - 1], cut + ds, strict, w.g0, w.g1);
+    std::vector<int32_t> J0, J1;
+    tile_windows(G.h_nu, w.g0, w.g1, nu, nnu, window_reach(sh.line_shape, G, nu[nnu - 1] + ds, cut) + ds, J0, J1);
+    w.ntile256 = (int)J0.size();
+    w.jlo = J0.front();
+    w.jhi = J1.back();
+    w.pa = std::max(w.g0, w.jlo);
+    w.pb = std::min(w.g1, w.jhi);
+    w.mb = sh.vvh ? vvh_mirror_end(G.h_nu, w.pa, w.pb, nu[0], cut) : w.pa;
+    std::vector<WaveWin> win;
+    w.xtiles = wave_windows(G.h_nu, w.g0, w.g1, nu, nnu, cut, win, 64, ds);
+    w.nwin = (int)win.size();
+    if ((rc = upload(w.J0, J0.data(), J0.size(), s)) || (rc = upload(w.J1, J1.data(), J1.size(), s)) || (rc = upload(w.win, win.data(), win.size(), s)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(s));   // J0, J1, win are locals
+    return CS_OK;
+}
+
+static void pass_windows(GasPass &p, const GroupWindows &w)
+{
+    p.jlo = w.jlo; p.jhi = w.jhi; p.pa = w.pa; p.pb = w.pb; p.mb = w.mb; p.ds = w.ds;
+    p.ntile256 = w.ntile256; p.J0 = w.J0.as<int32_t>(); p.J1 = w.J1.as<int32_t>(); p.win = w.win.as<WaveWin>(); p.xtiles = w.xtiles;
+}
+
+// element idx of every state's row of conc [N][stride] -- a column's gases, or its tables, at its node states; B columns one after the
+// other are B K such rows -- checked and gathered into out[N]
+static int gather_conc(const double *conc, int idx, int stride, int64_t N, double *out)
+{
+    for (int64_t n = 0; n < N; n++) {
+        out[n] = conc[idx + (size_t)stride * n];
+        if (!(out[n] >= 0 && out[n] <= 1)) return fail(CS_EINVAL, "gas molar concentrations must be in [0,1], not %g", out[n]);
+    }
+    return CS_OK;
+}
+
+// What a group of table G needs per state, at N states (T, P): from the partial pressures pp [nmem][N] of its members (tables mem[nmem]; a
+// gas on its own is its one member) the Lorentz-width bound over the members, and the state tables of G; Pp, gmax, lrt, qref uploaded
+static int upload_group_states(hipStream_t s, GroupStates &st, const GasTable &G, const GasTable *const *mem, int nmem, int64_t N, const double *T,
+                               const double *P, const double *pp)
+{
+    std::vector<double> gb, lrt, qr;
+    for (int m = 0; m < nmem; m++) {
+        const std::vector<double> gm = gamma_bound(*mem[m], (int)N, T, P, pp + (size_t)m * N);
+        if (m == 0) gb = gm;
+        else
+            for (int64_t k = 0; k < N; k++) gb[k] = std::max(gb[k], gm[k]);
+    }
+    state_tables(G, (int)N, T, lrt, qr);
+    int rc;
+    if ((rc = upload(st.Pp, pp, (size_t)nmem * N, s)) || (rc = upload(st.gmax, gb.data(), N, s)) || (rc = upload(st.lrt, lrt.data(), lrt.size(), s)) ||
+        (rc = upload(st.qref, qr.data(), qr.size(), s)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(s));   // (locals)
+    return CS_OK;
+}
+
+// ... of a launch group of the resident column, at N of its node states (one set of them, or a batch's B sets one after the other) with the
+// concentrations conc [N][ngas] of the column's gases: Pp = C P of every member (gases.jl:126), and the members' concentrations themselves
+static int column_group_states(cs_ctx *ctx, const ColGas &cg, GroupStates &st, int64_t N, const double *T, const double *P, const double *conc,
+                               hipStream_t s)
+{
+    const Column &c = ctx->col;
+    const int nm = (int)cg.mem.size();
+    std::vector<double> cc((size_t)nm * N), pp((size_t)nm * N);
+    std::vector<const GasTable *> mem(nm);
+    int rc;
+    for (int m = 0; m < nm; m++) {
+        if ((rc = gather_conc(conc, cg.mem[m], c.ngas, N, cc.data() + (size_t)m * N))) return rc;
+        for (int64_t n = 0; n < N; n++) pp[(size_t)m * N + n] = cc[(size_t)m * N + n] * P[n];
+        mem[m] = &ctx->gas[c.ugas[cg.mem[m]].slot];
+    }
+    if ((rc = upload(st.conc, cc.data(), cc.size(), s))) return rc;
+    return upload_group_states(s, st, *cg.tab, mem.data(), nm, N, T, P, pp.data());
+}
+
+static void pass_states(GasPass &p, const GroupStates &st, int64_t k0)   // states k0 .. of st (p.G is set; p.scale is the caller's: only columns have one)
+{
+    p.Ppk = st.Pp.as<double>() + k0; p.gbound = st.gmax.as<double>() + k0;
+    p.lrt = st.lrt.as<double>() + k0; p.qrefq = st.qref.as<double>() + (size_t)k0 * p.G->niso;
+}
+
+// the line workspace of kn states of tables of at most maxL lines on nnu points: the records, and where asked for (NULL: not) the near-line
+// ranges with the per-(tile, state) flags, the fp32 records of mixed precision, launch_pedestal's workspace, the spare plane of a second code-5/6 group
+static int reserve_lines(size_t kn, size_t maxL, int64_t nnu, DevBuf &hot, DevBuf &cold, DevBuf *ranges, DevBuf *hot32, DevBuf *ped, DevBuf *spare)
+{
+    HIPCHK(hot.reserve((kn * maxL + 4) * sizeof(LineHot)));
+    HIPCHK(cold.reserve(kn * maxL * sizeof(LineCold)));
+    if (ranges) HIPCHK(ranges->reserve(kn * nnu * sizeof(int2) + 2 * kn * ((nnu + 63) / 64) * sizeof(int)));
+    if (hot32) HIPCHK(hot32->reserve((kn * maxL + 4) * sizeof(LineF32)));
+    if (ped) HIPCHK(ped->reserve(ped_bytes((int64_t)kn, (int64_t)maxL)));
+    if (spare) HIPCHK(spare->reserve(kn * nnu * sizeof(double)));
+    return CS_OK;
+}
+
 // where gas_states puts sigma [K][nnu]: host rows of pitch ld (it owns the buffer of a chunk and copies each chunk out), or a device plane
 // written in place, which plane() hands out once the call has passed its checks (cs_bake: only then is the table in the slot given up)
 struct StatesOut {
@@ -2180,16 +2314,15 @@ struct StatesOut {
 };
 
 // sigma of one gas at K states on the grid nu, behind cs_shape_batch / cs_shape_points / cs_bake (which have checked the slot, the shape
-// code -- base code `shape`, CS_SHAPE_PSHIFT as `pshift` -- their sizes and the grid): the states in chunks that bound the workspace
-static int gas_states(cs_ctx *ctx, GasTable &G, int shape, bool pshift, double dnu_cut, int64_t nnu, const double *nu, int K,
+// code, their sizes and the grid): the states in chunks that bound the workspace
+static int gas_states(cs_ctx *ctx, GasTable &G, const ShapeSpec &sh, double dnu_cut, int64_t nnu, const double *nu, int K,
                       const double *T, const double *P, const double *Pp, bool strict, const StatesOut &out)
 {
     int rc;
-    const bool ped = shape == SH_VOIGT_CKD || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum, then the pedestal behind it
-    const bool vvh = shape == SH_VOIGT_VVH || shape == SH_VOIGT_CKD_VVH;   // the Voigt line sum of S / R(nul, T), then R(nu, T) and the mirror term
-    if (ped || vvh) shape = SH_VOIGT;
+    const int shape = sh.line_shape;
+    const bool ped = sh.ped;
     double ds = 0.0;   // CS_SHAPE_PSHIFT: every window and the line range widened by the largest shift of these states
-    if (pshift && (rc = shift_width(G, P, K, ds))) return rc;
+    if (sh.pshift && (rc = shift_width(G, P, K, ds))) return rc;
     if ((rc = check_gas_states(G, K, T))) return rc;
     if (shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, dnu_cut, ds))) return rc;
     ph_set_grid(ctx, ctx->ph, nu, nnu, ++g_grid_counter);
@@ -2197,64 +2330,43 @@ static int gas_states(cs_ctx *ctx, GasTable &G, int shape, bool pshift, double d
     hipStream_t s = ctx->stream;
     double *Z = nullptr;   // the caller's plane; NULL: a chunk buffer of our own, copied to out.host
     if (out.plane && (rc = out.plane(Z))) return rc;
-    if (pshift && (rc = ensure_shifts(G, s))) return rc;
-    int64_t g0, g1, pairs, inr;
-    included_range(G.h_nu, nu[0], nu[nnu - 1], dnu_cut + ds, strict, g0, g1);
-    std::vector<int32_t> J0, J1;
-    tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(shape, G, nu[nnu - 1] + ds, dnu_cut) + ds, J0, J1, pairs, inr);
-    const int ntile = (int)J0.size();
-    DevBuf dnu, dT, dP, dPp, dJ0, dJ1, hot, cold, dsig, dwin, dzones, dgmax, dranges, dlrt, dqref, dped;
-    {
-        std::vector<double> lrt, qr;
-        state_tables(G, K, T, lrt, qr);
-        if ((rc = upload(dlrt, lrt.data(), lrt.size(), s)) || (rc = upload(dqref, qr.data(), qr.size(), s))) return rc;
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    std::vector<WaveWin> win;
-    const int xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, dnu_cut, win, 64, ds);
-    const std::vector<double> gb = gamma_bound(G, K, T, P, Pp);
-    if ((rc = upload(dnu, nu, nnu, s)) || (rc = upload(dT, T, K, s)) || (rc = upload(dP, P, K, s)) ||
-        (rc = upload(dPp, Pp, K, s)) || (rc = upload(dJ0, J0.data(), ntile, s)) || (rc = upload(dJ1, J1.data(), ntile, s)) ||
-        (rc = upload(dwin, win.data(), win.size(), s)) || (rc = upload(dgmax, gb.data(), K, s)))
-        return rc;
+    GroupWindows w;
+    GroupStates st;        // (one member, the caller's Pp: no concentration plane)
+    const GasTable *mem = &G;
+    if ((rc = build_windows(w, G, sh, dnu_cut, ds, nu, nnu, strict, s)) || (rc = upload_group_states(s, st, G, &mem, 1, K, T, P, Pp))) return rc;
+    DevBuf dnu, dT, dP, hot, cold, dsig, dzones, dranges, dped;
+    if ((rc = upload(dnu, nu, nnu, s)) || (rc = upload(dT, T, K, s)) || (rc = upload(dP, P, K, s))) return rc;
     // bound the workspace: process the states in chunks
     const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) +
                              (Z ? (size_t)nnu * sizeof(int2) : (size_t)nnu * (sizeof(double) + sizeof(int2))) + (ped ? ped_bytes(1, G.L) : 0);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));   // gridDim.y limit
-    if (ped) HIPCHK(dped.reserve(ped_bytes(kc, G.L)));
-    HIPCHK(hot.reserve(((size_t)kc * G.L + 4) * sizeof(LineHot)));
-    HIPCHK(cold.reserve((size_t)kc * G.L * sizeof(LineCold)));
+    const bool mixed = ctx->mixed && shape == SH_VOIGT && !sh.pshift;
+    if ((rc = reserve_lines(kc, G.L, nnu, hot, cold, &dranges, mixed ? &ctx->hot32 : nullptr, ped ? &dped : nullptr, nullptr))) return rc;
     if (!Z) HIPCHK(dsig.reserve((size_t)kc * nnu * sizeof(double)));
-    HIPCHK(dzones.reserve((size_t)kc * win.size() * sizeof(Zone)));
-    HIPCHK(dranges.reserve((size_t)kc * nnu * sizeof(int2) + (size_t)2 * kc * ((nnu + 63) / 64) * sizeof(int)));   // + per-(tile, state) flags
+    HIPCHK(dzones.reserve((size_t)kc * w.nwin * sizeof(Zone)));
     GasPass p;
-    p.G = &G; p.shape = shape; p.jlo = J0.front(); p.jhi = J1.back(); p.cut = dnu_cut; p.ped = ped; p.vvh = vvh;
-    p.pa = std::max<int64_t>(g0, J0.front()); p.pb = std::min<int64_t>(g1, J1.back());   // the included lines whose records exist
-    if (vvh) p.mb = vvh_mirror_end(G.h_nu, p.pa, p.pb, nu[0], dnu_cut);
+    p.G = &G; p.shape = shape; p.cut = dnu_cut; p.ped = ped; p.vvh = sh.vvh;
+    pass_windows(p, w);
     // (the strict pre-filter of a shifted line is its own state's: prep_body parks the lines whose shifted centre fails it)
-    p.pshift = pshift; p.ds = ds; p.flo = strict ? nu[0] - dnu_cut : -INFINITY; p.fhi = strict ? nu[nnu - 1] + dnu_cut : INFINITY;
-    p.dnu = dnu.as<double>(); p.nu = nu; p.nnu = nnu; p.ntile256 = ntile; p.J0 = dJ0.as<int32_t>(); p.J1 = dJ1.as<int32_t>();
-    p.win = dwin.as<WaveWin>(); p.xtiles = xtiles;
+    p.pshift = sh.pshift; p.flo = strict ? nu[0] - dnu_cut : -INFINITY; p.fhi = strict ? nu[nnu - 1] + dnu_cut : INFINITY;
+    p.dnu = dnu.as<double>(); p.nu = nu; p.nnu = nnu;
     p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<int2>(); p.ped_ws = dped.as<double>();
-    if (ctx->mixed && shape == SH_VOIGT && !pshift) {
-        HIPCHK(ctx->hot32.reserve(((size_t)kc * G.L + 4) * sizeof(LineF32)));
-        p.hot32 = ctx->hot32.as<LineF32>();
-    }
+    if (mixed) p.hot32 = ctx->hot32.as<LineF32>();
     p.clamp = true;   // the gas's own sigma, complete
     p.far_s = ctx->far_s; p.ph = &ctx->ph;
     ChebGrid cheb;
     GasInterp ginterp;
-    if (ctx->interp && (shape == SH_VOIGT || shape == SH_LORENTZ)) {
+    if (ctx->interp && sh.voigt_family()) {
         if ((rc = cheb_build(ctx, cheb, nu, dnu.as<double>(), nnu, dnu_cut, s)) ||
-            (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, g0, g1, nu, nnu, dnu_cut, kc, s, true, ds)))
+            (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, w.g0, w.g1, nu, nnu, dnu_cut, kc, s, true, w.ds)))
             return rc;
         p.itp = interp_view(cheb, ginterp, kc);
         interp_settings(ctx, p.itp);
     }
     for (int k0 = 0; k0 < K; k0 += kc) {
         p.kn = std::min(kc, K - k0);
-        p.Tk = dT.as<double>() + k0; p.Pk = dP.as<double>() + k0; p.Ppk = dPp.as<double>() + k0; p.gbound = dgmax.as<double>() + k0;
-        p.lrt = dlrt.as<double>() + k0; p.qrefq = dqref.as<double>() + (size_t)k0 * G.niso;
+        p.Tk = dT.as<double>() + k0; p.Pk = dP.as<double>() + k0;
+        pass_states(p, st, k0);
         p.sigma = Z ? Z + (size_t)k0 * nnu : dsig.as<double>();
         launch_gas(s, p);
         HIPCHK(hipGetLastError());
@@ -2271,14 +2383,14 @@ static int shape_impl(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t 
 {
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (slot < 0 || slot >= CS_MAX_GAS || !ctx->gas[slot].present) return fail(CS_EINVAL, "gas slot %d is empty", slot);
-    bool pshift;
+    ShapeSpec sh;
     int rc;
-    if ((rc = decode_shape(shape, shape, pshift))) return rc;
+    if ((rc = decode_shape(shape, sh))) return rc;
     if (K < 1 || ld_state < nnu) return fail(CS_EINVAL, "bad K/ld_state");
     if ((rc = check_ascending(nu, nnu))) return rc;
     StatesOut out;
     out.host = sigma; out.ld = ld_state;   // no plane: gas_states owns the chunk buffer
-    return gas_states(ctx, ctx->gas[slot], shape, pshift, dnu_cut, nnu, nu, K, T, P, Pp, strict, out);
+    return gas_states(ctx, ctx->gas[slot], sh, dnu_cut, nnu, nu, K, T, P, Pp, strict, out);
 }
 
 int cs_shape_batch(cs_ctx *ctx, int slot, int shape, double dnu_cut, int64_t nnu, const double *nu, int K,
@@ -2299,9 +2411,9 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (gas_slot < 0 || gas_slot >= CS_MAX_GAS || !ctx->gas[gas_slot].present) return fail(CS_EINVAL, "gas slot %d is empty", gas_slot);
     if (table_slot < 0 || table_slot >= CS_MAX_TABLE) return fail(CS_EINVAL, "table slot %d out of range", table_slot);
-    bool pshift;
+    ShapeSpec sh;
     int rc;
-    if ((rc = decode_shape(shape, shape, pshift))) return rc;
+    if ((rc = decode_shape(shape, sh))) return rc;
     if (nT < 2 || nP < 2) return fail(CS_EINVAL, "need at least 2 x 2 grid points");
     if ((rc = check_ascending(nu, nnu))) return rc;
     for (int64_t i = 0; i < nnu; i++)
@@ -2325,7 +2437,7 @@ int cs_bake(cs_ctx *ctx, int gas_slot, int table_slot, int shape, double dnu_cut
         return (int)CS_OK;
     };
     // (bake uses the vector method: strict pre-filter, per state when shifted; codes 4, 6 clamped before k_table_log)
-    if ((rc = gas_states(ctx, ctx->gas[gas_slot], shape, pshift, dnu_cut, nnu, nu, M, Ts.data(), Ps.data(), Pp.data(), true, out))) return rc;
+    if ((rc = gas_states(ctx, ctx->gas[gas_slot], sh, dnu_cut, nnu, nu, M, Ts.data(), Ps.data(), Pp.data(), true, out))) return rc;
     hipStream_t s = ctx->stream;
     CS_LAUNCH(k_table_log, dim3((unsigned)((nnu + 255) / 256)), dim3(256), 0, s, tb.Z.as<double>(), M, nnu);
     HIPCHK(hipGetLastError());
@@ -2414,10 +2526,7 @@ static int upload_tables(cs_ctx *ctx, const double *conc_tab)
     for (int t = 0; t < nt; t++) {
         TableDev &tb = ctx->tab[c.tab[t].slot];
         if ((rc = table_weights(tb, c.K, c.h_Tk.data(), c.h_Pk.data(), W))) return rc;
-        for (int k = 0; k < c.K; k++) {
-            cc[k] = conc_tab[t + (size_t)nt * k];
-            if (!(cc[k] >= 0 && cc[k] <= 1)) return fail(CS_EINVAL, "gas molar concentrations must be in [0,1], not %g", cc[k]);
-        }
+        if ((rc = gather_conc(conc_tab, t, nt, c.K, cc.data()))) return rc;
         if ((rc = upload(c.tab[t].W, W.data(), W.size(), s)) || (rc = upload(c.tab[t].conc, cc.data(), c.K, s))) return rc;
     }
     HIPCHK(hipStreamSynchronize(s));
@@ -2837,9 +2946,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     if (ctx->interp) {   // interval sizes from the narrowest Voigt cut-off of the column
         double cmin = 0.0;
         for (int gi = 0; gi < ngas; gi++) {
-            int sh = shapes ? shapes[gi] : CS_SHAPE_VOIGT;
-            if (sh >= 0 && (sh & CS_SHAPE_PSHIFT)) sh &= ~CS_SHAPE_PSHIFT;   // (a flagged Voigt / Lorentz gas interpolates its far wings too)
-            if (sh == SH_VOIGT || sh == SH_LORENTZ || sh == SH_VOIGT_CKD || sh == SH_VOIGT_VVH || sh == SH_VOIGT_CKD_VVH) {
+            if (shape_spec(shapes ? shapes[gi] : CS_SHAPE_VOIGT).voigt_family()) {   // (a flagged Voigt / Lorentz gas interpolates its far wings too)
                 const double cu = dnu_cuts ? dnu_cuts[gi] : 25.0;
                 cmin = cmin > 0.0 ? std::min(cmin, cu) : cu;
             }
@@ -2855,12 +2962,11 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         if (ug.slot < 0 || ug.slot >= CS_MAX_GAS || !ctx->gas[ug.slot].present)
             return fail(CS_EINVAL, "gas slot %d is empty", ug.slot);
         ug.generation = ctx->gas[ug.slot].generation;
-        int base;
-        bool psh;
-        if ((rc = decode_shape(ug.shape, base, psh))) return rc;
+        ShapeSpec sh;
+        if ((rc = decode_shape(ug.shape, sh))) return rc;
         const GasTable &G = ctx->gas[ug.slot];
         double ds_unused;
-        if (psh && (rc = shift_width(G, P, np, ds_unused))) return rc;
+        if (sh.pshift && (rc = shift_width(G, P, np, ds_unused))) return rc;
         ug.pairs_per_state = -1;   // counted on demand (cs_column_counts): O(nnu log L) on the host
         ug.lines_in_range = std::upper_bound(G.h_nu.begin(), G.h_nu.end(), nu[nnu - 1] + ug.cut) -
                             std::lower_bound(G.h_nu.begin(), G.h_nu.end(), nu[0] - ug.cut);   // (the reference's count: inside the cut-off)
@@ -2869,7 +2975,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         // slot named twice stays apart (a merged table tags a line with ONE member).  ug.shape is the caller's code, CS_SHAPE_PSHIFT included:
         // a flagged group merges only with flagged gases of the same base code and cut-off
         bool placed = false;
-        if (ctx->merge && (base == SH_VOIGT || base == SH_LORENTZ || base == SH_VOIGT_CKD || base == SH_VOIGT_VVH || base == SH_VOIGT_CKD_VVH))
+        if (ctx->merge && sh.voigt_family())
             for (auto &grp : groups) {
                 const UserGas &h = c.ugas[grp[0]];
                 bool dup = false;
@@ -2880,20 +2986,17 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     }
     // code-5 and code-6 groups first: each runs on its own (no deferred node-sum apply, no side streams: R(nu, T) multiplies everything its
     // line sum adds) and the first one's sum is the plane itself; the groups after them share the deferred apply and the near-line plane as before
-    std::stable_partition(groups.begin(), groups.end(), [&](const std::vector<int> &g) {
-        return c.ugas[g[0]].shape == SH_VOIGT_VVH || c.ugas[g[0]].shape == SH_VOIGT_CKD_VVH;
-    });
+    std::stable_partition(groups.begin(), groups.end(), [&](const std::vector<int> &g) { return shape_spec(c.ugas[g[0]].shape).vvh; });
     c.gas.resize(groups.size());
-    size_t maxL = 0;
+    c.maxL = 0;
+    c.any_ped = c.has_phco2 = false;
+    bool any_voigt = false;
     for (size_t qi = 0; qi < groups.size(); qi++) {
         ColGas &cg = c.gas[qi];
         cg.mem = groups[qi];
-        cg.shape = c.ugas[cg.mem[0]].shape;
-        cg.pshift = (cg.shape & CS_SHAPE_PSHIFT) != 0;
-        if (cg.pshift) cg.shape &= ~CS_SHAPE_PSHIFT;
-        cg.ped = cg.shape == SH_VOIGT_CKD || cg.shape == SH_VOIGT_CKD_VVH;
-        cg.vvh = cg.shape == SH_VOIGT_VVH || cg.shape == SH_VOIGT_CKD_VVH;
-        if (cg.ped || cg.vvh) cg.shape = SH_VOIGT;   // every kernel of a Voigt group, then the pedestal and / or R(nu, T) and the mirror term
+        const ShapeSpec sh = shape_spec(c.ugas[cg.mem[0]].shape);
+        cg.shape = sh.line_shape;   // codes 4, 5, 6: every kernel of a Voigt group, then the pedestal and / or R(nu, T) and the mirror term
+        cg.pshift = sh.pshift; cg.ped = sh.ped; cg.vvh = sh.vvh;
         cg.cut = c.ugas[cg.mem[0]].cut;
         if (cg.mem.size() == 1) {
             cg.tab = &ctx->gas[c.ugas[cg.mem[0]].slot];
@@ -2904,30 +3007,19 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
             cg.tab = cg.hold.get();
         }
         const GasTable &G = *cg.tab;
-        cg.ds = 0.0;   // CS_SHAPE_PSHIFT: windows and line range widened by the group's largest shift at the node pressures
-        if (cg.pshift && ((rc = shift_width(G, c.h_Pk.data(), K, cg.ds)) || (rc = ensure_shifts(G, s)))) return rc;
-        if (cg.shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, cg.cut, cg.ds))) return rc;
-        int64_t g0, g1, pairs_unused, inr_unused;
-        included_range(G.h_nu, nu[0], nu[nnu - 1], cg.cut, false, g0, g1);
-        std::vector<int32_t> J0, J1;
-        tile_windows(G.h_nu, g0, g1, nu, nnu, window_reach(cg.shape, G, nu[nnu - 1] + cg.ds, cg.cut) + cg.ds, J0, J1, pairs_unused, inr_unused);
-        cg.jlo = J0.front();
-        cg.jhi = J1.back();
-        cg.pa = std::max(g0, cg.jlo);
-        cg.pb = std::min(g1, cg.jhi);
-        cg.mb = cg.vvh ? vvh_mirror_end(G.h_nu, cg.pa, cg.pb, nu[0], cg.cut) : cg.pa;
-        std::vector<WaveWin> win;
-        cg.xtiles = wave_windows(G.h_nu, g0, g1, nu, nnu, cg.cut, win, 64, cg.ds);
-        if ((rc = upload(cg.J0, J0.data(), J0.size(), s)) || (rc = upload(cg.J1, J1.data(), J1.size(), s)) ||
-            (rc = upload(cg.win, win.data(), win.size(), s)))
+        double ds = 0.0;   // CS_SHAPE_PSHIFT: windows and line range widened by the group's largest shift at the node pressures
+        if (sh.pshift && (rc = shift_width(G, c.h_Pk.data(), K, ds))) return rc;
+        if (cg.shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, cg.cut, ds))) return rc;
+        if ((rc = build_windows(cg.w, G, sh, cg.cut, ds, nu, nnu, false, s))) return rc;
+        HIPCHK(cg.zones.reserve((size_t)c.K * cg.w.nwin * sizeof(Zone)));
+        HIPCHK(cg.st.gmax.reserve((size_t)c.K * sizeof(double)));
+        if (c.cheb.nlev > 0 && sh.voigt_family() &&
+            (rc = gas_interp_build(ctx, cg.itp, c.cheb, G.h_nu, cg.w.g0, cg.w.g1, nu, nnu, cg.cut, c.K, s, false, cg.w.ds)))
             return rc;
-        HIPCHK(cg.zones.reserve((size_t)c.K * win.size() * sizeof(Zone)));
-        HIPCHK(cg.gmax.reserve((size_t)c.K * sizeof(double)));
-        if (c.cheb.nlev > 0 && (cg.shape == SH_VOIGT || cg.shape == SH_LORENTZ) &&
-            (rc = gas_interp_build(ctx, cg.itp, c.cheb, G.h_nu, g0, g1, nu, nnu, cg.cut, c.K, s, false, cg.ds)))
-            return rc;
-        HIPCHK(hipStreamSynchronize(s));   // J0, J1, win are locals
-        maxL = std::max(maxL, (size_t)G.L);
+        c.maxL = std::max(c.maxL, (size_t)G.L);
+        any_voigt = any_voigt || cg.shape == SH_VOIGT;
+        c.any_ped = c.any_ped || cg.ped;
+        c.has_phco2 = c.has_phco2 || cg.shape == SH_PHCO2;
     }
     if (c.cheb.nlev > 0) {
         const size_t fb = (size_t)c.cheb.nItot * CS_NC * cheb_kpad(K) * sizeof(double);
@@ -2936,15 +3028,12 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
             HIPCHK(hipMemsetAsync(c.chebF.p, 0, c.chebF.bytes, s));   // padding states stay finite
         }
     }
-    HIPCHK(c.hot.reserve(((size_t)K * maxL + 4) * sizeof(LineHot)));
-    HIPCHK(c.cold.reserve((size_t)K * maxL * sizeof(LineCold)));
+    // (the fp32 records of mixed precision are the context's, sized when a step first needs them: sigma_impl; the spare plane: a second code-5 group)
+    if ((rc = reserve_lines(K, c.maxL, nnu, c.hot, c.cold, ngas > 0 ? &c.ranges : nullptr, nullptr, c.any_ped ? &c.ped : nullptr,
+                            c.gas.size() > 1 && c.gas[1].vvh ? &c.vvh : nullptr)))
+        return rc;
     HIPCHK(c.sigma.reserve((size_t)K * nnu * sizeof(double)));
-    bool any_voigt = false, any_ped = false;
-    for (auto &cg : c.gas) any_voigt = any_voigt || cg.shape == SH_VOIGT, any_ped = any_ped || cg.ped;
-    if (any_ped) HIPCHK(c.ped.reserve(ped_bytes(K, maxL)));
-    if (c.gas.size() > 1 && c.gas[1].vvh) HIPCHK(c.vvh.reserve((size_t)K * nnu * sizeof(double)));   // (a second code-5 group)
     if (any_voigt) HIPCHK(c.sigma2.reserve((size_t)K * nnu * sizeof(double)));
-    if (ngas > 0) HIPCHK(c.ranges.reserve((size_t)K * nnu * sizeof(int2) + (size_t)2 * K * ((nnu + 63) / 64) * sizeof(int)));   // + per-(tile, state) flags
     HIPCHK(c.tau.reserve((size_t)nl * nnu * sizeof(double)));   // the caller's output, or k_flux_chunk's scratch between its two sweeps
     if (!c.ticket.p) {
         HIPCHK(c.ticket.reserve((size_t)(1 + 512 / CS_FLUX_GROUP) * sizeof(unsigned)));
@@ -2965,6 +3054,20 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     return CS_OK;
 }
 
+// node states (discretized.jl:150,162,169) of B sets of T_nodes / mu_nodes [nl][nlob], one after the other: Tk, muk [B][K]
+static void unpack_nodes(const Column &c, int B, const double *T_nodes, const double *mu_nodes, std::vector<double> &Tk, std::vector<double> &muk)
+{
+    const int K = c.K, q = c.nlob - 1;   // state 0 is node 0 of layer 0, state k > 0 node (k - 1) % q + 1 of layer (k - 1) / q
+    Tk.resize((size_t)B * K);
+    muk.resize((size_t)B * K);
+    for (int b = 0; b < B; b++)
+        for (int k = 0; k < K; k++) {
+            const size_t j = (size_t)b * c.nlob * c.nl + (k ? (size_t)((k - 1) / q) * c.nlob + (k - 1) % q + 1 : 0);
+            Tk[(size_t)b * K + k] = T_nodes[j];
+            muk[(size_t)b * K + k] = mu_nodes[j];
+        }
+}
+
 int cs_column_update_state(cs_ctx *ctx, const double *T_nodes, const double *mu_nodes, const double *T_levels,
                            const double *conc, const double *conc_tab)
 {
@@ -2972,15 +3075,9 @@ int cs_column_update_state(cs_ctx *ctx, const double *T_nodes, const double *mu_
     Column &c = ctx->col;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const int K = c.K, nl = c.nl, nlob = c.nlob;
-    std::vector<double> Tk(K), muk(K);
-    Tk[0] = T_nodes[0];
-    muk[0] = mu_nodes[0];
-    for (int i = 0; i < nl; i++)
-        for (int n = 1; n < nlob; n++) {
-            Tk[i * (nlob - 1) + n] = T_nodes[n + (size_t)nlob * i];
-            muk[i * (nlob - 1) + n] = mu_nodes[n + (size_t)nlob * i];
-        }
+    const int K = c.K;
+    std::vector<double> Tk, muk;
+    unpack_nodes(c, 1, T_nodes, mu_nodes, Tk, muk);
     int rc;
     c.h_Tk = Tk;
     for (int gi = 0; gi < c.ngas; gi++)
@@ -2988,28 +3085,8 @@ int cs_column_update_state(cs_ctx *ctx, const double *T_nodes, const double *mu_
     if ((rc = upload(c.Tk, Tk.data(), K, s)) || (rc = upload(c.muk, muk.data(), K, s)) ||
         (rc = upload(c.Tlev, T_levels, c.np, s)))
         return rc;
-    for (auto &cg : c.gas) {   // per group: concentration and partial pressure of every member [nmem][K], Lorentz-width bound over the members
-        const int nm = (int)cg.mem.size();
-        std::vector<double> cc((size_t)nm * K), pp((size_t)nm * K), gb(K, 0.0);
-        for (int m = 0; m < nm; m++) {
-            const int gi = cg.mem[m];
-            for (int k = 0; k < K; k++) {
-                const double v = conc[gi + (size_t)c.ngas * k];
-                if (!(v >= 0 && v <= 1))
-                    return fail(CS_EINVAL, "gas molar concentrations must be in [0,1], not %g", v);
-                cc[(size_t)m * K + k] = v;
-                pp[(size_t)m * K + k] = v * c.h_Pk[k];  // Pp = C*P, gases.jl:126
-            }
-            const std::vector<double> gm = gamma_bound(ctx->gas[c.ugas[gi].slot], K, Tk.data(), c.h_Pk.data(), pp.data() + (size_t)m * K);
-            for (int k = 0; k < K; k++) gb[k] = std::max(gb[k], gm[k]);
-        }
-        std::vector<double> lrt, qr;
-        state_tables(*cg.tab, K, Tk.data(), lrt, qr);
-        if ((rc = upload(cg.conc, cc.data(), cc.size(), s)) || (rc = upload(cg.Pp, pp.data(), pp.size(), s)) ||
-            (rc = upload(cg.gmax, gb.data(), K, s)) || (rc = upload(cg.lrt, lrt.data(), lrt.size(), s)) || (rc = upload(cg.qref, qr.data(), qr.size(), s)))
-            return rc;
-        HIPCHK(hipStreamSynchronize(s));   // (locals)
-    }
+    for (auto &cg : c.gas)
+        if ((rc = column_group_states(ctx, cg, cg.st, K, Tk.data(), c.h_Pk.data(), conc, s))) return rc;
     HIPCHK(hipStreamSynchronize(s));
     if (!c.tab.empty()) {
         if (!conc_tab) return fail(CS_EINVAL, "the resident column has opacity tables: conc_tab is required");
@@ -3024,10 +3101,9 @@ static GasPass column_pass(cs_ctx *ctx, const ColGas &cg)
 {
     const Column &c = ctx->col;
     GasPass p;
-    p.G = cg.tab; p.shape = cg.shape; p.jlo = cg.jlo; p.jhi = cg.jhi; p.cut = cg.cut;
-    p.ped = cg.ped; p.vvh = cg.vvh; p.pa = cg.pa; p.pb = cg.pb; p.mb = cg.mb; p.pshift = cg.pshift; p.ds = cg.ds;
-    p.dnu = c.nu.as<double>(); p.nu = c.h_nu.data(); p.nnu = c.nnu; p.ntile256 = c.ntile;
-    p.J0 = cg.J0.as<int32_t>(); p.J1 = cg.J1.as<int32_t>(); p.win = cg.win.as<WaveWin>(); p.xtiles = cg.xtiles;
+    p.G = cg.tab; p.shape = cg.shape; p.cut = cg.cut; p.ped = cg.ped; p.vvh = cg.vvh; p.pshift = cg.pshift;
+    pass_windows(p, cg.w);
+    p.dnu = c.nu.as<double>(); p.nu = c.h_nu.data(); p.nnu = c.nnu;
     p.hot32 = (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr;
     p.base = c.sigma_gray;   // (clamp stays off: the column's sigma is complete only after its last absorber)
     p.far_s = ctx->far_s; p.ph = &ctx->ph;
@@ -3048,29 +3124,19 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     if (!c.cia.empty() && (!cia_P1 || !cia_P2)) return fail(CS_EINVAL, "the resident column has CIA pairs: cia_P1 and cia_P2 are required");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const int K = c.K, nl = c.nl, nlob = c.nlob, np = c.np;
+    const int K = c.K, np = c.np;
     const int64_t BK = (int64_t)B * K;
-    const size_t nn = (size_t)nlob * nl;
-    std::vector<double> Tk(BK), muk(BK), Pk(BK);
-    for (int b = 0; b < B; b++) {
-        const double *Tn = T_nodes + b * nn, *mn = mu_nodes + b * nn;
-        double *t = Tk.data() + (size_t)b * K, *m = muk.data() + (size_t)b * K;
-        t[0] = Tn[0];
-        m[0] = mn[0];
-        for (int i = 0; i < nl; i++)
-            for (int n = 1; n < nlob; n++) {
-                t[i * (nlob - 1) + n] = Tn[n + (size_t)nlob * i];
-                m[i * (nlob - 1) + n] = mn[n + (size_t)nlob * i];
-            }
-        std::copy(c.h_Pk.begin(), c.h_Pk.end(), Pk.begin() + (size_t)b * K);
-    }
+    std::vector<double> Tk, muk, Pk(BK);
+    unpack_nodes(c, B, T_nodes, mu_nodes, Tk, muk);
+    for (int b = 0; b < B; b++) std::copy(c.h_Pk.begin(), c.h_Pk.end(), Pk.begin() + (size_t)b * K);
     int rc;
     for (int gi = 0; gi < c.ngas; gi++)
         if ((rc = check_gas_states(ctx->gas[c.ugas[gi].slot], (int)BK, Tk.data()))) return rc;
     const double *extra = c.has_extra ? c.extra.as<double>() : nullptr;
     if (extra) return fail(CS_EINVAL, "host-evaluated sigma(nu,T,P) terms are not supported in batch mode");
     const bool shared_sigma = c.accel.slot >= 0;   // AcceleratedAbsorber: cross-sections do not depend on the thermal state (absorbers.jl:203)
-    DevBuf dped, dvvh, dTk, dPk, dmuk, dTlev, dsig, dtau, dpart, dF, dranges, dconc, dPp, dgb, dzones, dizones, dF2, dsep, dedge, hot, cold, dlrt, dqref;
+    DevBuf dped, dvvh, dTk, dPk, dmuk, dTlev, dsig, dtau, dpart, dF, dranges, dzones, dizones, dF2, dsep, dedge, hot, cold;
+    GroupStates st;   // of one group at all B K states: the next group's take their place
     if ((rc = upload(dTk, Tk.data(), BK, s)) || (rc = upload(dPk, Pk.data(), BK, s)) || (rc = upload(dmuk, muk.data(), BK, s)) ||
         (rc = upload(dTlev, T_levels, (size_t)B * np, s)))
         return rc;
@@ -3087,48 +3153,20 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
         const int64_t tot = BK * c.nnu;
         CS_LAUNCH(k_fill, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, c.sigma_gray, (const double *)nullptr, sig);
     }
-    size_t maxL = 0;
-    for (auto &g : c.gas) maxL = std::max(maxL, (size_t)g.tab->L);
-    bool any_ped = false;
-    for (auto &cg : c.gas) any_ped = any_ped || cg.ped;
+    const size_t maxL = c.maxL;
+    const bool any_ped = c.any_ped;
     const bool vvh2 = c.gas.size() > 1 && c.gas[1].vvh;   // a second code-5 group: its line sum goes to a plane of its own first
     const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + (size_t)c.nnu * sizeof(int2) +
                              (any_ped ? ped_bytes(1, (int64_t)maxL) : 0) + (vvh2 ? (size_t)c.nnu * sizeof(double) : 0);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BK, ((size_t)8 << 30) / std::max<size_t>(per_state, 1), (size_t)65535}));
-    if (c.ngas > 0) {
-        HIPCHK(hot.reserve(((size_t)kc * maxL + 4) * sizeof(LineHot)));
-        HIPCHK(cold.reserve((size_t)kc * maxL * sizeof(LineCold)));
-        HIPCHK(dranges.reserve((size_t)kc * c.nnu * sizeof(int2) + (size_t)2 * kc * ((c.nnu + 63) / 64) * sizeof(int)));
-        if (ctx->mixed) HIPCHK(ctx->hot32.reserve(((size_t)kc * maxL + 4) * sizeof(LineF32)));
-        if (any_ped) HIPCHK(dped.reserve(ped_bytes(kc, (int64_t)maxL)));
-        if (vvh2) HIPCHK(dvvh.reserve((size_t)kc * c.nnu * sizeof(double)));
-    }
-    for (auto &cg : c.gas)
-        if (cg.shape == SH_PHCO2) { ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id); break; }
+    if (c.ngas > 0 && (rc = reserve_lines(kc, maxL, c.nnu, hot, cold, &dranges, ctx->mixed ? &ctx->hot32 : nullptr, any_ped ? &dped : nullptr,
+                                          vvh2 ? &dvvh : nullptr)))
+        return rc;
+    if (c.has_phco2) ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id);
     for (size_t qi = 0; qi < c.gas.size(); qi++) {
         ColGas &cg = c.gas[qi];
-        const GasTable &G = *cg.tab;
-        const int nm = (int)cg.mem.size();
-        std::vector<double> cc((size_t)nm * BK), pp((size_t)nm * BK), gb(BK, 0.0);
-        for (int m = 0; m < nm; m++) {
-            const int gi = cg.mem[m];
-            double *cm = cc.data() + (size_t)m * BK, *pm = pp.data() + (size_t)m * BK;
-            for (int b = 0; b < B; b++)
-                for (int k = 0; k < K; k++) {
-                    const double v = conc[(size_t)b * c.ngas * K + gi + (size_t)c.ngas * k];
-                    if (!(v >= 0 && v <= 1)) return fail(CS_EINVAL, "gas molar concentrations must be in [0,1], not %g", v);
-                    cm[(size_t)b * K + k] = v;
-                    pm[(size_t)b * K + k] = v * c.h_Pk[k];
-                }
-            const std::vector<double> gm = gamma_bound(ctx->gas[c.ugas[gi].slot], (int)BK, Tk.data(), Pk.data(), pm);
-            for (int64_t k = 0; k < BK; k++) gb[k] = std::max(gb[k], gm[k]);
-        }
         const size_t nt64 = (size_t)((c.nnu + 63) / 64);
-        std::vector<double> lrt, qr;
-        state_tables(G, (int)BK, Tk.data(), lrt, qr);
-        if ((rc = upload(dconc, cc.data(), cc.size(), s)) || (rc = upload(dPp, pp.data(), pp.size(), s)) || (rc = upload(dgb, gb.data(), BK, s)) ||
-            (rc = upload(dlrt, lrt.data(), lrt.size(), s)) || (rc = upload(dqref, qr.data(), qr.size(), s)))
-            return rc;
+        if ((rc = column_group_states(ctx, cg, st, BK, Tk.data(), Pk.data(), conc, s))) return rc;
         HIPCHK(dzones.reserve((size_t)kc * nt64 * sizeof(Zone)));
         GasPass p = column_pass(ctx, cg);
         p.mstride = (int)BK;
@@ -3153,13 +3191,13 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
         }
         for (int64_t k0 = 0; k0 < BK; k0 += kc) {
             p.kn = (int)std::min<int64_t>(kc, BK - k0);
-            p.Tk = dTk.as<double>() + k0; p.Pk = dPk.as<double>() + k0; p.Ppk = dPp.as<double>() + k0; p.scale = dconc.as<double>() + k0;
-            p.lrt = dlrt.as<double>() + k0; p.qrefq = dqref.as<double>() + (size_t)k0 * G.niso; p.gbound = dgb.as<double>() + k0;
+            p.Tk = dTk.as<double>() + k0; p.Pk = dPk.as<double>() + k0; p.scale = st.conc.as<double>() + k0;
+            pass_states(p, st, k0);
             p.sigma = sig + (size_t)k0 * c.nnu;
             launch_gas(s, p);
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipStreamSynchronize(s));   // cc/pp/gb are locals; the device buffers are reused by the next group
+        HIPCHK(hipStreamSynchronize(s));   // the device buffers are reused by the next group
     }
     // baked gases of the column at all B*K states: the Gas functor fC(T,P)*exp(Phi(T, ln P)) (gases.jl:85,278) -- what RCM holds
     // inside its AcceleratedAbsorber (radiative_convective.jl:6-103)
@@ -3170,12 +3208,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
         for (int t = 0; t < nt; t++) {
             TableDev &tb = ctx->tab[c.tab[t].slot];
             if ((rc = table_weights(tb, (int)BK, Tk.data(), Pk.data(), W))) return rc;
-            for (int b = 0; b < B; b++)
-                for (int k = 0; k < K; k++) {
-                    const double v = conc_tab[(size_t)b * nt * K + t + (size_t)nt * k];
-                    if (!(v >= 0 && v <= 1)) return fail(CS_EINVAL, "gas molar concentrations must be in [0,1], not %g", v);
-                    ct[(size_t)b * K + k] = v;
-                }
+            if ((rc = gather_conc(conc_tab, t, nt, BK, ct.data()))) return rc;
             if ((rc = upload(dW, W.data(), W.size(), s)) || (rc = upload(dct, ct.data(), BK, s))) return rc;
             const int M = tb.nT * tb.nP;
             if ((rc = launch_table_eval(s, tb.Z.as<double>(), M, c.nnu, dW.as<double>(), (int)BK, dct.as<double>(), sig))) return rc;
@@ -3242,15 +3275,10 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
         const int64_t tot = (int64_t)K * c.nnu;
         CS_LAUNCH(k_fill, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, c.sigma_gray, extra, sig);
     }
-    if (ctx->mixed) {
-        size_t maxL = 0;
-        for (auto &g : c.gas) maxL = std::max(maxL, (size_t)g.tab->L);
-        HIPCHK(ctx->hot32.reserve(((size_t)K * maxL + 4) * sizeof(LineF32)));   // no-op once sized (not capturable the first time)
-    }
+    if (ctx->mixed) HIPCHK(ctx->hot32.reserve(((size_t)K * c.maxL + 4) * sizeof(LineF32)));   // no-op once sized (not capturable the first time)
     ChebApply apply;
     apply.ngas = 0;
-    for (auto &cg : c.gas)
-        if (cg.shape == SH_PHCO2) { ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id); break; }
+    if (c.has_phco2) ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id);
     int n_itp = 0;
     for (auto &cg : c.gas) n_itp += cg.itp.nlev > 0 && !cg.vvh ? 1 : 0;   // (the groups whose node sums go into the deferred apply)
     // cs_set_tuning key 2: node sums on a side stream -- 1: where the grid is short (fewer than 16384 (tile, state) waves), 2: always
@@ -3270,8 +3298,8 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
         ColGas &cg = c.gas[gi];
         GasPass p = column_pass(ctx, cg);
         p.kn = K;
-        p.Tk = c.Tk.as<double>(); p.Pk = c.Pk.as<double>(); p.Ppk = cg.Pp.as<double>(); p.scale = cg.conc.as<double>(); p.mstride = K;
-        p.lrt = cg.lrt.as<double>(); p.qrefq = cg.qref.as<double>(); p.gbound = cg.gmax.as<double>();
+        p.Tk = c.Tk.as<double>(); p.Pk = c.Pk.as<double>(); p.scale = cg.st.conc.as<double>(); p.mstride = K;
+        pass_states(p, cg.st, 0);
         p.hot = c.hot.as<LineHot>(); p.cold = c.cold.as<LineCold>(); p.zones = cg.zones.as<Zone>(); p.ranges = c.ranges.as<int2>(); p.ped_ws = c.ped.as<double>();
         // (code 4: the pedestal comes off the plane the group's first kernel initialised; the near-line plane and the wings still to come only add)
         p.extra = extra; p.sigma = sig; p.accumulate = gi > 0; p.spare = c.vvh.as<double>();
@@ -3351,10 +3379,8 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
         CS_LAUNCH(k_fold, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, sig, c.sigma2.as<double>());
     }
     if (!near_plane_live) {   // the cross-sections are the result: complete here, so the max(0, .) of a code-4 or code-6 group applies
-        bool any_ped = false;
-        for (auto &cg : c.gas) any_ped = any_ped || cg.ped;
         const int64_t tot = (int64_t)K * c.nnu;
-        if (any_ped) CS_LAUNCH(k_clamp0, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, sig);
+        if (c.any_ped) CS_LAUNCH(k_clamp0, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, sig);
     }
     HIPCHK(hipGetLastError());
     return CS_OK;
@@ -3902,14 +3928,14 @@ static void work_direct(const Column &c, const ColGas &g, const WorkTables &T, W
 // per-(state, line) records are still in HBM -- the last Voigt group of the column (the only one when its gases are merged)
 static int work_near(const Column &c, Work &w)
 {
-    if (c.gas.empty() || c.gas.back().shape != SH_VOIGT || c.gas.back().jhi <= c.gas.back().jlo) return CS_OK;
+    if (c.gas.empty() || c.gas.back().shape != SH_VOIGT || c.gas.back().w.jhi <= c.gas.back().w.jlo) return CS_OK;
     const ColGas &g = c.gas.back();
-    const int64_t L = g.tab->L, nj = g.jhi - g.jlo;
+    const int64_t L = g.tab->L, nj = g.w.jhi - g.w.jlo;
     std::vector<LineHot> rec((size_t)nj);
     const double *vv = c.h_nu.data();
     const int64_t nnu = c.nnu;
     for (int k = 0; k < c.K; k++) {
-        HIPCHK(hipMemcpy(rec.data(), c.hot.as<LineHot>() + (size_t)k * L + g.jlo, rec.size() * sizeof(LineHot), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(rec.data(), c.hot.as<LineHot>() + (size_t)k * L + g.w.jlo, rec.size() * sizeof(LineHot), hipMemcpyDeviceToHost));
         for (int64_t j = 0; j < nj; j++) {
             const LineHot &h = rec[j];
             auto within = [&](double smax) -> int64_t {   // points with x^2 + y^2 < smax and |dnu| <= cut
@@ -3945,7 +3971,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
         const VoigtPlan &pl = g.plan;
         const int nlev = g.itp.nlev, nItot = c.cheb.nItot;
         WorkTables T;
-        if ((rc = download(T.win, g.win, (size_t)pl.nt64)) || (rc = download(T.zn, g.zones, (size_t)K * pl.nt64)) ||
+        if ((rc = download(T.win, g.w.win, (size_t)pl.nt64)) || (rc = download(T.zn, g.zones, (size_t)K * pl.nt64)) ||
             (nlev > 0 && (rc = download(T.iz, g.itp.iz, (size_t)K * nItot))) ||
             (pl.use_sep && (rc = download(T.sz, g.itp.sep, (size_t)pl.ngrp * nItot))) ||
             (pl.use_edge && (rc = download(T.ez, g.itp.edge, (size_t)pl.ngrp * pl.nt64))))
