@@ -14,6 +14,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <fcntl.h>
@@ -555,37 +556,53 @@ RtGeom rt_geometry(int64_t nnu, int np, int ncol, int ns = 0, bool allow_streams
     return g;
 }
 
-template <int NS>
-void launch_rt_ns(const RtGeom &g, int B, hipStream_t s, const RtParams &p, const double *nu, const double *wts,
-                  int64_t nnu, const double *sigma, const double *muk, const double *P, const double *Tlev,
-                  const double *S, const double *alb, double *tau, double *Mup, double *Mdn, double *partial, size_t sig_bstride,
-                  const double *sigma2)
+// what every flux launch passes (host only; the kernels keep their argument lists, pointer by pointer)
+struct FluxArgs {
+    const RtParams *p;
+    const double *nu, *wts;
+    int64_t nnu;
+    const double *sigma, *muk, *P, *Tlev, *S, *alb;   // S, alb: NULL without a stellar beam / an albedo
+    double *tau, *Mup, *Mdn;                          // optional outputs
+    double *partial;
+    hipStream_t s;
+};
+
+// f(std::integral_constant<int, NS>) for the column's stream count: the one place that turns it into a template argument
+template <class F>
+void with_nstream(int ns, F &&f)
 {
-    if (g.streams) {
-        if constexpr (NS >= 2 && NS <= 8) {
-            if (g.shmem > 65536) (void)hipFuncSetAttribute((const void *)k_rt_streams<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.shmem);
-            CS_LAUNCH((k_rt_streams<NS>), dim3(g.nblk, B), dim3(g.threads), g.shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup,
-                      Mdn, partial, sig_bstride, sigma2);
-        }
-    } else if (g.ud)
-        CS_LAUNCH((k_rt<NS, true>), dim3(g.nblk, B), dim3(g.threads), g.shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb,
-                           tau, Mup, Mdn, partial, sig_bstride, sigma2);
-    else
-        CS_LAUNCH((k_rt<NS, false>), dim3(g.nblk, B), dim3(g.threads), g.shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb,
-                           tau, Mup, Mdn, partial, sig_bstride, sigma2);
+#define CS_NS(N) f(std::integral_constant<int, N>{}); break
+    switch (ns) {
+    case 1: CS_NS(1); case 2: CS_NS(2); case 3: CS_NS(3); case 4: CS_NS(4);
+    case 5: CS_NS(5); case 6: CS_NS(6); case 7: CS_NS(7); case 8: CS_NS(8);
+    case 9: CS_NS(9); case 10: CS_NS(10); case 11: CS_NS(11); case 12: CS_NS(12);
+    case 13: CS_NS(13); case 14: CS_NS(14); case 15: CS_NS(15); case 16: CS_NS(16);
+    }
+#undef CS_NS
 }
 
-void launch_rt(int ns, const RtGeom &g, int B, hipStream_t s, const RtParams &p, const double *nu, const double *wts,
-               int64_t nnu, const double *sigma, const double *muk, const double *P, const double *Tlev,
-               const double *S, const double *alb, double *tau, double *Mup, double *Mdn, double *partial, size_t sig_bstride = 0,
-               const double *sigma2 = nullptr)
+// a flux kernel with the arguments all of them begin with, then its own; more than 64 KB of dynamic LDS has to be asked for first
+template <class Kern, class... Rest>
+void launch_flux_kernel(Kern kern, dim3 grid, int threads, size_t shmem, const FluxArgs &a, Rest... rest)
 {
-#define CS_RT_CASE(N) case N: launch_rt_ns<N>(g, B, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, sig_bstride, sigma2); break;
-    switch (ns) {
-        CS_RT_CASE(1) CS_RT_CASE(2) CS_RT_CASE(3) CS_RT_CASE(4) CS_RT_CASE(5) CS_RT_CASE(6) CS_RT_CASE(7) CS_RT_CASE(8)
-        CS_RT_CASE(9) CS_RT_CASE(10) CS_RT_CASE(11) CS_RT_CASE(12) CS_RT_CASE(13) CS_RT_CASE(14) CS_RT_CASE(15) CS_RT_CASE(16)
-    }
-#undef CS_RT_CASE
+    if (shmem > 65536) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    CS_LAUNCH(kern, grid, dim3(threads), shmem, a.s, *a.p, a.nu, a.wts, a.nnu, a.sigma, a.muk, a.P, a.Tlev, a.S, a.alb, a.tau, a.Mup, a.Mdn, a.partial,
+              rest...);
+}
+
+// the sweeps over finished cross-sections (form 0): B columns of a batch, sigma2 = the near-line plane (NULL: none)
+void launch_rt(const RtGeom &g, int B, const FluxArgs &a, size_t sig_bstride = 0, const double *sigma2 = nullptr)
+{
+    with_nstream(a.p->nstream, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        const dim3 grid(g.nblk, B);
+        if (g.streams) {
+            if constexpr (NS >= 2 && NS <= 8) launch_flux_kernel(k_rt_streams<NS>, grid, g.threads, g.shmem, a, sig_bstride, sigma2);
+        } else if (g.ud)
+            launch_flux_kernel(k_rt<NS, true>, grid, g.threads, g.shmem, a, sig_bstride, sigma2);
+        else
+            launch_flux_kernel(k_rt<NS, false>, grid, g.threads, g.shmem, a, sig_bstride, sigma2);
+    });
 }
 
 // which form of the flux kernel a step of the resident column uses: 0 = k_rt / k_rt_streams reading finished cross-sections from HBM,
@@ -623,38 +640,35 @@ int flux_form(const cs_ctx *ctx, const Column &c, size_t *shmem, int *nblk, int 
     return 2;
 }
 
-// RAD: the column holds a CIA object flagged CS_CIA_RADIATION (kernels that can form R(nu, T_k); every other column runs the ones it always ran)
-template <int NS, bool RAD>
-void launch_flux_ns(int form, size_t shmem, int nblk, int threads, hipStream_t s, const RtParams &p, const double *nu, const double *wts,
-                           int64_t nnu, const double *sigma, const double *muk, const double *P, const double *Tlev, const double *S,
-                           const double *alb, double *tau, double *Mup, double *Mdn, double *partial, const FluxFuse &f, bool three_waves = true, bool scan_recompute = false)
+// the fused forms (flux_form 3 and 2).  rad: the column holds a CIA object flagged CS_CIA_RADIATION (kernels that can form R(nu, T_k);
+// every other column runs the ones it always ran)
+void launch_flux(int form, size_t shmem, int nblk, int threads, const FluxArgs &a, const FluxFuse &f, bool rad, bool three_waves, bool scan_recompute)
 {
-    if (form == 3) {
-        if constexpr (NS >= 2 && NS <= 8) {
-            // a chunk of up to 5 layers (60 layers over 12 waves) keeps its transmissivities in registers between the sweeps and passes
-            const int nw = threads / 64, per = (p.np - 1 + nw - 1) / nw;
-            bool in_regs = false;
-            if constexpr (NS <= 6) {   // (seven streams and up: the 5 x NS values no longer fit beside the rest at three waves per SIMD)
-                if (per <= 5 && !scan_recompute) {
-                    if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_scan<NS, 5, RAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                    CS_LAUNCH((k_flux_scan<NS, 5, RAD>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f);
-                    in_regs = true;
+    with_nstream(a.p->nstream, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        auto go = [&](auto radc) {
+            constexpr bool RAD = decltype(radc)::value;
+            const int ntile = (int)((a.nnu + 63) / 64);
+            if (form == 3) {
+                if constexpr (NS >= 2 && NS <= 8) {
+                    // a chunk of up to 5 layers (60 layers over 12 waves) keeps its transmissivities in registers between the sweeps and passes
+                    const int nw = threads / 64, per = (a.p->np - 1 + nw - 1) / nw;
+                    if constexpr (NS <= 6) {   // (seven streams and up: the 5 x NS values no longer fit beside the rest at three waves per SIMD)
+                        if (per <= 5 && !scan_recompute) {
+                            launch_flux_kernel(k_flux_scan<NS, 5, RAD>, dim3(nblk), threads, shmem, a, f);
+                            return;
+                        }
+                    }
+                    launch_flux_kernel(k_flux_scan<NS, 0, RAD>, dim3(nblk), threads, shmem, a, f);
                 }
-            }
-            if (!in_regs) {
-                if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_scan<NS, 0, RAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                CS_LAUNCH((k_flux_scan<NS, 0, RAD>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f);
-            }
-        }
-    } else if (three_waves) {
-        if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_chunk3<NS, RAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        CS_LAUNCH((k_flux_chunk3<NS, RAD>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f,
-                  (int)((nnu + 63) / 64));
-    } else {
-        if (shmem > 65536) (void)hipFuncSetAttribute((const void *)k_flux_chunk<NS, RAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        CS_LAUNCH((k_flux_chunk<NS, RAD>), dim3(nblk), dim3(threads), shmem, s, p, nu, wts, nnu, sigma, muk, P, Tlev, S, alb, tau, Mup, Mdn, partial, f,
-                  (int)((nnu + 63) / 64));
-    }
+            } else if (three_waves)
+                launch_flux_kernel(k_flux_chunk3<NS, RAD>, dim3(nblk), threads, shmem, a, f, ntile);
+            else
+                launch_flux_kernel(k_flux_chunk<NS, RAD>, dim3(nblk), threads, shmem, a, f, ntile);
+        };
+        if (rad) go(std::true_type{});
+        else go(std::false_type{});
+    });
 }
 
 // includedlines(::Vector) line_shapes.jl:18-22 -> [g0, g1) ; strict = 0 keeps every line (scalar-nu method :12-16)
@@ -3235,10 +3249,10 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     }
     if (bg.streams) log.disp.flags |= CS_DF_RT_STREAMS;
     c.log_last.disp = log.disp;
-    launch_rt(c.nstream, bg, B, s, c.rt, c.nu.as<double>(),
-                    c.wts.as<double>(), c.nnu, sig, dmuk.as<double>(), c.P.as<double>(), dTlev.as<double>(),
-                    c.has_S ? c.S_toa.as<double>() : nullptr, c.has_alb ? c.albedo.as<double>() : nullptr, (double *)nullptr, nullptr,
-                    nullptr, dpart.as<double>(), shared_sigma ? 0 : (size_t)K * c.nnu);   // batches return band fluxes only: no tau stored
+    const FluxArgs fa = {&c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, sig, dmuk.as<double>(), c.P.as<double>(), dTlev.as<double>(),
+                         c.has_S ? c.S_toa.as<double>() : nullptr, c.has_alb ? c.albedo.as<double>() : nullptr,
+                         nullptr, nullptr, nullptr, dpart.as<double>(), s};   // batches return band fluxes only: no tau stored
+    launch_rt(bg, B, fa, shared_sigma ? 0 : (size_t)K * c.nnu);
     CS_LAUNCH(k_freduce, dim3(2 * np, B), dim3(256), 0, s, dpart.as<double>(), bg.nblk, 2 * np, dF.as<double>());
     HIPCHK(hipGetLastError());
     std::vector<double> F((size_t)B * 2 * np);
@@ -3426,8 +3440,10 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
     c.sigma_partial = form != 0;
     c.flux_form_last = form;
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
-    const double *dS = c.has_S ? c.S_toa.as<double>() : nullptr, *dA = c.has_alb ? c.albedo.as<double>() : nullptr;
-    double *dMu = c.want_M ? c.Mup.as<double>() : nullptr, *dMd = c.want_M ? c.Mdn.as<double>() : nullptr;
+    FluxArgs fa = {&c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, sig, c.muk.as<double>(), c.P.as<double>(), c.Tlev.as<double>(),
+                   c.has_S ? c.S_toa.as<double>() : nullptr, c.has_alb ? c.albedo.as<double>() : nullptr,
+                   c.want_tau ? c.tau.as<double>() : nullptr, c.want_M ? c.Mup.as<double>() : nullptr, c.want_M ? c.Mdn.as<double>() : nullptr,
+                   c.partial.as<double>(), s};
     bool reduced = false;
     if (form) {
         fuse.sigma2 = near_live ? c.sigma2.as<double>() : nullptr;
@@ -3440,23 +3456,13 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
         if (form == 2 && (ctx->tune[15] & 8)) log.disp.flags |= CS_DF_CHUNK4;
         if ((ctx->tune[15] & 128) && c.fluxdbg.reserve((8 + 2 * (size_t)fblk + 32) * sizeof(unsigned long long)) == hipSuccess) fuse.dbg = c.fluxdbg.as<unsigned long long>();
         // the chunked form always writes the layer optical depths (its upward sweep reads them back): into the caller's plane or scratch
-        double *dtau = (c.want_tau || form == 2) ? c.tau.as<double>() : nullptr;   // (forms 1 and 3 keep the optical depths in LDS)
+        if (form == 2) fa.tau = c.tau.as<double>();   // (forms 0 and 3 keep the optical depths in LDS unless the caller wants them)
         bool rad = false;
         for (int t = 0; t < fuse.ncia; t++) rad = rad || fuse.cia[t].Tr != nullptr;
-#define CS_FLUX_ARGS form, fsh, fblk, fthr, s, c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, sig, c.muk.as<double>(), c.P.as<double>(), \
-                     c.Tlev.as<double>(), dS, dA, dtau, dMu, dMd, c.partial.as<double>(), fuse, (ctx->tune[15] & 8) == 0, (ctx->tune[15] & 2048) != 0
-#define CS_FLUX_CASE(N) case N: if (rad) launch_flux_ns<N, true>(CS_FLUX_ARGS); else launch_flux_ns<N, false>(CS_FLUX_ARGS); break;
-        switch (c.nstream) {
-            CS_FLUX_CASE(1) CS_FLUX_CASE(2) CS_FLUX_CASE(3) CS_FLUX_CASE(4) CS_FLUX_CASE(5) CS_FLUX_CASE(6) CS_FLUX_CASE(7) CS_FLUX_CASE(8)
-            CS_FLUX_CASE(9) CS_FLUX_CASE(10) CS_FLUX_CASE(11) CS_FLUX_CASE(12) CS_FLUX_CASE(13) CS_FLUX_CASE(14) CS_FLUX_CASE(15) CS_FLUX_CASE(16)
-        }
-#undef CS_FLUX_CASE
-#undef CS_FLUX_ARGS
+        launch_flux(form, fsh, fblk, fthr, fa, fuse, rad, (ctx->tune[15] & 8) == 0, (ctx->tune[15] & 2048) != 0);
     } else {
         if (c.rtg.streams) log.disp.flags |= CS_DF_RT_STREAMS;
-        launch_rt(c.nstream, c.rtg, 1, s, c.rt, c.nu.as<double>(), c.wts.as<double>(),
-                  c.nnu, sig, c.muk.as<double>(), c.P.as<double>(), c.Tlev.as<double>(), dS, dA, c.want_tau ? c.tau.as<double>() : nullptr,
-                  dMu, dMd, c.partial.as<double>(), 0, near_live ? c.sigma2.as<double>() : nullptr);
+        launch_rt(c.rtg, 1, fa, 0, near_live ? c.sigma2.as<double>() : nullptr);
     }
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
     if (!reduced)

@@ -2988,6 +2988,128 @@ __device__ __forceinline__ double wave_sum(double v)
     return r;
 }
 
+// ---- the pieces of radiate! (discretized.jl:282-322) that every flux kernel form below is built from.  The forms differ in where the
+// cross-sections, the layer optical depths and the transmissivities come from, and in which wave carries what; these lines they share.
+
+// what a lane knows about its wavenumber: point j of the grid (lanes past a ragged end repeat the last point with weight 0, so that
+// barriers and wave sums stay uniform), trapezoid weight w, stellar flux fS and albedo fa (0 where the column has none)
+struct RtLane {
+    int lane;
+    int64_t j, jj;   // the point; the point clamped to the grid (loads)
+    bool live;       // stores happen
+    double v, w, fS, fa;
+};
+__device__ __forceinline__ RtLane rt_lane(int64_t tile, bool tile_live, int64_t nnu, const double *nu, const double *wts, const double *S_toa,
+                                          const double *albedo)
+{
+    RtLane L;
+    L.lane = threadIdx.x & 63;
+    L.j = tile * 64 + L.lane;
+    L.live = tile_live && L.j < nnu;
+    L.jj = L.j < nnu ? L.j : nnu - 1;
+    L.v = nu[L.jj];
+    L.w = L.live ? wts[L.jj] : 0.0;
+    L.fS = S_toa ? S_toa[L.jj] : 0.0;
+    L.fa = albedo ? albedo[L.jj] : 0.0;
+    return L;
+}
+
+// blockIdx.y = column of a batch (cs_column_batch): same grid, pressures and stream rule, its own node states
+__device__ __forceinline__ void rt_batch_column(const RtParams &p, int64_t nnu, size_t sig_bstride, const double *__restrict__ &sigma,
+                                                const double *__restrict__ &muk, const double *__restrict__ &Tlev, double *__restrict__ &tau,
+                                                double *__restrict__ &partial)
+{
+    const size_t b = blockIdx.y;
+    sigma += b * sig_bstride;     // K*nnu, or 0 when the columns of a batch share their cross-sections (AcceleratedAbsorber)
+    muk += b * p.K;
+    Tlev += b * p.np;
+    if (tau) tau += b * (size_t)(p.np - 1) * nnu;
+    partial += b * (size_t)gridDim.x * 2 * p.np;
+}
+
+// beta at a node, discretized.jl:150
+__device__ __forceinline__ double node_beta(double C, double sigma, double mu) { return C * (sigma / mu); }
+
+// dDepth! (discretized.jl:136-177): optical depth of the layer whose first node is kl -- Lobatto weights times beta at its nodes, first
+// node, inner nodes, last node, then the floor (max(tau, taumin), :147,174: a NaN depth stays NaN, as Julia's max keeps it).  The end
+// nodes are shared with the neighbouring layers: a caller that walks the layers hands over the beta it kept.  sg(k) is the
+// cross-section at node k from wherever the caller holds it; b_last() is asked for after the inner nodes, which is where a caller
+// that fetches end nodes one layer ahead issues its next load.
+template <class Sg, class Last>
+__device__ __forceinline__ double layer_depth(const RtParams &p, const double *muk, double dP, int kl, double b_first, Last b_last,
+                                              Sg sg)
+{
+    const int nlob = p.nlobatto;
+    double ti = (dP * p.ws[0]) * b_first;
+    for (int n = 1; n < nlob - 1; n++) ti += (dP * p.ws[n]) * node_beta(p.C, sg(kl + n), muk[kl + n]);
+    ti += (dP * p.ws[nlob - 1]) * b_last();
+    return ti < 1e-6 ? 1e-6 : ti;
+}
+
+// one stream through one layer, discretized.jl:287-291 / :314-318: I <- I e^(-tau m_k) + B_eff, the layer entered at B1 and left at B2
+__device__ __forceinline__ double stream_tr(double t, double mk) { return exp_rt(-(t * mk)); }
+__device__ __forceinline__ double stream_step(double I, double B1, double B2, double itau_k, double tr)
+{
+    const double Be = layerplanck_inv(B1, B2, itau_k, tr);
+    return I * tr + Be;
+}
+// all NS streams through one layer of optical depth t (it = 1/t); returns sum_k W_k I_k.  The transmissivities are formed here
+// (TR_EXP), formed and left in trv for a later pass over the same layer (TR_KEEP), or taken from trv (TR_KEPT: t is not looked at).
+// A != NULL (k_flux_scan, phase 1): the product of the transmissivities is accumulated per stream beside I, and nothing is summed.
+enum { TR_EXP, TR_KEEP, TR_KEPT };
+template <int NS, int TR>
+__device__ __forceinline__ double sweep_step(const RtParams &p, double t, double it, double B1, double B2, double (&I)[NS], double (*trv)[NS],
+                                             double (*A)[NS])
+{
+    double M = 0.0;
+#pragma unroll
+    for (int k = 0; k < NS; k++) {
+        const double tr = TR == TR_KEPT ? (*trv)[k] : stream_tr(t, p.m[k]);
+        if (TR == TR_KEEP) (*trv)[k] = tr;
+        I[k] = stream_step(I[k], B1, B2, it * p.im[k], tr);
+        if (A) (*A)[k] *= tr;
+        else M += p.W[k] * I[k];
+    }
+    return M;
+}
+
+// surface: Lambertian reflection of the downward flux + Planck emission, discretized.jl:309-310
+__device__ __forceinline__ double surface_intensity(double Md, double fa, double Bs) { return Md * fa / kPi + Bs; }
+
+// what radiate! returns at a level: the tile's share of the band flux into its slot of `red` (lane 0), the flux itself into the
+// caller's plane if there is one
+__device__ __forceinline__ void level_out(const RtLane &L, double M, double *red_slot, double *plane, int level, int64_t nnu)
+{
+    const double r = wave_sum(L.w * M);
+    if (L.lane == 0) *red_slot = r;
+    if (plane && L.live) plane[(size_t)level * nnu + L.j] = M;
+}
+
+// (agent-scope accesses of the block partials: the note above flux_last_block_reduce)
+__device__ __forceinline__ void flux_store_dev(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double flux_load_dev(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the block's partial sums, layout [block][2*np] (Fup then Fdn), once every wave has left its levels in `red` (call after the barrier).
+// dev: a later block of this launch adds them (flux_last_block_reduce).  Blocks of several tiles hold red[2*np][nw], one column per wave
+__device__ __forceinline__ void block_partial_waves(const double *red, int nw, int np, double *partial, bool dev)
+{
+    for (int e = threadIdx.x; e < 2 * np; e += blockDim.x) {
+        const double *q = red + e * nw;
+        double t = q[0];
+        for (int x = 1; x < nw; x++) t += q[x];
+        if (dev) flux_store_dev(&partial[(size_t)blockIdx.x * 2 * np + e], t);
+        else partial[(size_t)blockIdx.x * 2 * np + e] = t;
+    }
+}
+// ... blocks of one tile hold red[2*np]
+__device__ __forceinline__ void block_partial_tile(const double *red, int np, double *partial, bool dev)
+{
+    for (int e = threadIdx.x; e < 2 * np; e += blockDim.x) {
+        if (dev) flux_store_dev(&partial[(size_t)blockIdx.x * 2 * np + e], red[e]);
+        else partial[(size_t)blockIdx.x * 2 * np + e] = red[e];
+    }
+}
+
 // K3: one lane per wavenumber.  Pass 1 walks TOA -> surface: layer optical depths from the node cross-sections
 // (dDepth!) and the downward sweep of all NS streams at once; pass 2 walks surface -> TOA (upward sweep).
 // All NS intensities advance together, so M-[i+1] = sum_k W_k I_k + stellar beam is complete when layer i is done --
@@ -3015,94 +3137,54 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p, const double *__restrict
     extern __shared__ double red[];  // [2*np][nw] (+ UD: [nw][64] surface downward flux)
     const int nwv = blockDim.x >> 6;
     const int nw = UD ? nwv >> 1 : nwv;   // 64-point tiles per block: 4 (2 with UD) for big grids, 1 for small ones (more blocks than CUs)
-    {   // blockIdx.y = column of a batch (cs_column_batch): same grid, pressures and stream rule, its own node states
-        const size_t b = blockIdx.y;
-        sigma += b * sig_bstride;     // K*nnu, or 0 when the columns of a batch share their cross-sections (AcceleratedAbsorber)
-        muk += b * p.K;
-        Tlev += b * p.np;
-        if (tau) tau += b * (size_t)(p.np - 1) * nnu;
-        partial += b * (size_t)gridDim.x * 2 * p.np;
-    }
-    const int lane = threadIdx.x & 63;
+    rt_batch_column(p, nnu, sig_bstride, sigma, muk, Tlev, tau, partial);
     const int wva = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool up_role = UD && wva >= nw, down_role = !UD || wva < nw;
     const int wv = up_role ? wva - nw : wva;
-    const int64_t j = ((int64_t)blockIdx.x * nw + wv) * 64 + lane;
-    const bool live = j < nnu;
-    const int64_t jj = live ? j : nnu - 1;
+    const RtLane L = rt_lane((int64_t)blockIdx.x * nw + wv, true, nnu, nu, wts, S_toa, albedo);
+    const int lane = L.lane;
     const int np = p.np, nl = np - 1, nlob = p.nlobatto;
     double *xch = red + (size_t)2 * np * nw;
-    const double v = nu[jj];
-    const double w = live ? wts[jj] : 0.0;
-    const double fS = S_toa ? S_toa[jj] : 0.0;
-    const double fa = albedo ? albedo[jj] : 0.0;
     const double c = p.cos_ts;
-    auto sg = [&](size_t idx) { return sigma2 ? sigma[idx] + sigma2[idx] : sigma[idx]; };
+    auto sg = [&](int k) { const size_t idx = (size_t)k * nnu + L.jj; return sigma2 ? sigma[idx] + sigma2[idx] : sigma[idx]; };   // node k
 
     double I[NS];
     double Md = 0.0, Bprev = 0.0;
     if (down_role) {
 #pragma unroll
         for (int k = 0; k < NS; k++) I[k] = 0.0;
-        double b1 = p.C * (sg((size_t)jj) / muk[0]);  // beta at node 0, discretized.jl:150
-        double Ms = c * fS;                      // M-[1] = c*fS(nu), discretized.jl:299
+        double b1 = node_beta(p.C, sg(0), muk[0]);
+        double Ms = c * L.fS;                    // M-[1] = c*fS(nu), discretized.jl:299
         Md = Ms;
-        Bprev = planck(v, Tlev[0]);
-        {
-            double r = wave_sum(w * Md);
-            if (lane == 0) red[(np + 0) * nw + wv] = r;
-            if (Mdn && live) Mdn[j] = Md;
-        }
-        double sg_next = sg((size_t)(nlob - 1) * nnu + jj);   // end node of layer 0; later layers are fetched one layer ahead
+        Bprev = planck(L.v, Tlev[0]);
+        level_out(L, Md, &red[(np + 0) * nw + wv], Mdn, 0, nnu);
+        double sg_next = sg(nlob - 1);   // end node of layer 0; later layers are fetched one layer ahead
         for (int i = 0; i < nl; i++) {
             const double dP = P[i + 1] - P[i];
-            double ti = (dP * p.ws[0]) * b1;
-            for (int n = 1; n < nlob - 1; n++) {
-                const int k = i * (nlob - 1) + n;
-                ti += (dP * p.ws[n]) * (p.C * (sg((size_t)k * nnu + jj) / muk[k]));
-            }
-            const int ke = (i + 1) * (nlob - 1);
-            const double sgv = sg_next;
-            if (i + 1 < nl) sg_next = sg((size_t)(ke + nlob - 1) * nnu + jj);   // in flight during this layer's exp/divide chain
-            const double bn = p.C * (sgv / muk[ke]);
-            ti += (dP * p.ws[nlob - 1]) * bn;
-            b1 = bn;
-            const double t = ti < 1e-6 ? 1e-6 : ti;  // floor, discretized.jl:147,174 (max(tau, taumin): a NaN depth stays NaN, as Julia's max keeps it)
-            if (tau && live) tau[(size_t)i * nnu + j] = t;
-            const double Bnext = planck(v, Tlev[i + 1]);
-            Md = 0.0;
-            const double it = 1.0 / t;
-#pragma unroll
-            for (int k = 0; k < NS; k++) {
-                const double tk = t * p.m[k];
-                const double tr = exp_rt(-tk);
-                const double Be = layerplanck_inv(Bprev, Bnext, it * p.im[k], tr);
-                I[k] = I[k] * tr + Be;
-                Md += p.W[k] * I[k];
-            }
+            const double t = layer_depth(p, muk, dP, i * (nlob - 1), b1, [&] {
+                const int ke = (i + 1) * (nlob - 1);
+                const double sgv = sg_next;
+                if (i + 1 < nl) sg_next = sg(ke + nlob - 1);   // in flight during this layer's exp/divide chain
+                return b1 = node_beta(p.C, sgv, muk[ke]);   // (kept: the next layer's first node)
+            }, sg);
+            if (tau && L.live) tau[(size_t)i * nnu + L.j] = t;
+            const double Bnext = planck(L.v, Tlev[i + 1]);
+            Md = sweep_step<NS, TR_EXP>(p, t, 1.0 / t, Bprev, Bnext, I, nullptr, nullptr);
             if (S_toa) Ms *= exp(-t / c);   // (wave-uniform; without a stellar beam Ms stays 0)
             Md += Ms;
             Bprev = Bnext;
-            double r = wave_sum(w * Md);
-            if (lane == 0) red[(np + i + 1) * nw + wv] = r;
-            if (Mdn && live) Mdn[(size_t)(i + 1) * nnu + j] = Md;
+            level_out(L, Md, &red[(np + i + 1) * nw + wv], Mdn, i + 1, nnu);
         }
         if (UD && albedo) xch[wv * 64 + lane] = Md;
     }
     if (UD && albedo) __syncthreads();   // (block-uniform condition) the up-waves need the surface downward flux of their tile
     if (!down_role || !UD) {
         if (UD) {
-            Bprev = planck(v, Tlev[np - 1]);
+            Bprev = planck(L.v, Tlev[np - 1]);
             Md = albedo ? xch[wv * 64 + lane] : 0.0;
         }
-        // surface: Lambertian reflection + Planck emission, discretized.jl:309-310
-        const double Is = Md * fa / kPi + Bprev;
-        double Mu = Is * kPi;
-        {
-            double r = wave_sum(w * Mu);
-            if (lane == 0) red[(np - 1) * nw + wv] = r;
-            if (Mup && live) Mup[(size_t)(np - 1) * nnu + j] = Mu;
-        }
+        const double Is = surface_intensity(Md, L.fa, Bprev);
+        level_out(L, Is * kPi, &red[(np - 1) * nw + wv], Mup, np - 1, nnu);
 #pragma unroll
         for (int k = 0; k < NS; k++) I[k] = Is;
         double Bhi = Bprev;  // B at level i+1
@@ -3111,51 +3193,32 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p, const double *__restrict
         const bool recompute = UD || !tau;   // no tau output requested ("OLR-only"): optical depths never touch HBM
         double t_next = 1.0, b_hi = 0.0, sg_lo = 0.0;
         if (recompute) {
-            b_hi = p.C * (sg((size_t)(p.K - 1) * nnu + jj) / muk[p.K - 1]);
-            sg_lo = sg((size_t)(nl - 1) * (nlob - 1) * nnu + jj);
+            b_hi = node_beta(p.C, sg(p.K - 1), muk[p.K - 1]);
+            sg_lo = sg((nl - 1) * (nlob - 1));
         } else {
-            t_next = live ? tau[(size_t)(nl - 1) * nnu + j] : 1.0;
+            t_next = L.live ? tau[(size_t)(nl - 1) * nnu + L.j] : 1.0;
         }
         for (int i = nl - 1; i >= 0; i--) {
             double t;
             if (recompute) {
                 const double dP = P[i + 1] - P[i];
                 const int kl = i * (nlob - 1);
-                const double b_lo = p.C * (sg_lo / muk[kl]);
-                if (i > 0) sg_lo = sg((size_t)(kl - (nlob - 1)) * nnu + jj);   // one layer ahead
-                double ti = (dP * p.ws[0]) * b_lo;
-                for (int n = 1; n < nlob - 1; n++) ti += (dP * p.ws[n]) * (p.C * (sg((size_t)(kl + n) * nnu + jj) / muk[kl + n]));
-                ti += (dP * p.ws[nlob - 1]) * b_hi;
+                const double b_lo = node_beta(p.C, sg_lo, muk[kl]);
+                if (i > 0) sg_lo = sg(kl - (nlob - 1));   // one layer ahead
+                t = layer_depth(p, muk, dP, kl, b_lo, [&] { return b_hi; }, sg);
                 b_hi = b_lo;
-                t = ti < 1e-6 ? 1e-6 : ti;
             } else {
                 t = t_next;
-                if (i > 0) t_next = live ? tau[(size_t)(i - 1) * nnu + j] : 1.0;   // one layer ahead
+                if (i > 0) t_next = L.live ? tau[(size_t)(i - 1) * nnu + L.j] : 1.0;   // one layer ahead
             }
-            const double Blo = planck(v, Tlev[i]);
-            Mu = 0.0;
-            const double it = 1.0 / t;
-#pragma unroll
-            for (int k = 0; k < NS; k++) {
-                const double tk = t * p.m[k];
-                const double tr = exp_rt(-tk);
-                const double Be = layerplanck_inv(Bhi, Blo, it * p.im[k], tr);
-                I[k] = I[k] * tr + Be;
-                Mu += p.W[k] * I[k];
-            }
+            const double Blo = planck(L.v, Tlev[i]);
+            const double Mu = sweep_step<NS, TR_EXP>(p, t, 1.0 / t, Bhi, Blo, I, nullptr, nullptr);
             Bhi = Blo;
-            double r = wave_sum(w * Mu);
-            if (lane == 0) red[i * nw + wv] = r;
-            if (Mup && live) Mup[(size_t)i * nnu + j] = Mu;
+            level_out(L, Mu, &red[i * nw + wv], Mup, i, nnu);
         }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < 2 * np; e += blockDim.x) {
-        const double *q = red + e * nw;
-        double t = q[0];
-        for (int x = 1; x < nw; x++) t += q[x];
-        partial[(size_t)blockIdx.x * 2 * np + e] = t;
-    }
+    block_partial_waves(red, nw, np, partial, false);
 }
 
 // K3 for short grids (a nu-shard, a small column): there a sweep is one chain per lane -- per layer a global load of the layer's
@@ -3180,131 +3243,88 @@ __global__ __launch_bounds__(2 * NS * 64) void k_rt_streams(RtParams p, const do
     extern __shared__ double sh[];   // Blev[np][64] | tl[nl][64] | xch[2 buffers][2 roles][NS][64] | red[2 np] | msurf[64]
     const int np = p.np, nl = np - 1, nlob = p.nlobatto;
     double *Blev = sh, *tl = sh + (size_t)np * 64, *xch = tl + (size_t)nl * 64, *red = xch + (size_t)2 * 2 * NS * 64, *msurf = red + 2 * np;
-    {   // blockIdx.y = column of a batch (cs_column_batch)
-        const size_t b = blockIdx.y;
-        sigma += b * sig_bstride;
-        muk += b * p.K;
-        Tlev += b * p.np;
-        if (tau) tau += b * (size_t)(p.np - 1) * nnu;
-        partial += b * (size_t)gridDim.x * 2 * p.np;
-    }
-    const int lane = threadIdx.x & 63;
+    rt_batch_column(p, nnu, sig_bstride, sigma, muk, Tlev, tau, partial);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool up = wave >= NS;
     const int k = up ? wave - NS : wave;
-    const int64_t j = (int64_t)blockIdx.x * 64 + lane;
-    const bool live = j < nnu;
-    const int64_t jj = live ? j : nnu - 1;
-    const double v = nu[jj];
-    const double w = live ? wts[jj] : 0.0;
-    const double fS = S_toa ? S_toa[jj] : 0.0;
-    const double fa = albedo ? albedo[jj] : 0.0;
+    const RtLane L = rt_lane((int64_t)blockIdx.x, true, nnu, nu, wts, S_toa, albedo);
+    const int lane = L.lane;
     const double c = p.cos_ts;
     for (int i = wave; i < np; i += 2 * NS) {
-        Blev[(size_t)i * 64 + lane] = planck(v, Tlev[i]);
-        if (i < nl) {   // optical depth of layer i exactly as k_rt forms it (dDepth!, discretized.jl:136-177): beta at the layer's nodes, 1e-6 floor
-            const double dP = P[i + 1] - P[i];
+        Blev[(size_t)i * 64 + lane] = planck(L.v, Tlev[i]);
+        if (i < nl) {   // optical depth of layer i exactly as k_rt forms it
             const int kl = i * (nlob - 1);
-            auto sg = [&](size_t idx) { return sigma2 ? sigma[idx] + sigma2[idx] : sigma[idx]; };   // (near-line plane, see k_rt)
-            double ti = (dP * p.ws[0]) * (p.C * (sg((size_t)kl * nnu + jj) / muk[kl]));
-            for (int n = 1; n < nlob - 1; n++) ti += (dP * p.ws[n]) * (p.C * (sg((size_t)(kl + n) * nnu + jj) / muk[kl + n]));
-            ti += (dP * p.ws[nlob - 1]) * (p.C * (sg((size_t)(kl + nlob - 1) * nnu + jj) / muk[kl + nlob - 1]));
-            const double t = ti < 1e-6 ? 1e-6 : ti;
+            auto sg = [&](int kk) { const size_t idx = (size_t)kk * nnu + L.jj; return sigma2 ? sigma[idx] + sigma2[idx] : sigma[idx]; };   // (near-line plane, see k_rt)
+            const double t = layer_depth(p, muk, P[i + 1] - P[i], kl, node_beta(p.C, sg(kl), muk[kl]),
+                                         [&] { return node_beta(p.C, sg(kl + nlob - 1), muk[kl + nlob - 1]); }, sg);
             tl[(size_t)i * 64 + lane] = t;
-            if (tau && live) tau[(size_t)i * nnu + j] = t;
+            if (tau && L.live) tau[(size_t)i * nnu + L.j] = t;
         }
     }
     __syncthreads();
     const bool serial = albedo != nullptr;           // (block-uniform) the upward sweep waits for the surface downward flux
     const double mk = p.m[k], imk = p.im[k], Wk = p.W[k];
     auto slot = [&](int buf, int role, int kk) { return xch + (((size_t)buf * 2 + role) * NS + kk) * 64 + lane; };
-    double I = 0.0, Ms = c * fS;
+    // this wave's stream through a layer of optical depth t, entered at level a and left at level b
+    auto step = [&](double I, double t, int a, int b) {
+        return stream_step(I, Blev[(size_t)a * 64 + lane], Blev[(size_t)b * 64 + lane], (1.0 / t) * imk, stream_tr(t, mk));
+    };
+    auto stream_sum = [&](int buf, int role) {       // the role's sum over the streams, in stream order
+        double M = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < NS; kk++) M += *slot(buf, role, kk);
+        return M;
+    };
+    double I = 0.0, Ms = c * L.fS;
     // ---- downward sweep (the up-waves run their own sweep in the same loop when nothing ties them to this one)
-    if (!up && k == 0) {   // level 0: M-[1] = c fS(nu), discretized.jl:299
-        const double r = wave_sum(w * Ms);
-        if (lane == 0) red[np + 0] = r;
-        if (Mdn && live) Mdn[j] = Ms;
-    }
+    if (!up && k == 0) level_out(L, Ms, &red[np + 0], Mdn, 0, nnu);   // level 0: M-[1] = c fS(nu), discretized.jl:299
     double Iu = 0.0;
     if (up && !serial) {   // surface: Planck emission only (no reflected part without an albedo), discretized.jl:309-310
         Iu = Blev[(size_t)(np - 1) * 64 + lane];
-        if (k == 0) {
-            const double Mu = Iu * kPi;
-            const double r = wave_sum(w * Mu);
-            if (lane == 0) red[np - 1] = r;
-            if (Mup && live) Mup[(size_t)(np - 1) * nnu + j] = Mu;
-        }
+        if (k == 0) level_out(L, Iu * kPi, &red[np - 1], Mup, np - 1, nnu);
     }
     for (int s = 0; s < nl; s++) {
         const int buf = s & 1;
         if (!up) {
             const double t = tl[(size_t)s * 64 + lane];
-            const double tr = exp_rt(-(t * mk));
-            const double Be = layerplanck_inv(Blev[(size_t)s * 64 + lane], Blev[(size_t)(s + 1) * 64 + lane], (1.0 / t) * imk, tr);
-            I = I * tr + Be;
+            I = step(I, t, s, s + 1);
             *slot(buf, 0, k) = Wk * I;
             if (k == 0 && S_toa) Ms *= exp(-t / c);
         } else if (!serial) {
             const int i = nl - 1 - s;
-            const double t = tl[(size_t)i * 64 + lane];
-            const double tr = exp_rt(-(t * mk));
-            const double Be = layerplanck_inv(Blev[(size_t)(i + 1) * 64 + lane], Blev[(size_t)i * 64 + lane], (1.0 / t) * imk, tr);
-            Iu = Iu * tr + Be;
+            Iu = step(Iu, tl[(size_t)i * 64 + lane], i + 1, i);
             *slot(buf, 1, k) = Wk * Iu;
         }
         __syncthreads();
-        if (k == 0 && (!up || !serial)) {   // the role's sum over the streams, in stream order
-            const int role = up ? 1 : 0;
-            double M = 0.0;
-#pragma unroll
-            for (int kk = 0; kk < NS; kk++) M += *slot(buf, role, kk);
+        if (k == 0 && (!up || !serial)) {
+            const double M = stream_sum(buf, up ? 1 : 0);
             if (!up) {
-                M += Ms;
-                const double r = wave_sum(w * M);
-                if (lane == 0) red[np + s + 1] = r;
-                if (Mdn && live) Mdn[(size_t)(s + 1) * nnu + j] = M;
-                if (serial && s == nl - 1) msurf[lane] = M;
+                const double Md = M + Ms;
+                level_out(L, Md, &red[np + s + 1], Mdn, s + 1, nnu);
+                if (serial && s == nl - 1) msurf[lane] = Md;
             } else {
-                const int i = nl - 1 - s;
-                const double r = wave_sum(w * M);
-                if (lane == 0) red[i] = r;
-                if (Mup && live) Mup[(size_t)i * nnu + j] = M;
+                level_out(L, M, &red[nl - 1 - s], Mup, nl - 1 - s, nnu);
             }
         }
     }
-    if (serial) {   // ---- upward sweep after the downward one: Lambertian reflection + Planck emission at the surface
+    if (serial) {   // ---- upward sweep after the downward one
         __syncthreads();
         if (up) {
-            Iu = msurf[lane] * fa / kPi + Blev[(size_t)(np - 1) * 64 + lane];
-            if (k == 0) {
-                const double Mu = Iu * kPi;
-                const double r = wave_sum(w * Mu);
-                if (lane == 0) red[np - 1] = r;
-                if (Mup && live) Mup[(size_t)(np - 1) * nnu + j] = Mu;
-            }
+            Iu = surface_intensity(msurf[lane], L.fa, Blev[(size_t)(np - 1) * 64 + lane]);
+            if (k == 0) level_out(L, Iu * kPi, &red[np - 1], Mup, np - 1, nnu);
         }
         for (int s = 0; s < nl; s++) {
             const int buf = s & 1, i = nl - 1 - s;
             if (up) {
-                const double t = tl[(size_t)i * 64 + lane];
-                const double tr = exp_rt(-(t * mk));
-                const double Be = layerplanck_inv(Blev[(size_t)(i + 1) * 64 + lane], Blev[(size_t)i * 64 + lane], (1.0 / t) * imk, tr);
-                Iu = Iu * tr + Be;
+                Iu = step(Iu, tl[(size_t)i * 64 + lane], i + 1, i);
                 *slot(buf, 1, k) = Wk * Iu;
             }
             __syncthreads();
-            if (up && k == 0) {
-                double M = 0.0;
-#pragma unroll
-                for (int kk = 0; kk < NS; kk++) M += *slot(buf, 1, kk);
-                const double r = wave_sum(w * M);
-                if (lane == 0) red[i] = r;
-                if (Mup && live) Mup[(size_t)i * nnu + j] = M;
-            }
+            if (up && k == 0) level_out(L, stream_sum(buf, 1), &red[i], Mup, i, nnu);
         }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < 2 * np; e += blockDim.x) partial[(size_t)blockIdx.x * 2 * np + e] = red[e];
+    block_partial_tile(red, np, partial, false);
 }
 
 // K4: F[e] = sum over blocks of partial[b][e], fixed order (bitwise reproducible run to run)
@@ -3727,8 +3747,7 @@ __device__ __forceinline__ void flux_sigma_tile(const FluxFuse &f, int K, int64_
 // memory model; the relaxed form is correct for the hardware named in the #error above, which is why the host hands out a ticket only
 // on a device that reports gfx950 (cs_create; otherwise k_freduce, a second launch, adds the partials) -- tests/test_gpu_flux_fused.py
 // compares the two bit for bit.
-__device__ __forceinline__ void flux_store_dev(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double flux_load_dev(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// (flux_store_dev / flux_load_dev are defined with the flux helpers, above k_rt)
 __device__ __forceinline__ void flux_last_block_reduce(const FluxFuse &f, const double *__restrict__ partial, int nblk, int n2)
 {
     __shared__ unsigned last;
@@ -3775,11 +3794,12 @@ __device__ __forceinline__ void flux_last_block_reduce(const FluxFuse &f, const 
     if (f.dbg && threadIdx.x == 0) f.dbg[7] = wall_clock64();   // (measurement hook: the last block's last word)
 }
 
-// K5 on short grids, second form: the sweeps as a SCAN over layer chunks.  In k_flux_streams a wave walks all layers of one stream: 60
-// dependent steps of one exponential each, one barrier per layer -- 45 us that no amount of idle chip shortens.  But only the recurrence
-// I <- I e^(-tau m) + B_eff is sequential, and it is linear: a run of layers acts on the incoming intensity as I -> A I + B.  One block =
-// one tile, NW waves, wave w = a chunk of consecutive layers, all NS streams, both sweeps:
-//   phase A, 0  as k_flux_streams: cross-sections, then optical depths and Planck values of every layer into LDS;
+// K5 on short grids: the sweeps as a SCAN over layer chunks.  A wave that walks all layers of one stream (k_rt_streams, reading finished
+// cross-sections) runs 60 dependent steps of one exponential each, one barrier per layer -- 45 us that no amount of idle chip shortens.
+// But only the recurrence I <- I e^(-tau m) + B_eff is sequential, and it is linear: a run of layers acts on the incoming intensity as
+// I -> A I + B.  One block = one tile, NW waves, wave w = a chunk of consecutive layers, all NS streams, both sweeps:
+//   phase A, 0  the tile's cross-sections (flux_sigma_tile), then optical depths and Planck values of every layer into LDS, level / layer i
+//               by wave i mod NW, as k_rt_streams forms them;
 //   phase 1     every wave runs its chunk from zero incoming intensity -- NS independent chains per lane, no barrier -- and keeps the
 //               chunk's (A, B) per stream and sweep (and the stellar beam's attenuation) in registers;
 //   phase 2     the incoming intensities travel from chunk to chunk: NW steps of one fused multiply-add per stream, downward sweep in
@@ -3801,31 +3821,22 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int NW = (int)(blockDim.x >> 6);
-    const int64_t j = (int64_t)blockIdx.x * 64 + lane;
-    const bool live = j < nnu;
-    const int64_t jj = live ? j : nnu - 1;
     flux_stamp(f, 0);
     flux_stamp_block(f, 0);
     flux_sigma_tile<RAD>(f, K, nnu, (int)blockIdx.x, sigma, nu, sig, wave, NW, lane);
     __syncthreads();
     flux_stamp(f, 1);
-    const double v = nu[jj];
-    const double w = live ? wts[jj] : 0.0;
-    const double fS = S_toa ? S_toa[jj] : 0.0;
-    const double fa = albedo ? albedo[jj] : 0.0;
+    const RtLane L = rt_lane((int64_t)blockIdx.x, true, nnu, nu, wts, S_toa, albedo);
     const double c = p.cos_ts;
     for (int i = wave; i < np; i += NW) {
-        Blev[(size_t)i * 64 + lane] = planck(v, Tlev[i]);
-        if (i < nl) {   // optical depth of layer i exactly as k_rt forms it (dDepth!, discretized.jl:136-177): beta at the layer's nodes, 1e-6 floor
-            const double dP = P[i + 1] - P[i];
+        Blev[(size_t)i * 64 + lane] = planck(L.v, Tlev[i]);
+        if (i < nl) {   // optical depth of layer i exactly as k_rt forms it
             const int kl = i * (nlob - 1);
             auto sg = [&](int kk) { return sig[(size_t)kk * 64 + lane]; };
-            double ti = (dP * p.ws[0]) * (p.C * (sg(kl) / muk[kl]));
-            for (int n = 1; n < nlob - 1; n++) ti += (dP * p.ws[n]) * (p.C * (sg(kl + n) / muk[kl + n]));
-            ti += (dP * p.ws[nlob - 1]) * (p.C * (sg(kl + nlob - 1) / muk[kl + nlob - 1]));
-            const double t = ti < 1e-6 ? 1e-6 : ti;
+            const double t = layer_depth(p, muk, P[i + 1] - P[i], kl, node_beta(p.C, sg(kl), muk[kl]),
+                                         [&] { return node_beta(p.C, sg(kl + nlob - 1), muk[kl + nlob - 1]); }, sg);
             tl[(size_t)i * 64 + lane] = t;
-            if (tau && live) tau[(size_t)i * nnu + j] = t;
+            if (tau && L.live) tau[(size_t)i * nnu + L.j] = t;
         }
     }
     __syncthreads();
@@ -3833,95 +3844,84 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
     // this wave's layers [l0, l1)
     const int per = (nl + NW - 1) / NW;
     const int l0 = min(wave * per, nl), l1 = min(l0 + per, nl);
-    // ---- phase 1: the chunk from zero incoming intensity.  PER > 0 (a chunk has at most PER layers): the transmissivities of the chunk
-    // -- one exponential per (layer, stream) -- stay in registers for the upward sweep and for phase 3, which would form the same
-    // numbers again (PER = 0: they do; same results either way)
+    // PER > 0 (a chunk has at most PER layers): the transmissivities of the chunk -- one exponential per (layer, stream) -- stay in
+    // registers from the downward sweep of phase 1 for its upward sweep and for phase 3, which would form the same numbers again
+    // (PER = 0: they do; same results either way).  The two differ in the loop around a layer (unrolled over the PER register slots q
+    // with a guard, or over the chunk's layers), not in what is done to it: the four per-layer bodies below are shared.
+    constexpr bool KEPT = PER > 0;
+    constexpr int PQ = KEPT ? PER : 1;
+    constexpr int TR_UP = KEPT ? TR_KEPT : TR_EXP;      // every pass after the first one over a layer
     double Ad[NS], Bd[NS], Au[NS], Bu[NS], As = 1.0;
-    constexpr int PQ = PER > 0 ? PER : 1;
     double trv[PQ][NS], itv[PQ], trs[PQ];
+    double Id[NS], Iu[NS], Ms = 0.0;
+    auto depth = [&](int i, int q, double &t, double &it) __attribute__((always_inline)) {   // (a kept 1/t stands for t: nothing looks at t then)
+        if constexpr (KEPT) { t = 0.0; it = itv[q]; }
+        else { t = tl[(size_t)i * 64 + lane]; it = 1.0 / t; }
+    };
+    auto B = [&](int i) { return Blev[(size_t)i * 64 + lane]; };
+    // ---- phase 1: the chunk from zero incoming intensity: I -> A I + B per stream and sweep, the beam's attenuation As
+    auto chunk_down = [&](int i, int q) __attribute__((always_inline)) {
+        const double t = tl[(size_t)i * 64 + lane], it = 1.0 / t;
+        if constexpr (KEPT) itv[q] = it;
+        sweep_step<NS, KEPT ? TR_KEEP : TR_EXP>(p, t, it, B(i), B(i + 1), Bd, &trv[q], &Ad);
+        if (S_toa) {
+            const double e = exp(-t / c);
+            if constexpr (KEPT) trs[q] = e;
+            As *= e;
+        }
+    };
+    auto chunk_up = [&](int i, int q) __attribute__((always_inline)) {
+        double t, it;
+        depth(i, q, t, it);
+        sweep_step<NS, TR_UP>(p, t, it, B(i + 1), B(i), Bu, &trv[q], &Au);
+    };
+    // ---- phase 3: the chunk from its true incoming intensities; what radiate! returns at its levels
+    auto levels_down = [&](int i, int q) __attribute__((always_inline)) {
+        double t, it;
+        depth(i, q, t, it);
+        double Md = sweep_step<NS, TR_UP>(p, t, it, B(i), B(i + 1), Id, &trv[q], nullptr);
+        if (S_toa) Ms *= KEPT ? trs[q] : exp(-t / c);
+        Md += Ms;
+        level_out(L, Md, &red[np + i + 1], Mdn, i + 1, nnu);
+    };
+    auto levels_up = [&](int i, int q) __attribute__((always_inline)) {
+        double t, it;
+        depth(i, q, t, it);
+        const double Mu = sweep_step<NS, TR_UP>(p, t, it, B(i + 1), B(i), Iu, &trv[q], nullptr);
+        level_out(L, Mu, &red[i], Mup, i, nnu);
+    };
 #pragma unroll
     for (int k = 0; k < NS; k++) { Ad[k] = 1.0; Bd[k] = 0.0; Au[k] = 1.0; Bu[k] = 0.0; }
-    if constexpr (PER > 0) {
+    if constexpr (KEPT) {
 #pragma unroll
         for (int q = 0; q < PER; q++) {      // downward: layers ascending
-            const int i = l0 + q;
             itv[q] = 0.0; trs[q] = 1.0;
 #pragma unroll
             for (int k = 0; k < NS; k++) trv[q][k] = 1.0;
-            if (i < l1) {                    // (wave-uniform)
-                const double t = tl[(size_t)i * 64 + lane], it = 1.0 / t;
-                const double B1 = Blev[(size_t)i * 64 + lane], B2 = Blev[(size_t)(i + 1) * 64 + lane];
-                itv[q] = it;
-#pragma unroll
-                for (int k = 0; k < NS; k++) {
-                    const double tr = exp_rt(-(t * p.m[k]));
-                    const double Be = layerplanck_inv(B1, B2, it * p.im[k], tr);
-                    trv[q][k] = tr;
-                    Bd[k] = Bd[k] * tr + Be;
-                    Ad[k] *= tr;
-                }
-                if (S_toa) { trs[q] = exp(-t / c); As *= trs[q]; }
-            }
+            if (l0 + q < l1) chunk_down(l0 + q, q);      // (wave-uniform)
         }
 #pragma unroll
-        for (int q = PER - 1; q >= 0; q--) { // upward: layers descending
-            const int i = l0 + q;
-            if (i < l1) {
-                const double it = itv[q];
-                const double Bhi = Blev[(size_t)(i + 1) * 64 + lane], Blo = Blev[(size_t)i * 64 + lane];
-#pragma unroll
-                for (int k = 0; k < NS; k++) {
-                    const double tr = trv[q][k];
-                    const double Be = layerplanck_inv(Bhi, Blo, it * p.im[k], tr);
-                    Bu[k] = Bu[k] * tr + Be;
-                    Au[k] *= tr;
-                }
-            }
-        }
+        for (int q = PER - 1; q >= 0; q--)   // upward: layers descending
+            if (l0 + q < l1) chunk_up(l0 + q, q);
     } else {
-    for (int i = l0; i < l1; i++) {          // downward: layers ascending
-        const double t = tl[(size_t)i * 64 + lane], it = 1.0 / t;
-        const double B1 = Blev[(size_t)i * 64 + lane], B2 = Blev[(size_t)(i + 1) * 64 + lane];
-#pragma unroll
-        for (int k = 0; k < NS; k++) {
-            const double tr = exp_rt(-(t * p.m[k]));
-            const double Be = layerplanck_inv(B1, B2, it * p.im[k], tr);
-            Bd[k] = Bd[k] * tr + Be;
-            Ad[k] *= tr;
-        }
-        if (S_toa) As *= exp(-t / c);
-    }
-    for (int i = l1 - 1; i >= l0; i--) {     // upward: layers descending
-        const double t = tl[(size_t)i * 64 + lane], it = 1.0 / t;
-        const double Bhi = Blev[(size_t)(i + 1) * 64 + lane], Blo = Blev[(size_t)i * 64 + lane];
-#pragma unroll
-        for (int k = 0; k < NS; k++) {
-            const double tr = exp_rt(-(t * p.m[k]));
-            const double Be = layerplanck_inv(Bhi, Blo, it * p.im[k], tr);
-            Bu[k] = Bu[k] * tr + Be;
-            Au[k] *= tr;
-        }
-    }
+        for (int i = l0; i < l1; i++) chunk_down(i, 0);
+        for (int i = l1 - 1; i >= l0; i--) chunk_up(i, 0);
     }
     flux_stamp(f, 3);
     // ---- phase 2: incoming intensities from chunk to chunk.  xin[0][k] = what enters the current chunk going down, xin[1][k] going up;
     // xin[0][NS] = the stellar beam entering the chunk
     auto X = [&](int sweep, int k) { return xin + ((size_t)sweep * (NS + 1) + k) * 64 + lane; };
-    double Id[NS], Iu[NS], Ms_in = 0.0;
     const bool serial = albedo != nullptr;   // (block-uniform) the surface term of the upward sweep needs the downward flux only with an albedo
     if (wave == 0) {
 #pragma unroll
         for (int k = 0; k < NS; k++) *X(0, k) = 0.0;
-        *X(0, NS) = c * fS;                  // M-[1] = c fS(nu), discretized.jl:299
+        *X(0, NS) = c * L.fS;                // M-[1] = c fS(nu), discretized.jl:299
     }
-    auto surface = [&](double Md) {          // Lambertian reflection + Planck emission, discretized.jl:309-310
-        const double Is = Md * fa / kPi + Blev[(size_t)(np - 1) * 64 + lane];
+    auto surface = [&](double Md) {
+        const double Is = surface_intensity(Md, L.fa, B(np - 1));
 #pragma unroll
         for (int k = 0; k < NS; k++) *X(1, k) = Is;
-        const double Mu = Is * kPi;
-        const double r = wave_sum(w * Mu);
-        if (lane == 0) red[np - 1] = r;
-        if (Mup && live) Mup[(size_t)(np - 1) * nnu + j] = Mu;
+        level_out(L, Is * kPi, &red[np - 1], Mup, np - 1, nnu);
     };
     if (!serial && wave == NW - 1) surface(0.0);   // (no reflected part: both sweeps travel in the same steps below)
     for (int s = 0; s < NW; s++) {
@@ -3930,8 +3930,8 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
         if (wave == s) {
 #pragma unroll
             for (int k = 0; k < NS; k++) { Id[k] = *X(0, k); *X(0, k) = Id[k] * Ad[k] + Bd[k]; }
-            Ms_in = *X(0, NS);
-            *X(0, NS) = Ms_in * As;
+            Ms = *X(0, NS);
+            *X(0, NS) = Ms * As;
         }
         if (!serial && wave == NW - 1 - s) {
 #pragma unroll
@@ -3956,96 +3956,26 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
         }
     }
     flux_stamp(f, 4);
-    // ---- phase 3: the chunk from its true incoming intensities; what radiate! returns at its levels
-    if (wave == 0) {   // level 0 of the downward flux
-        const double r = wave_sum(w * Ms_in);
-        if (lane == 0) red[np + 0] = r;
-        if (Mdn && live) Mdn[j] = Ms_in;
-    }
-    double Ms = Ms_in;
-    if constexpr (PER > 0) {
+    // ---- phase 3
+    if (wave == 0) level_out(L, Ms, &red[np + 0], Mdn, 0, nnu);   // level 0 of the downward flux
+    if constexpr (KEPT) {
 #pragma unroll
         for (int q = 0; q < PER; q++) {
-            const int i = l0 + q;
-            if (i < l1) {
-                const double it = itv[q];
-                const double B1 = Blev[(size_t)i * 64 + lane], B2 = Blev[(size_t)(i + 1) * 64 + lane];
-                double Md = 0.0;
-#pragma unroll
-                for (int k = 0; k < NS; k++) {
-                    const double tr = trv[q][k];
-                    const double Be = layerplanck_inv(B1, B2, it * p.im[k], tr);
-                    Id[k] = Id[k] * tr + Be;
-                    Md += p.W[k] * Id[k];
-                }
-                if (S_toa) Ms *= trs[q];
-                Md += Ms;
-                const double r = wave_sum(w * Md);
-                if (lane == 0) red[np + i + 1] = r;
-                if (Mdn && live) Mdn[(size_t)(i + 1) * nnu + j] = Md;
-            }
+            if (l0 + q < l1) levels_down(l0 + q, q);
             flux_stamp_fine(f, 16 + q);
         }
 #pragma unroll
         for (int q = PER - 1; q >= 0; q--) {
-            const int i = l0 + q;
-            if (i < l1) {
-                const double it = itv[q];
-                const double Bhi = Blev[(size_t)(i + 1) * 64 + lane], Blo = Blev[(size_t)i * 64 + lane];
-                double Mu = 0.0;
-#pragma unroll
-                for (int k = 0; k < NS; k++) {
-                    const double tr = trv[q][k];
-                    const double Be = layerplanck_inv(Bhi, Blo, it * p.im[k], tr);
-                    Iu[k] = Iu[k] * tr + Be;
-                    Mu += p.W[k] * Iu[k];
-                }
-                const double r = wave_sum(w * Mu);
-                if (lane == 0) red[i] = r;
-                if (Mup && live) Mup[(size_t)i * nnu + j] = Mu;
-            }
+            if (l0 + q < l1) levels_up(l0 + q, q);
             flux_stamp_fine(f, 24 + q);
         }
     } else {
-    for (int i = l0; i < l1; i++) {
-        const double t = tl[(size_t)i * 64 + lane], it = 1.0 / t;
-        const double B1 = Blev[(size_t)i * 64 + lane], B2 = Blev[(size_t)(i + 1) * 64 + lane];
-        double Md = 0.0;
-#pragma unroll
-        for (int k = 0; k < NS; k++) {
-            const double tr = exp_rt(-(t * p.m[k]));
-            const double Be = layerplanck_inv(B1, B2, it * p.im[k], tr);
-            Id[k] = Id[k] * tr + Be;
-            Md += p.W[k] * Id[k];
-        }
-        if (S_toa) Ms *= exp(-t / c);
-        Md += Ms;
-        const double r = wave_sum(w * Md);
-        if (lane == 0) red[np + i + 1] = r;
-        if (Mdn && live) Mdn[(size_t)(i + 1) * nnu + j] = Md;
-    }
-    for (int i = l1 - 1; i >= l0; i--) {
-        const double t = tl[(size_t)i * 64 + lane], it = 1.0 / t;
-        const double Bhi = Blev[(size_t)(i + 1) * 64 + lane], Blo = Blev[(size_t)i * 64 + lane];
-        double Mu = 0.0;
-#pragma unroll
-        for (int k = 0; k < NS; k++) {
-            const double tr = exp_rt(-(t * p.m[k]));
-            const double Be = layerplanck_inv(Bhi, Blo, it * p.im[k], tr);
-            Iu[k] = Iu[k] * tr + Be;
-            Mu += p.W[k] * Iu[k];
-        }
-        const double r = wave_sum(w * Mu);
-        if (lane == 0) red[i] = r;
-        if (Mup && live) Mup[(size_t)i * nnu + j] = Mu;
-    }
+        for (int i = l0; i < l1; i++) levels_down(i, 0);
+        for (int i = l1 - 1; i >= l0; i--) levels_up(i, 0);
     }
     __syncthreads();
     flux_stamp(f, 5);
-    for (int e = threadIdx.x; e < 2 * np; e += blockDim.x) {
-        if (f.ticket) flux_store_dev(&partial[(size_t)blockIdx.x * 2 * np + e], red[e]);
-        else partial[(size_t)blockIdx.x * 2 * np + e] = red[e];
-    }
+    block_partial_tile(red, np, partial, f.ticket != nullptr);
     flux_stamp_block(f, 1);
     if (f.ticket) flux_last_block_reduce(f, partial, (int)gridDim.x, 2 * np);
     flux_stamp(f, 6);
@@ -4067,19 +3997,15 @@ __device__ __forceinline__ void flux_chunk_body(const RtParams &p, const double 
     const int nw = blockDim.x >> 6;
     const int np = p.np, nl = np - 1, nlob = p.nlobatto, K = p.K;
     const int R = 16 + nlob - 1;
-    const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     double *red = sh, *ring = sh + (size_t)2 * np * nw + (size_t)wv * R * 64;
     const int tile = (int)blockIdx.x * nw + wv;
     const bool wave_live = tile < ntile;
     const int tl_ = wave_live ? tile : ntile - 1;     // (a wave past the last tile repeats it with zero weights: barriers stay uniform)
-    const int64_t j = (int64_t)tl_ * 64 + lane;
-    const bool live = wave_live && j < nnu;
-    const int64_t jj = j < nnu ? j : nnu - 1;
-    const double v = nu[jj];
-    const double w = live ? wts[jj] : 0.0;
-    const double fS = S_toa ? S_toa[jj] : 0.0;
-    const double fa = albedo ? albedo[jj] : 0.0;
+    const RtLane L = rt_lane(tl_, wave_live, nnu, nu, wts, S_toa, albedo);
+    const int lane = L.lane;
+    const int64_t jj = L.jj;
+    const double v = L.v;
     const double c = p.cos_ts;
     const int lr = lane & 15, lq = lane >> 4;
     int chunk_next = 0;                // first node state not yet in the ring
@@ -4135,88 +4061,42 @@ __device__ __forceinline__ void flux_chunk_body(const RtParams &p, const double 
 #pragma unroll
     for (int k = 0; k < NS; k++) I[k] = 0.0;
     load_chunk();
-    double b1 = p.C * (sg(0) / muk[0]);  // beta at node 0, discretized.jl:150
-    double Ms = c * fS;                   // M-[1] = c*fS(nu), discretized.jl:299
+    double b1 = node_beta(p.C, sg(0), muk[0]);
+    double Ms = c * L.fS;                 // M-[1] = c*fS(nu), discretized.jl:299
     double Md = Ms;
     double Bprev = planck(v, Tlev[0]);
-    {
-        const double r = wave_sum(w * Md);
-        if (lane == 0) red[(np + 0) * nw + wv] = r;
-        if (Mdn && live) Mdn[j] = Md;
-    }
+    level_out(L, Md, &red[(np + 0) * nw + wv], Mdn, 0, nnu);
     for (int i = 0; i < nl; i++) {
         const int ke = (i + 1) * (nlob - 1);
         while (ke >= chunk_next) load_chunk();      // (wave-uniform)
         const double dP = P[i + 1] - P[i];
-        double ti = (dP * p.ws[0]) * b1;
-        for (int n = 1; n < nlob - 1; n++) {
-            const int k = i * (nlob - 1) + n;
-            ti += (dP * p.ws[n]) * (p.C * (sg(k) / muk[k]));
-        }
-        const double bn = p.C * (sg(ke) / muk[ke]);
-        ti += (dP * p.ws[nlob - 1]) * bn;
-        b1 = bn;
-        const double t = ti < 1e-6 ? 1e-6 : ti;  // floor, discretized.jl:147,174
-        if (live) tau[(size_t)i * nnu + j] = t;
+        const double t = layer_depth(p, muk, dP, i * (nlob - 1), b1, [&] { return b1 = node_beta(p.C, sg(ke), muk[ke]); }, sg);
+        if (L.live) tau[(size_t)i * nnu + L.j] = t;
         const double Bnext = planck(v, Tlev[i + 1]);
-        Md = 0.0;
-        const double it = 1.0 / t;
-#pragma unroll
-        for (int k = 0; k < NS; k++) {
-            const double tk = t * p.m[k];
-            const double tr = exp_rt(-tk);
-            const double Be = layerplanck_inv(Bprev, Bnext, it * p.im[k], tr);
-            I[k] = I[k] * tr + Be;
-            Md += p.W[k] * I[k];
-        }
+        Md = sweep_step<NS, TR_EXP>(p, t, 1.0 / t, Bprev, Bnext, I, nullptr, nullptr);
         if (S_toa) Ms *= exp(-t / c);   // (wave-uniform; without a stellar beam Ms stays 0)
         Md += Ms;
         Bprev = Bnext;
-        const double r = wave_sum(w * Md);
-        if (lane == 0) red[(np + i + 1) * nw + wv] = r;
-        if (Mdn && live) Mdn[(size_t)(i + 1) * nnu + j] = Md;
+        level_out(L, Md, &red[(np + i + 1) * nw + wv], Mdn, i + 1, nnu);
     }
     {
-        // surface: Lambertian reflection + Planck emission, discretized.jl:309-310
-        const double Is = Md * fa / kPi + Bprev;
-        double Mu = Is * kPi;
-        {
-            const double r = wave_sum(w * Mu);
-            if (lane == 0) red[(np - 1) * nw + wv] = r;
-            if (Mup && live) Mup[(size_t)(np - 1) * nnu + j] = Mu;
-        }
+        const double Is = surface_intensity(Md, L.fa, Bprev);
+        level_out(L, Is * kPi, &red[(np - 1) * nw + wv], Mup, np - 1, nnu);
 #pragma unroll
         for (int k = 0; k < NS; k++) I[k] = Is;
         double Bhi = Bprev;  // B at level i+1
-        double t_next = live ? tau[(size_t)(nl - 1) * nnu + j] : 1.0;      // (this lane's own store, same address: program order)
+        double t_next = L.live ? tau[(size_t)(nl - 1) * nnu + L.j] : 1.0;      // (this lane's own store, same address: program order)
         for (int i = nl - 1; i >= 0; i--) {
             const double t = t_next;
-            if (i > 0) t_next = live ? tau[(size_t)(i - 1) * nnu + j] : 1.0;   // one layer ahead
+            if (i > 0) t_next = L.live ? tau[(size_t)(i - 1) * nnu + L.j] : 1.0;   // one layer ahead
             const double Blo = planck(v, Tlev[i]);
-            Mu = 0.0;
-            const double it = 1.0 / t;
-#pragma unroll
-            for (int k = 0; k < NS; k++) {
-                const double tk = t * p.m[k];
-                const double tr = exp_rt(-tk);
-                const double Be = layerplanck_inv(Bhi, Blo, it * p.im[k], tr);
-                I[k] = I[k] * tr + Be;
-                Mu += p.W[k] * I[k];
-            }
+            const double Mu = sweep_step<NS, TR_EXP>(p, t, 1.0 / t, Bhi, Blo, I, nullptr, nullptr);
             Bhi = Blo;
-            const double r = wave_sum(w * Mu);
-            if (lane == 0) red[i * nw + wv] = r;
-            if (Mup && live) Mup[(size_t)i * nnu + j] = Mu;
+            level_out(L, Mu, &red[i * nw + wv], Mup, i, nnu);
         }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < 2 * np; e += blockDim.x) {
-        const double *q = red + e * nw;
-        double t = q[0];
-        for (int x = 1; x < nw; x++) t += q[x];
-        if (f.ticket) flux_store_dev(&partial[(size_t)blockIdx.x * 2 * np + e], t);
-        else partial[(size_t)blockIdx.x * 2 * np + e] = t;
-    }
+    block_partial_waves(red, nw, np, partial, f.ticket != nullptr);
     if (f.ticket) flux_last_block_reduce(f, partial, (int)gridDim.x, 2 * np);
 }
 

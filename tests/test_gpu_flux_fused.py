@@ -2,7 +2,7 @@
 and adds the block partials itself -- fluxes.jl:270-277 does depth and flux of a wavenumber in one loop body -- against the separate
 kernels (k_cheb_apply_mfma, k_cia, k_fold, k_rt / k_rt_streams, k_freduce: cs_set_tuning key 15 = 1) and against the oracle.
 
-k_flux_streams and k_flux_chunk run the separate kernels' operations in the same order, so optical depths and monochromatic fluxes of
+k_flux_chunk runs the separate kernels' operations in the same order, so optical depths and monochromatic fluxes of
 line-by-line columns must come out BITWISE equal; band fluxes differ by the order in which block partials are added (1e-15), CIA terms
 by the order of the bilinear interpolation (1e-14 of the CIA term).  k_flux_scan (the default on short grids) walks the layers in chunks:
 optical depths bitwise, intensities to a few units in the last place (the intensity entering a chunk is formed as A I + B instead of

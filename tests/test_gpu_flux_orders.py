@@ -8,7 +8,7 @@ compares with the oracle at the suite's tolerances (sigma and tau 1e-11 relative
 conftest.source_rounding_bound, F+- 1e-11 of max F+; columns with a CIA pair 1e-10, as test_gpu_flux_fused) and with a second form:
 bitwise where an existing test documents identical results, else test_gpu_merge._close(..., 5e-13, 1e-12).  Forms are forced only by the
 existing cs_set_tuning keys (5, 15 and its bits 2, 8, 2048).  Grid-size rules are taken from their formulas in cs_api.hip (rt_geometry,
-flux_form, launch_flux_ns), so a moved threshold fails here instead of leaving a form unrun.
+flux_form, launch_flux), so a moved threshold fails here instead of leaving a form unrun.
 
 Inputs: HITRAN CO2 fixture line by line, a gray term, a stellar beam (theta_s = 0.6), an albedo function; a CIA pair (CO2-CO2) in part
 of the cases; 2577-point grids (41 tiles, a last tile of 17 points) unless a rule needs another.
@@ -38,7 +38,7 @@ of the cases; 2577-point grids (41 tiles, a last tile of 17 points) unless a rul
   with CS_EINVAL by cs_column_setup, cs_fluxes_discretized and cs_fluxes_discretized_members (test_orders_outside_the_abi_refused).
 
 Instances that no input reaches: k_flux_scan<NS, 5> for NS 7, 8 and k_flux_scan / k_rt_streams for NS 1, 9..16 are not instantiated
-(`if constexpr` in launch_flux_ns / launch_rt_ns); flux_form returns 3 and rt_geometry sets `streams` only for 2 <= NS <= 8, which
+(`if constexpr` in launch_flux / launch_rt); flux_form returns 3 and rt_geometry sets `streams` only for 2 <= NS <= 8, which
 test_stream_sweep asserts for every NS outside that range (those branches would launch nothing).
 """
 import functools
@@ -105,7 +105,7 @@ def _scan_sh(np_, nlob, ns):
     return (_K(np_, nlob) * 64 + (2 * np_ - 1) * 64 + 2 * (ns + 1) * 64 + 2 * np_) * 8
 
 
-def _scan_per(np_):                              # launch_flux_ns: layers per wave
+def _scan_per(np_):                              # launch_flux: layers per wave
     nl = np_ - 1
     return -(-nl // _scan_nw(nl))
 
