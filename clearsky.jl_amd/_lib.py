@@ -88,6 +88,8 @@ SIGNATURES = {
     "cs_column_work": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "cs_interp_plan": (C.c_int, [C.c_int64, _dp, C.c_double, _ip]),
     "cs_phco2_plan": (C.c_int, [C.c_int64, _dp, C.c_double, C.c_int, _ip, _ip, _ip]),
+    "cs_phco2_plan_ctx": (C.c_int, [_vp, C.c_int64, _dp, C.c_double, C.c_int, C.c_int, _ip, _ip, _ip]),
+    "cs_phco2_wide_regions": (C.c_int, [C.c_int, _dp, _dp, C.c_double]),
     "cs_column_batch": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "cs_shape_points": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int64, _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_int64]),
     "cs_column_sigma_run": (C.c_int, [_vp, _vp]),

@@ -218,6 +218,17 @@ def phco2_plan(nu, cut=500.0):
     return [(sz[i], nd[i], tuple(r + 1 for r in range(3) if (rg[i] >> r) & 1)) for i in range(n)]
 
 
+def phco2_wide_regions(T, gamma_bound, cut=500.0):
+    """The chi-regions (a tuple out of (1, 2, 3)) that states of temperatures T and Lorentz-width bounds gamma_bound [cm^-1] keep out of
+    the PHCO2 levels of a launch (cs_phco2_wide_regions).  Host only."""
+    T, g = as_f64(np.atleast_1d(T)), as_f64(np.atleast_1d(gamma_bound))
+    assert len(T) == len(g)
+    m = lib().cs_phco2_wide_regions(len(T), dptr(T), dptr(g), float(cut))
+    if m < 0:
+        check(m)
+    return tuple(r + 1 for r in range(3) if (m >> r) & 1)
+
+
 class Context:
     """One HIP context (cs_ctx) = one device + stream + resident gas tables.  Not re-entrant."""
 
@@ -258,6 +269,15 @@ class Context:
     def set_interp_plan(self, first_level: int = -1, size_min: int = 128, size_max: int = 2048):
         """Tuning: first interval level every gas uses (-1 = by line density) and the range of interval sizes considered."""
         check(lib().cs_set_interp_plan(self._h, int(first_level), int(size_min), int(size_max)))
+
+    def phco2_plan(self, nu, cut=500.0, drop=()):
+        """phco2_plan under this context's settings, with the regions of `drop` (out of (1, 2, 3)) kept out of every level."""
+        nu = as_f64(nu)
+        sz, nd, rg = (C.c_int * 16)(), (C.c_int * 16)(), (C.c_int * 16)()
+        n = lib().cs_phco2_plan_ctx(self._h, nu.size, dptr(nu), float(cut), sum(1 << (r - 1) for r in drop), 16, sz, nd, rg)
+        if n < 0:
+            check(n)
+        return [(sz[i], nd[i], tuple(r + 1 for r in range(3) if (rg[i] >> r) & 1)) for i in range(n)]
 
     def set_matrix_cores(self, on=True):
         """Separable far-wing node sums on the matrix cores: True/1 (default) where the grid is long enough to pay, 2 always,

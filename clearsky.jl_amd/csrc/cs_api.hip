@@ -255,6 +255,7 @@ struct GroupWindows {
 struct GroupStates {
     DevBuf conc, Pp;          // [nmem][N] concentration and partial pressure of every member (conc: groups of a column only)
     DevBuf gmax;              // [N] max Lorentz width over the members (gamma_bound; Voigt fast path)
+    std::vector<double> h_T, h_gmax;   // host copies of T and gmax [N] (ph_wide_regions: which chi-regions these states let PHCO2 interpolate)
     DevBuf lrt, qref;         // state_tables(): [N], [N][niso]
 };
 
@@ -320,12 +321,15 @@ struct Column {
     hipStream_t last_stream = nullptr;   // the stream that run was enqueued on (cs_column_fetch waits for it, not for the whole device)
     // cs_set_tuning key 4: the step as ONE hipGraph launch (captured on the second run after a change, replayed from the third on):
     // kernel arguments are device addresses that stay put between cs_column_update_state calls, so only what changes launch
-    // geometry or pointers (setup, tables, CIA pairs, accelerated absorber, spectra switched on or off) drops the graph
+    // geometry or pointers (setup, tables, CIA pairs, accelerated absorber, spectra switched on or off) drops the graph -- and, for a
+    // PHCO2 group, new states that change which chi-regions its levels carry (ph_wide_regions: cs_column_update_state compares), or any
+    // rebuild of the context's PHCO2 levels since the capture (another grid, cut-off or region mask: graph_ph_builds)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int runs_since_change = 0;
     bool graph_near_live = false, graph_sigma_partial = false;   // what the captured run left in near_live / sigma_partial / launches: a replay leaves the same
     int graph_launches = 0;
+    uint64_t graph_ph_builds = 0;   // PhScratch::builds when the step was captured
     std::vector<ColTab> tab;
     std::vector<ColCia> cia;
     ColAccel accel;
@@ -370,13 +374,15 @@ struct PhScratch {
     uint64_t grid_id = 0;
     double lev_span[8] = {};   // widest interval of 8192 >> i points on this grid (ph_set_grid)
     int force64 = 0;           // cs_set_tuning key 10: 64 nodes for every interval (bit 0), tiles as 64-point intervals too (bit 1)
+    uint64_t builds = 0;       // how often ph_interp_ready has (re)built the levels: a captured step holds the layout of one build
+    int drop = 0;              // regions (bit r = region r + 1) the states of the coming launch keep out of the levels (ph_wide_regions)
     // interval sizes in use (descending) and the virtual levels on them (PhVLevels); nodes [sum nI x nc], Cm[v] [nI][nc][itv]
     struct Grid {
         PhLevels lv; PhVLevels vl; PhFine fine;
         int nnodes = 0, nslots = 0;
         DevBuf nodes, Cm[CS_MAX_ALEVEL];
     } grid;
-    uint64_t built_id = 0; int64_t built_nnu = 0; double built_cut = 0.0, built_margin = 0.0; int built_min = 0, built_max = 0, built_force = 0;
+    uint64_t built_id = 0; int64_t built_nnu = 0; double built_cut = 0.0, built_margin = 0.0; int built_min = 0, built_max = 0, built_force = 0, built_drop = 0;
 };
 
 // what cs_fluxes_discretized_multi keeps between calls (in its first context)
@@ -1140,6 +1146,7 @@ static int ph_plan(PhScratch *ph, int64_t nnu, double cut)
         for (int r = 0; r < 3; r++) {
             const double dn = std::max(Dn[r], ph->margin * h);
             need[i][r] = 0;
+            if ((ph->drop >> r) & 1) continue;                                  // a state too wide for this region's interpolation (ph_wide_regions)
             if (!(Df[r] - dn - sz * dnu >= 0.05 * (Df[r] - Dn[r]))) continue;   // (next to) nothing to hold at this size
             const double x0 = 1.0 + std::max(Dn[r] / h, ph->margin), lr = std::log10(x0 + std::sqrt(x0 * x0 - 1.0));
             need[i][r] = (ph->force64 & 1) ? 64 : (15.0 * lr >= 18.0 ? 16 : (31.0 * lr >= 18.0 ? 32 : 64));
@@ -1199,13 +1206,39 @@ static int ph_plan(PhScratch *ph, int64_t nnu, double cut)
     g.vl.boff[nv] = g.nslots;
     return nv;
 }
-bool ph_interp_ready(PhScratch *ph, const double *dnu, int64_t nnu, double cut, int kn, hipStream_t s)
+// The node counts of ph_plan take the line centre, max(D_r, margin h) away, for the nearest singularity of a line's term.  The term's
+// denominator x^2 + (chi y)^2 vanishes where d = nu - nul = +-i gamma chi_r(d), chi_r(d) = exp(a_r - b_r d): |d| = gamma exp(a_r - b_r Re d)
+// and arg d = pi/2 - b_r Im d.  For a narrow line these are the Lorentzian's own poles, +-i gamma beside the centre; for a wide one the
+// phase b_r Im d turns them towards the real axis -- at 25 K and 3e6 Pa (gamma = 12 cm^-1, chi up to 4.5 since B1 < 0 below 143.6 K) one
+// sits 35 cm^-1 from the centre and 20 above the axis, over the region-2 set of a 2048-point interval, whose 32 nodes then leave 5e-12
+// (measured: tests/test_gpu_phco2_line.py).  With G_r = gamma max(e^(a_r), e^(a_r - 2 b_r D_far)) bounding |d| for 0 <= Re d <= 2 D_far
+// (the larger end of a monotone function), Re d = |d| sin(b_r Im d) <= G_r sin(min(|b_r| G_r, pi/2)): a region is interpolated only while
+// that reach stays below a tenth of its near distance D_r for every state of the launch (the 18 digits ph_plan asks for keep 16 with the
+// distance 10 % short); else k_phco2 sums its lines per point.  Returns the regions to drop (bit r).
+int ph_wide_regions(const double *T, const double *gmax, int64_t n, double cut)
+{
+    int drop = 0;
+    const double Dn[3] = {3.0, 30.0, 120.0}, Df[3] = {30.0, 120.0, cut};
+    for (int64_t k = 0; k < n; k++) {
+        const double B1 = 0.0888 - 0.16 * std::exp(-0.0041 * T[k]), B2 = 0.0526 * std::exp(-0.00152 * T[k]), B3 = 0.0232;
+        const double a[3] = {3.0 * B1, -27.0 * B1 + 30.0 * B2, -27.0 * B1 - 90.0 * B2 + 120.0 * B3}, b[3] = {B1, B2, B3};
+        for (int r = 0; r < 3; r++) {
+            const double G = gmax[k] * std::exp(std::max(a[r], a[r] - 2.0 * b[r] * Df[r]));
+            const double reach = G * std::sin(std::min(std::fabs(b[r]) * G, 1.5707963267948966));
+            if (!(reach <= 0.1 * Dn[r])) drop |= 1 << r;
+        }
+    }
+    return drop;
+}
+bool ph_interp_ready(PhScratch *ph, const double *dnu, int64_t nnu, double cut, int kn, hipStream_t s, int drop)
 {
     if (!ph->itp_on) return false;
+    ph->drop = drop;
     PhScratch::Grid &g = ph->grid;
     if (!(ph->built_id == ph->grid_id && ph->built_nnu == nnu && ph->built_cut == cut && ph->built_min == ph->itp_min &&
-          ph->built_max == ph->itp_max && ph->built_margin == ph->margin && ph->built_force == ph->force64)) {
+          ph->built_max == ph->itp_max && ph->built_margin == ph->margin && ph->built_force == ph->force64 && ph->built_drop == ph->drop)) {
         ph->built_id = 0;
+        ph->builds++;
         const int nv = ph_plan(ph, nnu, cut);
         if (nv > 0) {
             if (g.nodes.reserve((size_t)g.nnodes * sizeof(double)) != hipSuccess) return false;
@@ -1218,7 +1251,7 @@ bool ph_interp_ready(PhScratch *ph, const double *dnu, int64_t nnu, double cut, 
             if (hipGetLastError() != hipSuccess) return false;
         }
         ph->built_id = ph->grid_id; ph->built_nnu = nnu; ph->built_cut = cut; ph->built_min = ph->itp_min; ph->built_max = ph->itp_max;
-        ph->built_margin = ph->margin; ph->built_force = ph->force64;
+        ph->built_margin = ph->margin; ph->built_force = ph->force64; ph->built_drop = ph->drop;
     }
     if (g.vl.nv == 0) return false;
     if (ph->piw.reserve((size_t)g.lv.nItot * sizeof(PhIWin)) != hipSuccess) return false;
@@ -1303,6 +1336,7 @@ struct GasPass {
     int mstride = 0;                // members of a merged table: element (m, k) of Ppk / scale at m * mstride + k
     const double *lrt = nullptr, *qrefq = nullptr;   // state_tables(): [kn], [kn][niso]
     const double *gbound = nullptr; // [kn] largest Lorentz width (gamma_bound)
+    const double *h_Tk = nullptr, *h_gbound = nullptr;   // host copies of Tk and gbound (NULL: none kept -- PHCO2 then interpolates no region)
     // the grid and its windows
     const double *dnu = nullptr, *nu = nullptr;      // on the device, on the host
     int64_t nnu = 0;
@@ -1644,7 +1678,7 @@ static void line_sum_phco2(hipStream_t s, const GasPass &p, PrepArgs pa, unsigne
     IzParams P;
     memset(&P, 0, sizeof P);
     CS_LAUNCH(k_gas_setup, dim3(nb_prep + nb_zones), dim3(256), 0, s, nb_prep, nb_zones, pa, za, P, (IZone *)nullptr);
-    const bool use_itp = ph_interp_ready(p.ph, p.dnu, nnu, p.cut, kn, s);
+    const bool use_itp = ph_interp_ready(p.ph, p.dnu, nnu, p.cut, kn, s, p.h_Tk && p.h_gbound ? ph_wide_regions(p.h_Tk, p.h_gbound, kn, p.cut) : 7);
     const PhScratch::Grid &pg = p.ph->grid;
     PhArgs pw;
     pw.nu = p.dnu; pw.nul = G.nu.as<double>(); pw.nnu = nnu; pw.ntile = nt64; pw.J0 = (int32_t)jlo; pw.J1 = (int32_t)jhi; pw.cut = p.cut;
@@ -2273,6 +2307,8 @@ static int upload_group_states(hipStream_t s, GroupStates &st, const GasTable &G
             for (int64_t k = 0; k < N; k++) gb[k] = std::max(gb[k], gm[k]);
     }
     state_tables(G, (int)N, T, lrt, qr);
+    st.h_T.assign(T, T + N);
+    st.h_gmax = gb;
     int rc;
     if ((rc = upload(st.Pp, pp, (size_t)nmem * N, s)) || (rc = upload(st.gmax, gb.data(), N, s)) || (rc = upload(st.lrt, lrt.data(), lrt.size(), s)) ||
         (rc = upload(st.qref, qr.data(), qr.size(), s)))
@@ -2303,6 +2339,7 @@ static int column_group_states(cs_ctx *ctx, const ColGas &cg, GroupStates &st, i
 static void pass_states(GasPass &p, const GroupStates &st, int64_t k0)   // states k0 .. of st (p.G is set; p.scale is the caller's: only columns have one)
 {
     p.Ppk = st.Pp.as<double>() + k0; p.gbound = st.gmax.as<double>() + k0;
+    p.h_Tk = st.h_T.data() + k0; p.h_gbound = st.h_gmax.data() + k0;
     p.lrt = st.lrt.as<double>() + k0; p.qrefq = st.qref.as<double>() + (size_t)k0 * p.G->niso;
 }
 
@@ -3099,8 +3136,13 @@ int cs_column_update_state(cs_ctx *ctx, const double *T_nodes, const double *mu_
     if ((rc = upload(c.Tk, Tk.data(), K, s)) || (rc = upload(c.muk, muk.data(), K, s)) ||
         (rc = upload(c.Tlev, T_levels, c.np, s)))
         return rc;
-    for (auto &cg : c.gas)
+    for (auto &cg : c.gas) {
+        // a PHCO2 group's levels carry the regions its states allow: a captured step holds the launches of one such choice
+        const bool ph = cg.shape == SH_PHCO2 && (int)cg.st.h_T.size() == K;
+        const int was = ph ? ph_wide_regions(cg.st.h_T.data(), cg.st.h_gmax.data(), K, cg.cut) : 0;
         if ((rc = column_group_states(ctx, cg, cg.st, K, Tk.data(), c.h_Pk.data(), conc, s))) return rc;
+        if (cg.shape == SH_PHCO2 && (!ph || was != ph_wide_regions(cg.st.h_T.data(), cg.st.h_gmax.data(), K, cg.cut))) drop_graph(c);
+    }
     HIPCHK(hipStreamSynchronize(s));
     if (!c.tab.empty()) {
         if (!conc_tab) return fail(CS_EINVAL, "the resident column has opacity tables: conc_tab is required");
@@ -3489,6 +3531,7 @@ int cs_column_run(cs_ctx *ctx, void *stream)
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     Column &c = ctx->col;
     if (!ctx->tune[4]) return run_impl(ctx, s, nullptr);
+    if (c.graph_exec && c.has_phco2 && ctx->ph.builds != c.graph_ph_builds) drop_graph(c);   // (the captured launches name another layout of the levels)
     if (c.graph_exec) {
         {   // (a replayed graph carries the kernel arguments of the slots' old contents: gas tables, opacity tables, knots)
             const int rc0 = column_current(ctx);
@@ -3518,6 +3561,7 @@ int cs_column_run(cs_ctx *ctx, void *stream)
     c.graph_near_live = c.near_live;   // (set by the captured run_impl)
     c.graph_sigma_partial = c.sigma_partial;
     c.graph_launches = c.launches;
+    c.graph_ph_builds = ctx->ph.builds;
     if (hipGraphInstantiate(&c.graph_exec, g, nullptr, nullptr, 0) != hipSuccess) { c.graph_exec = nullptr; drop_graph(c); return run_impl(ctx, s, nullptr); }
     HIPCHK(hipGraphLaunch(c.graph_exec, s));
     return CS_OK;
@@ -3714,6 +3758,28 @@ int cs_phco2_plan(int64_t nnu, const double *nu, double dnu_cut, int cap, int *i
         regions[v] = ph.grid.vl.rmask[v];
     }
     return nv;
+}
+
+// test hooks: the plan under a context's settings (interpolation on / off, size range, margin, cs_set_tuning key 10) with the regions of
+// `drop` (bit r = region r + 1) kept out, and the mask ph_wide_regions forms from K states (T, Lorentz-width bound)
+int cs_phco2_plan_ctx(cs_ctx *ctx, int64_t nnu, const double *nu, double dnu_cut, int drop, int cap, int *interval_sizes, int *nodes, int *regions)
+{
+    if (!ctx || !nu || nnu < 1 || !interval_sizes || !nodes || !regions || cap < 1 || drop < 0 || drop > 7) return fail(CS_EINVAL, "bad arguments");
+    PhScratch ph;
+    ph_set_grid(ctx, ph, nu, nnu, 1);
+    ph.drop = drop;
+    const int nv = ph.itp_on ? ph_plan(&ph, nnu, dnu_cut) : 0;
+    for (int v = 0; v < std::min(nv, cap); v++) {
+        interval_sizes[v] = ph.grid.lv.itv[ph.grid.vl.rl[v]];
+        nodes[v] = ph.grid.vl.nc[v];
+        regions[v] = ph.grid.vl.rmask[v];
+    }
+    return nv;
+}
+int cs_phco2_wide_regions(int K, const double *T, const double *gamma_bound, double dnu_cut)
+{
+    if (!T || !gamma_bound || K < 1) return fail(CS_EINVAL, "bad arguments");
+    return ph_wide_regions(T, gamma_bound, K, dnu_cut);
 }
 
 // ---- cs_column_work: one routine per kernel family.  Each counts one Voigt / Lorentz group of the column from the tables its last run

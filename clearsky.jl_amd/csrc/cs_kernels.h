@@ -2438,8 +2438,13 @@ __global__ __launch_bounds__(256) void k_phwin(unsigned nb_tiles, unsigned nb_it
     else wavewin_body(blockIdx.x - nb_tiles - nb_itv, wa);
 }
 
-// far-wing term with a per-lane Lorentz-width factor chi: y -> chi y.  FOUR: 4-term series (s >= 1e4), else 2-term + y-dependent u^2
-// terms (exact wherever k_zones' Q bounds put a line, which it derived for the unscaled, i.e. larger, y)
+// far-wing term with a per-lane Lorentz-width factor chi: y -> chi y.  FOUR: 4-term series (s >= 1e4), else the series through u^2 with
+// every y-dependent term of that order: P = 1 + 1.5 u + (3.75 - 2 y^2 - 15 t + 12 t^2) u^2, t = y^2 u.  What it drops is u^3 p3(t), |p3| <=
+// 13.125 on [0, 1]: below 1.4e-17 wherever s >= far_s = 1e6, whatever y is.  k_zones' Q bounds and two[r] of k_phco2_nodes are formed
+// with the UNSCALED y, and chi is not <= 1: B1(T) < 0 below 143.6 K, where chi rises to 4.5 at 30 cm^-1 (25 K) -- but they only choose
+// between two bodies that are both inside the 1e-15 budget for s >= 1e6, so the scaled y needs no bound of its own (measured on isolated
+// lines at 25 .. 143 K against 40-digit values: worst error / sharp bound 0.39 in this body, 0.36 in the 4-term one;
+// tests/test_gpu_phco2_line.py)
 template <bool PRED, bool FOUR>
 __device__ __forceinline__ double ph_term(const LineHot &h, double chi, double v, double cut, const FarK &c)
 {
@@ -2564,7 +2569,8 @@ __global__ __launch_bounds__(256) void k_phco2_nodes(const double *__restrict__ 
     const PhCoef pc = ph_coef(Tk[k]);
     const double dc = v - nu_c;
     // the two-term body does for a region whose every line has s >= max(cbrt(1.5e16 y^2), far_s) -- the bound behind Zone::Q0, Q1
-    // (zones_body), with the widest Doppler width of the window for x and the narrowest for y (chi <= 1 only shrinks y)
+    // (zones_body), with the widest Doppler width of the window for x and the narrowest for y.  The bound takes the unscaled y; chi > 1
+    // below 143.6 K (B1 < 0) makes chi y larger than it, which costs nothing: ph_term's two-term body holds for any y from s >= far_s on
     bool two[3];
     {
         const double vhi = nodes[n0], vlo = nodes[n0 + nc - 1];   // nodes run from the upper end down

@@ -186,6 +186,14 @@ int cs_interp_plan(int64_t nnu, const double *nu, double dnu_cut, int *interval_
  * away) and the chi-regions summed with that node count (bit 0: 3-30 cm^-1, bit 1: 30-120, bit 2: 120-cut-off).  Host only.  Returns
  * their number (at most 16; 0: every pair per point); the arrays hold `cap` entries. */
 int cs_phco2_plan(int64_t nnu, const double *nu, double dnu_cut, int cap, int *interval_sizes, int *nodes, int *regions);
+/* test hooks.  cs_phco2_plan_ctx: the same plan under the settings of `ctx` (cs_set_interp, cs_set_interp_plan, cs_set_tuning keys 3 and
+ * 10) with the chi-regions of `drop` (bit 0: 3-30 cm^-1, bit 1: 30-120, bit 2: 120-cut-off) kept out of every level.
+ * cs_phco2_wide_regions: the regions (same bits) that K states (temperature, upper bound of the Lorentz width in cm^-1) keep out of the
+ * levels of a launch -- a state so wide that a zero of the profile's denominator comes within a tenth of the region's near distance of
+ * the real axis.  A launch sums such a region per point. */
+int cs_phco2_plan_ctx(cs_ctx *ctx, int64_t nnu, const double *nu, double dnu_cut, int drop, int cap, int *interval_sizes, int *nodes,
+                      int *regions);
+int cs_phco2_wide_regions(int K, const double *T, const double *gamma_bound, double dnu_cut);
 
 /* Re w(x+iy) evaluated on the device for n points (host pointers): the kernels' Faddeeva, test hook for
  * Faddeyeva985.faddeyeva (call site line_shapes.jl:375). */

@@ -8,6 +8,9 @@ Restated from the reference's absorption/line_shapes.jl:
   alpha_doppler    alphadoppler (:144): (nul / c) sqrt(2 R T / mu)
   gamma_lorentz    gammalorentz (:255-257): (Tref / T)^na (gamma_a (P - Pp) + gamma_s Pp) / atm
   florentz, fdoppler, fvoigt   (:273, :160, :366-378) with w(z) = exp(-z^2) erfc(-i z)
+  chi (code 3)     XPHCO2 (:467-481): 1 below 3 cm^-1, exp(-B1 (d - 3)) on [3, 30), exp(-27 B1 - B2 (d - 30)) on [30, 120), exp(-27 B1 - 90 B2 -
+                   B3 (d - 120)) beyond, B1 = 0.0888 - 0.16 exp(-0.0041 T), B2 = 0.0526 exp(-0.00152 T), B3 = 0.0232; PHCO2 (:496-499) is
+                   fvoigt(d, alpha, chi gamma).  B1 < 0 below T = 143.6 K: chi > 1 there in region 1 and well into region 2
 and from include/clearsky_hip.h: code 4's pedestal f(cut), code 5's R(x, T) = x tanh(c2 x / 2T), S~ = S / R(nul, T) and mirror term
 f(nu + nul) where nu + nul <= cut, code 6 (both), and the CS_SHAPE_PSHIFT centre nul + delta P / P0 (S, alpha, gamma from the unshifted nul).
 c2 = 100 h c / k is the double the sources form (line_shapes.jl:5), sqrt(ln 2), sqrt(pi) are exact.
@@ -127,24 +130,69 @@ def widths(line, T, P, Pp):
     """(alpha, gamma) as doubles: what the probe offsets are multiples of"""
     return float(alpha_doppler(line, T)), float(gamma_lorentz(line, T, P, Pp))
 
+PH_D = (3.0, 30.0, 120.0)                # the region boundaries of XPHCO2 (:469, :473, :477)
+
+
+def ph_coefs(T):
+    """(B1, B2, B3) of XPHCO2 (:472, :476, :480) at 40 digits from the doubles the source writes"""
+    T_ = _m(T)
+    return _m(0.0888) - _m(0.16) * mp.exp(-_m(0.0041) * T_), _m(0.0526) * mp.exp(-_m(0.00152) * T_), _m(0.0232)
+
+
+def ph_coef_abs(T):
+    """per coefficient B_q: what U multiplies in the absolute error of a double evaluation of it, plus 3 |B_q| for the roundings of a
+    product B_q x m (the factor m, the product, the sum it joins) -- B1: the final subtraction rounds to U |B1| <= U 0.0888, the
+    subtrahend 0.16 e^(-0.0041 T) carries its argument's rounding (0.0041 T), the exponential's (1, 2 on the device: inside the count of 3) and the
+    product's; B2 likewise; B3 is the source's own double"""
+    B1, B2, B3 = (float(b) for b in ph_coefs(T))
+    e1 = math.exp(-0.0041 * T)
+    return (0.0888 + 0.16 * e1 * (3.0 + 0.0041 * T) + 3.0 * abs(B1), B2 * (3.0 + 0.00152 * T) + 3.0 * B2, 3.0 * B3)
+
+
+def chi_phco2(d, T, side=0):
+    """(chi, region 0..3, (m1, m2, m3)) of XPHCO2 at the distance d >= 0: chi = exp(-(B1 m1 + B2 m2 + B3 m3)); side = -1 / +1 evaluates
+    the formula of the region below / above where d sits exactly on a boundary (the continuity test), 0 the source's own choice"""
+    B = ph_coefs(T)
+    r = sum(1 for D in PH_D if d >= D)
+    if side < 0 and d in [_m(D) for D in PH_D]:
+        r -= 1
+    m = (mp.mpf(0),) * 3 if r == 0 else (d - 3, 0, 0) if r == 1 else (mp.mpf(27), d - 30, 0) if r == 2 else (mp.mpf(27), mp.mpf(90), d - 120)
+    chi = mp.mpf(1) if r == 0 else mp.exp(-sum(b * x for b, x in zip(B, m)))
+    return chi, r, tuple(float(x) for x in m)
+
+
+_PARAMS = {}
+
+
+def line_params(line, T, P, Pp, vvh=False):
+    """(S(T), Q condition, alpha, gamma) at 40 digits, kept per (line, state): every probe of a pair shares them"""
+    key = (line["nu"], line["S"], line["gamma_a"], line["gamma_s"], line["Epp"], line["na"], line["mu"], line["cheb"].tobytes(), T, P, Pp, vvh)
+    if key not in _PARAMS:
+        if len(_PARAMS) > 4096:
+            _PARAMS.clear()
+        _PARAMS[key] = intensity(line, T, vvh) + (alpha_doppler(line, T), gamma_lorentz(line, T, P, Pp))
+    return _PARAMS[key]
+
 
 def sigma_isolated(shape, nu, line, T, P, Pp, cut, C=1.0):
-    """C x the 40-digit cross-section of ONE line at the point nu under shape code `shape` (0, 1, 2, 4, 5, 6; | 16 = CS_SHAPE_PSHIFT on
-    0-2), as (float value, mpf value, info); info holds S, alpha, gamma (doubles) and the terms of lineparam_bound."""
+    """C x the 40-digit cross-section of ONE line at the point nu under shape code `shape` (0, 1, 2, 3, 4, 5, 6; | 16 = CS_SHAPE_PSHIFT
+    on 0-2), as (float value, mpf value, info); info holds S, alpha, gamma (doubles) and the terms of lineparam_bound.  Code 3 (PHCO2):
+    the profile is fvoigt(d, alpha, chi gamma), the cut-off inclusive as for code 0; info gains chi, region (0: |d| < 3, 1 .. 3), chi_m
+    (the multipliers m_q of B_q in chi's exponent), chi_abs (ph_coef_abs) and chi_rnd, the rounding term of chi as ONE exponential."""
     base, psh = shape & ~PSHIFT, bool(shape & PSHIFT)
-    assert base in (0, 1, 2, 4, 5, 6) and not (psh and base > 2)
+    assert base in (0, 1, 2, 3, 4, 5, 6) and not (psh and base > 2)
     vvh, ped = base in (5, 6), base in (4, 6)
     nul, v, D = _m(line["nu"]), _m(nu), _m(cut)
     s = _m(line["delta"]) * _m(P) / _m(C_.atm) if psh else mp.mpf(0)
     c = nul + s
     d = v - c
-    S, qcond = intensity(line, T, vvh)
-    al, ga = alpha_doppler(line, T), gamma_lorentz(line, T, P, Pp)
+    S, qcond, al, ga = line_params(line, T, P, Pp, vvh)
     x_T, x_r = C2 * line["nu"] / T, C2 * line["nu"] / C_.Tref
     pl = lambda x: float((1 + x) / mp.expm1(_m(x)))
     info = dict(shape=shape, S=float(S), alpha=float(al), gamma=float(ga), qcond=qcond, a_T=abs(C2 * line["Epp"] / T),
                 a_ref=abs(C2 * line["Epp"] / C_.Tref), planck_T=0.0 if vvh else pl(x_T), planck_ref=pl(x_r),
-                pow=abs(line["na"] * math.log(C_.Tref / T)), doppler=0.0, alpha7=0.0, centre=0.0, voigt=base in VOIGT_CODES, rel=1.0)
+                pow=abs(line["na"] * math.log(C_.Tref / T)), doppler=0.0, alpha7=0.0, centre=0.0, chi_rnd=0.0,
+                voigt=base in VOIGT_CODES or base == 3, rel=1.0)
     slope = mp.mpf(0)
     if base == 1:
         f = lambda t: florentz(t, ga)
@@ -154,6 +202,11 @@ def sigma_isolated(shape, nu, line, T, P, Pp, cut, C=1.0):
         slope = -2 * d / (al * al)
         info["doppler"] = float(2 * (d / al) ** 2)
         info["alpha7"] = float(7 * (d / al) ** 2)
+    elif base == 3:
+        chi, region, m = chi_phco2(abs(d), T)
+        f = lambda t: fvoigt(t, al, chi * ga)
+        cabs = ph_coef_abs(T)
+        info.update(chi=float(chi), region=region, chi_m=m, chi_abs=cabs, chi_rnd=chi_rounding(m, cabs, 1) if region else 0.0)
     else:
         f = lambda t: fvoigt(t, al, ga)
         if psh:
@@ -177,16 +230,24 @@ def sigma_isolated(shape, nu, line, T, P, Pp, cut, C=1.0):
     return float(val), val, info
 
 
+def chi_rounding(mult, cabs, nexp):
+    """code 3: what U multiplies in the relative rounding error of chi = a product of `nexp` exponentials whose arguments are sums of
+    B_q x (multipliers adding up to mult[q]): sum_q mult[q] x ph_coef_abs[q] -- the arguments' absolute errors, which are chi's relative
+    ones -- plus 2 per exponential (the device's exp: 2 ulp, module docstring).  The profile is at most linear in chi beyond 3 cm^-1
+    (|d ln K(x, chi y) / d ln chi| = |1 - 2 (chi y)^2 / s| <= 1 for the Lorentz-like wing, s >= 1e4), so the term enters with factor 1."""
+    return sum(a * b for a, b in zip(mult, cabs)) + 2.0 * nexp
+
+
 def model_terms(info):
     """the bracket of lineparam_bound without c0"""
     return (info["a_T"] + info["a_ref"] + info["planck_T"] + info["planck_ref"] + info["qcond"] + info["pow"] + info["doppler"]
-            + info["alpha7"] + info["centre"])
+            + info["alpha7"] + info["centre"] + info.get("chi_rnd", 0.0))
 
 
 def lineparam_bound(info, c0):
     """Relative error a double evaluation of one line's cross-section may have against sigma_isolated -- a first-order rounding model:
 
-        [ U (c0 + |a/T| + |a/Tref| + p(c2 nul/T) + p(c2 nul/Tref) + Qcond + |na ln(Tref/T)| + (2 + 7) (dnu/alpha)^2 + centre) + F ] / rel
+        [ U (c0 + |a/T| + |a/Tref| + p(c2 nul/T) + p(c2 nul/Tref) + Qcond + |na ln(Tref/T)| + (2 + 7) (dnu/alpha)^2 + chi + centre) + F ] / rel
 
       |a/T|, |a/Tref|     exp(a/T), a = -c2 Epp: a relative rounding of its argument moves it by |a/T| of itself; likewise at Tref
       p(x) = (1+x)/(e^x-1) 1 - exp(-x) at x = c2 nul / T: the argument's rounding (x e^-x / (1 - e^-x)) and the rounding of exp(-x) before the
@@ -198,12 +259,14 @@ def lineparam_bound(info, c0):
       7 (dnu/alpha)^2     Doppler only: the other roundings that reach that exponent e = dnu^2 / alpha^2.  alpha = (nul / c) sqrt(2 R T / mu) carries
                           3 U (the quotient nul / c; the product and the quotient under the root, halved by it; the root; the product), so
                           alpha^2 carries 2 x 3 + 1 = 7, dnu^2 one and the quotient one: 9 U e in all, of which the term above names 2
+      chi                 code 3 beyond 3 cm^-1: chi_rounding -- the scalar form (one exponential) here; tests/phco2_line_ref.py replaces it by
+                          the factorised form's (two exponentials about the grid's centre) where the fast path serves the probe
       centre              CS_SHAPE_PSHIFT with a non-zero shift s = delta P / P0 only: the device rounds delta P, the division and the sum,
                           |dc| <= U (|c| + 2 |s|) on the centre c = nul + s, while nu - c is exact here; times |d ln f / d nu| of the profile at
                           the probe (2 |d| / (d^2 + gamma^2), 2 |d| / alpha^2, or the Voigt profile's own slope)
       c0                  every rounding whose amplification is 1 (products, quotients, square root, the constants): measured, see the
                           module docstring
-      F                   Voigt codes: 2e-13, the Faddeeva allowance
+      F                   Voigt codes and code 3: 2e-13, the Faddeeva allowance
       rel                 codes 4 and 6: (profile - pedestal) / profile at the probe, 1 otherwise"""
     return (U * (c0 + model_terms(info)) + (FADDEEVA if info["voigt"] else 0.0)) / info["rel"]
 

@@ -31,7 +31,7 @@ def test_header_names():
     assert len(protos) == 48, len(protos)
     from clearsky_jl_amd import _lib
     assert (_lib.CS_CIA_EXTRAPOLATE, _lib.CS_CIA_SINGLES, _lib.CS_CIA_RADIATION) == (1, 2, 4)
-    assert len(_lib.SIGNATURES) == 60
+    assert len(_lib.SIGNATURES) == 62      # (+ cs_phco2_plan_ctx, cs_phco2_wide_regions: test hooks of clearsky_hip_dev.h)
 
 
 def _h2o(cs, nu, x=0.02):

@@ -129,7 +129,8 @@ def test_header_parses_every_symbol():
     pub = header_prototypes()
     lab = set(protos) - set(pub)
     assert lab == {"cs_set_tuning", "cs_set_interp_plan", "cs_set_matrix_cores", "cs_set_merge", "cs_column_profile", "cs_column_counts",
-                   "cs_column_info", "cs_column_work", "cs_interp_plan", "cs_phco2_plan", "cs_faddeeva_batch", "cs_devfn_batch"}, sorted(lab)
+                   "cs_column_info", "cs_column_work", "cs_interp_plan", "cs_phco2_plan", "cs_phco2_plan_ctx", "cs_phco2_wide_regions", "cs_faddeeva_batch",
+                   "cs_devfn_batch"}, sorted(lab)
     assert len(pub) <= 48, len(pub)
     assert protos["cs_fluxes_discretized"][1][:4] == ["void*", "int64", "double*", "int"]
     assert protos["cs_balanced_ranges"][1][4] == "double**"
