@@ -46,6 +46,8 @@ int fail(int code, const char *fmt, ...)
 thread_local int g_nlaunch = 0;   // kernel launches since the last reset (cs_column_run reports its count)
 #define CS_LAUNCH(...) do { g_nlaunch++; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
+// the three forms of the piece-table build (cs_kernels.h: sepzones_body, edgezones_body), by the values CS_WORK_TABLES documents
+enum { TABLES_NONE = 0, TABLES_MERGED = 1, TABLES_LANES16 = 2, TABLES_ONE_THREAD = 3 };   // no matrix-core kernels; blocks of k_gas_setup_mx; k_mxzones16; k_mxzones
 // How one Voigt / Lorentz launch group is run: everything that follows from sizes, settings and which buffers exist (voigt_plan, the one
 // place that holds the rules).  line_sum_voigt launches by it, a column keeps the plan of its last run and cs_column_work counts from it.
 // What depends on the state of the step -- the side streams, who clears the near-line plane, the fused apply -- is not in here.
@@ -56,8 +58,7 @@ struct VoigtPlan {
     int near_prio;              // wave priority of k_voigt_sub / k_voigt_near (0, 3)
     bool use_sep, use_edge;     // node sums (k_cheb_nodes_mx) / window ends (k_voigt_edge_mx) on the matrix cores
     bool core;                  // ... and the window cores on sub-tiles (k_voigt_sub)
-    bool mx_one_thread, mx_merged;   // the piece tables: k_mxzones, blocks of k_gas_setup_mx (neither: k_mxzones16)
-    int tables;                 // ... as cs_column_work reports them: 0 none, 1 k_gas_setup_mx, 2 k_mxzones16, 3 k_mxzones
+    int tables;                 // which kernel builds the piece tables (TABLES_*), as cs_column_work reports it
     bool nsplit4;               // k_cheb_nodes with four waves per (interval, state)
     int nsplit;                 // k_cheb_nodes_mx: intervals (from q0 on) the four waves of a block share ...
     unsigned nblk_mx;           // ... and its blocks
@@ -1442,13 +1443,13 @@ static VoigtPlan voigt_plan(const GasPass &p)
         const int64_t nsep = pl.use_sep ? (int64_t)(itp.nItot - pl.q0) * pl.ngrp : 0, nedge = pl.use_edge ? (int64_t)pl.nt64 * pl.ngrp : 0;
         // sixteen lanes per item shorten the chain where the items are few (a nu-shard: 21 -> 8 us; the bench column 27 -> 9); from
         // ~50 000 items on one thread per item has parallelism enough and sixteen times fewer threads (BASELINE configs[4]: 0.256 vs 0.276 ms)
-        pl.mx_one_thread = itp.mxzones_one_thread || nsep + nedge > 50000;   // (cs_set_tuning key 15 | 16: always)
+        const bool one_thread = itp.mxzones_one_thread || nsep + nedge > 50000;   // (cs_set_tuning key 15 | 16: always)
         // merged on short grids, where the head of the step is a chain of launch tails (1/8 of the bench column: 0.347 -> 0.340 ms);
         // at full size the second set of searches beside 300 MB of record stores costs more than the launch it saves (1.900 -> 1.908)
         // (cs_set_tuning key 21: 1 = never, 2 = always, A/B)
-        pl.mx_merged = !pl.mx_one_thread && itp.mxzones_merge != 1 && (itp.mxzones_merge == 2 || pl.nt64 < 1024);
-        pl.tables = pl.mx_merged ? 1 : (pl.mx_one_thread ? 3 : 2);
-        const int per = pl.mx_one_thread ? 256 : 16;   // items per block
+        const bool merged = !one_thread && itp.mxzones_merge != 1 && (itp.mxzones_merge == 2 || pl.nt64 < 1024);
+        pl.tables = one_thread ? TABLES_ONE_THREAD : (merged ? TABLES_MERGED : TABLES_LANES16);
+        const int per = one_thread ? 256 : 16;   // items per block
         pl.nb_sep = (unsigned)((nsep + per - 1) / per);
         pl.nb_edge = (unsigned)((nedge + per - 1) / per);
     }
@@ -1507,7 +1508,7 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
     EdgeArgs ea;
     memset(&sa, 0, sizeof sa);
     memset(&ea, 0, sizeof ea);
-    if (pl.tables) {
+    if (pl.tables != TABLES_NONE) {
         sa.nodes = itp.nodes; sa.nul = G.nu.as<double>(); sa.gbound = p.gbound; sa.Tk = p.Tk; sa.iz = itp.iz; sa.out = itp.sep;
         sa.nItot = itp.nItot; sa.q0 = pl.q0; sa.K = kn; sa.ngrp = pl.ngrp; sa.mu_min = G.mu_min; sa.cut = p.cut; sa.min_states = itp.mx_min_states;
         ea.nu = p.dnu; ea.nul = G.nu.as<double>(); ea.gbound = p.gbound; ea.Tk = p.Tk; ea.win = p.win; ea.zones = p.zones;
@@ -1517,7 +1518,7 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
         ea.core = pl.core ? 1 : 0;
         ea.core4 = itp.core4;
     }
-    if (pl.mx_merged)
+    if (pl.tables == TABLES_MERGED)
         CS_LAUNCH(p.vvh ? k_gas_setup_mx_vvh : k_gas_setup_mx, dim3(nb_prep + pl.nb_zones + pl.nb_iz + pl.nb_sep + pl.nb_edge), dim3(256), 0, s, nb_prep, pl.nb_zones, pl.nb_iz, pl.nb_sep, pa, za, P, itp.iz, sa, ea);
     else
         CS_LAUNCH(p.vvh ? k_gas_setup_vvh : k_gas_setup, dim3(nb_prep + pl.nb_zones + pl.nb_iz), dim3(256), 0, s, nb_prep, pl.nb_zones, pa, za, P, itp.iz);
@@ -1532,10 +1533,8 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
         const int q_acc = (p.defer && p.defer->ngas > 0 && p.defer->l0[0] < itp.nlev) ? itp.ioff[p.defer->l0[0]] : itp.nItot;
         const bool nsplit4 = pl.nsplit4;
         const dim3 gridn(nsplit4 ? (unsigned)kn * (unsigned)(itp.nItot - q0) : (unsigned)((kn + 3) / 4) * (unsigned)(itp.nItot - q0));
-        if (pl.tables && !pl.mx_merged) {
-            if (pl.mx_one_thread) CS_LAUNCH(k_mxzones, dim3(pl.nb_sep + pl.nb_edge), dim3(256), 0, s, pl.nb_sep, sa, ea);
-            else CS_LAUNCH(k_mxzones16, dim3(pl.nb_sep + pl.nb_edge), dim3(256), 0, s, pl.nb_sep, sa, ea);   // sixteen lanes per item
-        }
+        if (pl.tables == TABLES_ONE_THREAD) CS_LAUNCH(k_mxzones, dim3(pl.nb_sep + pl.nb_edge), dim3(256), 0, s, pl.nb_sep, sa, ea);
+        if (pl.tables == TABLES_LANES16) CS_LAUNCH(k_mxzones16, dim3(pl.nb_sep + pl.nb_edge), dim3(256), 0, s, pl.nb_sep, sa, ea);
         if (p.evg) (void)hipEventRecord(p.evg[0], s);
         const SepZone *sepz = use_sep ? itp.sep : nullptr;
         hipStream_t sm = s;   // main stream
@@ -3831,7 +3830,8 @@ static void work_nodes(const Column &c, const ColGas &g, const WorkTables &T, Wo
             if (pl.use_sep) {
                 const SepZone &s4 = T.sz[(size_t)(k >> 4) * nItot + q];
                 for (int p = 0; p < 4; p++) {   // of the group's piece, this state's part: the lines beyond its own series radius (k_cheb_nodes_mx's mask)
-                    const int pa = p < 2 ? s4.a[p] : std::max(s4.a[p], z.S1), pb = p < 2 ? std::min(s4.b[p], z.S0) : s4.b[p];
+                    const SepShare sh = sep_share(s4, p, z);
+                    const int pa = sh.a, pb = sh.b;
                     if (pb > pa) {
                         sa[p] = pa; sb[p] = pb; w.sepn += (int64_t)CS_NC * (pb - pa);
                         const int n3 = p < 2 ? std::max(0, std::min(s4.m[p], pb) - pa) : std::max(0, pb - std::max(s4.m[p], pa));
@@ -3968,13 +3968,9 @@ static void work_direct(const Column &c, const ColGas &g, const WorkTables &T, W
                 }
             }
             int64_t n = (win.W1 - win.W0) - (pm[1] - pm[0]) - (pm[3] - pm[2]) - (cc1 - cc0);
-            int sa0 = z.M0, sa1 = z.M0, sb0 = z.M1, sb1 = z.M1;
-            if (nlev > 0) {   // same clamps as k_voigt_far
-                const IZone &zi = T.iz[(size_t)k * nItot + c.cheb.ioff[nlev - 1] + (t >> pl.ishift)];
-                sa0 = std::min(std::max(zi.E0, W0), z.N0); sa1 = std::min(std::max(zi.Z0, sa0), z.N0);
-                sb0 = std::max(std::min(zi.Z1, W1), z.N1); sb1 = std::max(std::min(zi.E1, W1), sb0);
-                n -= (sa1 - sa0) + (sb1 - sb0);
-            }
+            const FarCovered fc = nlev > 0 ? far_covered(z, T.iz[(size_t)k * nItot + c.cheb.ioff[nlev - 1] + (t >> pl.ishift)], T.win[t]) : far_covered(z);
+            const int sa0 = fc.sa0, sa1 = fc.sa1, sb0 = fc.sb0, sb1 = fc.sb1;
+            n -= (sa1 - sa0) + (sb1 - sb0);   // (both empty without interpolated wings)
             w.direct += 64 * n;
             // the same segments k_voigt_far runs inside its three clip windows
             const int a = std::min(std::max(win.E0, W0), z.Q0), a1 = std::min(std::max(win.E0, z.Q0), z.M0);

@@ -586,6 +586,18 @@ __device__ __forceinline__ SepRadii sep_radii(double gamma, double alpha)
     return {kSepR3 * sqrt(g2 + kSepA3 * a2) * safe, kSepR4 * sqrt(g2 + kSepA4 * a2) * safe, kSepR8 * sqrt(g2 + kSepA8 * a2) * safe};
 }
 struct __attribute__((aligned(16))) IZone { int32_t E0, Q0, M0, Z0, Z1, M1, Q1, E1, P0, P1, P2, P3, S0, S1, pad0, pad1; };
+// the lines of a (state, tile) window the interpolated sum already covers, [sa0, sa1) left of the tile and [sb0, sb1) right of it: the
+// set [E0, Z0) U [Z1, E1) of the tile's interval of the smallest size (zi), clipped to the window w and kept out of the near zone --
+// without zi (no interpolated wings) both empty.  k_voigt_far skips them, the edge pieces lie between them and the near zone, and
+// cs_column_work counts by them
+struct FarCovered { int sa0, sa1, sb0, sb1; };
+__host__ __device__ __forceinline__ FarCovered far_covered(const Zone &z) { return {z.M0, z.M0, z.M1, z.M1}; }
+__host__ __device__ __forceinline__ FarCovered far_covered(const Zone &z, const IZone &zi, const WaveWin &w)
+{
+    const int sa0 = min(max(zi.E0, w.W0), z.N0), sa1 = min(max(zi.Z0, sa0), z.N0);
+    const int sb0 = max(min(zi.Z1, w.W1), z.N1), sb1 = max(min(zi.E1, w.W1), sb0);
+    return {sa0, sa1, sb0, sb1};
+}
 
 // nodes[T][m] = centre + h cos(pi m/63) and C[T][m][i] = l_m(nu_i): Lagrange basis of the extrema, barycentric form
 // nc <= CS_NC nodes per interval (64 everywhere on the Voigt path; 16 or 32 where the lines of a set are many half-widths away:
@@ -773,6 +785,13 @@ __global__ __launch_bounds__(256) void k_gas_setup_vvh(unsigned nb_prep, unsigne
 // the group's states -- are what this kernel then skips.
 struct __attribute__((aligned(16))) SepZone { int32_t a[4], b[4], m[4]; };   // piece p = [a[p], b[p]); empty: a = b.  m[p] splits it: the lines
                                                                               // farther than it (below m on the left, from m on the right) need 3 terms
+// of piece p of its group, the lines [a, b) the matrix cores sum for the state with interval zones z: those beyond its OWN series radius
+// (IZone::S0, S1 -- its coefficients are zero for the rest in k_cheb_nodes_mx).  Empty (b <= a): the whole piece stays on the vector unit
+struct SepShare { int a, b; };
+__host__ __device__ __forceinline__ SepShare sep_share(const SepZone &sz, int p, const IZone &z)
+{
+    return {p < 2 ? sz.a[p] : max(sz.a[p], z.S1), p < 2 ? min(sz.b[p], z.S0) : sz.b[p]};
+}
 // the same for the per-point sum (k_voigt_edge_mx), per (state group, 64-point tile): the window ends [W0, eL) and [eR, W1), and the
 // pieces [mL0, mL1), [mR0, mR1) between the interpolated sets and the near zone (empty: m.1 <= m.0)
 // mL3, mR3 split the middle pieces like SepZone::m; far3 bit 0 / 1: the left / right window end needs 3 terms only; bit 2: the
@@ -868,8 +887,8 @@ __global__ __launch_bounds__(256) void k_cheb_nodes(const double *__restrict__ n
         // rest of the piece stays here
 #pragma unroll
         for (int p = 0; p < 4; p++) {
-            const int pa = p < 2 ? sz.a[p] : max(sz.a[p], z.S1), pb = p < 2 ? min(sz.b[p], z.S0) : sz.b[p];
-            if (pb > pa) { sa[p] = pa; sb[p] = pb; }
+            const SepShare s = sep_share(sz, p, z);
+            if (s.b > s.a) { sa[p] = s.a; sb[p] = s.b; }
         }
     }
     double acc = node_sum_valu<MIXED, LOR>(v, hk, hf, gnul, z, sa, sb, cut, c, S > 1 ? wv : 0, S);
@@ -893,7 +912,7 @@ __global__ __launch_bounds__(256) void k_cheb_nodes(const double *__restrict__ n
 // (node, line) pair of a 16-node sub-tile, forms w .. w^4 (10 VALU instructions) and, as (state, line), the four coefficients
 // of its own record; 16 matrix instructions per 4 lines x 64 nodes x 16 states.  The loop runs at the matrix pipe's rate (0.92
 // of it in tools/ubench/sep_nodes.hip: 2.5x the scalar-load VALU loop for the same triples) and leaves the vector unit to the
-// kernels beside it.  Pieces from sepzones_body (k_mxzones).
+// kernels beside it.  Pieces from sepzones_body (the piece-table kernels: k_mxzones, k_mxzones16, k_gas_setup_mx).
 // four binary searches over the same sorted array side by side (one thread: their dependent loads overlap instead of queueing up):
 // r[q] = first index in [p, e) whose value is >= val[q] (q < 2: lower bound) resp. > val[q] (q >= 2: upper bound)
 __device__ __forceinline__ void search4(const double *__restrict__ a, const double (&val)[4], int p, int e, int (&r)[4])
@@ -1024,65 +1043,76 @@ struct SepArgs {
     int min_states;   // a line joins a group's matrix-core piece when at least this many of its states are beyond their series radius
     double mu_min, cut;
 };
-// per (state group, interval): the four pieces common to the group's states, clipped to the distance at which the 4-term series
-// holds for the widest line of the group (gbound: Lorentz width bound per state; Doppler width at the upper end of the window)
-__device__ __forceinline__ void sepzones_body(unsigned bid, const SepArgs &a)
+// ---- the piece tables (SepZone per (interval, state group), EdgeZone per (tile, state group)) in three stages, each written once:
+// state: what one state of the group contributes, from its zones (sep_state, edge_state); group: integer min / max and fmax over the
+// group's present states, plus the rank selection of the series bounds -- the order of the fold cannot change a bit; finishing: from
+// the group's values and one search4 to the record (sep_pieces, edge_pieces: every "shorter than 8 lines" rule, the 3-term split, the
+// core test and the lean bits live there and nowhere else).
+// The bodies are templates in W, the lanes per item (threadIdx.x = item * W + lane): lane l folds the states l, l + W, .. of the group
+// and redW finishes the fold across the item's lanes (the identity for W = 1); element j of the group is held by lane j % W in slot
+// j / W -- every index a compile-time constant (see the rank in sepzones_body).  W = 1 (k_mxzones): sixteen zone records read one after
+// the other and a 16 x 16 counting rank, ~3000 instructions in a chain, but sixteen times fewer threads -- for grids of many items.
+// W = 16 (k_mxzones16): every lane reads its own state's records, the rank is sixteen shuffled comparisons, a chain ten times shorter --
+// the launch sits at the head of every step, where a nu-shard of a few hundred tiles has six blocks of it to run (21 us of 0.39 ms).
+// RC: the per-state zones are computed here (izone_compute / zone_compute: the searches of k_gas_setup's zone blocks again, every lane its
+// own state's) instead of read -- then the piece tables need nothing k_gas_setup writes and are blocks of ITS launch (k_gas_setup_mx):
+// one launch and one dependent kernel boundary less at the head of every step (14 + 3 us on a 1/8 shard of the bench column)
+template <int W, class T, class Op> __device__ __forceinline__ T redW(T v, Op op)
 {
-    const int idx = bid * blockDim.x + threadIdx.x;
-    const int nq = a.nItot - a.q0;
-    if (idx >= nq * a.ngrp) return;
-    const int g = idx / nq, T = a.q0 + (idx - g * nq);
-    const double vhi = a.nodes[(size_t)T * CS_NC], vlo = a.nodes[(size_t)T * CS_NC + CS_NC - 1];   // nodes run from the upper end down
-    int lo[4] = {0, 0, 0, 0}, hi[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
-    double R3 = 0.0;
-    int E0 = 0, E1 = 0;
-    int s0v[16], s1v[16], ns = 0;
 #pragma unroll
-    for (int kk = 0; kk < 16; kk++) { s0v[kk] = -0x7fffffff; s1v[kk] = 0x7fffffff; }   // (a group's missing tail states never count)
+    for (int m = W >> 1; m > 0; m >>= 1) v = op(v, __shfl_xor(v, m, W));
+    return v;
+}
+template <int W> __device__ __forceinline__ int bcastW(int v, int lane) { return W == 1 ? v : __shfl(v, lane, W); }   // lane's v, to every lane of the item
+// the series radii of a state for the lines a column up to vhi can see: its Lorentz-width bound, the Doppler width at the upper end of the window
+__device__ __forceinline__ SepRadii state_radii(double vhi, double cut, double Tk, double mu_min, double gb)
+{
+    const double amax = ((vhi + cut) / kC) * sqrt(2.0 * kRgas * Tk) / sqrt(mu_min);
+    return sep_radii(gb, amax);
+}
+
+// SepZone, state stage: the four windows a piece must lie in ([lo[p], hi[p]): own set minus the parent's), the state's series bounds
+// and its 3-term radius.  As initialised: a state the group does not have -- it bounds nothing and never counts in the rank.
+// Group stage: the same record, lo / hi / r3 folded (sep_fold, sep_group), S0 / S1 chosen by rank (sepzones_body)
+struct SepState {
+    int lo[4] = {0, 0, 0, 0}, hi[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff}, S0 = -0x7fffffff, S1 = 0x7fffffff;
+    double r3 = 0.0;
+};
+__device__ __forceinline__ SepState sep_state(const IZone &z, double r3)
+{
+    SepState s;
+    s.lo[0] = z.E0; s.hi[0] = z.P0;
+    s.lo[1] = z.P1; s.hi[1] = z.Z0;
+    s.lo[2] = z.Z1; s.hi[2] = z.P2;
+    s.lo[3] = z.P3; s.hi[3] = z.E1;
+    s.S0 = z.S0; s.S1 = z.S1; s.r3 = r3;
+    return s;
+}
+__device__ __forceinline__ void sep_fold(SepState &g, const SepState &s)
+{
 #pragma unroll
-    for (int kk = 0; kk < 16; kk++) {
-        const int k = g * 16 + kk;
-        if (k >= a.K) continue;
-        const IZone z = a.iz[(size_t)k * a.nItot + T];
-        lo[0] = max(lo[0], z.E0); hi[0] = min(hi[0], z.P0);
-        lo[1] = max(lo[1], z.P1); hi[1] = min(hi[1], z.Z0);
-        lo[2] = max(lo[2], z.Z1); hi[2] = min(hi[2], z.P2);
-        lo[3] = max(lo[3], z.P3); hi[3] = min(hi[3], z.E1);
-        E0 = z.E0; E1 = z.E1;
-        s0v[kk] = z.S0; s1v[kk] = z.S1; ns = kk + 1;
-        const double amax = ((vhi + a.cut) / kC) * sqrt(2.0 * kRgas * a.Tk[k]) / sqrt(a.mu_min);
-        const double gb = a.gbound[k];
-        R3 = fmax(R3, sep_radii(gb, amax).r3);
+    for (int p = 0; p < 4; p++) { g.lo[p] = max(g.lo[p], s.lo[p]); g.hi[p] = min(g.hi[p], s.hi[p]); }
+    g.r3 = fmax(g.r3, s.r3);
+}
+template <int W> __device__ __forceinline__ void sep_group(SepState &g)
+{
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        g.lo[p] = redW<W>(g.lo[p], [](int x, int y) { return max(x, y); });
+        g.hi[p] = redW<W>(g.hi[p], [](int x, int y) { return min(x, y); });
     }
-    // A matrix step costs the same whether one or sixteen states of the group can use a line (the others' coefficients are zero:
-    // IZone::S0, S1), the vector unit per (state, line): a line joins the piece when at least min_states states are beyond their own
-    // series radius -- ~500 cycles per line and 64 nodes for the group against ~80 per state on the vector unit.  The states' bounds are
-    // ordered (sort them: 16 values): left pieces end at the min_states-th largest S0, right pieces start at the min_states-th smallest S1
-    const int rk = min(max(a.min_states, 1), ns) - 1;
-    int S0 = 0, S1 = 0;
-    // rank selection with every index static (the arrays stay in registers; a sort with run-time indices puts them in scratch memory,
-    // 0.027 -> 0.045 ms for this kernel): element i is the rk-th largest S0 when rk others precede it in descending order
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        int c0 = 0, c1 = 0;
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            c0 += (s0v[j] > s0v[i] || (s0v[j] == s0v[i] && j < i)) ? 1 : 0;
-            c1 += (s1v[j] < s1v[i] || (s1v[j] == s1v[i] && j < i)) ? 1 : 0;
-        }
-        if (c0 == rk) S0 = s0v[i];
-        if (c1 == rk) S1 = s1v[i];
-    }
-    S1 = max(S1, S0);
-    int sr[4];
-    {
-        const double sv[4] = {vlo - R3, vlo - R3, vhi + R3, vhi + R3};
-        search4(a.nul, sv, E0, E1, sr);
-    }
+    g.r3 = redW<W>(g.r3, [](double x, double y) { return fmax(x, y); });
+}
+// finishing stage: g = the group's windows and the series bounds S0, S1 of its rank; sr = search4 of {vlo - R3, vlo - R3, vhi + R3,
+// vhi + R3} over the lines of the window -- the four pieces common to the group's states, clipped to the distance at which the 4-term
+// series holds for min_states of them, and split where three terms do for the widest
+__device__ __forceinline__ SepZone sep_pieces(const SepState &g, const int (&sr)[4])
+{
+    const int S0 = g.S0, S1 = max(g.S1, S0);
     const int T0 = min(sr[1], S0), T1 = max(sr[3], S1);   // three terms do in [E0, T0) and [T1, E1): beyond the 3-term radius of the group's WIDEST state
     SepZone z;
     for (int p = 0; p < 4; p++) {
-        int pa = lo[p], pb = hi[p];
+        int pa = g.lo[p], pb = g.hi[p];
         if (p < 2) pb = min(pb, S0); else pa = max(pa, S1);
         if (pb - pa < 8) { pa = 0; pb = 0; }   // (too short to be worth a wave's trip)
         z.a[p] = pa; z.b[p] = pb;
@@ -1091,7 +1121,63 @@ __device__ __forceinline__ void sepzones_body(unsigned bid, const SepArgs &a)
         if (p >= 2 && pb - pm < 8) pm = pb;
         z.m[p] = pm;
     }
-    a.out[(size_t)g * a.nItot + T] = z;
+    return z;
+}
+template <int W, bool RC>
+__device__ __forceinline__ void sepzones_body(unsigned bid, const SepArgs &a, const IzParams *ip = nullptr, const ZoneArgs *za = nullptr)
+{
+    static_assert(W == 1 || W == 16, "lanes per item");
+    const int item = (int)(bid * (blockDim.x / W) + threadIdx.x / W), l = threadIdx.x % W;
+    const int nq = a.nItot - a.q0;
+    if (item >= nq * a.ngrp) return;            // (uniform over the lanes of an item)
+    const int g = item / nq, T = a.q0 + (item - g * nq);
+    const double vhi = a.nodes[(size_t)T * CS_NC], vlo = a.nodes[(size_t)T * CS_NC + CS_NC - 1];   // nodes run from the upper end down
+    const int ns = min(16, a.K - g * 16);       // states the group has
+    SepState G;                                 // (as initialised: no state yet)
+    int s0v[16 / W], s1v[16 / W], E0 = 0, E1 = 0;
+#pragma unroll
+    for (int j = 0; j < 16 / W; j++) {
+        const int kk = j * W + l, k = g * 16 + kk;
+        s0v[j] = G.S0; s1v[j] = G.S1;           // (a group's missing tail states never count)
+        if (kk >= ns) continue;
+        const IZone z = RC ? izone_compute(*ip, *za, k, T) : a.iz[(size_t)k * a.nItot + T];
+        const SepState s = sep_state(z, state_radii(vhi, a.cut, a.Tk[k], a.mu_min, a.gbound[k]).r3);
+        sep_fold(G, s);
+        s0v[j] = s.S0; s1v[j] = s.S1;
+        if (kk == ns - 1) { E0 = z.E0; E1 = z.E1; }
+    }
+    sep_group<W>(G);
+    E0 = bcastW<W>(E0, (ns - 1) % W); E1 = bcastW<W>(E1, (ns - 1) % W);   // the window of the group's LAST present state
+    // A matrix step costs the same whether one or sixteen states of the group can use a line (the others' coefficients are zero:
+    // IZone::S0, S1), the vector unit per (state, line): a line joins the piece when at least min_states states are beyond their own
+    // series radius -- ~500 cycles per line and 64 nodes for the group against ~80 per state on the vector unit.  The states' bounds are
+    // ordered: left pieces end at the min_states-th largest S0, right pieces start at the min_states-th smallest S1
+    const int rk = min(max(a.min_states, 1), ns) - 1;
+    // rank selection with every index static (the arrays stay in registers; a sort with run-time indices puts them in scratch memory,
+    // 0.027 -> 0.045 ms for the one-thread kernel): element i is the rk-th largest S0 when rk others precede it in descending order (ties:
+    // the lower state first).  The ranks are a permutation, so exactly one element of the group is chosen
+    int S0 = -0x7fffffff - 1, S1 = -0x7fffffff - 1;
+#pragma unroll
+    for (int ji = 0; ji < 16 / W; ji++) {
+        const int i = ji * W + l;
+        int c0 = 0, c1 = 0;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const int t0 = bcastW<W>(s0v[j / W], j % W), t1 = bcastW<W>(s1v[j / W], j % W);
+            c0 += (t0 > s0v[ji] || (t0 == s0v[ji] && j < i)) ? 1 : 0;
+            c1 += (t1 < s1v[ji] || (t1 == s1v[ji] && j < i)) ? 1 : 0;
+        }
+        if (c0 == rk) S0 = s0v[ji];
+        if (c1 == rk) S1 = s1v[ji];
+    }
+    G.S0 = redW<W>(S0, [](int x, int y) { return max(x, y); });
+    G.S1 = redW<W>(S1, [](int x, int y) { return max(x, y); });
+    int sr[4];
+    {
+        const double sv[4] = {vlo - G.r3, vlo - G.r3, vhi + G.r3, vhi + G.r3};
+        search4(a.nul, sv, E0, E1, sr);          // (every lane of the item: same loads, no divergence)
+    }
+    if (l == 0) a.out[(size_t)g * a.nItot + T] = sep_pieces(G, sr);
 }
 
 #define CS_MX_PITCH 66   // LDS row pitch (doubles) of the partial sums: rows of the four lane groups land on different banks
@@ -1456,6 +1542,7 @@ __global__ __launch_bounds__(256) CS_FAR_ATTR void k_voigt_far(const double *__r
         z = zones[(size_t)k * ntile + tile];
         const FarK c = load_fark();
         // lines already covered by the interpolated sum: [sa0,sa1) and [sb0,sb1) (empty when interpolation is off)
+        // (far_covered written out: through the helper the same instructions come out with other scalar register names)
         int sa0 = z.M0, sa1 = z.M0, sb0 = z.M1, sb1 = z.M1;
         if (iz) {
             const IZone zi = iz[(size_t)k * nI + (tile >> ishift)];
@@ -1639,49 +1726,46 @@ __device__ __forceinline__ bool sub_series_free(double vlo, double cut, double n
     const double xb = Rc * kSqLn2 / amin, yb = gb * kSqLn2 / amin;
     return __builtin_fma(xb, xb, yb * yb) < kSerS;
 }
-// per (state group, tile): the pieces common to the group's states -- the window ends left of every state's first interpolated or
-// near-zone line and right of the last; between every state's interpolated sets and near zone -- clipped to the distance at which
-// the 4-term series holds for the widest line of the group
-__device__ __forceinline__ void edgezones_body(unsigned bid, const EdgeArgs &a)
+// EdgeZone, state stage: the lines of the state's window the interpolated sum covers, its near zone [N0, N1) and its series radii
+struct EdgeState { FarCovered c; int N0, N1; SepRadii r; };
+__device__ __forceinline__ EdgeState edge_state(const Zone &z, const FarCovered &c, const SepRadii &r) { return {c, z.N0, z.N1, r}; }
+// group stage: the window ends left of every state's first covered line and right of the last ([W0, eL), [eR, W1)), the middle
+// pieces between every state's covered lines and near zone ([mL0, mL1), [mR0, mR1)), and the radii of the group's widest state
+struct EdgeGroup { int eL, eR, mL0, mL1, mR0, mR1; double R, R3, R8; };
+__device__ __forceinline__ EdgeGroup edge_group_none(const WaveWin &w) { return {w.W1, w.W0, w.W0, w.W1, w.W0, w.W1, 0.0, 0.0, 0.0}; }
+__device__ __forceinline__ void edge_fold(EdgeGroup &g, const EdgeState &s)
 {
-    const int idx = bid * blockDim.x + threadIdx.x;
-    if (idx >= a.ntile * a.ngrp) return;
-    const int g = idx / a.ntile, t = idx - g * a.ntile;
-    const int64_t i0 = (int64_t)t * 64, i1 = (i0 + 63 < a.nnu ? i0 + 63 : a.nnu - 1);
-    const double vlo = a.nu[i0], vhi = a.nu[i1];
-    const WaveWin w = a.win[t];
-    int eL = w.W1, eR = w.W0, mL0 = w.W0, mL1 = w.W1, mR0 = w.W0, mR1 = w.W1;
-    double R = 0.0, R3 = 0.0, R8 = 0.0;
-    for (int k = g * 16; k < min(g * 16 + 16, a.K); k++) {
-        const Zone z = a.zones[(size_t)k * a.ntile + t];
-        int sa0 = z.M0, sa1 = z.M0, sb0 = z.M1, sb1 = z.M1;   // (as k_voigt_far)
-        if (a.iz) {
-            const IZone zi = a.iz[(size_t)k * a.nI + (t >> a.ishift)];
-            sa0 = min(max(zi.E0, w.W0), z.N0); sa1 = min(max(zi.Z0, sa0), z.N0);
-            sb0 = max(min(zi.Z1, w.W1), z.N1); sb1 = max(min(zi.E1, w.W1), sb0);
-        }
-        eL = min(eL, sa0); eR = max(eR, sb1);
-        mL0 = max(mL0, sa1); mL1 = min(mL1, z.N0);
-        mR0 = max(mR0, z.N1); mR1 = min(mR1, sb0);
-        const double amax = ((vhi + a.cut) / kC) * sqrt(2.0 * kRgas * a.Tk[k]) / sqrt(a.mu_min);
-        const double gb = a.gbound[k];
-        const SepRadii sr = sep_radii(gb, amax);
-        R = fmax(R, sr.r4); R3 = fmax(R3, sr.r3); R8 = fmax(R8, sr.r8);
-    }
-    int sr[4];
-    {
-        const double sv[4] = {vlo - R, vlo - R3, vhi + R, vhi + R3};
-        search4(a.nul, sv, w.W0, w.W1, sr);
-    }
+    g.eL = min(g.eL, s.c.sa0); g.eR = max(g.eR, s.c.sb1);
+    g.mL0 = max(g.mL0, s.c.sa1); g.mL1 = min(g.mL1, s.N0);
+    g.mR0 = max(g.mR0, s.N1); g.mR1 = min(g.mR1, s.c.sb0);
+    g.R = fmax(g.R, s.r.r4); g.R3 = fmax(g.R3, s.r.r3); g.R8 = fmax(g.R8, s.r.r8);
+}
+template <int W> __device__ __forceinline__ void edge_group(EdgeGroup &g)
+{
+    const auto imax = [](int x, int y) { return max(x, y); };
+    const auto imin = [](int x, int y) { return min(x, y); };
+    const auto dmax = [](double x, double y) { return fmax(x, y); };
+    g.eL = redW<W>(g.eL, imin); g.eR = redW<W>(g.eR, imax);
+    g.mL0 = redW<W>(g.mL0, imax); g.mL1 = redW<W>(g.mL1, imin);
+    g.mR0 = redW<W>(g.mR0, imax); g.mR1 = redW<W>(g.mR1, imin);
+    g.R = redW<W>(g.R, dmax); g.R3 = redW<W>(g.R3, dmax); g.R8 = redW<W>(g.R8, dmax);
+}
+// finishing stage: sr = search4 of {vlo - R, vlo - R3, vhi + R, vhi + R3} over the window -- the group's pieces clipped to the distance
+// at which the 4-term series holds for its widest state.  full: all 64 points of the tile exist; lean(Rc): the group's sub_series_free
+// bits at core radius Rc, asked for only where the tile has a core (by every lane of an item alike: it may reduce across them)
+template <class Lean>
+__device__ __forceinline__ EdgeZone edge_pieces(const EdgeGroup &g, const int (&sr)[4], const WaveWin &w, double span, bool full, bool core,
+                                                double core4, Lean lean)
+{
     const int S0 = sr[0], S1 = max(sr[2], S0);            // the series holds in [W0, S0) and [S1, W1)
     const int T0 = min(sr[1], S0), T1 = max(sr[3], S1);   // ... with three terms in [W0, T0) and [T1, W1)
     EdgeZone e;
-    e.eL = max(min(eL, S0), w.W0);
-    e.eR = min(max(eR, S1), w.W1);
+    e.eL = max(min(g.eL, S0), w.W0);
+    e.eR = min(max(g.eR, S1), w.W1);
     if (e.eL - w.W0 < 8) e.eL = w.W0;   // (too short to be worth a wave's trip)
     if (w.W1 - e.eR < 8) e.eR = w.W1;
-    e.mL0 = mL0; e.mL1 = min(mL1, S0);
-    e.mR0 = max(mR0, S1); e.mR1 = mR1;
+    e.mL0 = g.mL0; e.mL1 = min(g.mL1, S0);
+    e.mR0 = max(g.mR0, S1); e.mR1 = g.mR1;
     if (e.mL1 - e.mL0 < 8 || e.mL0 < e.eL) e.mL0 = e.mL1 = 0;
     if (e.mR1 - e.mR0 < 8 || e.mR1 > e.eR) e.mR0 = e.mR1 = 0;
     e.far3 = (e.eL <= T0 ? 1 : 0) | (e.eR >= T1 ? 2 : 0);    // (a window end is 20 cm^-1 away: all of it or none)
@@ -1692,188 +1776,68 @@ __device__ __forceinline__ void edgezones_body(unsigned bid, const EdgeArgs &a)
     // core: from the end of the left middle piece (or of every state's interpolated set) to the start of the right one.  Worth
     // it where a sub-tile's neighbourhood (16 points + 2 R) is well below the tile's (64 points + 2 R), and only with all 16 points
     // of every sub-tile present (a ragged last tile keeps the tile-wide pass)
-    e.cL = e.mL1 > e.mL0 ? e.mL1 : mL0;
-    e.cR = e.mR1 > e.mR0 ? e.mR0 : mR1;
+    e.cL = e.mL1 > e.mL0 ? e.mL1 : g.mL0;
+    e.cR = e.mR1 > e.mR0 ? e.mR0 : g.mR1;
     // the pairs of the core inside the radius are k_voigt_sub's: the radius of the 4-term series where it is short against the tile
     // (the low-pressure groups), else that of the 8-term series -- twice the matrix instructions for the core's lines, a radius
     // 12 times shorter (the groups whose Lorentz widths set it)
-    const bool core8 = !(R < a.core4 * (vhi - vlo));
-    const double Rc = core8 ? R8 : R;
-    const bool core_ok = a.core && a.iz && i0 + 63 < a.nnu && mL0 <= mL1 && mR0 <= mR1 && e.cL <= mL1 && e.cR >= mR0 && e.cR > e.cL &&
-                         Rc < (core8 ? 0.3 : 0.75) * (vhi - vlo);   // (an 8-term core costs twice the matrix instructions: only where the sub-tiles then see few lines)
+    const bool core8 = !(g.R < core4 * span);
+    const double Rc = core8 ? g.R8 : g.R;
+    const bool core_ok = core && full && g.mL0 <= g.mL1 && g.mR0 <= g.mR1 && e.cL <= g.mL1 && e.cR >= g.mR0 && e.cR > e.cL &&
+                         Rc < (core8 ? 0.3 : 0.75) * span;   // (an 8-term core costs twice the matrix instructions: only where the sub-tiles then see few lines)
     if (!core_ok) e.cL = e.cR = 0;
     else if (core8) e.far3 |= 4;
     e.R = Rc;
-    // bit o: none of the states 8 o .. 8 o + 7 of the group can reach the series inside Rc -- k_voigt_sub's range-only pass
-    int lean = 0;
-    if (core_ok) {
-        lean = 3;
-        for (int k = g * 16; k < min(g * 16 + 16, a.K); k++)
-            if (!sub_series_free(vlo, a.cut, a.nul[w.W0 < w.W1 ? w.W0 : 0], w.W1 > w.W0, a.Tk[k], a.gbound[k], a.mu_max, Rc)) lean &= ~(1 << ((k >> 3) & 1));
-    }
-    e.lean = lean;
+    e.lean = core_ok ? lean(Rc) : 0;
     e.pad1 = 0.0;
-    a.out[idx] = e;
+    return e;
 }
-// k_sepzones and the edge zones in one launch (both need the zones of k_gas_setup)
-__global__ __launch_bounds__(256) void k_mxzones(unsigned nb_sep, SepArgs sa, EdgeArgs ea)
+template <int W, bool RC>
+__device__ __forceinline__ void edgezones_body(unsigned bid, const EdgeArgs &a, const IzParams *ip = nullptr, const ZoneArgs *za = nullptr)
 {
-    if (blockIdx.x < nb_sep) sepzones_body(blockIdx.x, sa);
-    else edgezones_body(blockIdx.x - nb_sep, ea);
-}
-// The same two tables with SIXTEEN lanes per item, lane = state of the group (k_mxzones16): the bodies above are one thread per item --
-// sixteen zone records read one after the other and a 16 x 16 counting rank, ~3000 instructions in a chain -- and their launch sits at the
-// head of every step, where a nu-shard of a few hundred tiles has six blocks of it to run (21 us of 0.39 ms).  Here every lane reads its
-// own state's records, the group's bounds are 16-lane reductions, the rank of a state's series bound is sixteen shuffled comparisons,
-// and lane 0 stores: the same integers, a chain ten times shorter.
-template <class T, class Op> __device__ __forceinline__ T red16(T v, Op op)
-{
-#pragma unroll
-    for (int m = 8; m > 0; m >>= 1) v = op(v, __shfl_xor(v, m, 16));
-    return v;
-}
-// RC: the per-state zones are computed here (izone_compute / zone_compute: the searches of k_gas_setup's zone blocks again, every lane its
-// own state's) instead of read -- then the piece tables need nothing k_gas_setup writes and are blocks of ITS launch (k_gas_setup_mx):
-// one launch and one dependent kernel boundary less at the head of every step (14 + 3 us on a 1/8 shard of the bench column)
-template <bool RC>
-__device__ __forceinline__ void sepzones_body16(unsigned bid, const SepArgs &a, const IzParams *ip = nullptr, const ZoneArgs *za = nullptr)
-{
-    const int item = (int)(bid * (blockDim.x >> 4) + (threadIdx.x >> 4)), kk = threadIdx.x & 15;
-    const int nq = a.nItot - a.q0;
-    if (item >= nq * a.ngrp) return;            // (uniform over the 16 lanes of an item)
-    const int g = item / nq, T = a.q0 + (item - g * nq);
-    const double vhi = a.nodes[(size_t)T * CS_NC], vlo = a.nodes[(size_t)T * CS_NC + CS_NC - 1];   // nodes run from the upper end down
-    const int k = g * 16 + kk;
-    const bool have = k < a.K;
-    IZone z = {};
-    if (have) z = RC ? izone_compute(*ip, *za, k, T) : a.iz[(size_t)k * a.nItot + T];
-    const auto imax = [](int x, int y) { return max(x, y); };
-    const auto imin = [](int x, int y) { return min(x, y); };
-    int lo[4], hi[4];
-    lo[0] = red16(have ? z.E0 : 0, imax); hi[0] = red16(have ? z.P0 : 0x7fffffff, imin);
-    lo[1] = red16(have ? z.P1 : 0, imax); hi[1] = red16(have ? z.Z0 : 0x7fffffff, imin);
-    lo[2] = red16(have ? z.Z1 : 0, imax); hi[2] = red16(have ? z.P2 : 0x7fffffff, imin);
-    lo[3] = red16(have ? z.P3 : 0, imax); hi[3] = red16(have ? z.E1 : 0x7fffffff, imin);
-    const int ns = min(16, a.K - g * 16);
-    const int E0 = __shfl(z.E0, ns - 1, 16), E1 = __shfl(z.E1, ns - 1, 16);      // (the last state's, as the one-thread body leaves them)
-    double R3 = 0.0;
-    if (have) {
-        const double amax = ((vhi + a.cut) / kC) * sqrt(2.0 * kRgas * a.Tk[k]) / sqrt(a.mu_min);
-        const double gb = a.gbound[k];
-        R3 = sep_radii(gb, amax).r3;
-    }
-    R3 = red16(R3, [](double x, double y) { return fmax(x, y); });
-    // rank of this state's series bounds among the group's (ties: the lower state first), as in the one-thread body
-    const int s0 = have ? z.S0 : -0x7fffffff, s1 = have ? z.S1 : 0x7fffffff;
-    int c0 = 0, c1 = 0;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int t0 = __shfl(s0, j, 16), t1 = __shfl(s1, j, 16);
-        c0 += (t0 > s0 || (t0 == s0 && j < kk)) ? 1 : 0;
-        c1 += (t1 < s1 || (t1 == s1 && j < kk)) ? 1 : 0;
-    }
-    const int rk = min(max(a.min_states, 1), ns) - 1;
-    const int S0 = red16(c0 == rk ? s0 : -0x7fffffff - 1, imax);
-    int S1 = red16(c1 == rk ? s1 : -0x7fffffff - 1, imax);
-    S1 = max(S1, S0);
-    int sr[4];
-    {
-        const double sv[4] = {vlo - R3, vlo - R3, vhi + R3, vhi + R3};
-        search4(a.nul, sv, E0, E1, sr);          // (every lane of the item: same loads, no divergence)
-    }
-    if (kk != 0) return;
-    const int T0 = min(sr[1], S0), T1 = max(sr[3], S1);
-    SepZone o;
-    for (int p = 0; p < 4; p++) {
-        int pa = lo[p], pb = hi[p];
-        if (p < 2) pb = min(pb, S0); else pa = max(pa, S1);
-        if (pb - pa < 8) { pa = 0; pb = 0; }
-        o.a[p] = pa; o.b[p] = pb;
-        int pm = p < 2 ? min(max(T0, pa), pb) : min(max(T1, pa), pb);
-        if (p < 2 && pm - pa < 8) pm = pa;
-        if (p >= 2 && pb - pm < 8) pm = pb;
-        o.m[p] = pm;
-    }
-    a.out[(size_t)g * a.nItot + T] = o;
-}
-template <bool RC>
-__device__ __forceinline__ void edgezones_body16(unsigned bid, const EdgeArgs &a, const IzParams *ip = nullptr, const ZoneArgs *za = nullptr)
-{
-    const int item = (int)(bid * (blockDim.x >> 4) + (threadIdx.x >> 4)), kk = threadIdx.x & 15;
-    if (item >= a.ntile * a.ngrp) return;
+    static_assert(W == 1 || W == 16, "lanes per item");
+    const int item = (int)(bid * (blockDim.x / W) + threadIdx.x / W), l = threadIdx.x % W;
+    if (item >= a.ntile * a.ngrp) return;       // (uniform over the lanes of an item)
     const int g = item / a.ntile, t = item - g * a.ntile;
     const int64_t i0 = (int64_t)t * 64, i1 = (i0 + 63 < a.nnu ? i0 + 63 : a.nnu - 1);
     const double vlo = a.nu[i0], vhi = a.nu[i1];
     const WaveWin w = a.win[t];
-    const int k = g * 16 + kk;
-    const bool have = k < a.K;
-    int eL = w.W1, eR = w.W0, mL0 = w.W0, mL1 = w.W1, mR0 = w.W0, mR1 = w.W1;
-    double R = 0.0, R3 = 0.0, R8 = 0.0;
-    if (have) {
+    const int ns = min(16, a.K - g * 16);       // states the group has
+    EdgeGroup G = edge_group_none(w);
+    for (int kk = l; kk < ns; kk += W) {        // (no rank here, so no static index: a loop for W = 1, one pass for W = 16)
+        const int k = g * 16 + kk;
         const Zone z = RC ? zone_compute(*za, k, t) : a.zones[(size_t)k * a.ntile + t];
-        int sa0 = z.M0, sa1 = z.M0, sb0 = z.M1, sb1 = z.M1;   // (as k_voigt_far)
-        if (a.iz) {
-            const IZone zi = RC ? izone_compute(*ip, *za, k, ip->ioff[ip->nlev - 1] + (t >> a.ishift)) : a.iz[(size_t)k * a.nI + (t >> a.ishift)];
-            sa0 = min(max(zi.E0, w.W0), z.N0); sa1 = min(max(zi.Z0, sa0), z.N0);
-            sb0 = max(min(zi.Z1, w.W1), z.N1); sb1 = max(min(zi.E1, w.W1), sb0);
-        }
-        eL = min(eL, sa0); eR = max(eR, sb1);
-        mL0 = max(mL0, sa1); mL1 = min(mL1, z.N0);
-        mR0 = max(mR0, z.N1); mR1 = min(mR1, sb0);
-        const double amax = ((vhi + a.cut) / kC) * sqrt(2.0 * kRgas * a.Tk[k]) / sqrt(a.mu_min);
-        const double gb = a.gbound[k];
-        const SepRadii sr = sep_radii(gb, amax);
-        R = sr.r4; R3 = sr.r3; R8 = sr.r8;
+        const FarCovered c = !a.iz ? far_covered(z)
+                             : far_covered(z, RC ? izone_compute(*ip, *za, k, ip->ioff[ip->nlev - 1] + (t >> a.ishift)) : a.iz[(size_t)k * a.nI + (t >> a.ishift)], w);
+        edge_fold(G, edge_state(z, c, state_radii(vhi, a.cut, a.Tk[k], a.mu_min, a.gbound[k])));
     }
-    const auto imax = [](int x, int y) { return max(x, y); };
-    const auto imin = [](int x, int y) { return min(x, y); };
-    const auto dmax = [](double x, double y) { return fmax(x, y); };
-    eL = red16(eL, imin); eR = red16(eR, imax);
-    mL0 = red16(mL0, imax); mL1 = red16(mL1, imin);
-    mR0 = red16(mR0, imax); mR1 = red16(mR1, imin);
-    R = red16(R, dmax); R3 = red16(R3, dmax); R8 = red16(R8, dmax);
+    edge_group<W>(G);
     int sr[4];
     {
-        const double sv[4] = {vlo - R, vlo - R3, vhi + R, vhi + R3};
+        const double sv[4] = {vlo - G.R, vlo - G.R3, vhi + G.R, vhi + G.R3};
         search4(a.nul, sv, w.W0, w.W1, sr);
     }
-    const bool core8 = !(R < a.core4 * (vhi - vlo));
-    const double Rc = core8 ? R8 : R;
-    // (every lane its own state against the group's radius; the octets that hold a state which can reach the series, OR-ed to lane 0)
-    const bool reach = have && !sub_series_free(vlo, a.cut, a.nul[w.W0 < w.W1 ? w.W0 : 0], w.W1 > w.W0, a.Tk[have ? k : 0], a.gbound[have ? k : 0], a.mu_max, Rc);
-    const int lean = 3 & ~red16(reach ? 1 << (kk >> 3) : 0, [](int x, int y) { return x | y; });
-    if (kk != 0) return;
-    const int S0 = sr[0], S1 = max(sr[2], S0);            // the series holds in [W0, S0) and [S1, W1)
-    const int T0 = min(sr[1], S0), T1 = max(sr[3], S1);   // ... with three terms in [W0, T0) and [T1, W1)
-    EdgeZone e;
-    e.eL = max(min(eL, S0), w.W0);
-    e.eR = min(max(eR, S1), w.W1);
-    if (e.eL - w.W0 < 8) e.eL = w.W0;   // (too short to be worth a wave's trip)
-    if (w.W1 - e.eR < 8) e.eR = w.W1;
-    e.mL0 = mL0; e.mL1 = min(mL1, S0);
-    e.mR0 = max(mR0, S1); e.mR1 = mR1;
-    if (e.mL1 - e.mL0 < 8 || e.mL0 < e.eL) e.mL0 = e.mL1 = 0;
-    if (e.mR1 - e.mR0 < 8 || e.mR1 > e.eR) e.mR0 = e.mR1 = 0;
-    e.far3 = (e.eL <= T0 ? 1 : 0) | (e.eR >= T1 ? 2 : 0);
-    e.mL3 = min(max(T0, e.mL0), e.mL1);
-    if (e.mL3 - e.mL0 < 8) e.mL3 = e.mL0;
-    e.mR3 = min(max(T1, e.mR0), e.mR1);
-    if (e.mR1 - e.mR3 < 8) e.mR3 = e.mR1;
-    e.cL = e.mL1 > e.mL0 ? e.mL1 : mL0;
-    e.cR = e.mR1 > e.mR0 ? e.mR0 : mR1;
-    const bool core_ok = a.core && a.iz && i0 + 63 < a.nnu && mL0 <= mL1 && mR0 <= mR1 && e.cL <= mL1 && e.cR >= mR0 && e.cR > e.cL &&
-                         Rc < (core8 ? 0.3 : 0.75) * (vhi - vlo);
-    if (!core_ok) e.cL = e.cR = 0;
-    else if (core8) e.far3 |= 4;
-    e.R = Rc;
-    e.lean = core_ok ? lean : 0;
-    e.pad1 = 0.0;
-    a.out[item] = e;
+    // bit o: none of the states 8 o .. 8 o + 7 of the group can reach the series inside Rc -- k_voigt_sub's range-only pass
+    const auto lean = [&](double Rc) {
+        int reach = 0;
+        for (int kk = l; kk < ns; kk += W)
+            if (!sub_series_free(vlo, a.cut, a.nul[w.W0 < w.W1 ? w.W0 : 0], w.W1 > w.W0, a.Tk[g * 16 + kk], a.gbound[g * 16 + kk], a.mu_max, Rc)) reach |= 1 << (kk >> 3);
+        return 3 & ~redW<W>(reach, [](int x, int y) { return x | y; });
+    };
+    const EdgeZone e = edge_pieces(G, sr, w, vhi - vlo, i0 + 63 < a.nnu, a.core && a.iz, a.core4, lean);
+    if (l == 0) a.out[item] = e;
 }
+// the two tables in one launch, one thread per item (both need the zones of k_gas_setup)
+__global__ __launch_bounds__(256) void k_mxzones(unsigned nb_sep, SepArgs sa, EdgeArgs ea)
+{
+    if (blockIdx.x < nb_sep) sepzones_body<1, false>(blockIdx.x, sa);
+    else edgezones_body<1, false>(blockIdx.x - nb_sep, ea);
+}
+// ... and with sixteen lanes per item, lane = state of the group
 __global__ __launch_bounds__(256) void k_mxzones16(unsigned nb_sep, SepArgs sa, EdgeArgs ea)
 {
-    if (blockIdx.x < nb_sep) sepzones_body16<false>(blockIdx.x, sa);
-    else edgezones_body16<false>(blockIdx.x - nb_sep, ea);
+    if (blockIdx.x < nb_sep) sepzones_body<16, false>(blockIdx.x, sa);
+    else edgezones_body<16, false>(blockIdx.x - nb_sep, ea);
 }
 // k_gas_setup and k_mxzones16 in ONE launch: zone blocks, interval-zone blocks, the piece tables of the matrix-core kernels (which
 // compute the zones they need themselves), record blocks
@@ -1889,8 +1853,8 @@ __device__ __forceinline__ void gas_setup_mx_body(unsigned nb_prep, unsigned nb_
     b -= nb_iz;
     const unsigned nb_mx = gridDim.x - nb_zones - nb_iz - nb_prep;
     if (b < nb_mx) {
-        if (b < nb_sep) sepzones_body16<true>(b, sa, &ip, &za);
-        else edgezones_body16<true>(b - nb_sep, ea, &ip, &za);
+        if (b < nb_sep) sepzones_body<16, true>(b, sa, &ip, &za);
+        else edgezones_body<16, true>(b - nb_sep, ea, &ip, &za);
         return;
     }
     prep_body<VVH>(b - nb_mx, pa);

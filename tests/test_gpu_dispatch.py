@@ -60,11 +60,11 @@ def _disp(r):
 
 
 @functools.lru_cache(maxsize=3)
-def _run(n, np_=NP_DEF, tune=(), first_level=-1):
+def _run(n, np_=NP_DEF, tune=(), first_level=-1, p_surf=1e5):
     """one column (synthetic H2O + CO2, Discretized(5, 2)) on an n-point grid with the given cs_set_tuning keys; every output"""
     cs = clearsky_jl_amd
     nu = _nu(n)
-    P = cs.pressuregrid(10.0, 1e5, np_)
+    P = cs.pressuregrid(10.0, p_surf, np_)
     T = W.earth_temperature(P)
     gases = (cs.DirectGas(W.lines("synthetic", "H2O"), W.fC_h2o, nu), cs.DirectGas(W.lines("synthetic", "CO2"), 400e-6, nu))
     ctx = cs.Context(0)
@@ -257,6 +257,61 @@ def test_piece_tables_one_thread_above_50000_items(O):
     f = _run(na - 1, np_, ((15, 16),), first_level=0)
     assert _disp(f)["tables"] == 3
     _same(f, rb, True)
+
+
+# the three builds of the matrix-core piece tables, each forced by its key: (tuning, Column.work()["dispatch"]["tables"])
+TABLE_FORMS = ((((21, 2),), 1), (((21, 1),), 2), (((15, 16),), 3))
+
+
+def _work_but_form(r):
+    """Column.work() without the two fields that may differ between the forms: which form ran, and the flux kernel's time stamps"""
+    w = dict(r["work"])
+    del w["flux_scan_ns"]
+    w["dispatch"] = {k: v for k, v in w["dispatch"].items() if k != "tables"}
+    return w
+
+
+@pytest.mark.parametrize("np_,p_surf,tiles,min_states", [(17, 5e3, 40, (None,)), (40, 1e5, 420, (None, 1, 16))], ids=["K17", "K40"])
+def test_piece_table_forms_same_tables(np_, p_surf, tiles, min_states):
+    """the piece tables as blocks of k_gas_setup_mx (key 21 = 2), by k_mxzones16 (key 21 = 1) and by k_mxzones (key 15 = 16) on one short
+    grid of whole tiles and a last tile of ONE point (the core test's "all 64 points present" clause decides there), with the matrix-core
+    kernels kept on it (key 1 = 1): bitwise equal outputs, and equal work counts -- cs_column_work counts from the tables it reads back, so
+    every piece bound of both tables enters them.  K = 17: a second state group of ONE state (its rank clamped to it); K = 40: a
+    half-filled second group (one octet of the lean bits has no state), also with key 8 (min_states) at 1 and at 16.  The counts that
+    must not be zero keep the comparison from being one between empty tables.
+
+    Grids.  K = 40: n = 64 * 419 + 1.  On 40 tiles (300 .. 320 cm^-1) no tile has a lean bit at any key 8 (sub_lean_evals 0 with
+    core_tile_states 624, matrix_evals_3term 17 465 344); lengthened in whole tiles the first bits come at 418 tiles (sub_lean_evals 0 at
+    417, 3584 at 418, 10 240 at 420: the Doppler widths grow with the wavenumber), so 420.
+    K = 17: n = 64 * 39 + 1, on levels from 10 Pa to 5e3 Pa instead of the file's 1e5 Pa.  A tile's core and the 3-term split go by the
+    group's WIDEST state (edge_pieces): a core needs its 8-term radius, 8.66 x its largest Lorentz width, below 0.3 x the tile's
+    0.504 cm^-1, so a width below 0.0175 cm^-1 -- pressures below some 1.5e4 Pa for the tables' widths of up to 0.1 cm^-1 / atm.  With 17
+    levels up to 1e5 Pa the first group's sixteenth state lies at 9.2e4 Pa and the second group is the surface state, so no tile of any
+    grid length has a core there (core_tile_states = matrix_evals_3term = 0 on 40, 80, 160, 320, 640, 1000, 1500, 2000, 3000 and 4000
+    tiles, the last reaching the end of the line tables; node_evals_matrix 8 724 736, direct_evals_matrix 2 517 632 on 40).  Up to
+    5e3 Pa the widest width is 0.1 x 5e3 / 101325 x (296 / 200)^0.8 < 0.007 cm^-1: both groups, the one of ONE state too, have a
+    core on each of the 39 whole tiles (core_tile_states 663 = 39 x 17, matrix_evals_3term 9 992 448, node_evals_matrix 10 022 464,
+    direct_evals_matrix 4 781 760)"""
+    n = 64 * (tiles - 1) + 1
+    first, lean = [], []
+    for ms in min_states:
+        base = ((1, 1),) + (((8, ms),) if ms is not None else ())
+        runs = [_run(n, np_, base + tune, p_surf=p_surf) for tune, _ in TABLE_FORMS]
+        for r, (tune, form) in zip(runs, TABLE_FORMS):
+            assert _disp(r)["tables"] == form, (tune, _disp(r))
+        for r in runs[1:]:
+            _same(r, runs[0], True)
+            assert _work_but_form(r) == _work_but_form(runs[0]), (ms, _disp(r))
+        w = runs[0]["work"]
+        print(f"K = {np_}, {tiles} tiles, min_states {ms}: node_evals_matrix {w['node_evals_matrix']}, direct_evals_matrix {w['direct_evals_matrix']}, "
+              f"core_tile_states {w['core_tile_states']}, matrix_evals_3term {w['matrix_evals_3term']}, sub_lean_evals {w['sub_lean_evals']}")
+        first.append(w)
+        lean.append(w["sub_lean_evals"])
+    for w in first:
+        assert w["node_evals_matrix"] > 0 and w["direct_evals_matrix"] > 0, w
+        assert w["core_tile_states"] > 0 and w["matrix_evals_3term"] > 0, w
+    if np_ == 40:
+        assert max(lean) > 0, lean
 
 
 # The switches no other test compares with the defaults, each on a grid where it changes what runs: (tuning, grid in tiles, what the

@@ -59,4 +59,4 @@ def test_device_constants_match_the_tool():
     # every zone routine takes its radii from the one helper: no radius is written out anywhere else
     assert len(re.findall(r"kSepR[348]\s*\*", KERNELS)) == 3
     assert not re.search(r"\b(133\.6|682\.0|11\.55)\b", KERNELS)
-    assert KERNELS.count("sep_radii(gb, amax)") == 5
+    assert KERNELS.count("sep_radii(gb, amax)") == 2               # izone_compute, and state_radii for both piece tables
