@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 from mpmath import mp, mpf
 
+from flux_ref import mp_fluxes, to_float
 
 
 def _legendre_coeffs(n):
@@ -142,66 +143,23 @@ def _column(nlob):
 
 
 def _mp_fluxes(nstream, nlob, Tn, mun, Tlev, extra):
-    """dDepth!, layerplanck and dMonoflux! of discretized.jl in 30-digit arithmetic on the same double inputs; band fluxes by the
-    trapezoid rule (util.jl:26-33)"""
+    """dDepth!, layerplanck and dMonoflux! of discretized.jl in 30-digit arithmetic on the same double inputs (flux_ref.mp_fluxes with
+    the 50-digit quadrature numbers and the exact sum of the gray and the extra term); band fluxes by the trapezoid rule (util.jl:26-33)"""
     with mp.workdps(30):
-        xs, ws = _LOBATTO[nlob]
-        m, W = _STREAMS[nstream]
-        h, c, kB, Na = mpf(6.62607015e-34), mpf(299792458.0), mpf(1.38064852e-23), mpf(6.02214076e23)
-        C = mpf("1e-4") * Na / mpf(G)
-        np_, nl = len(P), len(P) - 1
-        Pm = [mpf(float(p)) for p in P]
-        cth = mp.cos(mpf(THETA_S))
-        nnu = len(NU)
-        tau = np.zeros((nl, nnu))
-        Mu = np.zeros((np_, nnu))
-        Md = np.zeros((np_, nnu))
-        Mu_mp, Md_mp = [], []
-        for j, v in enumerate(NU):
-            num = 100 * mpf(float(v))
-            B = [100 * 2 * h * c ** 2 * num ** 3 / (mp.exp(h * c * num / (kB * mpf(float(T)))) - 1) for T in Tlev]
-
-            def beta(i, n):      # node n of layer i: node 0 is the last node of the layer above (the top level: Tn[0, 0], mun[0, 0])
-                mu = mun[n, i] if n else (mun[0, 0] if i == 0 else mun[nlob - 1, i - 1])
-                return C * ((mpf(SIGMA_GRAY) + mpf(float(extra[i * (nlob - 1) + n, j]))) / mpf(float(mu)))
-
-            t = []
-            for i in range(nl):
-                dP = Pm[i + 1] - Pm[i]
-                ti = mp.fsum((dP * ws[n]) * beta(i, n) for n in range(nlob))
-                t.append(max(ti, mpf("1e-6")))
-            tau[:, j] = [float(x) for x in t]
-            lp = lambda B1, B2, tt, tr: B2 * (1 - tr) - (B1 - B2) * tr + (1 - tr) * (B1 - B2) / tt
-            md = [mpf(0)] * np_
-            mu_ = [mpf(0)] * np_
-            for k in range(nstream):
-                I = mpf(0)
-                for i in range(nl):
-                    ti = t[i] * m[k]
-                    tr = mp.exp(-ti)
-                    I = I * tr + lp(B[i], B[i + 1], ti, tr)
-                    md[i + 1] += W[k] * I
-            md[0] += cth * mpf(float(S_TOA[j]))
-            Ms = md[0]
-            for i in range(nl):
-                Ms *= mp.exp(-t[i] / cth)
-                md[i + 1] += Ms
-            Is = md[-1] * mpf(float(ALBEDO[j])) / mp.pi + B[-1]
-            mu_[-1] = Is * mp.pi
-            for k in range(nstream):
-                I = Is
-                for i in range(nl - 1, -1, -1):
-                    ti = t[i] * m[k]
-                    tr = mp.exp(-ti)
-                    I = I * tr + lp(B[i + 1], B[i], ti, tr)
-                    mu_[i] += W[k] * I
-            Mu[:, j] = [float(x) for x in mu_]
-            Md[:, j] = [float(x) for x in md]
-            Mu_mp.append(mu_)
-            Md_mp.append(md)
+        sigma = np.empty(extra.shape, dtype=object)
+        for k in range(extra.shape[0]):
+            for j in range(extra.shape[1]):
+                sigma[k, j] = mpf(SIGMA_GRAY) + mpf(float(extra[k, j]))
+        ws, (m, W) = _LOBATTO[nlob][1], _STREAMS[nstream]
+        # node k = i (nlob - 1) + n: node 0 of a layer is the last node of the layer above (the top level: mun[0, 0])
+        muk = [mun[0, 0]] + [mun[n, i] for i in range(mun.shape[1]) for n in range(1, nlob)]
+        r = mp_fluxes(NU, P, G, muk, Tlev, sigma, S_TOA, ALBEDO, THETA_S, ws, m, W, dps=30)
+        Mu_mp, Md_mp = r["Mup"].T, r["Mdn"].T                  # [nnu][np]
+        nnu, np_ = len(NU), len(P)
         nuv = [mpf(float(v)) for v in NU]
         trapz = lambda M: [float(mp.fsum((nuv[j + 1] - nuv[j]) * (M[j][i] + M[j + 1][i]) / 2 for j in range(nnu - 1))) for i in range(np_)]
-        return dict(tau=tau, Mup=Mu, Mdn=Md, Fup=np.array(trapz(Mu_mp)), Fdn=np.array(trapz(Md_mp)))
+        return dict(tau=to_float(r["tau"]), Mup=to_float(r["Mup"]), Mdn=to_float(r["Mdn"]), Fup=np.array(trapz(Mu_mp)),
+                    Fdn=np.array(trapz(Md_mp)))
 
 
 def _source_rounding(nstream, Tlev, tau):
