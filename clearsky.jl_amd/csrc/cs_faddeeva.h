@@ -4,9 +4,21 @@
 //              cuts of the same series where they are exact to 1e-15)
 //   s >= 100 : 10-term Laplace continued fraction as the rational  z*PA(z^2)/PB(z^2)
 //   s <  100 : trapezoid rule, h = 1/2, on the integer or half-shifted grid + pole correction when y < 2*pi
-// Max relative error ~1e-14 against 40-digit mpmath (tools/faddeeva_proto.py) for fad_re below, whose far branch divides (1.0 / s);
-// the kernels' far bodies take rcp_fast instead, typically as good and 3.2e-14 at worst (see there).  The reference's own Faddeeva
-// (ACM TOMS Algorithm 985) is only ~4e-5 accurate, so this is strictly closer to the exact profile.
+// Accuracy against 40-digit values of Re exp(-z^2) erfc(-iz), y > 0 (tests/faddeeva_ref.py: 2,600 structured probes -- both sides of every
+// threshold in s, of the grid choice and of the pole-correction switch, y from 1e-12 to 1e4, x to 10^7.5):
+//   what the algorithm drops (exact, per probe)   series 5.9e-15 at s = 1e4 (its fifth term), continued fraction 1.4e-15 at s = 100,
+//                                                 trapezoid rule 7.6e-15 at x = 6.125 and 6.375 (the first node left out, t = 6.5 / 6.25,
+//                                                 is 3/8 resp. 1/8 away), below 3e-16 on the integer grid
+//   with IEEE divisions and libm (CPU restatement) 7.6e-15 measured; bound 6.7e-15 (series), 4.3e-14 (continued fraction), 2.4e-14 (near)
+//   fad_re below (far branch divides, 1.0 / s)    1.24e-14 measured on an MI355X (fad_near, x = 6.375, y = 0.01; series 6.2e-15, continued
+//                                                 fraction 5.5e-15); bound 6.7e-15 (series), 4.3e-14 (continued fraction, rcp_nr), 3.4e-14
+//                                                 (fad_near: its 24 rcp_fast, 1.4e-14 .. 3.2e-14 each and of one sign, are nearly all of
+//                                                 it); tests/test_gpu_faddeeva.py holds every probe to its own bound
+// The kernels' far bodies take rcp_fast instead of the division: typically as good and 3.2e-14 at worst (see there).  The reference's own
+// Faddeeva (ACM TOMS Algorithm 985) is only ~4e-5 accurate, so this is strictly closer to the exact profile.
+// y = 0 (a state at P = 0): Re w = exp(-x^2).  fad_near returns it (the pole term alone) to the same bound; from s = 100 on fad_mid and the
+// series return an exact 0, every term of theirs carrying the factor y, where the true value is at most exp(-100) = 3.8e-44.  A line of a
+// vacuum state therefore steps from 4e-44 of its peak to 0 at |x| = 10: kept, and asserted as such (got == 0 or within w of w).
 #pragma once
 #include <hip/hip_runtime.h>
 

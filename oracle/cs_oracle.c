@@ -50,6 +50,8 @@ enum { SHAPE_VOIGT = 0, SHAPE_LORENTZ = 1, SHAPE_DOPPLER = 2, SHAPE_PHCO2 = 3 };
  *   s <  100 : trapezoid rule (h = 1/2) for (i/pi) int exp(-t^2)/(z-t) dt on the integer or half-shifted
  *              grid (whichever keeps x >= h/4 away from a node) plus the pole (Poisson) correction
  *              2 exp(-z^2)/(1 -+ exp(-2 pi i z/h)) when y < pi/h.
+ * Held to 40-digit values per probe by tests/test_faddeeva_ref.py (7.6e-15 at worst, at x = 6.125).  y = 0: exp(-x^2) below s = 100 (the
+ * pole term alone); an exact 0 from s = 100 on, where the true value is at most exp(-100) = 3.8e-44 (every term carries the factor y).
  * ------------------------------------------------------------------------------------------ */
 #define FAD_H 0.5
 #define FAD_N 12

@@ -6,7 +6,9 @@ Inputs.  CO2-like tables (lineparam_ref.table) whose lines lie more than 2 x cut
 one line (the host test counts them with lines_within), so the device's value at a probe IS one line's term in one evaluation form.  Three
 grids, each the smallest beyond the rules of cs_api.hip that select forms (SHORT_N, FOUR_N from the tile and level counts, long_n() from
 the rule formulas as test_gpu_dispatch.py builds its grids); PLACEMENTS puts the centre of a line at the tile, interval and cut-off edges
-of the short grid.
+of the short grid.  On those grids a point is 35 and more Doppler widths from the next, so a (line, state) has a handful of probes in the
+line core; "col/fine" is the short grid's point count at a step of 2.5e-4 cm^-1, a third of a Doppler width, where the probes about the
+centre (+-12 steps, the sub-tile ends of three tiles, both sides of s = 100 and 1e3) are all core probes of the six narrower states.
 
 Clusters.  A piece of the matrix-core tables shorter than 8 lines is left to the vector unit (sepzones_body, edgezones_body: "too
 short to be worth a wave's trip"), a window end goes to the 16 tile nodes from 16 lines on and is cut into phases from 48
@@ -22,8 +24,8 @@ within the cut-off, of the 8-point sub-tiles in the centre's tile and its neighb
 cut-off, the grid's ends; 32 log-spaced distances per side.  One test holds at most MAX_PROBES of them, so a call of K states is compared
 in at most eight (STATES_COMPARED), and the long grid deals those eight out among its lines.
 
-The sharp bound (probes with s >= 1e3 in their state).  lineparam_bound keeps its rounding terms U (c0 + terms) and loses the 2e-13
-Faddeeva allowance F, which is replaced by what the sources state for the form that can serve the probe:
+The sharp bound (every probe of the Voigt codes; s = x^2 + y^2 in the probe's state).  lineparam_bound keeps its rounding terms U (c0 +
+terms) and loses the 2e-13 Faddeeva allowance F, which is replaced by what the sources state for the form that can serve the probe:
 
     form      truncation                              reciprocals                       roundings (2 per series term)
     vector    1e-15 (eps, series_radii.json) where    rcp_fast(s)                       2 x 4 U    far bodies of k_voigt_far, k_cheb_nodes
@@ -35,12 +37,22 @@ Faddeeva allowance F, which is replaced by what the sources state for the form t
                                                       record; w = 1/dnu^2 takes two
                                                       Newton steps: a rounding)
     matrix8   1e-15                                   the same                          2 x 8 U    the cores on the matrix pipe (8 terms)
-    scalar    as `vector` where s >= 1e4; 1e-14       none (IEEE division)              2 x 4 U    the oracle (cs_oracle.c), which the host test holds
-              below (the continued fraction: the                                                   to the same model
-              header's own figure, cs_faddeeva.h:7)
-    mid       1e-14 (the same figure)                 (inside it)                       2 x 4 U    1e3 <= s < 1e4 on the device: no 4-term body serves a
-                                                                                                   probe there, but k_linesum, which sums the groups
-                                                                                                   under CS_SHAPE_PSHIFT, takes fad_mid up to s = 1e4
+    scalar    as `vector` where s >= 1e4              none (IEEE division)              2 x 4 U    the oracle (cs_oracle.c), which the host test holds
+                                                                                                   to the same model
+    mid       faddeeva_ref.bound(x, y, form, "mid"): the probe's own truncation and     100 <= s < 1e4: fad_mid -- tier 0 of k_voigt_near /
+              rounding of the continued fraction, form "device" (rcp_nr) or "scalar"    k_voigt_near_both below 1e3; k_linesum's fad_re (the
+                                                                                                   CS_SHAPE_PSHIFT groups) up to 1e4; the oracle
+    near      faddeeva_ref.bound(x, y, form, "near"): trapezoid sum (24 x rcp_fast on   s < 100: fad_near -- tier 1 of the near-line kernels,
+              the device) and pole term, each with its share of the 40-digit value      k_linesum's fad_re; the oracle
+
+Below s = 1e3 nothing but `mid` and `near` serves a probe (k_voigt_sub and the near-zone pass hand those pairs over at kSerS); from 1e3
+to 1e4 `near6`, the matrix forms and `mid` can; within S_EDGE = 1e-9 of a threshold the forms of both sides count, since the device's own
+s (its alpha and x carry a few U) may fall on either.  Between 1e3 and 1e4 this model took the constant MID = 1e-14 (+ 8 U)
+for the continued fraction; the per-probe figure of faddeeva_ref replaces it wherever it is the smaller one.  Where it is the larger --
+at small y, where nr bi - ni br cancels to 1/19 of its parts and a worst case of every rounding gives up to 3.9e-14 -- the constant
+stays as a cap (MID_CAP): a bound these probes are held to already does not widen (the device measures 5.5e-15 in that branch, the oracle
+6.8e-15).  Below 1e3 no constant was ever asserted and the per-probe figure stands alone.  tests/phco2_line_ref.py, whose sharp model is
+its own, takes allowance_s, the model as it was.
 
 Two figures are not what was first assumed of them, and the model says so with the sources:
   - The four-term body between s = 1e4 and 1e6 is NOT inside eps: the first term it drops is u^4 p4(t), u = 1 / s, t = y^2 u in [0, 1],
@@ -60,7 +72,7 @@ end-point filter differs) -- and the allowance is the largest among those, since
 and a core take whole tiles (a probe at s >= 1e4 shares its tile with a line inside dA).  Lorentz (code 1) has no series: its body is
 the exact profile with rcp_nr1 (2e-15), already inside c0 of the hard bound -- a "sharp" bound of the hard one plus 2e-15 would say nothing,
 so code 1 is held to the hard bound alone (about 4e-15; recorded ratio 0.94).  Sharp bounds of the Voigt codes: 2.8e-14 to 4.7e-14, up to
-9e-14 at a margin of 15 per cent, against the hard 2e-13.
+9e-14 at a margin of 15 per cent, against the hard 2e-13; below s = 1e3: 5e-15 to 4.5e-14.
 
 Interpolated probes.  A line is summed on the 64 Chebyshev nodes of interval I at level l where it is inside the cut-off of both ends of
 I and at least max(dA, margin h) away (izone_frame, cs_kernels.h; h the half-width, dA = 100 alpha / sqrt(ln 2), here with the line's own
@@ -81,6 +93,7 @@ import os
 
 import numpy as np
 
+import faddeeva_ref as FR
 import lineparam_ref as R
 
 U = R.U
@@ -91,7 +104,8 @@ with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "se
 EPS = float(_SR["eps"])
 RADII = {int(n): (float(v["kSep"]), float(v["alpha_factor"])) for n, v in _SR["radii"].items()}
 S_CROSS = (100.0, 1e3, 1e4)
-S_SHARP = 1e3
+S_SHARP = 1e3                                                       # (tests/phco2_line_ref.py: its own sharp model starts here)
+S_EDGE = 1e-9                                                       # within this of a threshold in s the device's own s (its alpha, its x: some U each) may fall on either side
 LEBESGUE = 2.0 / math.pi * math.log(64.0) + 1.0
 RCP_NR1, TRUNC6, MID = 2e-15, 2e-15, 1e-14                        # cs_faddeeva.h: rcp_nr1, kSerS, the header's overall figure
 MAX_PROBES = 2500
@@ -140,16 +154,38 @@ class RunForm:
     def __init__(self, matrix=True, interp=True, margin=0.3, first=0, cascade=True, scalar=False):
         self.matrix, self.interp, self.margin, self.first, self.cascade, self.scalar = matrix, interp, margin, first, cascade, scalar
 
-    def allowance(self, s, lorentz=False):
+    def allowance_s(self, s, lorentz=False):
+        """from s alone, with the constant MID between 1e3 and 1e4: what tests/phco2_line_ref.py (its own sharp model, s >= 1e3) takes"""
         if lorentz:
             return 0.0 if self.scalar else ALLOW["lorentz"]
         t4 = trunc4(s)
         if self.scalar:
             return (EPS + t4 if s >= 1e4 else MID) + 2 * 4 * U
         forms = [ALLOW["near6"] + rcp_fast(s)] + ([ALLOW["matrix"], ALLOW["matrix8"]] if self.matrix else [])
-        # s >= 1e4: the far bodies; below: the continued fraction (fad_mid) of k_linesum, which sums the CS_SHAPE_PSHIFT groups
         forms.append(ALLOW["vector"] + t4 + rcp_fast(s) if s >= 1e4 else MID + 2 * 4 * U)
         return max(forms)
+
+    def allowance(self, x, y, lorentz=False):
+        """the Faddeeva allowance of a probe at (x, y), s = x^2 + y^2: the forms that can serve it (module docstring); within S_EDGE of a
+        threshold, those of either side"""
+        if lorentz:
+            return 0.0 if self.scalar else ALLOW["lorentz"]
+        s = x * x + y * y
+        at = lambda S: abs(s / S - 1.0) < S_EDGE
+        fform = "scalar" if self.scalar else "device"
+        out = []
+        if s >= 1e4 or at(1e4):              # the far bodies (the oracle: the same four terms, IEEE division)
+            sf = max(s, 1e4)
+            out.append((EPS + trunc4(sf)) + 2 * 4 * U if self.scalar else ALLOW["vector"] + trunc4(sf) + rcp_fast(sf))
+        if (s >= 1e3 or at(1e3)) and not self.scalar:
+            out += [ALLOW["near6"] + rcp_fast(s)] + ([ALLOW["matrix"], ALLOW["matrix8"]] if self.matrix else [])
+        if (s < 1e4 or at(1e4)) and (s >= 100.0 or at(100.0)):
+            mid = FR.bound(x, y, fform, "mid")
+            out.append(min(mid, MID + 2 * 4 * U) if s >= 1e3 and not at(1e3) else mid)     # (MID_CAP, module docstring)
+        if s < 100.0 or at(100.0):
+            fr = 2.0 * x - math.floor(2.0 * x)       # (within S_EDGE of the grid choice's boundary: either grid)
+            out += [FR.bound(x, y, fform, b) for b in (("near-int", "near-half") if min(abs(fr - 0.25), abs(fr - 0.75)) < S_EDGE else ("near",))]
+        return max(out)
 
 
 # ---- tables and states ----------------------------------------------------------------------------------------------------------------
@@ -189,6 +225,7 @@ SHORT_N = 64 * SHORT_TILES + 1                     # 40 tiles and a last tile of
 SHORT_NU0, LOW_NU0, HIGH_NU0 = 640.0, 0.5, 10000.0
 FOUR_DNU, FOUR_N = 0.008, 8 * 1024 + 1              # eight intervals of the largest of four sizes, and a last one of one point
 LONG_NU0, LONG_GAP = 600.0, 55.0
+FINE_NU0, FINE_DNU = 666.68, 2.5e-4                 # a third of a Doppler width per point: the line core (s < 1e3) fills the centre's tiles
 
 
 def grid(nu0, dnu, n):
@@ -350,6 +387,7 @@ class Case:
             return self
         n = len(self.pr)
         self.want, self.zero, self.s, self.infos = np.zeros(n), np.zeros(n, bool), np.zeros(n), []
+        self.x, self.y = np.zeros(n), np.zeros(n)
         for q, (k, i, l) in enumerate(self.pr):
             ln, C, frac, _ = self.lines[l]
             T, P = self.states[k]
@@ -357,6 +395,7 @@ class Case:
             self.zero[q] = v == 0
             self.infos.append(info)
             self.s[q] = s_of(self.nu[i] - self.centre(k, l), info["alpha"], info["gamma"])
+            self.x[q], self.y[q] = abs(self.nu[i] - self.centre(k, l)) * SQLN2 / info["alpha"], info["gamma"] * SQLN2 / info["alpha"]
         # codes 4, 6 at |d| = cut exactly (the grids hold such points): profile - pedestal cancels to an exact 0, rel = 0, and no relative
         # bound exists -- the device's value there is rounding of the two terms; it must be finite and >= 0 (`void`), nothing more
         self.void = np.array([f["rel"] <= 0.0 for f in self.infos]) & ((np.abs(self.nu[self.i] - [self.centre(k, l) for k, _, l in self.pr]) <= self.cut)
@@ -399,9 +438,10 @@ class Case:
         """(mask of the probes the sharp bound applies to, their bounds)"""
         self.reference()
         lor = (self.code & ~R.PSHIFT) == 1
-        m = ~self.zero & (self.s >= S_SHARP) & (not lor)      # (Lorentz: the hard bound is the sharp one, module docstring)
+        m = ~self.zero & (not lor)                              # (Lorentz: the hard bound is the sharp one, module docstring)
         cond = self.conditioning(form)
-        b = np.array([(U * (c0 + R.model_terms(f)) + form.allowance(s, lor) + cd) / f["rel"] for f, s, cd in zip(self.infos, self.s, cond)])
+        b = np.array([(U * (c0 + R.model_terms(f)) + form.allowance(x, y, lor) + cd) / f["rel"]
+                      for f, x, y, cd in zip(self.infos, self.x, self.y, cond)])
         return m, b
 
     def isolation(self):
@@ -443,6 +483,14 @@ def compare(case, got, form, what):
     return hard, sharp
 
 
+def core_ratio(case, got, form):
+    """worst error / sharp bound over the probes of the line core alone (s < 1e3: fad_mid and fad_near), for the record; 0 without any"""
+    m, b = case.sharp(form)
+    sel = m & ~case.void & (case.s < S_SHARP) & (np.abs(case.want) >= R.UNDERFLOW)
+    got = np.asarray(got, float)
+    return float(np.max(np.abs(got[sel] - case.want[sel]) / np.abs(case.want[sel]) / b[sel])) if sel.any() else 0.0
+
+
 # ---- the cases of the two test modules ----------------------------------------------------------------------------------------------------
 
 def column_states(cs):
@@ -456,7 +504,7 @@ MERGE_CONCS = (CONC, 0.02)
 
 
 class Cases:
-    """the cases by name, built on first use and kept: "batch/<placement>", "batch/low-vvh" (cs_shape_batch, cs_shape_points) and
+    """the cases by name, built on first use and kept: "batch/<placement>", "batch/low-vvh", "batch/fine" (cs_shape_batch, cs_shape_points) and
     "col/..." (a 61-state column)"""
 
     def __init__(self, cs, shifted=None):
@@ -474,9 +522,9 @@ class Cases:
         return self.cs.interp_plan(nu, CUT)
 
     def names(self):
-        return ([f"batch/{p}" for p in placements()] + ["batch/low-vvh", "col/short", "col/short-lorentz", "col/short-ckd", "col/low-vvh",
+        return ([f"batch/{p}" for p in placements()] + ["batch/low-vvh", "batch/fine", "col/short", "col/short-lorentz", "col/short-ckd", "col/low-vvh",
                 "col/low-ckdvvh", "col/short-shifted", "col/short-merge", "col/four", "col/long", "col/high", "col/short-cluster",
-                "col/four-cluster", "col/long-cluster"])
+                "col/four-cluster", "col/long-cluster", "col/fine"])
 
     def __getitem__(self, name):
         if name not in self._made:
@@ -490,6 +538,9 @@ class Cases:
             if what == "low-vvh":
                 sts = batch_states(16)
                 return Case(cs, self.low, self.plan(self.low), [one_line_table(cs, LOW_CENTRE)], [(T, P) for T, P, _ in sts], code=5)
+            if what == "fine":
+                nu = grid(FINE_NU0, FINE_DNU, SHORT_N)
+                return Case(cs, nu, self.plan(nu), [one_line_table(cs, float(nu[20 * 64 + 32]))], [(T, P) for T, P, _ in batch_states(33)])
             c, K = placements()[what]
             sts = batch_states(K)
             return Case(cs, self.short, self.plan(self.short), [one_line_table(cs, c)], [(T, P) for T, P, _ in sts])
@@ -502,6 +553,9 @@ class Cases:
             return one(self.short, [one_line_table(cs, mid, ghosts=gh)])
         if what == "high":               # at 10000 cm^-1 the Doppler width, and with it the 3-term zone of the widest states, reaches the cut-off edge
             nu = grid(HIGH_NU0, SHORT_DNU, SHORT_N)
+            return one(nu, [one_line_table(cs, float(nu[20 * 64 + 32]))])
+        if what == "fine":               # the short grid's point count at 1/100 of its step: x = 0.3 .. 0.4 per point, every probe about the centre in the core
+            nu = grid(FINE_NU0, FINE_DNU, SHORT_N)
             return one(nu, [one_line_table(cs, float(nu[20 * 64 + 32]))])
         if what == "short-lorentz":
             return one(self.short, [one_line_table(cs, mid)], 1)

@@ -40,7 +40,7 @@ The sharp bound (probes with s = x^2 + (chi y)^2 >= 1e3) replaces the 2e-13 Fadd
                                   y^2 u): what it drops is u^3 p3(t), |p3| <= 13.125 on [0, 1], below 1.4e-17 for s >= far_s = 1e6 WHATEVER y
                                   is -- so chi > 1 (T < 143.6 K) cannot take it out of its budget: the zone bound only decides between two
                                   bodies that are both inside eps there.  (The "15 y^2 / s^3" of the Voigt path's mode-0 body is not dropped here.)
-  core, inner Voigt pass          isolated_line_ref.RunForm().allowance(s): near6, the matrix forms, mid
+  core, inner Voigt pass          isolated_line_ref.RunForm().allowance_s(s): near6, the matrix forms, mid
   own core loop, k_linesum        fad_re: its far branch divides (IEEE), fad_mid below s = 1e4 (1e-14, cs_faddeeva.h:7): the scalar model;
                                   the own loop takes ph_term for lines no lane of the wave has inside s < 1e4, so the larger of both
   interpolated (node forms)       U x Lambda(nc) x max_I f / f(nu), Lambda(n) = (2 / pi) ln n + 1 the Lebesgue constant of the level's own node
@@ -414,7 +414,7 @@ def allowance(form, s, scalar=False):
         return scal
     vec = I.EPS + t4 + I.rcp_fast(s) + 2 * 4 * U
     if form[:2] == ("core", "voigt"):
-        return _VOIGT.allowance(s)
+        return _VOIGT.allowance_s(s)
     if form[:2] == ("core", "own"):
         return max(scal, vec)
     return vec

@@ -115,10 +115,11 @@ def test_crossing_probes_straddle(cs, cases):
     print(f"{n} crossings straddled")
 
 
-@pytest.mark.parametrize("name", ["batch/mid-tile", "batch/between-tiles-1024", "batch/low-vvh"])
+@pytest.mark.parametrize("name", ["batch/mid-tile", "batch/between-tiles-1024", "batch/low-vvh", "batch/fine"])
 def test_oracle_meets_both_bounds(cs, O, cases, name):
-    """the oracle at the device's probes: within lineparam_bound(C0_ORACLE) everywhere, and at s >= 1e3 within the sharp bound of the
-    scalar form (no reciprocal terms: its divisions are IEEE) -- the reference and the model are right before the device meets them"""
+    """the oracle at the device's probes: within lineparam_bound(C0_ORACLE) everywhere, and within the sharp bound of the scalar form (no
+    reciprocal terms: its divisions are IEEE; below s = 1e4 faddeeva_ref.bound(x, y, "scalar") per probe, the line core included) -- the
+    reference and the model are right before the device meets them"""
     import test_lineparam_ref as TL
     c = cases[name].reference()
     sl = c.tables[0]
@@ -135,7 +136,34 @@ def test_oracle_meets_both_bounds(cs, O, cases, name):
     m, b = c.sharp(I.RunForm(scalar=True, interp=False), c0=R.C0_ORACLE)
     worst_s = R.check(got[m], c.want[m], b[m], c.zero[m], what=name + ", sharp")
     assert R.split(c.want[~c.zero])[1] == 0.0          # the underflow class is empty
-    print(f"{name}: {len(c.pr)} probes ({int(m.sum())} sharp), oracle error / bound  hard {worst_h:.3f}  sharp {worst_s:.3f}")
+    assert np.array_equal(m, ~c.zero)                  # every probe with a term is under the sharp bound, the core included
+    core = [int(np.sum(m & (c.s < 100.0))), int(np.sum(m & (c.s >= 100.0) & (c.s < 1e3))), int(np.sum(m & (c.s >= 1e3) & (c.s < 1e4)))]
+    assert min(core) >= (100 if name == "batch/fine" else 4 if name == "batch/mid-tile" else 0), core
+    lo = c.s < 1e4
+    worst_c = R.check(got[m & lo], c.want[m & lo], b[m & lo], c.zero[m & lo], what=name + ", sharp, s < 1e4")
+    print(f"{name}: {len(c.pr)} probes ({int(m.sum())} sharp; s < 100: {core[0]}, < 1e3: {core[1]}, < 1e4: {core[2]}), oracle error / bound  hard {worst_h:.3f}  "
+          f"sharp {worst_s:.3f} (s < 1e4: {worst_c:.3f}; bounds there {b[m & lo].min():.1e} .. {b[m & lo].max():.1e})")
+
+
+def test_allowance_below_1e4(cs):
+    """the Faddeeva allowance of the sharp bound is faddeeva_ref's per-probe bound below s = 1e4, of the branch that serves the probe; both
+    branches count within S_EDGE of s = 100 and both grids within S_EDGE of the grid choice's boundary; from 1e3 on the six-term and the
+    matrix forms count as before, and the far side of 1e4 is what it was"""
+    import faddeeva_ref as FR
+    dev, sca = I.RunForm(), I.RunForm(scalar=True)
+    assert dev.allowance(3.0, 0.01) == FR.bound(3.0, 0.01, "device", "near") and sca.allowance(3.0, 0.01) == FR.bound(3.0, 0.01, "scalar", "near")
+    assert dev.allowance(12.0, 0.5) == FR.bound(12.0, 0.5, "device", "mid") < 5e-14
+    assert dev.allowance(6.0, 8.0) == max(FR.bound(6.0, 8.0, "device", "mid"), FR.bound(6.0, 8.0, "device", "near"))
+    assert dev.allowance(0.125, 0.01) == max(FR.bound(0.125, 0.01, "device", "near-int"), FR.bound(0.125, 0.01, "device", "near-half"))
+    x = math.sqrt(2e3)
+    cap = I.MID + 2 * 4 * I.U
+    assert dev.allowance(x, 0.1) == max(min(FR.bound(x, 0.1, "device", "mid"), cap), I.ALLOW["near6"] + I.rcp_fast(x * x + 0.01), I.ALLOW["matrix8"])
+    assert sca.allowance(x, 0.1) == min(FR.bound(x, 0.1, "scalar", "mid"), cap) == cap and sca.allowance(30.0, 40.0) == FR.bound(30.0, 40.0, "scalar", "mid") < cap
+    for xx, yy in ((x, 0.1), (30.0, 40.0), (60.0, 1e-3), (1.0, 99.0)):      # never above what the model took there before
+        assert dev.allowance(xx, yy) <= dev.allowance_s(xx * xx + yy * yy) and sca.allowance(xx, yy) <= sca.allowance_s(xx * xx + yy * yy)
+    for x in (125.0, 1000.0, 32768.0):
+        assert dev.allowance(x, 0.0) == dev.allowance_s(x * x) and sca.allowance(x, 0.0) == sca.allowance_s(x * x)
+    assert dev.allowance(5.0, 1.0, lorentz=True) == I.ALLOW["lorentz"]
 
 
 def test_conditioning_term(cs, cases):
