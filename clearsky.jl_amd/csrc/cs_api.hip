@@ -69,7 +69,7 @@ struct VoigtPlan {
     bool edge_big;              // k_voigt_edge_mx<1>: one wave per (tile, group); else <4>
     int edge_phases;            // ... cuts a cut-off edge by the sub-tiles its lines reach (<1> only)
     bool tnodes;                // ... and sums the lines inside every point's cut-off on the 16 tile nodes
-    int ngrpn, nrep;            // near-line kernels: CS_NEAR_R-tile stretches, and how many of them a wave takes in turn
+    int nrep;                   // near-line kernels: how many consecutive tiles a wave takes in turn
     bool near_both;             // ... both tiers in one launch
     int sub_lean;               // k_voigt_sub's range-only pass (cs_set_tuning key 18)
     unsigned nb_zones, nb_iz, nb_sep, nb_edge;   // blocks of the zone, interval-zone and piece-table parts of the setup launches
@@ -735,7 +735,7 @@ int check_near_density(const GasTable &G, double nu_hi, double span, double cut,
         return best;
     };
     const int64_t nzone = max_in(span + 2.0 * dA + 2.0 * ds), npt = max_in(2.0 * r0 + 2.0 * ds);
-    if (nzone >= (1 << 20) || npt >= (1 << 12))
+    if (nzone >= (1 << kNearFirstBits) || npt >= (1 << kNearCountBits))
         return fail(CS_EINVAL, "line table too dense for the near-line hand-off: %lld lines within %.3g cm^-1, %lld within %.3g cm^-1",
                     (long long)nzone, span + 2.0 * dA, (long long)npt, 2.0 * r0);
     return CS_OK;
@@ -1350,7 +1350,7 @@ struct GasPass {
     LineCold *cold = nullptr;
     LineF32 *hot32 = nullptr;       // fp32 records of the far wings beyond far_s (mixed precision); NULL: fp64 throughout
     Zone *zones = nullptr;
-    int2 *ranges = nullptr;
+    unsigned *ranges = nullptr;     // the near-line hand-off (NearHandoff)
     double *ped_ws = nullptr;       // ped_bytes(kn, G->L) where ped
     // the output: sigma = (accumulate ? sigma : base + extra) + this group, then max(0, .) if clamp (codes 4, 6 where the gas's own sigma
     // is complete: B1, bake)
@@ -1462,12 +1462,11 @@ static VoigtPlan voigt_plan(const GasPass &p)
     pl.edge_big = mx_big(pl.nt64, kn, 1024);
     pl.edge_phases = itp.edge_phases;
     pl.tnodes = pl.use_edge && pl.edge_big && itp.edge_phases && itp.tnodes != nullptr;
-    pl.ngrpn = (pl.nt64 + CS_NEAR_R - 1) / CS_NEAR_R;   // near kernels: one wave = CS_NEAR_R consecutive tiles ...
-    // ... times nrep, one after the other: where the table is sparse against the grid (few tiles have candidates at all) and the
+    // near kernels: one wave = nrep consecutive tiles, one after the other: eight where the table is sparse against the grid (few tiles have candidates at all) and the
     // grid long enough to keep the chip full with an eighth of the waves, and on every grid of half a million (tile, state) waves
     // and more -- there the launch of the waves is what a near-line kernel costs first (BASELINE configs[4]: 7.9e5 waves per
     // tier, step 7.06 -> 6.85 ms with eight tiles per wave; the bench column, 9.5e4 waves: a tie with two, a loss with four)
-    const int64_t nwaves_near = (int64_t)pl.ngrpn * kn;
+    const int64_t nwaves_near = (int64_t)pl.nt64 * kn;
     pl.nrep = (nwaves_near >= 524288 || (nlines < (int64_t)pl.nt64 * 2 && nwaves_near >= 262144)) ? 8 : 1;
     pl.near_both = pl.nrep == 1 && itp.near_both;   // (one tile per wave; cs_set_tuning key 16 | 4: two launches, A/B)
     return pl;
@@ -1609,11 +1608,10 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
     // 8 x (blocks of the longest XCD stretch): XCD-aware tile mapping (tile_block); xtiles is a multiple of 4 tiles
     const dim3 grid_s((unsigned)(8 * (p.xtiles * split / 4)), kn);
     const EdgeZone *edgez = use_edge ? itp.edge : nullptr;
-    double *zero2 = nullptr;   // (the far kernel can clear the plane itself: unused since k_voigt_sub adds to it beside k_voigt_far)
     // the window cores of the groups whose series radius is short: pairs inside it (the rest: k_voigt_edge_mx)
     auto launch_sub = [&](hipStream_t ss, double *out, bool assigns) {
         CS_LAUNCH(k_voigt_sub<CS_SUBW>, dim3((unsigned)nt64, (unsigned)((kn + 64 / CS_SUBW - 1) / (64 / CS_SUBW))), dim3(4096 / CS_SUBW), 0, ss, p.dnu, nnu, G.L, p.hot,
-                  G.nu.as<double>(), p.zones, itp.edge, nt64, kn, p.cut, out, reinterpret_cast<unsigned *>(p.ranges), pl.near_prio, assigns ? 1 : 0, pl.sub_lean);
+                  G.nu.as<double>(), p.zones, itp.edge, nt64, kn, p.cut, out, p.ranges, pl.near_prio, assigns ? 1 : 0, pl.sub_lean);
     };
     if (near_fork) {   // zones, records and piece tables are written: the side stream may start
         if (nodes_fork) {   // (nothing was enqueued on the main stream since that record: one event serves both side streams)
@@ -1626,18 +1624,18 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
         p.fork->zeroed = true;
         if (pl.core) launch_sub(p.fork->s3, p.fork->sigma2, sub_assigns);   // (it needs the zones only, not k_voigt_far: beside it)
     }
-    CS_LAUNCH(far_kernel(hot32 != nullptr, split, pl.lor, use_edge), grid_s, dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, hot32, G.nu.as<double>(), p.win, p.zones,
-              nt64, nblk_s, p.cut, p.base, p.extra, p.sigma, accumulate, p.ranges, iz, itp.nItot, pl.ishift, edgez, zero2);
+    CS_LAUNCH(far_kernel(hot32 != nullptr, split, pl.lor, use_edge), grid_s, dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, hot32, G.nu.as<double>(), p.win, kn, p.zones,
+              nt64, nblk_s, p.cut, p.base, p.extra, p.sigma, accumulate, p.ranges, iz, itp.nItot, pl.ishift, edgez);
     if (p.evg) (void)hipEventRecord(p.evg[3], s);
     if (pl.core && !near_fork) launch_sub(s, p.sigma, false);
     auto launch_near = [&](hipStream_t sn, double *out) {
-        const dim3 gridq((unsigned)(((pl.ngrpn + pl.nrep - 1) / pl.nrep + 3) / 4), kn);
+        const dim3 gridq((unsigned)(((nt64 + pl.nrep - 1) / pl.nrep + 3) / 4), kn);
         if (pl.near_both) {
-            CS_LAUNCH(k_voigt_near_both, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, p.cut, out, p.ranges, pl.near_prio);
+            CS_LAUNCH(k_voigt_near_both, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, kn, p.cut, out, p.ranges, pl.near_prio);
             return;
         }
-        CS_LAUNCH(k_voigt_near<0>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, pl.ngrpn, pl.nrep, p.cut, out, p.ranges, pl.near_prio);
-        CS_LAUNCH(k_voigt_near<1>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, pl.ngrpn, pl.nrep, p.cut, out, p.ranges, pl.near_prio);
+        CS_LAUNCH(k_voigt_near<0>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, kn, pl.nrep, p.cut, out, p.ranges, pl.near_prio);
+        CS_LAUNCH(k_voigt_near<1>, gridq, dim3(256), 0, sn, p.dnu, nnu, G.L, p.hot, p.cold, p.zones, nt64, kn, pl.nrep, p.cut, out, p.ranges, pl.near_prio);
     };
     if (near_fork) {   // the near kernels need the hand-off words of both k_voigt_far (main stream) and k_voigt_sub (theirs)
         (void)hipEventRecord(p.fork->ev_far3, s);
@@ -2066,7 +2064,7 @@ int cs_gas_upload(cs_ctx *ctx, int slot, int64_t L, const double *nu, const doub
     for (int64_t j = 1; j < L; j++)
         if (!(nu[j] >= nu[j - 1])) return fail(CS_EORDER, "line table must be sorted by wavenumber (par.jl:267)");
     // line indices travel as int32 (windows, zones) and as 26-bit fields of the near-line queue entries (k_voigt_near)
-    if (L >= ((int64_t)1 << 26)) return fail(CS_EINVAL, "line table too long (%lld lines; the limit is 2^26 - 1 per gas)", (long long)L);
+    if (L >= ((int64_t)1 << kNearLineBits)) return fail(CS_EINVAL, "line table too long (%lld lines; the limit is 2^26 - 1 per gas)", (long long)L);
     HIPCHK(hipSetDevice(ctx->device));
     GasTable &G = ctx->gas[slot];
     G.present = false;
@@ -2132,7 +2130,7 @@ static int merged_table(cs_ctx *ctx, const std::vector<int> &slots, std::shared_
     int64_t L = 0;
     int niso = 0;
     for (int sl : slots) { L += ctx->gas[sl].L; niso += ctx->gas[sl].niso; }
-    if (L >= ((int64_t)1 << 26)) return fail(CS_EINVAL, "merged line table too long (%lld lines; the limit is 2^26 - 1)", (long long)L);
+    if (L >= ((int64_t)1 << kNearLineBits)) return fail(CS_EINVAL, "merged line table too long (%lld lines; the limit is 2^26 - 1)", (long long)L);
     std::shared_ptr<GasTable> M(new GasTable());
     GasTable &G = *M;
     G.L = L;
@@ -2348,7 +2346,7 @@ static int reserve_lines(size_t kn, size_t maxL, int64_t nnu, DevBuf &hot, DevBu
 {
     HIPCHK(hot.reserve((kn * maxL + 4) * sizeof(LineHot)));
     HIPCHK(cold.reserve(kn * maxL * sizeof(LineCold)));
-    if (ranges) HIPCHK(ranges->reserve(kn * nnu * sizeof(int2) + 2 * kn * ((nnu + 63) / 64) * sizeof(int)));
+    if (ranges) HIPCHK(ranges->reserve(NearHandoff<unsigned>::bytes(kn, nnu)));
     if (hot32) HIPCHK(hot32->reserve((kn * maxL + 4) * sizeof(LineF32)));
     if (ped) HIPCHK(ped->reserve(ped_bytes((int64_t)kn, (int64_t)maxL)));
     if (spare) HIPCHK(spare->reserve(kn * nnu * sizeof(double)));
@@ -2388,7 +2386,7 @@ static int gas_states(cs_ctx *ctx, GasTable &G, const ShapeSpec &sh, double dnu_
     if ((rc = upload(dnu, nu, nnu, s)) || (rc = upload(dT, T, K, s)) || (rc = upload(dP, P, K, s))) return rc;
     // bound the workspace: process the states in chunks
     const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) +
-                             (Z ? (size_t)nnu * sizeof(int2) : (size_t)nnu * (sizeof(double) + sizeof(int2))) + (ped ? ped_bytes(1, G.L) : 0);
+                             (Z ? (size_t)nnu * kNearPointBytes : (size_t)nnu * (sizeof(double) + kNearPointBytes)) + (ped ? ped_bytes(1, G.L) : 0);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));   // gridDim.y limit
     const bool mixed = ctx->mixed && shape == SH_VOIGT && !sh.pshift;
     if ((rc = reserve_lines(kc, G.L, nnu, hot, cold, &dranges, mixed ? &ctx->hot32 : nullptr, ped ? &dped : nullptr, nullptr))) return rc;
@@ -2400,7 +2398,7 @@ static int gas_states(cs_ctx *ctx, GasTable &G, const ShapeSpec &sh, double dnu_
     // (the strict pre-filter of a shifted line is its own state's: prep_body parks the lines whose shifted centre fails it)
     p.pshift = sh.pshift; p.flo = strict ? nu[0] - dnu_cut : -INFINITY; p.fhi = strict ? nu[nnu - 1] + dnu_cut : INFINITY;
     p.dnu = dnu.as<double>(); p.nu = nu; p.nnu = nnu;
-    p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<int2>(); p.ped_ws = dped.as<double>();
+    p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<unsigned>(); p.ped_ws = dped.as<double>();
     if (mixed) p.hot32 = ctx->hot32.as<LineF32>();
     p.clamp = true;   // the gas's own sigma, complete
     p.far_s = ctx->far_s; p.ph = &ctx->ph;
@@ -3211,7 +3209,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     const size_t maxL = c.maxL;
     const bool any_ped = c.any_ped;
     const bool vvh2 = c.gas.size() > 1 && c.gas[1].vvh;   // a second code-5 group: its line sum goes to a plane of its own first
-    const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + (size_t)c.nnu * sizeof(int2) +
+    const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + (size_t)c.nnu * kNearPointBytes +
                              (any_ped ? ped_bytes(1, (int64_t)maxL) : 0) + (vvh2 ? (size_t)c.nnu * sizeof(double) : 0);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BK, ((size_t)8 << 30) / std::max<size_t>(per_state, 1), (size_t)65535}));
     if (c.ngas > 0 && (rc = reserve_lines(kc, maxL, c.nnu, hot, cold, &dranges, ctx->mixed ? &ctx->hot32 : nullptr, any_ped ? &dped : nullptr,
@@ -3225,7 +3223,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
         HIPCHK(dzones.reserve((size_t)kc * nt64 * sizeof(Zone)));
         GasPass p = column_pass(ctx, cg);
         p.mstride = (int)BK;
-        p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<int2>(); p.ped_ws = dped.as<double>();
+        p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<unsigned>(); p.ped_ws = dped.as<double>();
         p.accumulate = qi > 0; p.spare = dvvh.as<double>();   // (a second code-5/6 group: its bare line sum goes there first)
         p.log = &log;
         Interp &itp = p.itp;
@@ -3355,7 +3353,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
         p.kn = K;
         p.Tk = c.Tk.as<double>(); p.Pk = c.Pk.as<double>(); p.scale = cg.st.conc.as<double>(); p.mstride = K;
         pass_states(p, cg.st, 0);
-        p.hot = c.hot.as<LineHot>(); p.cold = c.cold.as<LineCold>(); p.zones = cg.zones.as<Zone>(); p.ranges = c.ranges.as<int2>(); p.ped_ws = c.ped.as<double>();
+        p.hot = c.hot.as<LineHot>(); p.cold = c.cold.as<LineCold>(); p.zones = cg.zones.as<Zone>(); p.ranges = c.ranges.as<unsigned>(); p.ped_ws = c.ped.as<double>();
         // (code 4: the pedestal comes off the plane the group's first kernel initialised; the near-line plane and the wings still to come only add)
         p.extra = extra; p.sigma = sig; p.accumulate = gi > 0; p.spare = c.vvh.as<double>();
         if (cg.itp.nlev > 0) p.itp = interp_view(c.cheb, cg.itp, K);

@@ -425,6 +425,76 @@ __device__ __forceinline__ FarK load_fark()
     c.km105 = vgpr_const(-105.0); c.k13p125 = vgpr_const(13.125); c.k210 = vgpr_const(210.0); c.km120 = vgpr_const(-120.0);
     return c;
 }
+// the higher coefficients, for the near-zone series (k_voigt_far, k_voigt_sub): scalar but for the leading one of each polynomial
+struct NearK { double q40, q41, q42, q43, q44, q50, q51, q52, q53, q54, q55; };
+__device__ __forceinline__ NearK load_neark()
+{
+    NearK q;
+    q.q40 = sgpr_const(59.0625); q.q41 = sgpr_const(-787.5); q.q42 = sgpr_const(2835.0); q.q43 = sgpr_const(-3780.0); q.q44 = vgpr_const(1680.0);   // a4 U8 in t
+    q.q50 = sgpr_const(324.84375); q.q51 = sgpr_const(-6496.875); q.q52 = sgpr_const(36382.5); q.q53 = sgpr_const(-83160.0);
+    q.q54 = sgpr_const(83160.0); q.q55 = vgpr_const(-30240.0);                                                                                    // a5 U10 in t
+    return q;
+}
+// Near-zone term, six terms (s >= 1e3):  A y/sqrt(pi) * u (1 + u p1(t) + ... + u^5 p5(t)),  u = 1/s, t = y^2 u
+__device__ __forceinline__ double near_zone_term(const LineHot &h, double u, const FarK &c, const NearK &q)
+{
+    const double t = h.p2 * u;
+    const double p5 = __builtin_fma(__builtin_fma(__builtin_fma(__builtin_fma(__builtin_fma(q.q55, t, q.q54), t, q.q53), t, q.q52), t, q.q51), t, q.q50);
+    const double p4 = __builtin_fma(__builtin_fma(__builtin_fma(__builtin_fma(q.q44, t, q.q43), t, q.q42), t, q.q41), t, q.q40);
+    const double p3 = __builtin_fma(__builtin_fma(__builtin_fma(c.km120, t, c.k210), t, c.km105), t, c.k13p125);
+    const double p2 = __builtin_fma(__builtin_fma(c.k12, t, c.km15), t, c.k3p75);
+    const double p1v = __builtin_fma(-2.0, t, c.k1p5);
+    double P = __builtin_fma(u, p5, p4);
+    P = __builtin_fma(u, P, p3);
+    P = __builtin_fma(u, P, p2);
+    P = __builtin_fma(u, P, p1v);
+    P = __builtin_fma(u, P, 1.0);
+    // (the term is made opaque before its caller's select: otherwise the compiler sinks the whole series into a branch under the
+    // lanes' exec mask -- which saves nothing on a wave that always has such lanes -- and with it the load of p3, so that
+    // every line waits twice for scalar memory instead of four lines waiting once)
+    double term = (h.p3 * u) * P;
+    asm volatile("" : "+v"(term));
+    return term;
+}
+
+// ---- the near-line hand-off: what k_voigt_far and k_voigt_sub leave k_voigt_near<0>, <1> / k_voigt_near_both, in 32-bit words ----------
+//   [2][K][nnu]    per tier (0: s < 1e3, 1: s < 100), state and point the lane's lines as one range word (0 = none)
+//   [2][K][ntile]  per tier, state and tile a flag "some lane has candidates": tiles without any (most tiles of a sparse table, every
+//                  tile of a high-pressure state, where y^2 alone exceeds 1e3) skip the word stores there and the whole wave here
+// A range word = (first line - N0) << 12 | count, N0 the start of the tile's near zone: check_near_density (cs_api.hip) refuses
+// tables dense enough to overflow either field.
+constexpr int kNearFirstBits = 20, kNearCountBits = 12;
+constexpr size_t kNearPointBytes = 2 * sizeof(unsigned);   // the two range words of a (state, point): what the state-chunk rules count
+__device__ __forceinline__ unsigned near_pack(int first, int last, int N0) { return ((unsigned)(first - N0) << kNearCountBits) | (unsigned)(last + 1 - first); }
+__device__ __forceinline__ void near_unpack(unsigned word, int N0, int &lo, int &hi)   // the lines [lo, hi)
+{
+    lo = N0 + (int)(word >> kNearCountBits);
+    hi = lo + (int)(word & ((1u << kNearCountBits) - 1u));
+}
+template <class W>   // unsigned (the writers), const unsigned (the readers)
+struct NearHandoff {
+    W *words; int K; int64_t nnu; int ntile;
+    __host__ __device__ size_t plane() const { return (size_t)K * nnu; }
+    __host__ __device__ W &word(int tier, size_t k, int64_t i) const { return words[(size_t)tier * plane() + (k * nnu + i)]; }
+    __host__ __device__ W &flag(int tier, size_t k, int tile) const { return words[2 * plane() + ((size_t)tier * K + k) * ntile + tile]; }
+    static size_t bytes(size_t K, int64_t nnu) { return K * nnu * kNearPointBytes + 2 * K * ((nnu + 63) / 64) * sizeof(unsigned); }
+};
+// the lines one lane has met so far that the series does not reach: first and last index per tier (empty: hi < lo)
+struct alignas(16) NearBounds {
+    int lo0, hi0, lo1, hi1;
+    __device__ __forceinline__ void reset() { lo0 = lo1 = 0x3fffffff; hi0 = hi1 = -1; }
+    __device__ __forceinline__ void note(bool in, double s, int j)   // line j (ascending) at s = x^2 + y^2; in: the pair is this kernel's (cut-off, radius)
+    {
+        if (in && s < kSerS) { lo0 = min(lo0, j); hi0 = j; }
+        if (in && s < kMidS) { lo1 = min(lo1, j); hi1 = j; }
+    }
+    __device__ __forceinline__ void merge(const NearBounds &o) { lo0 = min(lo0, o.lo0); hi0 = max(hi0, o.hi0); lo1 = min(lo1, o.lo1); hi1 = max(hi1, o.hi1); }
+    __device__ __forceinline__ unsigned word(int tier, int N0) const
+    {
+        const int lo = tier ? lo1 : lo0, hi = tier ? hi1 : hi0;
+        return hi >= lo ? near_pack(lo, hi, N0) : 0u;
+    }
+};
 
 // Far-wing term  A y/sqrt(pi) * u (1 + u p1(t) + u^2 p2(t) + u^3 p3(t)),  u = 1/s, t = y^2 u.  MODE:
 //   0  s >= 1e6 and y^2 <= 60 : 1 + u (1.5 + u (3.75 - 2 y^2))                          13 VALU instructions
@@ -1502,13 +1572,13 @@ template <bool MIXED, int S, bool LOR, bool EDGE = false>
 __global__ __launch_bounds__(256) CS_FAR_ATTR void k_voigt_far(const double *__restrict__ nu, int64_t nnu, int64_t L,
                                                     const LineHot *__restrict__ hot, const LineF32 *__restrict__ hot32,
                                                     const double *__restrict__ gnul, const WaveWin *__restrict__ win,
-                                                    const Zone *__restrict__ zones, int ntile, int nblk, double cut,
+                                                    int K, const Zone *__restrict__ zones, int ntile, int nblk, double cut,
                                                     double base, const double *__restrict__ extra,
-                                                    double *__restrict__ sigma, int accumulate, int2 *__restrict__ ranges,
-                                                    const IZone *__restrict__ iz, int nI, int ishift, const EdgeZone *__restrict__ edge,
-                                                    double *__restrict__ zero2 = nullptr)
+                                                    double *__restrict__ sigma, int accumulate, unsigned *__restrict__ ranges,
+                                                    const IZone *__restrict__ iz, int nI, int ishift, const EdgeZone *__restrict__ edge)
 {
-    // zero2 != NULL: the plane k_voigt_near will add this step's near-line pairs into (its first writer of the step clears it)
+    // (K sits in front of the pointers it is used with on purpose: behind `ntile` the same kernel takes 20-30 more VGPRs in its S = 2, 4
+    // forms on this compiler, by nothing but the argument offsets -- profiles/near_handoff_notes.md)
     // edge != NULL: the window ends [W0, eL) and [eR, W1) of the tile -- the cut-off edges and the far lines no interval could
     // take -- and the pieces [mL0, mL1), [mR0, mR1) between the interpolated sets and the near zone where the series in 1/dnu^2 holds
     // are summed for 16 states at a time on the matrix cores (k_voigt_edge_mx): skip them here.
@@ -1518,7 +1588,7 @@ __global__ __launch_bounds__(256) CS_FAR_ATTR void k_voigt_far(const double *__r
     // cost and add their partial sums through LDS -- S times more, S times shorter waves, for grids too small to fill the
     // chip otherwise (a nu-shard of a multi-GPU run, bake on a short grid).
     __shared__ double acc_sh[S > 1 ? 256 : 1];
-    __shared__ int4 rng_sh[S > 1 ? 256 : 1];
+    __shared__ NearBounds rng_sh[S > 1 ? 256 : 1];
     bool in_stretch;
     const int tb = tile_block(reinterpret_cast<const int32_t *>(win + ntile), 4 / S, in_stretch);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave-uniform by construction:
@@ -1528,10 +1598,10 @@ __global__ __launch_bounds__(256) CS_FAR_ATTR void k_voigt_far(const double *__r
     if (S == 1 && !work) return;
     // states from the last (the surface: highest pressure, widest lines, by far the longest waves of this kernel) to the first: the
     // grid is dealt out y-slowest, and the long waves must not be the tail
-    const int k = (int)(gridDim.y - 1 - blockIdx.y);
+    const int k = K - 1 - (int)blockIdx.y;
     const int64_t i = (int64_t)tile * 64 + lane;
     double acc = 0.0;
-    int bl = 0x3fffffff, bh = -1, cl = 0x3fffffff, ch = -1;
+    NearBounds nb; nb.reset();
     Zone z = {};
     bool core = false;   // (wave-uniform) the core of this (tile, state group) belongs to k_voigt_sub, the near-line hand-off with it
     if (work) {
@@ -1604,10 +1674,7 @@ __global__ __launch_bounds__(256) CS_FAR_ATTR void k_voigt_far(const double *__r
         // near zone: six-term series where s >= 1e3; the index ranges of this lane's s < 1e3 and s < 100 lines go to
         // k_voigt_near through `ranges` (relative to N0; empty = {0,0})
         if (HI(z.N1) > LO(z.N0)) {
-            const double q40 = sgpr_const(59.0625), q41 = sgpr_const(-787.5), q42 = sgpr_const(2835.0), q43 = sgpr_const(-3780.0),
-                         q44 = vgpr_const(1680.0);                                                            // a4 U8 in t
-            const double q50 = sgpr_const(324.84375), q51 = sgpr_const(-6496.875), q52 = sgpr_const(36382.5), q53 = sgpr_const(-83160.0),
-                         q54 = sgpr_const(83160.0), q55 = vgpr_const(-30240.0);                                // a5 U10 in t
+            const NearK nk = load_neark();
 #pragma unroll 4
             for (int j = LO(z.N0); j < HI(z.N1); j++) {
                 const LineHot h = hk[j];
@@ -1615,26 +1682,9 @@ __global__ __launch_bounds__(256) CS_FAR_ATTR void k_voigt_far(const double *__r
                 const double x = dv * h.p1;
                 const double s = __builtin_fma(x, x, h.p2);
                 const bool in = !(fabs(dv) > cut);
-                const double u = rcp_fast(s);
-                const double t = h.p2 * u;
-                const double p5 = __builtin_fma(__builtin_fma(__builtin_fma(__builtin_fma(__builtin_fma(q55, t, q54), t, q53), t, q52), t, q51), t, q50);
-                const double p4 = __builtin_fma(__builtin_fma(__builtin_fma(__builtin_fma(q44, t, q43), t, q42), t, q41), t, q40);
-                const double p3 = __builtin_fma(__builtin_fma(__builtin_fma(c.km120, t, c.k210), t, c.km105), t, c.k13p125);
-                const double p2 = __builtin_fma(__builtin_fma(c.k12, t, c.km15), t, c.k3p75);
-                const double p1v = __builtin_fma(-2.0, t, c.k1p5);
-                double P = __builtin_fma(u, p5, p4);
-                P = __builtin_fma(u, P, p3);
-                P = __builtin_fma(u, P, p2);
-                P = __builtin_fma(u, P, p1v);
-                P = __builtin_fma(u, P, 1.0);
-                // (the term is made opaque before the select: otherwise the compiler sinks the whole series into a branch under the
-                // lanes' exec mask -- which saves nothing on a wave that always has such lanes -- and with it the load of p3, so that
-                // every line waits twice for scalar memory instead of four lines waiting once)
-                double term = (h.p3 * u) * P;
-                asm volatile("" : "+v"(term));
+                const double term = near_zone_term(h, rcp_fast(s), c, nk);
                 acc += (in && s >= kSerS) ? term : 0.0;
-                if (in && s < kSerS) { bl = min(bl, j); bh = j; }
-                if (in && s < kMidS) { cl = min(cl, j); ch = j; }
+                nb.note(in, s, j);
                 // (tried, round 5: four lines per hand-unrolled step with the nine instructions of this range bookkeeping skipped -- a
                 //  scalar test of the records' y^2 >= 1e3, true for every line of the high-pressure states -- the kernel alone 0.275 ->
                 //  0.283 ms, the step +0.1 %: the compiler's own unrolling schedules the four scalar loads and series better)
@@ -1661,14 +1711,13 @@ __global__ __launch_bounds__(256) CS_FAR_ATTR void k_voigt_far(const double *__r
     }
     if (S > 1) {   // add the parts in part order (deterministic) and merge the index ranges
         acc_sh[threadIdx.x] = acc;
-        rng_sh[threadIdx.x] = make_int4(bl, bh, cl, ch);
+        rng_sh[threadIdx.x] = nb;
         __syncthreads();
         if (part != 0 || !work) return;
         for (int q = 1; q < S; q++) {
             const int o = threadIdx.x + 64 * q;
             acc += acc_sh[o];
-            const int4 r = rng_sh[o];
-            bl = min(bl, r.x); bh = max(bh, r.y); cl = min(cl, r.z); ch = max(ch, r.w);
+            nb.merge(rng_sh[o]);
         }
     }
     const bool live = i < nnu;
@@ -1676,24 +1725,17 @@ __global__ __launch_bounds__(256) CS_FAR_ATTR void k_voigt_far(const double *__r
         const size_t o = (size_t)k * nnu + i;
         if (!accumulate) sigma[o] = (base + (extra ? extra[o] : 0.0)) + acc;
         else if (acc != 0.0) sigma[o] += acc;   // (nothing to add -- most tiles of a sparse table: no trip to sigma at all; x + 0.0 = x bit for bit)
-        if (zero2) zero2[o] = 0.0;
     }
-    // hand-off to k_voigt_near<0>, <1>: per (nu, node) and tier one word, (first line - N0) << 12 | count -- 8 bytes per
-    // spectral point and node in all (cs_api.hip refuses tables dense enough to overflow 20 + 12 bits: check_near_density) --
-    // and per (tile, node) and tier a flag "some lane has candidates": tiles without any (most tiles of a sparse table, every
-    // tile of a high-pressure state, where y^2 alone exceeds 1e3) skip the store here and the whole wave there
+    // hand-off to k_voigt_near<0>, <1> (NearHandoff): the words where the tile has any, the flags always
     if (!LOR && !core) {   // (a Lorentz profile has no near-line kernels to hand anything to; a core's hand-off is k_voigt_sub's)
-        const unsigned r0 = (live && bh >= bl) ? ((unsigned)(bl - z.N0) << 12) | (unsigned)(bh + 1 - bl) : 0u;
-        const unsigned r1 = (live && ch >= cl) ? ((unsigned)(cl - z.N0) << 12) | (unsigned)(ch + 1 - cl) : 0u;
+        const NearHandoff<unsigned> ho{ranges, K, nnu, ntile};
+        const unsigned r0 = live ? nb.word(0, z.N0) : 0u, r1 = live ? nb.word(1, z.N0) : 0u;
         const bool any0 = __any(r0 != 0u), any1 = __any(r1 != 0u);
-        unsigned *__restrict__ rp = reinterpret_cast<unsigned *>(ranges);
-        const size_t plane = (size_t)gridDim.y * nnu;
-        if (any0 && live) rp[(size_t)k * nnu + i] = r0;
-        if (any1 && live) rp[plane + (size_t)k * nnu + i] = r1;
+        if (any0 && live) ho.word(0, k, i) = r0;
+        if (any1 && live) ho.word(1, k, i) = r1;
         if (lane == 0) {
-            unsigned *__restrict__ fl = rp + 2 * plane;
-            fl[(size_t)k * ntile + tile] = any0 ? 1u : 0u;
-            fl[((size_t)gridDim.y + k) * ntile + tile] = any1 ? 1u : 0u;
+            ho.flag(0, k, tile) = any0 ? 1u : 0u;
+            ho.flag(1, k, tile) = any1 ? 1u : 0u;
         }
     }
 }
@@ -2101,7 +2143,7 @@ template <int SW>
 __global__ __launch_bounds__(4096 / SW) void k_voigt_sub(const double *__restrict__ nu, int64_t nnu, int64_t L, const LineHot *__restrict__ hot,
                                                          const double *__restrict__ gnul, const Zone *__restrict__ zones,
                                                          const EdgeZone *__restrict__ edge, int ntile, int K, double cut,
-                                                         double *__restrict__ sigma, unsigned *__restrict__ rp, int prio, int assign, int lean_mode)
+                                                         double *__restrict__ sigma, unsigned *__restrict__ ranges, int prio, int assign, int lean_mode)
 {
     // assign != 0: `sigma` is the near-line plane of the step (its first writer on the side stream): every (state, point) of it is
     // WRITTEN here -- the sum where the tile has a core, a zero where it has not (and for the points of a ragged last tile) -- instead
@@ -2150,37 +2192,21 @@ __global__ __launch_bounds__(4096 / SW) void k_voigt_sub(const double *__restric
         jb = max(last, first);
     }
     // (every operand of the series is a vector register here -- the record is per lane -- so all its constants can be scalar)
-    const double k1p5 = sgpr_const(1.5), k3p75 = sgpr_const(3.75), k12 = vgpr_const(12.0), km15 = sgpr_const(-15.0), km105 = sgpr_const(-105.0),
-                 k13p125 = sgpr_const(13.125), k210 = sgpr_const(210.0), km120 = vgpr_const(-120.0);
-    const double q40 = sgpr_const(59.0625), q41 = sgpr_const(-787.5), q42 = sgpr_const(2835.0), q43 = sgpr_const(-3780.0), q44 = vgpr_const(1680.0);
-    const double q50 = sgpr_const(324.84375), q51 = sgpr_const(-6496.875), q52 = sgpr_const(36382.5), q53 = sgpr_const(-83160.0),
-                 q54 = sgpr_const(83160.0), q55 = vgpr_const(-30240.0);
-    struct { double k1p5, k3p75, k12, km15, km105, k13p125, k210, km120; } c = {k1p5, k3p75, k12, km15, km105, k13p125, k210, km120};
+    FarK c;
+    c.k1p5 = sgpr_const(1.5); c.k3p75 = sgpr_const(3.75); c.k12 = vgpr_const(12.0); c.km15 = sgpr_const(-15.0); c.km105 = sgpr_const(-105.0);
+    c.k13p125 = sgpr_const(13.125); c.k210 = sgpr_const(210.0); c.km120 = vgpr_const(-120.0);
+    const NearK nk = load_neark();
     double acc = 0.0;
-    int bl = 0x3fffffff, bh = -1, cl = 0x3fffffff, ch = -1;
+    NearBounds nb; nb.reset();
     // one line: the near-zone pass's series for this lane's (state, point) pair, hand-off ranges of the pairs the series does not reach
     auto eval = [&](const LineHot &h, int j) {
         const double dv = v - h.nul;
         const double x = dv * h.p1;
         const double s = __builtin_fma(x, x, h.p2);
         const bool in = fabs(dv) < Rg && !(fabs(dv) > cut);
-        const double u = rcp_fast(s);
-        const double t = h.p2 * u;
-        const double p5 = __builtin_fma(__builtin_fma(__builtin_fma(__builtin_fma(__builtin_fma(q55, t, q54), t, q53), t, q52), t, q51), t, q50);
-        const double p4 = __builtin_fma(__builtin_fma(__builtin_fma(__builtin_fma(q44, t, q43), t, q42), t, q41), t, q40);
-        const double p3 = __builtin_fma(__builtin_fma(__builtin_fma(c.km120, t, c.k210), t, c.km105), t, c.k13p125);
-        const double p2 = __builtin_fma(__builtin_fma(c.k12, t, c.km15), t, c.k3p75);
-        const double p1v = __builtin_fma(-2.0, t, c.k1p5);
-        double P = __builtin_fma(u, p5, p4);
-        P = __builtin_fma(u, P, p3);
-        P = __builtin_fma(u, P, p2);
-        P = __builtin_fma(u, P, p1v);
-        P = __builtin_fma(u, P, 1.0);
-        double term = (h.p3 * u) * P;
-        asm volatile("" : "+v"(term));
+        const double term = near_zone_term(h, rcp_fast(s), c, nk);
         acc += (in && s >= kSerS) ? term : 0.0;
-        if (in && s < kSerS) { bl = min(bl, j); bh = j; }
-        if (in && s < kMidS) { cl = min(cl, j); ch = j; }
+        nb.note(in, s, j);
     };
     // Range-only pass first where the piece tables say that no pair inside Rg can reach the series (EdgeZone::lean: the Doppler-dominated
     // state groups, where Rg is ~22 Doppler widths and s = 1e3 starts at ~38): the same x, s, `in` and hand-off ranges, no reciprocal and
@@ -2190,14 +2216,13 @@ __global__ __launch_bounds__(4096 / SW) void k_voigt_sub(const double *__restric
     bool full = true;
     if (lean_mode == 2 || (lean_mode == 0 && ((e.lean >> (((kq * NSW) >> 3) & 1)) & 1))) {   // (wave-uniform)
         bool any_series = false;
-        auto ranges = [&](double nul, double p1, double p2, int j) {
+        auto range_only = [&](double nul, double p1, double p2, int j) {
             const double dv = v - nul;
             const double x = dv * p1;
             const double s = __builtin_fma(x, x, p2);
             const bool in = fabs(dv) < Rg && !(fabs(dv) > cut);
             any_series |= in && s >= kSerS;
-            if (in && s < kSerS) { bl = min(bl, j); bh = j; }
-            if (in && s < kMidS) { cl = min(cl, j); ch = j; }
+            nb.note(in, s, j);
         };
         // (two lines per trip, the two record buffers swapping roles: the record of the line after next is in flight during a line, no copy)
         const LineHot *h0 = hk + (ja < jb ? ja : 0);
@@ -2206,17 +2231,17 @@ __global__ __launch_bounds__(4096 / SW) void k_voigt_sub(const double *__restric
         for (; j + 1 < jb; j += 2) {
             const double bn = hk[j + 1].nul, b1 = hk[j + 1].p1, b2 = hk[j + 1].p2;
             __builtin_amdgcn_sched_barrier(0);
-            ranges(an, a1, a2, j);
+            range_only(an, a1, a2, j);
             __builtin_amdgcn_sched_barrier(0);
             const LineHot *hn = hk + min(j + 2, jb - 1);
             an = hn->nul; a1 = hn->p1; a2 = hn->p2;
             __builtin_amdgcn_sched_barrier(0);
-            ranges(bn, b1, b2, j + 1);
+            range_only(bn, b1, b2, j + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (j < jb) ranges(an, a1, a2, j);
+        if (j < jb) range_only(an, a1, a2, j);
         full = __builtin_amdgcn_ballot_w64(any_series) != 0;
-        if (full) { bl = 0x3fffffff; bh = -1; cl = 0x3fffffff; ch = -1; }
+        if (full) nb.reset();
     }
     // (the records of the next TWO lines in flight, three buffers in rotation: k_voigt_sub alone 0.196 -> 0.184 ms, the step unchanged: round 5)
     // (two lines per trip here too, without the record copy: 51 -> 47 instructions per line, alone 0.158 -> 0.150 ms, the step lower in five of
@@ -2232,15 +2257,14 @@ __global__ __launch_bounds__(4096 / SW) void k_voigt_sub(const double *__restric
         }
     }
     const int N0 = zones[(size_t)(kin ? k : K - 1) * ntile + tile].N0;
-    const unsigned r0 = (kin && bh >= bl) ? ((unsigned)(bl - N0) << 12) | (unsigned)(bh + 1 - bl) : 0u;
-    const unsigned r1 = (kin && ch >= cl) ? ((unsigned)(cl - N0) << 12) | (unsigned)(ch + 1 - cl) : 0u;
-    const size_t plane = (size_t)K * nnu;
+    const NearHandoff<unsigned> ho{ranges, K, nnu, ntile};
+    const unsigned r0 = kin ? nb.word(0, N0) : 0u, r1 = kin ? nb.word(1, N0) : 0u;
     if (kin) {
         const size_t o = (size_t)k * nnu + i;
         if (assign) sigma[o] = acc;
         else if (acc != 0.0) sigma[o] += acc;
-        rp[o] = r0;            // (always written: whether the tile has candidates at all is known after the block's OR)
-        rp[plane + o] = r1;
+        ho.word(0, k, i) = r0;            // (always written: whether the tile has candidates at all is known after the block's OR)
+        ho.word(1, k, i) = r1;
     }
     // flags "some lane of (tile, state) has candidates", one word per tier: bit s = state NSW kq + s
     const uint64_t b0 = __builtin_amdgcn_ballot_w64(r0 != 0u), b1 = __builtin_amdgcn_ballot_w64(r1 != 0u);
@@ -2259,7 +2283,7 @@ __global__ __launch_bounds__(4096 / SW) void k_voigt_sub(const double *__restric
         unsigned f = 0u;
         for (int x = 0; x < NSW; x++) f |= fl_sh[x][tier];
         const int kk = NSW * kq + q;
-        if (kk < K) (rp + 2 * plane)[((size_t)tier * K + kk) * ntile + tile] = (f >> q) & 1u;
+        if (kk < K) ho.flag(tier, kk, tile) = (f >> q) & 1u;
     }
 }
 
@@ -2717,19 +2741,19 @@ __global__ __launch_bounds__(256) void k_phco2(const double *__restrict__ nu, in
 // (continued fraction for 100 <= s < 1e3, trapezoid + pole correction for s < 100) run with full lanes instead of
 // once per "deepest" lane -- then every lane sums its own results in ascending line order (deterministic).
 #define CS_NEAR_Q 256  // queue entries per wave; longer candidate lists go through the queue in windows
-#define CS_NEAR_R 1    // consecutive 64-point tiles per wave (2 and 4 fill the 64-wide trips better but measured slower: 0.47-0.58 vs 0.45 ms;
-static_assert(CS_NEAR_R == 1, "queue entries carry no sub-tile field");   //  a sub-tile field would have to come out of the 26 line-index bits)
-// candidates of lane l: for r = 0..R-1 the lines [lo[r], hi[r]) (absolute indices) against wavenumber (tile0 + r) * 64 + l
+// One 64-point tile per queue (two and four fill the 64-wide trips better but measured slower: 0.47-0.58 vs 0.45 ms, and their sub-tile field
+// would come out of the entry's line bits).  Entry = lane << 26 | line: cs_gas_upload and merged_table (cs_api.hip) refuse longer tables.
+constexpr int kNearLineBits = 26;
+__device__ __forceinline__ unsigned near_entry(int lane, int line) { return ((unsigned)lane << kNearLineBits) | (unsigned)line; }
+__device__ __forceinline__ int near_entry_lane(unsigned e) { return (int)(e >> kNearLineBits); }
+__device__ __forceinline__ int near_entry_line(unsigned e) { return (int)(e & ((1u << kNearLineBits) - 1u)); }
+// candidates of lane l: the lines [lo, hi) (absolute indices) against wavenumber tile * 64 + l
 template <int TIER>  // 0: 100 <= s < 1e3 (fad_mid), 1: s < 100 (fad_near)
-__device__ __forceinline__ void near_pass(const double *__restrict__ nu, int64_t nnu, int tile0, const int (&lo)[CS_NEAR_R],
-                                          const int (&hi)[CS_NEAR_R], double (&acc)[CS_NEAR_R], const LineHot *__restrict__ hk,
-                                          const LineCold *__restrict__ ck, double cut, unsigned *qidx, double *qres)
+__device__ __forceinline__ void near_pass(const double *__restrict__ nu, int64_t nnu, int tile, int lo, int hi, double &acc,
+                                          const LineHot *__restrict__ hk, const LineCold *__restrict__ ck, double cut, unsigned *qidx, double *qres)
 {
     const int lane = threadIdx.x & 63;
-    int cnt = 0, pre[CS_NEAR_R + 1];
-#pragma unroll
-    for (int r = 0; r < CS_NEAR_R; r++) { pre[r] = cnt; cnt += hi[r] - lo[r]; }
-    pre[CS_NEAR_R] = cnt;
+    const int cnt = hi - lo;
     // exclusive prefix sum of the candidate counts over the wave (rocPRIM: DPP row shifts + broadcasts, no LDS round trips)
     int incl;
     {
@@ -2740,13 +2764,10 @@ __device__ __forceinline__ void near_pass(const double *__restrict__ nu, int64_t
     const int off = incl - cnt;
     const int total = __builtin_amdgcn_readlane(incl, 63);
     for (int base = 0; base < total; base += CS_NEAR_Q) {   // wave-uniform
-        // this lane's candidates that fall into the window [base, base + Q): entry = lane | sub-tile | line
-#pragma unroll
-        for (int r = 0; r < CS_NEAR_R; r++) {
-            const int o = off + pre[r] - base;   // queue position of this sub-tile's first candidate
-            const int c0 = max(-o, 0), c1 = min(CS_NEAR_Q - o, hi[r] - lo[r]);
-            for (int c = c0; c < c1; c++) qidx[o + c] = ((unsigned)lane << 26) | (unsigned)(lo[r] + c);   // 6 + 26 bits: cs_gas_upload rejects L >= 2^26
-        }
+        // this lane's candidates that fall into the window [base, base + Q): queue positions o + c0 .. o + c1 - 1
+        const int o = off - base;
+        const int c0 = max(-o, 0), c1 = min(CS_NEAR_Q - o, cnt);
+        for (int c = c0; c < c1; c++) qidx[o + c] = near_entry(lane, lo + c);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         const int nwin = min(total - base, CS_NEAR_Q);
@@ -2758,10 +2779,10 @@ __device__ __forceinline__ void near_pass(const double *__restrict__ nu, int64_t
         double vn = 0.0;
         auto fetch = [&](int p) {
             en = qidx[p];
-            const int j = (int)(en & 0x3ffffffu);
+            const int j = near_entry_line(en);
             hn = hk[j];
             cn = ck[j];
-            const int64_t i = (int64_t)tile0 * 64 + (int)(en >> 26);
+            const int64_t i = (int64_t)tile * 64 + near_entry_lane(en);
             vn = nu[i < nnu ? i : nnu - 1];
         };
         if (lane < nwin) fetch(lane);
@@ -2784,24 +2805,19 @@ __device__ __forceinline__ void near_pass(const double *__restrict__ nu, int64_t
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int r = 0; r < CS_NEAR_R; r++) {   // ascending line order per (lane, sub-tile): deterministic
-            const int o = off + pre[r] - base;
-            const int c0 = max(-o, 0), c1 = min(CS_NEAR_Q - o, hi[r] - lo[r]);
-            for (int c = c0; c < c1; c++) acc[r] += qres[o + c];
-        }
+        for (int c = c0; c < c1; c++) acc += qres[o + c];   // ascending line order per lane: deterministic
         __builtin_amdgcn_wave_barrier();
     }
 }
 
 // one launch per tier: the tier-0 kernel is light (continued fraction, few registers, many waves in flight), the tier-1 kernel
-// carries the trapezoid + pole correction (exp, sincospi).  One wave = CS_NEAR_R consecutive tiles x one state.  The register
+// carries the trapezoid + pole correction (exp, sincospi).  One wave = nrep consecutive tiles x one state.  The register
 // allocator would give tier 1 161 VGPRs (3 waves per SIMD); capped at 96 (5 waves) it still does not spill and runs 12 % faster.
 template <int TIER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_voigt_near(const double *__restrict__ nu, int64_t nnu, int64_t L,
                                                      const LineHot *__restrict__ hot, const LineCold *__restrict__ cold,
-                                                     const Zone *__restrict__ zones, int ntile, int ngrp, int nrep, double cut,
-                                                     double *__restrict__ sigma, const int2 *__restrict__ ranges, int prio)
+                                                     const Zone *__restrict__ zones, int ntile, int K, int nrep, double cut,
+                                                     double *__restrict__ sigma, const unsigned *__restrict__ ranges, int prio)
 {
     wave_prio(prio);
     // nrep consecutive tiles per wave, one after the other: a wave that only reads its flag and exits still costs its launch -- 7.9e5 of
@@ -2810,43 +2826,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
     __shared__ unsigned qidx_s[4][CS_NEAR_Q];
     __shared__ double qres_s[4][CS_NEAR_Q];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp0 = __builtin_amdgcn_readfirstlane(((int)blockIdx.x * 4 + wv) * nrep);   // first group of CS_NEAR_R tiles
+    const int tile0 = __builtin_amdgcn_readfirstlane(((int)blockIdx.x * 4 + wv) * nrep);   // the wave's first tile
     const int k = blockIdx.y;
     const LineHot *__restrict__ hk = hot + (size_t)k * L;
     const LineCold *__restrict__ ck = cold + (size_t)k * L;
-    // two planes of packed words: tier 0 ranges, then tier 1 ranges, [gridDim.y][nnu] each; behind them the per-(tile, node) flags
-    const unsigned *__restrict__ fl = reinterpret_cast<const unsigned *>(ranges) + 2 * (size_t)gridDim.y * nnu + ((size_t)TIER * gridDim.y + k) * ntile;
-    const unsigned *__restrict__ rp = reinterpret_cast<const unsigned *>(ranges) + (size_t)TIER * gridDim.y * nnu + (size_t)k * nnu;
+    const NearHandoff<const unsigned> ho{ranges, K, nnu, ntile};
     // (the flags of the wave's tiles -- nrep <= 8 -- are requested together: one round trip, not one per tile)
     unsigned livemask = 0u;
 #pragma unroll
     for (int q = 0; q < 8; q++)
-        if (q < nrep && grp0 + q < ngrp && fl[grp0 + q] != 0u) livemask |= 1u << q;
+        if (q < nrep && tile0 + q < ntile && ho.flag(TIER, k, tile0 + q) != 0u) livemask |= 1u << q;
     livemask = __builtin_amdgcn_readfirstlane(livemask);
-    for (int grp = grp0; grp < min(grp0 + nrep, ngrp); grp++) {
-        if (!((livemask >> (grp - grp0)) & 1u)) continue;   // (wave-uniform: CS_NEAR_R = 1, group = tile)
-        const int tile0 = grp * CS_NEAR_R;
-        int lo[CS_NEAR_R], hi[CS_NEAR_R];
-        double acc[CS_NEAR_R];
-#pragma unroll
-        for (int r = 0; r < CS_NEAR_R; r++) {
-            const int tile = tile0 + r;
-            const int64_t i = (int64_t)tile * 64 + lane;
-            lo[r] = hi[r] = 0;
-            acc[r] = 0.0;
-            if (tile < ntile && i < nnu) {
-                const unsigned q = rp[i];
-                const int N0 = zones[(size_t)k * ntile + tile].N0;
-                lo[r] = N0 + (int)(q >> 12);
-                hi[r] = lo[r] + (int)(q & 0xfffu);
-            }
-        }
-        near_pass<TIER>(nu, nnu, tile0, lo, hi, acc, hk, ck, cut, qidx_s[wv], qres_s[wv]);
-#pragma unroll
-        for (int r = 0; r < CS_NEAR_R; r++) {
-            const int64_t i = (int64_t)(tile0 + r) * 64 + lane;
-            if (tile0 + r < ntile && i < nnu && acc[r] != 0.0) sigma[(size_t)k * nnu + i] += acc[r];
-        }
+    for (int tile = tile0; tile < min(tile0 + nrep, ntile); tile++) {
+        if (!((livemask >> (tile - tile0)) & 1u)) continue;   // (wave-uniform)
+        const int64_t i = (int64_t)tile * 64 + lane;
+        int lo = 0, hi = 0;
+        double acc = 0.0;
+        if (i < nnu) near_unpack(ho.word(TIER, k, i), zones[(size_t)k * ntile + tile].N0, lo, hi);
+        near_pass<TIER>(nu, nnu, tile, lo, hi, acc, hk, ck, cut, qidx_s[wv], qres_s[wv]);
+        if (i < nnu && acc != 0.0) sigma[(size_t)k * nnu + i] += acc;
     }
 }
 
@@ -2856,8 +2854,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
 // read once -- a 1/8 shard of the bench column 0.367 -> 0.360 ms, BASELINE configs[1] 0.136 -> 0.132, the bench column 1.947 -> 1.940
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_voigt_near_both(const double *__restrict__ nu, int64_t nnu, int64_t L,
                                                      const LineHot *__restrict__ hot, const LineCold *__restrict__ cold,
-                                                     const Zone *__restrict__ zones, int ntile, double cut,
-                                                     double *__restrict__ sigma, const int2 *__restrict__ ranges, int prio)
+                                                     const Zone *__restrict__ zones, int ntile, int K, double cut,
+                                                     double *__restrict__ sigma, const unsigned *__restrict__ ranges, int prio)
 {
     wave_prio(prio);
     __shared__ unsigned qidx_s[4][CS_NEAR_Q];
@@ -2866,29 +2864,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
     const int tile = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wv);
     const int k = blockIdx.y;
     if (tile >= ntile) return;
-    const unsigned *__restrict__ words = reinterpret_cast<const unsigned *>(ranges);
-    const size_t plane = (size_t)gridDim.y * nnu;
-    const unsigned *__restrict__ fl = words + 2 * plane;
-    const unsigned f0 = fl[(size_t)k * ntile + tile], f1 = fl[((size_t)gridDim.y + k) * ntile + tile];
+    const NearHandoff<const unsigned> ho{ranges, K, nnu, ntile};
+    const unsigned f0 = ho.flag(0, k, tile), f1 = ho.flag(1, k, tile);
     if (f0 == 0u && f1 == 0u) return;            // (wave-uniform)
     const int64_t i = (int64_t)tile * 64 + lane;
     const bool in = i < nnu;
-    const size_t o = (size_t)k * nnu + (in ? i : nnu - 1);
-    const unsigned q0 = (f0 != 0u && in) ? words[o] : 0u, q1 = (f1 != 0u && in) ? words[plane + o] : 0u;
+    const int64_t ic = in ? i : nnu - 1;
+    const size_t o = (size_t)k * nnu + ic;
+    const unsigned q0 = (f0 != 0u && in) ? ho.word(0, k, ic) : 0u, q1 = (f1 != 0u && in) ? ho.word(1, k, ic) : 0u;
     const int N0 = zones[(size_t)k * ntile + tile].N0;
     const double prev = sigma[o];
     const LineHot *__restrict__ hk = hot + (size_t)k * L;
     const LineCold *__restrict__ ck = cold + (size_t)k * L;
-    double a0[1] = {0.0}, a1[1] = {0.0};
+    double a0 = 0.0, a1 = 0.0;
+    int lo, hi;
     if (f0 != 0u) {
-        const int lo[1] = {N0 + (int)(q0 >> 12)}, hi[1] = {lo[0] + (int)(q0 & 0xfffu)};
+        near_unpack(q0, N0, lo, hi);
         near_pass<0>(nu, nnu, tile, lo, hi, a0, hk, ck, cut, qidx_s[wv], qres_s[wv]);
     }
     if (f1 != 0u) {
-        const int lo[1] = {N0 + (int)(q1 >> 12)}, hi[1] = {lo[0] + (int)(q1 & 0xfffu)};
+        near_unpack(q1, N0, lo, hi);
         near_pass<1>(nu, nnu, tile, lo, hi, a1, hk, ck, cut, qidx_s[wv], qres_s[wv]);
     }
-    if (in && (a0[0] != 0.0 || a1[0] != 0.0)) sigma[o] = (a0[0] != 0.0 ? prev + a0[0] : prev) + a1[0];
+    if (in && (a0 != 0.0 || a1 != 0.0)) sigma[o] = (a0 != 0.0 ? prev + a0 : prev) + a1;
 }
 
 // exp for the flux kernel, where it is half the instructions: Cody-Waite reduction x = n ln2 + r, |r| <= ln2 / 2, Taylor polynomial

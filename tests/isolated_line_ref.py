@@ -8,7 +8,8 @@ grids, each the smallest beyond the rules of cs_api.hip that select forms (SHORT
 the rule formulas as test_gpu_dispatch.py builds its grids); PLACEMENTS puts the centre of a line at the tile, interval and cut-off edges
 of the short grid.  On those grids a point is 35 and more Doppler widths from the next, so a (line, state) has a handful of probes in the
 line core; "col/fine" is the short grid's point count at a step of 2.5e-4 cm^-1, a third of a Doppler width, where the probes about the
-centre (+-12 steps, the sub-tile ends of three tiles, both sides of s = 100 and 1e3) are all core probes of the six narrower states.
+centre (+-12 steps, the sub-tile ends of three tiles, both sides of s = 100 and 1e3) are all core probes of the six narrower states.  "col/fine-rep8" is that grid as long as voigt_plan (cs_api.hip) asks before a wave of k_voigt_near<0>, <1> takes eight tiles
+in turn (rep_rules, rep_n) and one point more, with two lines (rep_centres) and the probes of the line core alone (core_probe_indices).
 
 Clusters.  A piece of the matrix-core tables shorter than 8 lines is left to the vector unit (sepzones_body, edgezones_body: "too
 short to be worth a wave's trip"), a window end goes to the 16 tile nodes from 16 lines on and is cut into phases from 48
@@ -258,6 +259,32 @@ def long_n(plan):
     return hi
 
 
+def rep_rules(n, nlines, K=NP_COL):
+    """the rule of cs_api.hip (voigt_plan) by which a wave of k_voigt_near<0>, <1> takes eight tiles in turn: half a million (tile, state)
+    waves, or a quarter of a million with fewer lines than two per tile"""
+    return tiles(n) * K >= 524288 or (nlines < 2 * tiles(n) and tiles(n) * K >= 262144)
+
+
+def rep_n(nlines):
+    """the smallest n that meets rep_rules"""
+    ok = lambda n: rep_rules(n, nlines)
+    lo, hi = 1000, 1000000
+    assert not ok(lo) and ok(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if ok(mid) else (mid, hi)
+    return hi
+
+
+REP_LINES, REP_TILE = 2, 1000                       # "col/fine-rep8": two lines; the first two points into this tile, the first of a wave's eight
+
+
+def rep_centres(nu):
+    """two points into tile REP_TILE (the core, +-90 points in the narrow states, lies in the last tile of one wave and the first of the
+    next), and the middle of the last complete tile (the core reaches the ragged tile, where a wave's eight tiles end at the grid's)"""
+    return [float(nu[64 * REP_TILE + 2]), float(nu[64 * (tiles(len(nu)) - 2) + 32])]
+
+
 def long_centres(n):
     span = FOUR_DNU * (n - 1)
     return LONG_NU0 + 0.5 * LONG_GAP + 0.00317 + LONG_GAP * np.arange(int((span - 0.5 * LONG_GAP) // LONG_GAP) + 1)
@@ -319,6 +346,20 @@ def probe_indices(nu, c, sizes, cut, crossings):
     return sorted(out)
 
 
+def subtile_ends(nu, c):
+    """first and last point of the 8-point sub-tiles (the tiles' own ends among them) of the centre's tile and its two neighbours"""
+    n = len(nu)
+    tc = min(max(int(round((c - nu[0]) / float(nu[1] - nu[0]))), 0), n - 1) // 64
+    return {i for t in (tc - 1, tc, tc + 1) for q in range(8) for i in (64 * t + 8 * q, 64 * t + 8 * q + 7) if 0 <= i < n}
+
+
+def core_probe_indices(nu, c, cut, crossings, alpha, gamma):
+    """the probes of probe_indices with s < 1e4 in the probe's state, the two sides of `crossings` (those up to s = 1e4: Case._build) and
+    subtile_ends: what a case about the near-line kernels is for -- the tile and interval ends of the whole cut-off are col/long's"""
+    keep = subtile_ends(nu, c) | {i for d in crossings for sg in (-1.0, 1.0) for i in _near(nu, c + sg * d)}
+    return sorted(i for i in probe_indices(nu, c, (), cut, crossings) if i in keep or s_of(nu[i] - c, alpha, gamma) < 1e4)
+
+
 def crossings_of(alpha, gamma, alpha_w, gamma_w, cut):
     """(distances, [(kind, threshold, distance)]): where s crosses S_CROSS and |d| crosses R8, R4, R3 of the state's own widths and of its
     group's widest -- those inside the cut-off (beyond it nothing is evaluated, and another line may be)"""
@@ -336,10 +377,12 @@ def crossings_of(alpha, gamma, alpha_w, gamma_w, cut):
 
 class Case:
     """one (grid, lines, states, shape code): lines = [(line dict, concentration C_l, Pp / P of its gas)], states = [(T, P)]; `which` maps a
-    line to the states it is compared in (default: every compared state).  C_l = None: a cs_shape_* call (no factor, Pp = frac x P)."""
+    line to the states it is compared in (default: every compared state).  C_l = None: a cs_shape_* call (no factor, Pp = frac x P).
+    core_only: the probes of core_probe_indices instead of probe_indices."""
 
-    def __init__(self, cs, nu, sizes, tables, states, code=0, cut=CUT, concs=None, fracs=None, ksel=None, which=None):
+    def __init__(self, cs, nu, sizes, tables, states, code=0, cut=CUT, concs=None, fracs=None, ksel=None, which=None, core_only=False):
         self.nu, self.sizes, self.code, self.cut, self.tables = np.asarray(nu, float), tuple(sizes), code, cut, tables
+        self.core_only = core_only
         self.states = [(float(T), float(P)) for T, P in states]
         self.K = len(self.states)
         self.lines, self.ghosts = [], []
@@ -372,9 +415,13 @@ class Case:
                 grp = range(16 * (k // 16), min(16 * (k // 16) + 16, self.K))
                 kw = max(grp, key=lambda q: radius(4, *w[q]))
                 dist, named = crossings_of(*w[k], *w[kw], self.cut)
+                if self.core_only:
+                    named = [x for x in named if s_of(x[2], *w[k]) <= 1e4 * (1.0 + S_EDGE)]
+                    dist = [x[2] for x in named]
                 self.cross[(k, l)] = named
                 c = self.centre(k, l)
-                pr += [(k, i, l) for i in probe_indices(self.nu, c, self.sizes, self.cut, dist)]
+                idx = core_probe_indices(self.nu, c, self.cut, dist, *w[k]) if self.core_only else probe_indices(self.nu, c, self.sizes, self.cut, dist)
+                pr += [(k, i, l) for i in idx]
         reach = lambda k, i, l: abs(self.nu[i] - self.centre(k, l)) <= self.cut
         others = lambda k, i, l: any(reach(k, i, m) for m in range(len(self.lines)) if m != l)
         self.pr = sorted(p for p in set(pr) if reach(*p) or not others(*p))      # (a point beyond its line's cut-off that another line reaches is that line's)
@@ -524,7 +571,7 @@ class Cases:
     def names(self):
         return ([f"batch/{p}" for p in placements()] + ["batch/low-vvh", "batch/fine", "col/short", "col/short-lorentz", "col/short-ckd", "col/low-vvh",
                 "col/low-ckdvvh", "col/short-shifted", "col/short-merge", "col/four", "col/long", "col/high", "col/short-cluster",
-                "col/four-cluster", "col/long-cluster", "col/fine"])
+                "col/four-cluster", "col/long-cluster", "col/fine", "col/fine-rep8"])
 
     def __getitem__(self, name):
         if name not in self._made:
@@ -557,6 +604,9 @@ class Cases:
         if what == "fine":               # the short grid's point count at 1/100 of its step: x = 0.3 .. 0.4 per point, every probe about the centre in the core
             nu = grid(FINE_NU0, FINE_DNU, SHORT_N)
             return one(nu, [one_line_table(cs, float(nu[20 * 64 + 32]))])
+        if what == "fine-rep8":          # the fine grid as long as a wave of k_voigt_near<0>, <1> needs to take eight tiles, and one point more
+            nu = grid(FINE_NU0, FINE_DNU, rep_n(REP_LINES) + 1)
+            return one(nu, [one_line_table(cs, rep_centres(nu))], core_only=True)
         if what == "short-lorentz":
             return one(self.short, [one_line_table(cs, mid)], 1)
         if what == "short-ckd":

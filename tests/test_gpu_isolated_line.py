@@ -34,12 +34,14 @@ Recorded figures (MI355X; worst error / bound over the forms of a case, hard | s
   col/low-ckdvvh        976 probes  2 forms   0.037 | 0.218
   col/short-shifted    1318 probes  2 forms   0.730 | 0.746
   col/fine             1435 probes  4 forms   0.051 | 0.338        (514 of them in the line core, s < 1e3; one and two near-line launches)
+  col/fine-rep8        1303 probes  2 forms   0.045 | 0.333        (885 of them in the line core; 2.75e5 points: eight tiles per wave in k_voigt_near<0>, <1>,
+                                                                    two lines whose cores cross a wave's last tile and the grid's ragged last tile)
   cs_shape_batch and cs_shape_points, worst of the placements   0.062 (fine) | 0.347 (between-tiles-1024); exactly-cut (points only)
   0.007 | 0.059; batch/fine (342 probes in the line core) 0.062 | 0.340; two P = 0 states through cs_shape_points 0.246, exact 0 from s = 100 on
 With the sharp bound on every probe (it began at s = 1e3 before) no ratio above moved but col/short-shifted's, whose worst probe is now one
 of the line core.  The line core alone (s < 1e3: fad_mid and fad_near in the near-line kernels, fad_re in k_linesum; worst error / sharp
 bound): col/short, -cluster, -merge 0.103; col/four 0.174; col/long 0.144; col/high 0.349; col/short-ckd 0.137; col/low-vvh, -ckdvvh
-0.053; col/short-shifted 0.746; col/fine 0.196; batch/fine 0.276; batch/mid-tile 0.196; the other placements 0.061 and less.
+0.053; col/short-shifted 0.746; col/fine 0.196; col/fine-rep8 0.289; batch/fine 0.276; batch/mid-tile 0.196; the other placements 0.061 and less.
 A seeded defect in the line core (c1[1] of fad_near raised by 1e-13, a scratch build): every Voigt case here fails the sharp bound, by
 up to 2.63, and none the hard bound -- tests/test_gpu_faddeeva.py has the record.
 With rcp_fast at the 3e-15 its header first claimed, the sharp ratios were 0.7 .. 0.98 and, with interpolation off, 1.04 .. 1.21 at
@@ -210,13 +212,16 @@ def column_forms(cs, cases, name, forms, shape="voigt", pshift=False):
 HIGH_FORMS = [BY_NAME[n] for n in ("default", "matrix-cores-2", "interp-off-vector")]
 # the line core on a grid of a third of a Doppler width per point: both forms of the near-line pass, with and without the sub-tile cores
 FINE_FORMS = [BY_NAME[n] for n in ("default", "near-two-launches", "matrix-cores-0", "interp-off")]
+# eight tiles per wave in k_voigt_near<0>, <1> (voigt_plan: nrep = 8, which has no switch but the grid): two launches whatever key 16 says
+_rep8 = lambda r: r["info"]["near_launches"] == 2 and r["work"]["near_pairs_tier0"] > 0 and r["work"]["near_pairs_tier1"] > 0
+REP8_FORMS = [Form("default", mc=None, expect=_rep8), Form("near-plane-off", tune={7: 0}, expect=lambda r: _rep8(r) and not _d(r)["streams"] & 2)]
 COLUMN_CASES = [("col/short", FORMS, "voigt", False), ("col/four", FORMS, "voigt", False), ("col/long", LONG_FORMS, "voigt", False),
                 ("col/short-cluster", FORMS, "voigt", False), ("col/four-cluster", FORMS, "voigt", False),
                 ("col/long-cluster", LONG_FORMS, "voigt", False), ("col/high", HIGH_FORMS, "voigt", False),
                 ("col/short-merge", MERGE_FORMS, "voigt", False), ("col/short-lorentz", CODE_FORMS, "lorentz", False),
                 ("col/short-ckd", CODE_FORMS, "voigtCKD", False), ("col/low-vvh", CODE_FORMS, "voigtVVH", False),
                 ("col/low-ckdvvh", CODE_FORMS, "voigtCKDVVH", False), ("col/short-shifted", CODE_FORMS, "voigt", True),
-                ("col/fine", FINE_FORMS, "voigt", False)]
+                ("col/fine", FINE_FORMS, "voigt", False), ("col/fine-rep8", REP8_FORMS, "voigt", False)]
 
 
 @pytest.mark.parametrize("name,forms,shape,pshift", COLUMN_CASES, ids=[c[0] for c in COLUMN_CASES])

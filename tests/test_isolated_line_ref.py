@@ -36,6 +36,15 @@ def test_grids_sit_on_the_rules(cs, cases):
     assert nu[0] < pl["edge-in-first-tile"][0] + I.CUT < nu[1] and pl["exactly-cut"][0] + I.CUT == nu[0]
     assert sorted({K for _, K in pl.values()} | {cases["batch/low-vvh"].K}) == [1, 16, 17, 33]
     assert I.LOW_CENTRE - I.CUT <= 0.0 and cases.low[0] + I.LOW_CENTRE <= I.CUT
+    # the eight-tiles-per-wave grid: the smallest point count of the rule and one point more (a ragged last tile); two lines more than
+    # 2 x cut apart, one two points into a tile that is the first of a wave's eight, one in the middle of the last complete tile
+    c = cases["col/fine-rep8"]
+    n = len(c.nu)
+    assert I.rep_rules(n - 1, I.REP_LINES) and not I.rep_rules(n - 2, I.REP_LINES) and n % 64 not in (0, 1) and I.tiles(n) * I.NP_COL < 524288
+    assert c.nu[0] == I.FINE_NU0 and abs((c.nu[-1] - c.nu[0]) / (n - 1) - I.FINE_DNU) < 1e-12 and len(c.lines) == I.REP_LINES
+    ca, cb = (ln[0]["nu"] for ln in c.lines)
+    assert cb - ca > 2 * I.CUT and I.REP_TILE % 8 == 0 and ca == c.nu[64 * I.REP_TILE + 2] and cb == c.nu[64 * (I.tiles(n) - 2) + 32]
+    print(f"eight-tile grid: {n} points, {I.tiles(n)} tiles, lines at {ca:.4f} and {cb:.4f}")
 
 
 def test_probes_isolated_capped_and_above_underflow(cs, cases):
@@ -115,7 +124,25 @@ def test_crossing_probes_straddle(cs, cases):
     print(f"{n} crossings straddled")
 
 
-@pytest.mark.parametrize("name", ["batch/mid-tile", "batch/between-tiles-1024", "batch/low-vvh", "batch/fine"])
+def test_rep8_core_probes(cs, cases):
+    """col/fine-rep8, per line: at least as many probes in each tier of the near-line kernels (100 <= s < 1e3, s < 100) as
+    test_gpu_isolated_line.py::test_coverage asks of col/fine (200); the cores of both lines cross the tile ends the case is about.
+    One count cannot reach 200: the second line sits in the last complete tile so that its core runs into the ragged tile and off the
+    grid, and the ring 100 <= s < 1e3 (30 to 90 points from the centre in the narrow states) has its upper half beyond the last point --
+    wherever in that tile the centre is put, at most 170 such probes exist.  The lower half is whole, so half the figure is asked there."""
+    c = cases["col/fine-rep8"].reference()
+    m, _ = c.sharp(I.RunForm())
+    line = np.array([l for _, _, l in c.pr])
+    nt = I.tiles(len(c.nu))
+    for l, tiles_met in ((0, (I.REP_TILE - 1, I.REP_TILE, I.REP_TILE + 1)), (1, (nt - 3, nt - 2, nt - 1))):
+        core0, core1 = (int(np.sum(m & (line == l) & sel)) for sel in ((c.s >= 100.0) & (c.s < 1e3), c.s < 100.0))
+        assert core1 >= 200 and core0 >= (200 if l == 0 else 100), (l, core0, core1)
+        met = sorted({int(i) // 64 for i in c.i[m & (line == l) & (c.s < 1e3)]})
+        assert set(tiles_met) <= set(met), (l, met)
+        print(f"col/fine-rep8 line {l}: {core0} probes with 100 <= s < 1e3, {core1} with s < 100, in tiles {met}")
+
+
+@pytest.mark.parametrize("name", ["batch/mid-tile", "batch/between-tiles-1024", "batch/low-vvh", "batch/fine", "col/fine-rep8"])
 def test_oracle_meets_both_bounds(cs, O, cases, name):
     """the oracle at the device's probes: within lineparam_bound(C0_ORACLE) everywhere, and within the sharp bound of the scalar form (no
     reciprocal terms: its divisions are IEEE; below s = 1e4 faddeeva_ref.bound(x, y, "scalar") per probe, the line core included) -- the
@@ -130,7 +157,7 @@ def test_oracle_meets_both_bounds(cs, O, cases, name):
         T, P = c.states[k]
         s = TL.oracle_sigma(cs, O, c.code, c.nu[pts], sl, T, P, I.CONC * P, c.cut)
         m = c.k == k
-        got[m] = s[col[m]]
+        got[m] = (c.lines[0][1] or 1.0) * s[col[m]]        # (a column case: the concentration is a factor of its values)
     hard = np.array([R.lineparam_bound(f, R.C0_ORACLE) for f in c.infos])
     worst_h = R.check(got, c.want, hard, c.zero, what=name + ", hard")
     m, b = c.sharp(I.RunForm(scalar=True, interp=False), c0=R.C0_ORACLE)
@@ -138,7 +165,7 @@ def test_oracle_meets_both_bounds(cs, O, cases, name):
     assert R.split(c.want[~c.zero])[1] == 0.0          # the underflow class is empty
     assert np.array_equal(m, ~c.zero)                  # every probe with a term is under the sharp bound, the core included
     core = [int(np.sum(m & (c.s < 100.0))), int(np.sum(m & (c.s >= 100.0) & (c.s < 1e3))), int(np.sum(m & (c.s >= 1e3) & (c.s < 1e4)))]
-    assert min(core) >= (100 if name == "batch/fine" else 4 if name == "batch/mid-tile" else 0), core
+    assert min(core) >= (100 if name in ("batch/fine", "col/fine-rep8") else 4 if name == "batch/mid-tile" else 0), core
     lo = c.s < 1e4
     worst_c = R.check(got[m & lo], c.want[m & lo], b[m & lo], c.zero[m & lo], what=name + ", sharp, s < 1e4")
     print(f"{name}: {len(c.pr)} probes ({int(m.sum())} sharp; s < 100: {core[0]}, < 1e3: {core[1]}, < 1e4: {core[2]}), oracle error / bound  hard {worst_h:.3f}  "

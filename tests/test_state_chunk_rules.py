@@ -11,8 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "clearsky.jl_amd", "csrc")
 
 # the two sides of the driver's per-state bytes: Z is the caller's device plane (NULL: the driver owns the chunk's sigma)
-OWNED = "(size_t)nnu * (sizeof(double) + sizeof(int2))"     # rule "shape"
-IN_PLACE = "(size_t)nnu * sizeof(int2)"                     # rule "bake"
+OWNED = "(size_t)nnu * (sizeof(double) + kNearPointBytes)"   # rule "shape"
+IN_PLACE = "(size_t)nnu * kNearPointBytes"                   # rule "bake"
 # function -> (rules, per-state bytes, kc) as written in the source, whitespace collapsed
 SOURCE = {
     "static int gas_states(": (("shape", "bake"),
@@ -21,7 +21,7 @@ SOURCE = {
         "const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));"),
     "int cs_column_batch(": (("column",),
         "const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + "
-        "(size_t)c.nnu * sizeof(int2) + (any_ped ? ped_bytes(1, (int64_t)maxL) : 0) + (vvh2 ? (size_t)c.nnu * sizeof(double) : 0);",
+        "(size_t)c.nnu * kNearPointBytes + (any_ped ? ped_bytes(1, (int64_t)maxL) : 0) + (vvh2 ? (size_t)c.nnu * sizeof(double) : 0);",
         "const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BK, ((size_t)8 << 30) / std::max<size_t>(per_state, 1), "
         "(size_t)65535}));"),
 }
@@ -84,6 +84,8 @@ def test_sizes_the_rules_count():
            "sizeof(double); }" in _norm(src)
     assert re.search(r"#define CS_PED_B (\d+)", k).group(1) == str(SC.PED_B)
     assert "struct __attribute__((aligned(32))) LineHot { double nul, p1, p2, p3; };" in k and SC.HOT == 32
+    # the two 32-bit range words of a (state, point) in the near-line hand-off (NearHandoff): the INT2 of the rules
+    assert "constexpr size_t kNearPointBytes = 2 * sizeof(unsigned);" in k and SC.INT2 == 2 * 4
     assert "struct __attribute__((aligned(16))) LineCold { double y, A; };" in k and SC.COLD == 16
     assert "struct __attribute__((aligned(16))) LineF32 { float d, y2, ay, c2; };" in k and SC.F32 == 16
     assert SC.ped_bytes(1, 100) == (300 + 2) * 8
