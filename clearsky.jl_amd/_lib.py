@@ -25,6 +25,11 @@ CS_CIA_EXTRAPOLATE, CS_CIA_SINGLES, CS_CIA_RADIATION = 1, 2, 4   # include/clear
 # CS_WORK_FLAGS -- Column.work()["dispatch"]["flags"]
 WORK_COUNT = 41
 DISPATCH_FLAGS = {"TNODES": 1, "NEAR_MEMSET": 2, "RT_STREAMS": 4, "BAND_SUM": 8, "FAR64_SHARED": 16, "CHUNK4": 32, "CASCADE_ASIDE": 64}
+# include/clearsky_hip_dev.h, CS_TUNE_*: the keys of cs_set_tuning by name (Context.set_tuning takes either; tests/test_host.py holds the
+# table against the header, which describes each key)
+TUNING = {"FUSE_APPLY": 0, "SMALL_MX": 1, "NODES_STREAM": 2, "MARGIN": 3, "GRAPH": 4, "RT_STREAMS": 5, "NSPLIT_LEVELS": 6, "NEAR_STREAM": 7,
+          "MX_MIN_STATES": 8, "PH_OWN_CORE": 9, "PH_NODES": 10, "FAR64": 11, "CASCADE": 12, "NODES_SPLIT": 13, "EDGE_FULL": 14, "FLUX": 15,
+          "NEAR_PRIO": 16, "FAR64_SHARED": 17, "SUB_LEAN": 18, "NEAR_MEMSET": 19, "TABLES_MERGE": 21, "FAR_SPLIT": 22, "EDGE_POINTS": 23}
 SHAPES = {"voigt": 0, "lorentz": 1, "doppler": 2, "PHCO2": 3, "phco2": 3, "voigtCKD": 4, "voigtVVH": 5,
           "voigtCKDVVH": 6}   # 4: CS_SHAPE_VOIGT_CKD, pedestal-removed Voigt; 5: CS_SHAPE_VOIGT_VVH, Van Vleck-Huber Voigt; 6: CS_SHAPE_VOIGT_CKD_VVH, both
 

@@ -15,7 +15,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import constants as K
-from ._lib import (CHEB_LD, CS_MAX_ACCEL, CS_MAX_CIA, CS_MAX_GAS, CS_MAX_TABLE, CS_SHAPE_PSHIFT, SHAPES, WORK_COUNT, ClearSkyHIPError, as_f64, check,
+from ._lib import (CHEB_LD, CS_MAX_ACCEL, CS_MAX_CIA, CS_MAX_GAS, CS_MAX_TABLE, CS_SHAPE_PSHIFT, SHAPES, TUNING, WORK_COUNT, ClearSkyHIPError, as_f64, check,
                    dptr, lib)
 from .hitran import TMAX, TMIN, SpectralLines
 from .cia import CIATables, Continuum, cia, readcia
@@ -289,11 +289,10 @@ class Context:
         launch set per gas."""
         check(lib().cs_set_merge(self._h, int(bool(on))))
 
-    def set_tuning(self, key: int, value: int):
-        """A/B switches (cs_set_tuning, a lab entry point: include/clearsky_hip_dev.h describes each key): where the interpolated
-        wings are applied, matrix-core kernels on short grids, side streams, interpolation margin, hipGraph replay, flux sweeps per
-        stream, series radius rank, PHCO2 core and node counts, low-order far pieces, level cascade, fused flux tail, ..."""
-        check(lib().cs_set_tuning(self._h, int(key), int(value)))
+    def set_tuning(self, key, value: int):
+        """A/B switches (cs_set_tuning, a lab entry point): `key` is a name of TUNING or its integer; include/clearsky_hip_dev.h
+        describes each key (CS_TUNE_*) and the bits of its value."""
+        check(lib().cs_set_tuning(self._h, TUNING[key] if isinstance(key, str) else int(key), int(value)))
 
     def slot_of(self, sl: SpectralLines, keep=(), shift: bool = False) -> int:
         """Upload `sl` (once) and return its gas slot.  `keep`: tables that must stay where they are (the other gases of the call this

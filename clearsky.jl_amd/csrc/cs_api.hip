@@ -63,7 +63,7 @@ struct VoigtPlan {
     int nsplit;                 // k_cheb_nodes_mx: intervals (from q0 on) the four waves of a block share ...
     unsigned nblk_mx;           // ... and its blocks
     bool far_R;                 // ... its far pieces on their level's nfar nodes (re-interpolation matrices in use), else on all 64
-    bool far64_shared;          // ... on all 64 because every item is shared (key 17), not for want of the matrices
+    bool far64_shared;          // ... on all 64 because every item is shared (CS_TUNE_FAR64_SHARED), not for want of the matrices
     int nfar[CS_MAX_LEVEL];
     int far_split;              // waves per tile of k_voigt_far
     bool edge_big;              // k_voigt_edge_mx<1>: one wave per (tile, group); else <4>
@@ -71,7 +71,7 @@ struct VoigtPlan {
     bool tnodes;                // ... and sums the lines inside every point's cut-off on the 16 tile nodes
     int nrep;                   // near-line kernels: how many consecutive tiles a wave takes in turn
     bool near_both;             // ... both tiers in one launch
-    int sub_lean;               // k_voigt_sub's range-only pass (cs_set_tuning key 18)
+    int sub_lean;               // k_voigt_sub's range-only pass (CS_TUNE_SUB_LEAN)
     unsigned nb_zones, nb_iz, nb_sep, nb_edge;   // blocks of the zone, interval-zone and piece-table parts of the setup launches
 };
 
@@ -320,7 +320,7 @@ struct Column {
     int launches = 0;            // kernel launches of the last cs_column_run
     bool near_live = false;      // the last cs_column_run left its near-line pairs in sigma2 (k_rt read both planes): cs_column_sigma_fetch folds them in
     hipStream_t last_stream = nullptr;   // the stream that run was enqueued on (cs_column_fetch waits for it, not for the whole device)
-    // cs_set_tuning key 4: the step as ONE hipGraph launch (captured on the second run after a change, replayed from the third on):
+    // CS_TUNE_GRAPH: the step as ONE hipGraph launch (captured on the second run after a change, replayed from the third on):
     // kernel arguments are device addresses that stay put between cs_column_update_state calls, so only what changes launch
     // geometry or pointers (setup, tables, CIA pairs, accelerated absorber, spectra switched on or off) drops the graph -- and, for a
     // PHCO2 group, new states that change which chi-regions its levels carry (ph_wide_regions: cs_column_update_state compares), or any
@@ -339,7 +339,7 @@ struct Column {
     DevBuf hot, cold, sigma, sigma2, tau, Mup, Mdn, partial, F, stage, ranges;   // sigma2: the near-line plane (k_voigt_near on a side stream)
     DevBuf ped;                // launch_pedestal's workspace for K states (columns with a code-4 group)
     DevBuf vvh;                // the line sum of a code-5 group that is not the column's first, before launch_vvh (K x nnu)
-    DevBuf fluxdbg;            // k_flux_scan: phase time stamps of block 0 (cs_set_tuning key 15 | 128; cs_column_work CS_WORK_FLUX_SCAN_NS ..)
+    DevBuf fluxdbg;            // k_flux_scan: phase time stamps of block 0 (CS_T15_SCAN_STAMPS; cs_column_work CS_WORK_FLUX_SCAN_NS ..)
     DevBuf ticket;             // k_flux: blocks finished (the last one adds the block partials up)
     int flux_form_last = 0;      // which flux kernel the last run used (flux_form)
     StepLog log_last;            // of the last cs_column_run (cs_column_info out[6], out[7]); its disp also of the last cs_column_batch
@@ -362,8 +362,101 @@ static void drop_graph(Column &c)
     c.runs_since_change = 0;
 }
 
+// The lab switches of a context (cs_set_tuning, cs_set_matrix_cores; include/clearsky_hip_dev.h describes each), one named field per
+// switch.  set_tuning() and set_matrix_cores() below decode the caller's integers into it and are the only code that knows a key number
+// or a bit of a key; a Settings{} is what cs_create sets.  Multi-valued switches keep the caller's integer as given.
+struct Settings {
+    int matrix_nodes = 1;           // cs_set_matrix_cores & 3: far-wing node sums and window ends on v_mfma_f64 -- 0 never, 1 where the grid fills the chip, 2 always
+    bool matrix_core = true;        // cs_set_matrix_cores | 4 clears it: the window core on sub-tiles (k_voigt_sub + the second mask of k_voigt_edge_mx)
+    bool fuse_apply = false;        // CS_TUNE_FUSE_APPLY: k_voigt_edge_mx carries the interpolated wings to the grid where the column has one launch group
+    bool small_mx = true;           // CS_TUNE_SMALL_MX: the matrix-core kernels on short grids too (their four-waves-per-item variants)
+    int nodes_stream = 2;           // CS_TUNE_NODES_STREAM: node sums on a side stream -- 0 never, 1 on short grids, 2 always
+    double margin = kChebMargin;    // CS_TUNE_MARGIN (per cent): distance of an interval's interpolated set, in half-widths
+    bool graph = false;             // CS_TUNE_GRAPH: cs_column_run replays the step as one hipGraph
+    bool rt_streams = true;         // CS_TUNE_RT_STREAMS: k_rt_streams on short grids
+    int nsplit_levels = 1;          // CS_TUNE_NSPLIT_LEVELS: interval sizes (largest first) whose node sums four waves share in k_cheb_nodes_mx
+    int near_stream = 1;            // CS_TUNE_NEAR_STREAM: near-line kernels on a second side stream -- 0 never, 1 where it pays, 2 always
+    int mx_min_states = 7;          // CS_TUNE_MX_MIN_STATES: states of a group beyond their series radius for a line to join its matrix-core node piece
+    bool ph_own_core = false;       // CS_TUNE_PH_OWN_CORE: the pairs within 3 cm^-1 in k_phco2's own core loop
+    int ph_nodes = 0;               // CS_TUNE_PH_NODES: PHCO2 levels -- bit 0: 64 nodes on every interval, bit 1: the tiles as 64-point intervals too
+    bool far64 = false;             // CS_TUNE_FAR64: the far pieces of the matrix-core node sums on all 64 nodes
+    int cascade = 0;                // CS_TUNE_CASCADE: levels folded into the smallest -- 0 where it pays (cascade_pays), 1 always, 2 never
+    int nodes_split = 0;            // CS_TUNE_NODES_SPLIT: k_cheb_nodes with four waves per (interval, state) -- 0 on short grids, 1 always, 2 never
+    bool edge_full = false;         // CS_TUNE_EDGE_FULL: k_voigt_edge_mx multiplies all four sub-tiles for every line of a cut-off edge
+    int flux_form = 0;              // CS_TUNE_FLUX & CS_T15_FORM_MASK: cross-sections finished in the flux kernel -- 0 where it pays, 1 never, 2 always
+    bool freduce_always = false;    // CS_T15_FREDUCE: the block partials always added by k_freduce
+    bool chunk4 = false;            // CS_T15_CHUNK4: k_flux_chunk with four waves per SIMD
+    bool tables_one_thread = false; // CS_T15_TABLES_ONE_THREAD: k_mxzones instead of k_mxzones16
+    bool multi_recut = false;       // CS_T15_MULTI_RECUT: cs_fluxes_discretized_multi re-cuts its partition also on shared devices
+    bool scan_stamps = false;       // CS_T15_SCAN_STAMPS: phase time stamps of block 0 of k_flux_scan
+    bool no_cascade_aside = false;  // CS_T15_NO_CASCADE_ASIDE: no folding of the levels on the node-sum side stream of short grids
+    bool scan_mid = false;          // CS_T15_SCAN_MID: the scan form also on grids of 1024 .. 4096 tiles
+    bool scan_recompute = false;    // CS_T15_SCAN_RECOMPUTE: k_flux_scan forms a chunk's transmissivities again instead of keeping them
+    int near_prio = 0;              // CS_TUNE_NEAR_PRIO & CS_T16_PRIO_MASK: issue priority for k_voigt_sub / k_voigt_near -- 0 from 512 tiles on, 1 never, 2 always
+    bool near_two_launches = false; // CS_T16_NEAR_TWO_LAUNCHES: k_voigt_near<0> + <1> also where k_voigt_near_both would do
+    bool far64_shared = false;      // CS_TUNE_FAR64_SHARED: far pieces of an item the four waves of a block share on all 64 nodes
+    int sub_lean = 0;               // CS_TUNE_SUB_LEAN: k_voigt_sub's range-only pass -- 0 where the piece tables predict no series pair, 1 never, 2 first in every wave
+    bool near_memset = false;       // CS_TUNE_NEAR_MEMSET: the near-line plane cleared by a memset instead of written by k_voigt_sub
+    int tables_merge = 0;           // CS_TUNE_TABLES_MERGE: the piece tables as blocks of k_gas_setup's launch -- 0 below 1024 tiles, 1 never, 2 always
+    int far_split = 0;              // CS_TUNE_FAR_SPLIT: waves per tile of k_voigt_far (1, 2, 4; 0 = by grid size)
+    bool edge_points = false;       // CS_TUNE_EDGE_POINTS: every window-end line of k_voigt_edge_mx at the points, none on the tile's 16 nodes
+};
+static void set_matrix_cores(Settings &st, int on)
+{
+    st.matrix_core = (on & 4) == 0;   // (tuning / tests: | 4 keeps the tile-wide near-zone pass everywhere)
+    st.matrix_nodes = (on & 3) > 2 ? 2 : (on & 3);
+}
+static void set_tuning(Settings &st, int key, int v)
+{
+    switch (key) {
+    case CS_TUNE_FUSE_APPLY: st.fuse_apply = v != 0; break;
+    case CS_TUNE_SMALL_MX: st.small_mx = v != 0; break;
+    case CS_TUNE_NODES_STREAM: st.nodes_stream = v; break;
+    case CS_TUNE_MARGIN: st.margin = v > 0 ? 0.01 * v : kChebMargin; break;
+    case CS_TUNE_GRAPH: st.graph = v != 0; break;
+    case CS_TUNE_RT_STREAMS: st.rt_streams = v != 0; break;
+    case CS_TUNE_NSPLIT_LEVELS: st.nsplit_levels = v > 0 ? v : 1; break;
+    case CS_TUNE_NEAR_STREAM: st.near_stream = v; break;
+    case CS_TUNE_MX_MIN_STATES: st.mx_min_states = v > 0 ? v : 7; break;
+    case CS_TUNE_PH_OWN_CORE: st.ph_own_core = v != 0; break;
+    case CS_TUNE_PH_NODES: st.ph_nodes = v; break;
+    case CS_TUNE_FAR64: st.far64 = v != 0; break;
+    case CS_TUNE_CASCADE: st.cascade = v; break;
+    case CS_TUNE_NODES_SPLIT: st.nodes_split = v; break;
+    case CS_TUNE_EDGE_FULL: st.edge_full = v != 0; break;
+    case CS_TUNE_FLUX:
+        st.flux_form = v & CS_T15_FORM_MASK;
+        st.freduce_always = (v & CS_T15_FREDUCE) != 0;
+        st.chunk4 = (v & CS_T15_CHUNK4) != 0;
+        st.tables_one_thread = (v & CS_T15_TABLES_ONE_THREAD) != 0;
+        st.multi_recut = (v & CS_T15_MULTI_RECUT) != 0;
+        st.scan_stamps = (v & CS_T15_SCAN_STAMPS) != 0;
+        st.no_cascade_aside = (v & CS_T15_NO_CASCADE_ASIDE) != 0;
+        st.scan_mid = (v & CS_T15_SCAN_MID) != 0;
+        st.scan_recompute = (v & CS_T15_SCAN_RECOMPUTE) != 0;
+        break;
+    case CS_TUNE_NEAR_PRIO:
+        st.near_prio = v & CS_T16_PRIO_MASK;
+        st.near_two_launches = (v & CS_T16_NEAR_TWO_LAUNCHES) != 0;
+        break;
+    case CS_TUNE_FAR64_SHARED: st.far64_shared = v != 0; break;
+    case CS_TUNE_SUB_LEAN: st.sub_lean = v; break;
+    case CS_TUNE_NEAR_MEMSET: st.near_memset = v != 0; break;
+    case CS_TUNE_TABLES_MERGE: st.tables_merge = v; break;
+    case CS_TUNE_FAR_SPLIT: st.far_split = v; break;
+    case CS_TUNE_EDGE_POINTS: st.edge_points = v != 0; break;
+    default: break;   // (key 20: accepted, unused)
+    }
+}
+// The settings a gas pass runs under (GasPass::set): the context's, or these defaults.  Today, as the call sites grew (DESIGN.md keeps the
+// question open whether the last two should follow the context):
+//   sigma_impl (the step of the resident column)       every group under the context's settings;
+//   gas_states (cs_shape_batch, cs_shape_points,       under the context's where the call builds an interpolation view (cs_set_interp on and a
+//     cs_bake) and cs_column_batch                      shape of the Voigt family | a group with interpolation levels), else under the defaults;
+//   the inner Voigt pass of PHCO2 (line_sum_phco2)     always under the defaults.
+static const Settings kDefaultSettings;
+
 // workspace of the PHCO2 fast path (k_phco2): per-(state, line) chi factors and per-tile region windows
-constexpr int CS_NTUNE = 24;
 // nu_lo .. grid_id: the grid of the call, set by the caller (ph_set_grid); cheb, piw, F: the interpolation levels of that grid for the
 // PHCO2 cut-off (k_phco2_nodes), rebuilt when the key (grid_id, nnu, cut) changes
 struct PhScratch {
@@ -371,10 +464,10 @@ struct PhScratch {
     struct Dens { const void *tab; uint64_t gen, grid; bool ok; };
     std::vector<Dens> dens;                  // check_near_density() per (table, grid), a few kept
     double nu_lo = 0.0, nu_hi = 0.0, nu_c = 0.0, max_span = 0.0, margin = kChebMargin;
-    int itp_on = 0, itp_min = 128, itp_max = 2048, own_core = 0;   // own_core: cs_set_tuning key 9
+    int itp_on = 0, itp_min = 128, itp_max = 2048, own_core = 0;   // own_core: Settings::ph_own_core
     uint64_t grid_id = 0;
     double lev_span[8] = {};   // widest interval of 8192 >> i points on this grid (ph_set_grid)
-    int force64 = 0;           // cs_set_tuning key 10: 64 nodes for every interval (bit 0), tiles as 64-point intervals too (bit 1)
+    int force64 = 0;           // Settings::ph_nodes: 64 nodes for every interval (bit 0), tiles as 64-point intervals too (bit 1)
     uint64_t builds = 0;       // how often ph_interp_ready has (re)built the levels: a captured step holds the layout of one build
     int drop = 0;              // regions (bit r = region r + 1) the states of the coming launch keep out of the levels (ph_wide_regions)
     // interval sizes in use (descending) and the virtual levels on them (PhVLevels); nodes [sum nI x nc], Cm[v] [nI][nc][itv]
@@ -395,8 +488,8 @@ struct cs_ctx {
     int device = 0;
     bool counted = false;   // cs_create finished: the context counts in g_live_ctx
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;            // side stream: node sums beside the per-point kernels (cs_set_tuning key 2)
-    hipStream_t stream3 = nullptr;            // side stream: near-line kernels beside the matrix-core per-point kernel (key 7)
+    hipStream_t stream2 = nullptr;            // side stream: node sums beside the per-point kernels (Settings::nodes_stream)
+    hipStream_t stream3 = nullptr;            // side stream: near-line kernels beside the matrix-core per-point kernel (Settings::near_stream)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_fork3 = nullptr, ev_join3 = nullptr, ev_far3 = nullptr;
     GasTable gas[CS_MAX_GAS];
     TableDev tab[CS_MAX_TABLE];
@@ -406,18 +499,9 @@ struct cs_ctx {
     int mixed = 0;
     int interp = 1;   // far wings by Chebyshev interpolation over 128..2048-point intervals (k_cheb_nodes / k_cheb_apply)
     int itp_first = -1, itp_min = 128, itp_max = 2048;   // cs_set_interp_plan: first level per gas (-1 = by line density), size range
-    int matrix_nodes = 1;   // cs_set_matrix_cores: separable far-wing node sums on v_mfma_f64 (k_cheb_nodes_mx)
-    int matrix_core = 1;    // ... and the window core on sub-tiles (k_voigt_sub + the second mask of k_voigt_edge_mx)
     int merge = 1;          // cs_set_merge: gases of a column with the same shape and cut-off share one merged line table
-    // cs_set_tuning (include/clearsky_hip.h has the full descriptions): [0] interpolated wings applied inside k_voigt_edge_mx, [1]
-    // matrix-core kernels on short grids, [2] node sums on a side stream, [3] interpolation margin (per cent), [4] hipGraph replay, [5]
-    // k_rt_streams on short grids, [6] split levels of k_cheb_nodes_mx, [7] near-line kernels on a second side stream, [8] states of a
-    // group that must be able to use a line for it to join the group's matrix-core node piece, [9] PHCO2 core in k_phco2 itself, [10]
-    // PHCO2 node counts / 64-point intervals, [11] far pieces of the node sums on all 64 nodes, [12] level cascade, [13] k_cheb_nodes
-    // with four waves per (interval, state), [14] cut-off edges of k_voigt_edge_mx without the sub-tile phases, [15] the flux kernel
-    // finishes the cross-sections on chip (k_flux): 0 = where it pays, 1 = never, 2 = always
+    Settings set;           // the lab switches: cs_set_tuning, cs_set_matrix_cores
     bool gfx950 = false;    // cs_create: the device reports gcnArchName gfx950 (the in-kernel band sum of k_flux_* is used only then)
-    int tune[CS_NTUNE] = {0, 1, 2, 0, 0, 1, 0, 1, 7, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<std::shared_ptr<GasTable>> merged;   // merged tables (keyed by their members' (slot, generation)), least recently used first
     double far_s = 1e6;
     DevBuf reinterp;        // [64][32] then [64][16]: values at the 64 nodes of an interval from those at its 32 / 16 nodes (build_reinterp)
@@ -431,9 +515,9 @@ void ph_set_grid(const cs_ctx *ctx, PhScratch &ph, const double *nu, int64_t nnu
     for (int64_t i0 = 0; i0 < nnu; i0 += 64) ph.max_span = std::max(ph.max_span, nu[std::min(i0 + 63, nnu - 1)] - nu[i0]);
     ph.grid_id = grid_id;
     ph.itp_on = ctx->interp; ph.itp_min = ctx->itp_min; ph.itp_max = ctx->itp_max;
-    ph.margin = ctx->tune[3] > 0 ? 0.01 * ctx->tune[3] : kChebMargin;
-    ph.own_core = ctx->tune[9];
-    ph.force64 = ctx->tune[10];
+    ph.margin = ctx->set.margin;
+    ph.own_core = ctx->set.ph_own_core;
+    ph.force64 = ctx->set.ph_nodes;
     for (int i = 0; i < 8; i++) {
         const int64_t sz = 8192 >> i;
         double w = 0.0;
@@ -616,7 +700,7 @@ void launch_rt(const RtGeom &g, int B, const FluxArgs &a, size_t sig_bstride = 0
 // 3 = k_flux_scan (short grids), 2 = k_flux_chunk (long grids)
 int flux_form(const cs_ctx *ctx, const Column &c, size_t *shmem, int *nblk, int *threads)
 {
-    if ((ctx->tune[15] & 3) == 1 || !c.tab.empty() || c.gas.empty()) return 0;   // (baked tables are added between wings and CIA pairs: own pass)
+    if (ctx->set.flux_form == 1 || !c.tab.empty() || c.gas.empty()) return 0;   // (baked tables are added between wings and CIA pairs: own pass)
     for (auto &cc : c.cia)
         if (cc.max_overlap > CS_CIA_ACT) return 0;
     const int np = c.np, ns = c.nstream, K = c.K;
@@ -624,9 +708,9 @@ int flux_form(const cs_ctx *ctx, const Column &c, size_t *shmem, int *nblk, int 
     const int nt64_ = (int)((c.nnu + 63) / 64);
     // the scan form: grids of up to 1024 tiles -- with a chunk's transmissivities in registers it beats the separate kernels on a half
     // (846 tiles: 1.10 -> 1.08 ms) and a quarter (407 tiles: 0.677 -> 0.610) of the bench column, not on the whole (1563 tiles: 1.94 ->
-    // 1.99) -- and, key 15 | 1024, every grid in k_rt's two-waves-per-tile regime (A/B)
-    // (key 15 = 2, `always`, keeps the chunked form on mid-size grids: tests)
-    const bool scan_ok = c.rtg.streams || (c.rtg.ud && ns >= 2 && ns <= 8 && nt64_ >= 1 && ((nt64_ <= 1024 && (ctx->tune[15] & 3) != 2) || (ctx->tune[15] & 1024)));
+    // 1.99) -- and, under Settings::scan_mid, every grid in k_rt's two-waves-per-tile regime (A/B)
+    // (Settings::flux_form = 2, `always`, keeps the chunked form on mid-size grids: tests)
+    const bool scan_ok = c.rtg.streams || (c.rtg.ud && ns >= 2 && ns <= 8 && nt64_ >= 1 && ((nt64_ <= 1024 && ctx->set.flux_form != 2) || ctx->set.scan_mid));
     if (scan_ok) {
         // the sweeps as a scan over layer chunks: five layers per wave where 12 waves reach (their transmissivities stay in registers,
         // k_flux_scan<NS, 5>), whole waves per SIMD (4, 8 or 12: ten waves of six layers load two SIMDs with three waves and two with two)
@@ -639,7 +723,7 @@ int flux_form(const cs_ctx *ctx, const Column &c, size_t *shmem, int *nblk, int 
     // long grids: where k_rt runs one wave per tile for both sweeps (>= 4096 tiles) the chunked form saves the passes over the plane; in
     // between (the bench column at full size: 1563 tiles, two waves per tile) the separate kernels are as fast (profiles/r04_notes.md)
     const int nt64 = (int)((c.nnu + 63) / 64);
-    if ((ctx->tune[15] & 3) != 2 && c.rtg.ud) return 0;
+    if (ctx->set.flux_form != 2 && c.rtg.ud) return 0;
     const int nw = 4, R = 16 + c.nlob - 1;
     const size_t sh = ((size_t)2 * np * nw + (size_t)nw * R * 64) * sizeof(double);
     if (sh > lim) return 0;
@@ -831,54 +915,18 @@ struct Interp {
     double *F = nullptr;
     SepZone *sep = nullptr;   // NULL: every node sum on the vector unit
     EdgeZone *edge = nullptr; // NULL: all of the per-point sum on the vector unit
-    bool sep_always = false;  // cs_set_matrix_cores(ctx, 2): also on grids too short to fill the chip with (interval, state group) blocks
-    bool core = true;         // cs_set_matrix_cores(ctx, on | 4) switches the sub-tile treatment of the window core (k_voigt_sub) off
-    double margin = kChebMargin;   // cs_set_tuning key 3 (per cent): distance of an interval's interpolated set, in half-widths
-    int mx_min_states = 7;    // cs_set_tuning key 8
     int nfar[CS_MAX_LEVEL] = {};   // nodes for the far pieces of a level in k_cheb_nodes_mx (16, 32; 64 = as the near pieces)
     const double *Rc[CS_MAX_LEVEL] = {};   // ChebGrid::Rc
-    int edge_phases = 1;           // cs_set_tuning key 14: k_voigt_edge_mx cuts a cut-off edge by the sub-tiles its lines reach (0: off)
-    int nodes_split = 0;           // cs_set_tuning key 13: k_cheb_nodes with four waves per (interval, state)
-    int cascade = 0;               // cs_set_tuning key 12: 0 = where it pays (cascade_pays), 1 = always, 2 = never
-    const double *R = nullptr;     // the context's re-interpolation matrices (cs_ctx::reinterp); NULL: every piece on 64 nodes (cs_set_tuning key 11)
-    int nsplit_levels = 1;    // cs_set_tuning key 6: interval sizes (largest first) whose node sums four waves share in k_cheb_nodes_mx
-    bool small_mx = false;    // cs_set_tuning key 1: the matrix-core kernels on short grids too (their four-waves-per-item variants)
-    bool mxzones_one_thread = false;   // cs_set_tuning key 15 | 16: k_mxzones instead of k_mxzones16
-    const double *tnodes = nullptr, *tC = nullptr;   // ChebGrid::tnodes, tC where the grid allows (tile_nodes_ok) and cs_set_tuning key 23 = 0
-    int far_split = 0;                 // cs_set_tuning key 22: waves per tile of k_voigt_far (1, 2, 4; 0 = by grid size)
-    bool far_shared_full = false;      // cs_set_tuning key 17: far pieces of an item the four waves of a block share on all 64 nodes (A/B)
-    int mxzones_merge = 0;             // cs_set_tuning key 21: the piece tables as blocks of k_gas_setup's launch (k_gas_setup_mx) -- 0 = on grids below 1024 tiles, 1 = never, 2 = always
-    bool near_both = true;             // both tiers of the near-line pairs in one launch where a wave takes one tile (cs_set_tuning key 16 | 4: off)
-    int near_prio = 0;                 // cs_set_tuning key 16: issue priority for k_voigt_sub / k_voigt_near (0 = from 512 tiles on, 1 = never, 2 = always)
-    bool fuse_apply = false;  // the column's only interpolating group: k_voigt_edge_mx may carry the node sums to the grid itself
-    int sub_lean = 0;         // cs_set_tuning key 18: k_voigt_sub's range-only pass -- 0 = where the piece tables predict no series pair, 1 = never, 2 = first in every wave
-    bool near_memset = false; // cs_set_tuning key 19: the near-line plane cleared by a memset in front of k_voigt_sub (1) instead of written by it (0, default)
-    double core4 = 0.0;       // the core takes the 4-term series where its radius is below core4 x the tile's span, else the 8-term one
-                              // (0: always the 8-term one -- measured at C3 with 0.75 / 0.3 / 0: 2.61 / 2.55 / 2.52 ms)
+    const double *R = nullptr;     // the context's re-interpolation matrices (cs_ctx::reinterp); NULL: every piece on 64 nodes (CS_TUNE_FAR64)
+    const double *tnodes = nullptr, *tC = nullptr;   // ChebGrid::tnodes, tC where the grid allows (tile_nodes_ok) and CS_TUNE_EDGE_POINTS = 0
 };
 
-static void interp_settings(const cs_ctx *ctx, Interp &itp)   // what cs_set_matrix_cores says, and the cs_set_tuning keys an Interp view carries
+// the buffers of a view that the context's settings select
+static void interp_select(const cs_ctx *ctx, Interp &itp)
 {
-    if (!ctx->matrix_nodes) itp.sep = nullptr, itp.edge = nullptr;
-    itp.sep_always = ctx->matrix_nodes == 2;
-    itp.core = ctx->matrix_core != 0;
-    itp.small_mx = ctx->tune[1] != 0;
-    itp.margin = ctx->tune[3] > 0 ? 0.01 * ctx->tune[3] : kChebMargin;
-    itp.nsplit_levels = ctx->tune[6] > 0 ? ctx->tune[6] : 1;
-    itp.mx_min_states = ctx->tune[8] > 0 ? ctx->tune[8] : 7;
-    itp.R = ctx->tune[11] ? nullptr : ctx->reinterp.as<double>();
-    itp.cascade = ctx->tune[12];
-    itp.nodes_split = ctx->tune[13];
-    itp.edge_phases = ctx->tune[14] ? 0 : 1;
-    itp.mxzones_one_thread = (ctx->tune[15] & 16) != 0;
-    itp.near_prio = ctx->tune[16] & 3;
-    itp.near_both = (ctx->tune[16] & 4) == 0;
-    itp.sub_lean = ctx->tune[18];
-    itp.near_memset = ctx->tune[19] != 0;
-    itp.mxzones_merge = ctx->tune[21];
-    itp.far_split = ctx->tune[22];
-    itp.far_shared_full = ctx->tune[17] != 0;
-    if (ctx->tune[23]) itp.tnodes = itp.tC = nullptr;     // (cs_set_tuning key 23 = 1: every window-end line at the points, A/B)
+    if (!ctx->set.matrix_nodes) itp.sep = nullptr, itp.edge = nullptr;
+    itp.R = ctx->set.far64 ? nullptr : ctx->reinterp.as<double>();
+    if (ctx->set.edge_points) itp.tnodes = itp.tC = nullptr;
 }
 
 // interval sizes worth using on this grid: an interval of width W leaves lines over (2 cut - 2.3 W) to interpolate
@@ -1132,7 +1180,7 @@ static int ph_plan(PhScratch *ph, int64_t nnu, double cut)
     if (nnu < 128) return 0;
     const double dnu = (ph->nu_hi - ph->nu_lo) / (double)(nnu - 1);
     // (cs_set_interp_plan's limits of 128 and 2048 points are the Voigt path's; left there, the wide PHCO2 window also takes 4096 and
-    //  8192 points; key 10 bit 1: also the tiles themselves as 64-point intervals with 16 or 32 nodes -- measured a tie at C3 size: 1.2 ms
+    //  8192 points; Settings::ph_nodes bit 1: also the tiles themselves as 64-point intervals with 16 or 32 nodes -- measured a tie at C3 size: 1.2 ms
     //  more in k_phco2_nodes, whose smallest waves are a chain of short batches, for 1.3 ms less in k_phco2)
     const int szmax = ph->itp_max >= 2048 ? 8192 : ph->itp_max, szmin = (ph->itp_min <= 128 && (ph->force64 & 2)) ? 64 : ph->itp_min;
     const double Dn[3] = {3.0, 30.0, 120.0}, Df[3] = {30.0, 120.0, cut};
@@ -1275,7 +1323,7 @@ constexpr int CS_EDGE_DENS = 4;
 // blocks to fill the chip -- on a short grid (a nu-shard) the one-state-per-wave vector kernel has the shorter critical path
 // (1/8 of C3: 0.17 vs 0.25 ms)
 static bool mx_big(int nblocks, int kn, int min_blocks) { return (int64_t)nblocks * ((kn + 15) / 16) >= min_blocks; }
-// `small`: cs_set_tuning key 1 -- short grids too, through the variants that share one (interval | tile, group) between the four
+// `small`: Settings::small_mx -- short grids too, through the variants that share one (interval | tile, group) between the four
 // waves of a block (k_cheb_nodes_mx with every level split, k_voigt_edge_mx<4>)
 static bool sep_in_use(bool have_sep, bool always, int nblocks_intervals, int kn, bool lor, bool mixed, bool small = false)
 {
@@ -1362,6 +1410,8 @@ struct GasPass {
     double *spare = nullptr;        // the line sum of a code-5/6 group that accumulates goes here first (one that does not: sigma itself)
     // how to run
     double far_s = 1e6;
+    const Settings *set = &kDefaultSettings;   // the lab switches this pass runs under (see kDefaultSettings for who follows the context)
+    bool fuse_apply = false;        // the column's only interpolating group, under Settings::fuse_apply: k_voigt_edge_mx may carry the node sums to the grid itself
     Interp itp;
     ChebApply *defer = nullptr;
     PhScratch *ph = nullptr;
@@ -1401,6 +1451,7 @@ static FarKernel far_kernel(bool mixed, int split, bool lor, bool edge)
 static VoigtPlan voigt_plan(const GasPass &p)
 {
     const Interp &itp = p.itp;
+    const Settings &st = *p.set;
     const int kn = p.kn;
     const int64_t nlines = std::max(p.jhi, p.jlo) - p.jlo;   // the lines some window can reach
     const bool mixed = p.shape == SH_VOIGT && !p.pshift && p.hot32 != nullptr;   // (no fp32 wings for shifted lines, nor a Lorentz variant)
@@ -1410,8 +1461,8 @@ static VoigtPlan voigt_plan(const GasPass &p)
     pl.nt64 = (int)((p.nnu + 63) / 64);
     pl.ngrp = (kn + 15) / 16;
     // wave priority of the near-line stream's kernels (wave_prio): long grids only
-    pl.near_prio = (itp.near_prio == 2 || (itp.near_prio == 0 && pl.nt64 >= 512)) ? 3 : 0;
-    pl.sub_lean = itp.sub_lean;
+    pl.near_prio = (st.near_prio == 2 || (st.near_prio == 0 && pl.nt64 >= 512)) ? 3 : 0;
+    pl.sub_lean = st.sub_lean;
     pl.nb_zones = (unsigned)(((int64_t)pl.nt64 * kn + 255) / 256);
     if (itp.nlev > 0) {
         pl.q0 = itp.ioff[itp.l0];
@@ -1420,34 +1471,34 @@ static VoigtPlan voigt_plan(const GasPass &p)
         pl.nb_iz = (unsigned)(((int64_t)nq * kn + 255) / 256);
         // what the matrix cores take of the interpolated sets and of the window ends (not of a shifted group: GasPass::pshift)
         if (!p.pshift) {
-            pl.use_sep = sep_in_use(itp.sep != nullptr, itp.sep_always, nq, kn, pl.lor, mixed, itp.small_mx);
-            pl.use_edge = edge_in_use(itp.edge != nullptr, itp.sep_always, pl.nt64, kn, pl.lor, mixed, nlines, itp.small_mx);
+            pl.use_sep = sep_in_use(itp.sep != nullptr, st.matrix_nodes == 2, nq, kn, pl.lor, mixed, st.small_mx);
+            pl.use_edge = edge_in_use(itp.edge != nullptr, st.matrix_nodes == 2, pl.nt64, kn, pl.lor, mixed, nlines, st.small_mx);
         }
-        // short grids: four waves per (interval, state) (cs_set_tuning key 13: 0 = below 16384 waves, 1 = always, 2 = never)
-        pl.nsplit4 = itp.nodes_split == 1 || (itp.nodes_split == 0 && (int64_t)nq * kn < 16384);
+        // short grids: four waves per (interval, state) (Settings::nodes_split: 0 = below 16384 waves, 1 = always, 2 = never)
+        pl.nsplit4 = st.nodes_split == 1 || (st.nodes_split == 0 && (int64_t)nq * kn < 16384);
         if (pl.use_sep) {
-            // the largest interval sizes in use are shared by the four waves of a block -- itp.nsplit_levels of them (all sizes on a
+            // the largest interval sizes in use are shared by the four waves of a block -- Settings::nsplit_levels of them (all sizes on a
             // grid too short to fill the chip with one (interval, group) per wave)
-            for (int l = itp.l0; l < std::min(itp.nlev, itp.l0 + itp.nsplit_levels); l++) pl.nsplit += itp.nI[l];
+            for (int l = itp.l0; l < std::min(itp.nlev, itp.l0 + st.nsplit_levels); l++) pl.nsplit += itp.nI[l];
             if (!mx_big(nq, kn, 2048) || pl.nsplit > nq) pl.nsplit = nq;
             pl.nblk_mx = (unsigned)(pl.nsplit * pl.ngrp) + (unsigned)(((int64_t)(nq - pl.nsplit) * pl.ngrp + 3) / 4);
-            pl.far_R = itp.R != nullptr && !(itp.far_shared_full && pl.nsplit == nq);
+            pl.far_R = itp.R != nullptr && !(st.far64_shared && pl.nsplit == nq);
             pl.far64_shared = itp.R != nullptr && !pl.far_R;
             for (int l = 0; l < itp.nlev; l++) pl.nfar[l] = itp.nfar[l] > 0 ? itp.nfar[l] : CS_NC;
         }
     }
-    pl.core = pl.use_edge && itp.core;
+    pl.core = pl.use_edge && st.matrix_core;
     // The piece tables per (interval | tile, state group) need the zones -- which their sixteen-lanes-per-item form computes itself, as
     // blocks of the SAME launch (k_gas_setup_mx); the one-thread-per-item form reads them, a launch of its own behind k_gas_setup
     if (pl.use_sep || pl.use_edge) {
         const int64_t nsep = pl.use_sep ? (int64_t)(itp.nItot - pl.q0) * pl.ngrp : 0, nedge = pl.use_edge ? (int64_t)pl.nt64 * pl.ngrp : 0;
         // sixteen lanes per item shorten the chain where the items are few (a nu-shard: 21 -> 8 us; the bench column 27 -> 9); from
         // ~50 000 items on one thread per item has parallelism enough and sixteen times fewer threads (BASELINE configs[4]: 0.256 vs 0.276 ms)
-        const bool one_thread = itp.mxzones_one_thread || nsep + nedge > 50000;   // (cs_set_tuning key 15 | 16: always)
+        const bool one_thread = st.tables_one_thread || nsep + nedge > 50000;
         // merged on short grids, where the head of the step is a chain of launch tails (1/8 of the bench column: 0.347 -> 0.340 ms);
         // at full size the second set of searches beside 300 MB of record stores costs more than the launch it saves (1.900 -> 1.908)
-        // (cs_set_tuning key 21: 1 = never, 2 = always, A/B)
-        const bool merged = !one_thread && itp.mxzones_merge != 1 && (itp.mxzones_merge == 2 || pl.nt64 < 1024);
+        // (Settings::tables_merge: 1 = never, 2 = always, A/B)
+        const bool merged = !one_thread && st.tables_merge != 1 && (st.tables_merge == 2 || pl.nt64 < 1024);
         pl.tables = one_thread ? TABLES_ONE_THREAD : (merged ? TABLES_MERGED : TABLES_LANES16);
         const int per = one_thread ? 256 : 16;   // items per block
         pl.nb_sep = (unsigned)((nsep + per - 1) / per);
@@ -1456,19 +1507,19 @@ static VoigtPlan voigt_plan(const GasPass &p)
     // k_voigt_far, waves per tile: enough waves to fill 256 CUs x 32 wave slots about 4 times over
     const int64_t nwave = (int64_t)pl.nt64 * kn;
     pl.far_split = nwave >= 16384 ? 1 : (nwave >= 4096 ? 2 : 4);   // (re-tuned with the far wings interpolated: waves are 3x shorter)
-    if (itp.far_split == 1 || itp.far_split == 2 || itp.far_split == 4) pl.far_split = itp.far_split;   // (cs_set_tuning key 22, A/B)
+    if (st.far_split == 1 || st.far_split == 2 || st.far_split == 4) pl.far_split = st.far_split;   // (A/B)
     // k_voigt_edge_mx: one wave per (tile, state group) where those fill the chip, else four (short grid) -- and no tile nodes in that
     // shared form (the 16-node path there: 16 more matrix steps per WAVE, no gain measured)
     pl.edge_big = mx_big(pl.nt64, kn, 1024);
-    pl.edge_phases = itp.edge_phases;
-    pl.tnodes = pl.use_edge && pl.edge_big && itp.edge_phases && itp.tnodes != nullptr;
+    pl.edge_phases = st.edge_full ? 0 : 1;
+    pl.tnodes = pl.use_edge && pl.edge_big && pl.edge_phases && itp.tnodes != nullptr;
     // near kernels: one wave = nrep consecutive tiles, one after the other: eight where the table is sparse against the grid (few tiles have candidates at all) and the
     // grid long enough to keep the chip full with an eighth of the waves, and on every grid of half a million (tile, state) waves
     // and more -- there the launch of the waves is what a near-line kernel costs first (BASELINE configs[4]: 7.9e5 waves per
     // tier, step 7.06 -> 6.85 ms with eight tiles per wave; the bench column, 9.5e4 waves: a tie with two, a loss with four)
     const int64_t nwaves_near = (int64_t)pl.nt64 * kn;
     pl.nrep = (nwaves_near >= 524288 || (nlines < (int64_t)pl.nt64 * 2 && nwaves_near >= 262144)) ? 8 : 1;
-    pl.near_both = pl.nrep == 1 && itp.near_both;   // (one tile per wave; cs_set_tuning key 16 | 4: two launches, A/B)
+    pl.near_both = pl.nrep == 1 && !st.near_two_launches;   // (one tile per wave; Settings::near_two_launches: A/B)
     return pl;
 }
 
@@ -1487,14 +1538,14 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
     const bool use_sep = pl.use_sep, use_edge = pl.use_edge;
     // the side streams (not while profiling): the node kernels beside what follows them on the main stream; the near-line kernels and
     // the sub-tile cores into their own plane (Voigt only) -- whose first writer of the step defines all of it: k_voigt_sub where it
-    // runs (sums where a tile has a core, zeros elsewhere: cs_set_tuning key 19 = 1 keeps the memset for A/B), else a memset
+    // runs (sums where a tile has a core, zeros elsewhere: Settings::near_memset keeps the memset for A/B), else a memset
     const bool nodes_fork = itp.nlev > 0 && p.fork && p.fork->use_nodes && p.defer && !p.evg;
     const bool near_fork = !pl.lor && p.fork && p.fork->use_near && p.fork->sigma2 && p.defer && !p.evg;
-    const bool sub_assigns = near_fork && pl.core && !p.fork->zeroed && !itp.near_memset;
+    const bool sub_assigns = near_fork && pl.core && !p.fork->zeroed && !p.set->near_memset;
     const bool near_memset = near_fork && !p.fork->zeroed && !sub_assigns;
     if (p.log) p.log->voigt_group(pl, (nodes_fork ? 1 : 0) | (near_fork ? 2 : 0), near_memset);
 
-    const ZoneArgs za = zone_args(p, pl.lor, itp.margin, p.pshift ? p.ds : 0.0);
+    const ZoneArgs za = zone_args(p, pl.lor, p.set->margin, p.pshift ? p.ds : 0.0);
     IzParams P;
     memset(&P, 0, sizeof P);
     if (itp.nlev > 0) {
@@ -1509,13 +1560,13 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
     memset(&ea, 0, sizeof ea);
     if (pl.tables != TABLES_NONE) {
         sa.nodes = itp.nodes; sa.nul = G.nu.as<double>(); sa.gbound = p.gbound; sa.Tk = p.Tk; sa.iz = itp.iz; sa.out = itp.sep;
-        sa.nItot = itp.nItot; sa.q0 = pl.q0; sa.K = kn; sa.ngrp = pl.ngrp; sa.mu_min = G.mu_min; sa.cut = p.cut; sa.min_states = itp.mx_min_states;
+        sa.nItot = itp.nItot; sa.q0 = pl.q0; sa.K = kn; sa.ngrp = pl.ngrp; sa.mu_min = G.mu_min; sa.cut = p.cut; sa.min_states = p.set->mx_min_states;
         ea.nu = p.dnu; ea.nul = G.nu.as<double>(); ea.gbound = p.gbound; ea.Tk = p.Tk; ea.win = p.win; ea.zones = p.zones;
         ea.iz = itp.iz + itp.ioff[itp.nlev - 1]; ea.out = itp.edge; ea.nnu = nnu; ea.ntile = nt64; ea.K = kn; ea.ngrp = pl.ngrp;
         ea.nI = itp.nItot; ea.ishift = pl.ishift;
         ea.mu_min = G.mu_min; ea.mu_max = G.mu_max; ea.cut = p.cut;
         ea.core = pl.core ? 1 : 0;
-        ea.core4 = itp.core4;
+        ea.core4 = 0.0;   // (always the 8-term series in the core: measured at C3 with 0.75 / 0.3 / 0 x the tile's span for the 4-term one: 2.61 / 2.55 / 2.52 ms)
     }
     if (pl.tables == TABLES_MERGED)
         CS_LAUNCH(p.vvh ? k_gas_setup_mx_vvh : k_gas_setup_mx, dim3(nb_prep + pl.nb_zones + pl.nb_iz + pl.nb_sep + pl.nb_edge), dim3(256), 0, s, nb_prep, pl.nb_zones, pl.nb_iz, pl.nb_sep, pa, za, P, itp.iz, sa, ea);
@@ -1581,7 +1632,7 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
             A.noff[l] = itp.ioff[l] * CS_NC;
             A.Cm[l] = itp.Cm[l];
         }
-        fuse = p.defer && itp.fuse_apply && use_edge && p.defer->ngas == 0;   // (then k_voigt_edge_mx below carries this group's node sums to the grid)
+        fuse = p.defer && p.fuse_apply && use_edge && p.defer->ngas == 0;   // (then k_voigt_edge_mx below carries this group's node sums to the grid)
         if (fuse) {
             Afuse = A;
             Afuse.ngas = 1;
@@ -1594,7 +1645,7 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
             A.F[A.ngas++] = itp.F;
         }
         if (!p.defer) {   // sigma = base + extra + interpolated far wings now; the per-point kernels add the rest
-            launch_apply_cascade(s, A, itp.Rc, itp.itv, itp.nI, itp.cascade, itp.Kpad, nnu, kn, p.base, p.extra, p.sigma, accumulate);
+            launch_apply_cascade(s, A, itp.Rc, itp.itv, itp.nI, p.set->cascade, itp.Kpad, nnu, kn, p.base, p.extra, p.sigma, accumulate);
             accumulate = 1;
         }               // (deferred: the caller applies the node sums of all its gases in one launch, after the last gas)
         iz = itp.iz + itp.ioff[itp.nlev - 1];
@@ -1650,7 +1701,7 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
         if (fuse) fork_join(p.fork, s);   // (it reads F)
         const unsigned ntx = pl.edge_big ? (unsigned)((nt64 + 3) / 4) : (unsigned)nt64;
         CS_LAUNCH(pl.edge_big ? k_voigt_edge_mx<1> : k_voigt_edge_mx<4>, dim3(ntx, (unsigned)pl.ngrp), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.win,
-                  itp.edge, nt64, kn, p.cut, p.sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), itp.edge_phases,
+                  itp.edge, nt64, kn, p.cut, p.sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), pl.edge_phases,
                   pl.tnodes ? itp.tnodes : (const double *)nullptr, pl.edge_big ? itp.tC : (const double *)nullptr);
     }
     if (p.evg) (void)hipEventRecord(p.evg[5], s);
@@ -1745,7 +1796,7 @@ static void line_sum_phco2(hipStream_t s, const GasPass &p, PrepArgs pa, unsigne
         const int nt4 = (nt64 + 3) / 4 * 4, per = ((nt4 / 4 + 7) / 8) * 4;   // (wave_windows' stretch length)
         GasPass in = p;   // same table, record range, states, records, grid, ranges and plane: the zones and sums of a Voigt pass with its own windows
         in.shape = SH_VOIGT; in.cut = 3.0; in.win = p.ph->win3.as<WaveWin>(); in.xtiles = per; in.zones = p.ph->zones3.as<Zone>();
-        in.base = 0.0; in.extra = nullptr; in.accumulate = 1; in.evg = nullptr; in.hot32 = nullptr; in.itp = Interp();
+        in.base = 0.0; in.extra = nullptr; in.accumulate = 1; in.evg = nullptr; in.hot32 = nullptr; in.itp = Interp(); in.set = &kDefaultSettings; in.fuse_apply = false;
         in.defer = nullptr; in.ph = nullptr; in.fork = nullptr; in.records_ready = true; in.keep = nullptr;
         in.flo = -INFINITY; in.fhi = INFINITY;   // (no K1 in this pass: nothing reads them)
         launch_line_sum(s, in);
@@ -2208,9 +2259,7 @@ int cs_set_matrix_cores(cs_ctx *ctx, int on)
 {
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (on < 0) on = 0;
-    ctx->matrix_core = (on & 4) ? 0 : 1;   // (tuning / tests: | 4 keeps the tile-wide near-zone pass everywhere)
-    on &= 3;
-    ctx->matrix_nodes = on > 2 ? 2 : on;
+    set_matrix_cores(ctx->set, on);
     drop_graph(ctx->col);
     return CS_OK;
 }
@@ -2224,16 +2273,17 @@ int cs_set_merge(cs_ctx *ctx, int on)
 
 static int interp_key(const cs_ctx *ctx)
 {
-    return (ctx->tune[5] ? 65536 : 0) + ctx->interp * 4096 + (ctx->itp_first + 1) * 256 + (ctx->itp_min >> 7) * 16 + (ctx->itp_max >> 7);
+    return (ctx->set.rt_streams ? 65536 : 0) + ctx->interp * 4096 + (ctx->itp_first + 1) * 256 + (ctx->itp_min >> 7) * 16 + (ctx->itp_max >> 7);
 }
 
+constexpr int CS_NTUNE = 24;   // keys 0 .. 23 are accepted
 int cs_set_tuning(cs_ctx *ctx, int key, int value)
 {
     if (!ctx) return fail(CS_EINVAL, "ctx is NULL");
     if (key < 0 || key >= CS_NTUNE) return fail(CS_EINVAL, "tuning key %d out of range", key);
-    if (key == 3 && value != 0 && (value < 15 || value > 100)) return fail(CS_EINVAL, "interpolation margin must be 15..100 per cent of the half-width");
-    if (key == 18 && (value < 0 || value > 2)) return fail(CS_EINVAL, "range-only pass of k_voigt_sub: 0 (by the tables), 1 (never) or 2 (always first)");
-    ctx->tune[key] = value;
+    if (key == CS_TUNE_MARGIN && value != 0 && (value < 15 || value > 100)) return fail(CS_EINVAL, "interpolation margin must be 15..100 per cent of the half-width");
+    if (key == CS_TUNE_SUB_LEAN && (value < 0 || value > 2)) return fail(CS_EINVAL, "range-only pass of k_voigt_sub: 0 (by the tables), 1 (never) or 2 (always first)");
+    set_tuning(ctx->set, key, value);
     drop_graph(ctx->col);
     return CS_OK;
 }
@@ -2409,7 +2459,8 @@ static int gas_states(cs_ctx *ctx, GasTable &G, const ShapeSpec &sh, double dnu_
             (rc = gas_interp_build(ctx, ginterp, cheb, G.h_nu, w.g0, w.g1, nu, nnu, dnu_cut, kc, s, true, w.ds)))
             return rc;
         p.itp = interp_view(cheb, ginterp, kc);
-        interp_settings(ctx, p.itp);
+        interp_select(ctx, p.itp);
+        p.set = &ctx->set;
     }
     for (int k0 = 0; k0 < K; k0 += kc) {
         p.kn = std::min(kc, K - k0);
@@ -2937,7 +2988,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     hipStream_t s = ctx->stream;
     c.nnu = nnu; c.np = np; c.nl = np - 1; c.nlob = nlobatto; c.K = (np - 1) * (nlobatto - 1) + 1;
     c.nstream = nstream; c.ngas = ngas; c.ntile = (int)((nnu + 255) / 256);
-    c.rtg = rt_geometry(nnu, np, 1, nstream, ctx->tune[5] != 0);
+    c.rtg = rt_geometry(nnu, np, 1, nstream, ctx->set.rt_streams);
     c.want_tau = want_tau != 0; c.want_M = want_M != 0;
     c.g = g; c.sigma_gray = sigma_gray; c.theta_s = theta_s;
     const int K = c.K, nl = c.nl;
@@ -3193,7 +3244,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     if ((rc = upload(dTk, Tk.data(), BK, s)) || (rc = upload(dPk, Pk.data(), BK, s)) || (rc = upload(dmuk, muk.data(), BK, s)) ||
         (rc = upload(dTlev, T_levels, (size_t)B * np, s)))
         return rc;
-    const RtGeom bg = rt_geometry(c.nnu, np, B, c.nstream, ctx->tune[5] != 0);
+    const RtGeom bg = rt_geometry(c.nnu, np, B, c.nstream, ctx->set.rt_streams);
     if (!shared_sigma) HIPCHK(dsig.reserve((size_t)BK * c.nnu * sizeof(double)));
     HIPCHK(dpart.reserve((size_t)B * bg.nblk * 2 * np * sizeof(double)));
     HIPCHK(dF.reserve((size_t)B * 2 * np * sizeof(double)));
@@ -3240,7 +3291,8 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
             HIPCHK(dedge.reserve((size_t)((kc + 15) / 16) * nt64 * sizeof(EdgeZone)));
             itp.sep = dsep.as<SepZone>();
             itp.edge = dedge.as<EdgeZone>();
-            interp_settings(ctx, itp);
+            interp_select(ctx, itp);
+            p.set = &ctx->set;
         }
         for (int64_t k0 = 0; k0 < BK; k0 += kc) {
             p.kn = (int)std::min<int64_t>(kc, BK - k0);
@@ -3334,17 +3386,17 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
     if (c.has_phco2) ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id);
     int n_itp = 0;
     for (auto &cg : c.gas) n_itp += cg.itp.nlev > 0 && !cg.vvh ? 1 : 0;   // (the groups whose node sums go into the deferred apply)
-    // cs_set_tuning key 2: node sums on a side stream -- 1: where the grid is short (fewer than 16384 (tile, state) waves), 2: always
-    // key 7: the near-line kernels on a second side stream, into a plane of their own (1, default; 0: after k_voigt_edge_mx, into sigma)
+    // Settings::nodes_stream: node sums on a side stream -- 1: where the grid is short (fewer than 16384 (tile, state) waves), 2: always
+    // Settings::near_stream: the near-line kernels on a second side stream, into a plane of their own (1, default; 0: after k_voigt_edge_mx, into sigma)
     Fork fk;
     memset(&fk, 0, sizeof fk);
     fk.s2 = ctx->stream2; fk.ev_fork = ctx->ev_fork; fk.ev_join = ctx->ev_join;
     fk.s3 = ctx->stream3; fk.ev_fork3 = ctx->ev_fork3; fk.ev_join3 = ctx->ev_join3; fk.ev_far3 = ctx->ev_far3;
-    fk.use_nodes = !ev && (ctx->tune[2] == 2 || (ctx->tune[2] == 1 && (c.nnu + 63) / 64 * (int64_t)K < 16384));
+    fk.use_nodes = !ev && (ctx->set.nodes_stream == 2 || (ctx->set.nodes_stream == 1 && (c.nnu + 63) / 64 * (int64_t)K < 16384));
     // (1 = where it was measured to pay: 1/8 shards of C3 -3..-6 %, C3 -1 %; not on tiny columns -- C2 +19 %: the join costs more than
     //  the kernels -- nor on very long sparse ones -- C5 +2 %; 2 = always)
     const int64_t tswaves = (c.nnu + 63) / 64 * (int64_t)K;
-    fk.use_near = !ev && c.sigma2.p != nullptr && (ctx->tune[7] == 2 || (ctx->tune[7] == 1 && tswaves >= 8192 && tswaves <= 300000));
+    fk.use_near = !ev && c.sigma2.p != nullptr && (ctx->set.near_stream == 2 || (ctx->set.near_stream == 1 && tswaves >= 8192 && tswaves <= 300000));
     fk.sigma2 = fk.use_near ? c.sigma2.as<double>() : nullptr;
     const bool use_fork = fk.use_nodes || fk.use_near;
     for (int gi = 0; gi < (int)c.gas.size(); gi++) {
@@ -3358,8 +3410,9 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
         p.extra = extra; p.sigma = sig; p.accumulate = gi > 0; p.spare = c.vvh.as<double>();
         if (cg.itp.nlev > 0) p.itp = interp_view(c.cheb, cg.itp, K);
         p.itp.F = c.chebF.as<double>();
-        interp_settings(ctx, p.itp);
-        p.itp.fuse_apply = ctx->tune[0] != 0 && n_itp == 1;
+        interp_select(ctx, p.itp);
+        p.set = &ctx->set;
+        p.fuse_apply = ctx->set.fuse_apply && n_itp == 1;
         p.defer = &apply; p.fork = use_fork ? &fk : nullptr; p.evg = ev ? ev + e : nullptr;
         p.log = log;
         const bool voigt = cg.shape == SH_VOIGT || cg.shape == SH_LORENTZ;   // (what line_sum_voigt runs, and plans)
@@ -3381,8 +3434,8 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
     // ... and with the node sums on a side stream the cascade is off the step's critical path whatever the number of levels: that stream
     // ends long before the other two at full size (the bench column: 1.34 against 1.60 and 1.86 ms into the step), so folding three levels
     // into one there makes the carry to the grid a third of its matrix products and of its reads of C (round 5: 1.880 -> 1.872 ms)
-    const bool casc_on = nl_itp >= 2 && ctx->tune[12] != 2 && (ctx->tune[12] == 1 || cascade_pays(nl_itp) || fk.pending);
-    if (apply.ngas == 1 && fk.pending && !(ctx->tune[15] & 256) && nl_itp >= 2 && (short_aside || casc_on)) {
+    const bool casc_on = nl_itp >= 2 && ctx->set.cascade != 2 && (ctx->set.cascade == 1 || cascade_pays(nl_itp) || fk.pending);
+    if (apply.ngas == 1 && fk.pending && !ctx->set.no_cascade_aside && nl_itp >= 2 && (short_aside || casc_on)) {
         const double *Rc[CS_MAX_LEVEL];
         for (int l = 0; l < CS_MAX_LEVEL; l++) Rc[l] = c.cheb.Rc[l].as<double>();
         launch_apply_cascade(fk.s2, apply, Rc, c.cheb.itv, c.cheb.nI, 1, cheb_kpad(K), c.nnu, K, 0.0, nullptr, sig, 1, &carried);
@@ -3398,7 +3451,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
     } else if (apply.ngas > 0) {
         const double *Rc[CS_MAX_LEVEL];
         for (int l = 0; l < CS_MAX_LEVEL; l++) Rc[l] = c.cheb.Rc[l].as<double>();
-        launch_apply_cascade(s, apply, Rc, c.cheb.itv, c.cheb.nI, ctx->tune[12], cheb_kpad(K), c.nnu, K, 0.0, nullptr, sig, 1,
+        launch_apply_cascade(s, apply, Rc, c.cheb.itv, c.cheb.nI, ctx->set.cascade, cheb_kpad(K), c.nnu, K, 0.0, nullptr, sig, 1,
                              fuse ? &fuse->A : nullptr);
         if (fuse) fuse->apply = 1;
     }
@@ -3488,17 +3541,17 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
         fuse.sigma2 = near_live ? c.sigma2.as<double>() : nullptr;
         fuse.F = c.flux_out();
         // up to 512 blocks the last ones to finish add the block partials (two stages of 16 and <= 32 terms); longer grids keep k_freduce
-        fuse.ticket = (fblk <= 512 && !(ctx->tune[15] & 4) && ctx->gfx950) ? c.ticket.as<unsigned>() : nullptr;   // (| 4: k_freduce always, for A/B)
+        fuse.ticket = (fblk <= 512 && !ctx->set.freduce_always && ctx->gfx950) ? c.ticket.as<unsigned>() : nullptr;
         fuse.gpartial = c.partial.as<double>() + (size_t)std::max<int64_t>(c.rtg.nblk, (c.nnu + 63) / 64) * 2 * c.np;
         reduced = fuse.ticket != nullptr;
         if (reduced) log.disp.flags |= CS_DF_BAND_SUM;
-        if (form == 2 && (ctx->tune[15] & 8)) log.disp.flags |= CS_DF_CHUNK4;
-        if ((ctx->tune[15] & 128) && c.fluxdbg.reserve((8 + 2 * (size_t)fblk + 32) * sizeof(unsigned long long)) == hipSuccess) fuse.dbg = c.fluxdbg.as<unsigned long long>();
+        if (form == 2 && ctx->set.chunk4) log.disp.flags |= CS_DF_CHUNK4;
+        if (ctx->set.scan_stamps && c.fluxdbg.reserve((8 + 2 * (size_t)fblk + 32) * sizeof(unsigned long long)) == hipSuccess) fuse.dbg = c.fluxdbg.as<unsigned long long>();
         // the chunked form always writes the layer optical depths (its upward sweep reads them back): into the caller's plane or scratch
         if (form == 2) fa.tau = c.tau.as<double>();   // (forms 0 and 3 keep the optical depths in LDS unless the caller wants them)
         bool rad = false;
         for (int t = 0; t < fuse.ncia; t++) rad = rad || fuse.cia[t].Tr != nullptr;
-        launch_flux(form, fsh, fblk, fthr, fa, fuse, rad, (ctx->tune[15] & 8) == 0, (ctx->tune[15] & 2048) != 0);
+        launch_flux(form, fsh, fblk, fthr, fa, fuse, rad, !ctx->set.chunk4, ctx->set.scan_recompute);
     } else {
         if (c.rtg.streams) log.disp.flags |= CS_DF_RT_STREAMS;
         launch_rt(c.rtg, 1, fa, 0, near_live ? c.sigma2.as<double>() : nullptr);
@@ -3527,7 +3580,7 @@ int cs_column_run(cs_ctx *ctx, void *stream)
     HIPCHK(hipSetDevice(ctx->device));   // (a process may drive several contexts on several devices: cs_fluxes_discretized_multi)
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     Column &c = ctx->col;
-    if (!ctx->tune[4]) return run_impl(ctx, s, nullptr);
+    if (!ctx->set.graph) return run_impl(ctx, s, nullptr);
     if (c.graph_exec && c.has_phco2 && ctx->ph.builds != c.graph_ph_builds) drop_graph(c);   // (the captured launches name another layout of the levels)
     if (c.graph_exec) {
         {   // (a replayed graph carries the kernel arguments of the slots' old contents: gas tables, opacity tables, knots)
@@ -3757,7 +3810,7 @@ int cs_phco2_plan(int64_t nnu, const double *nu, double dnu_cut, int cap, int *i
     return nv;
 }
 
-// test hooks: the plan under a context's settings (interpolation on / off, size range, margin, cs_set_tuning key 10) with the regions of
+// test hooks: the plan under a context's settings (interpolation on / off, size range, margin, CS_TUNE_PH_NODES) with the regions of
 // `drop` (bit r = region r + 1) kept out, and the mask ph_wide_regions forms from K states (T, Lorentz-width bound)
 int cs_phco2_plan_ctx(cs_ctx *ctx, int64_t nnu, const double *nu, double dnu_cut, int drop, int cap, int *interval_sizes, int *nodes, int *regions)
 {
@@ -4079,7 +4132,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
     out[CS_WORK_FLAGS] = c.log_last.disp.flags;
     out[CS_WORK_SUB_LEAN_EVALS] = w.subn_lean;
     // (the flux-phase stamps describe the stamp buffer's contents: the only part that looks at a setting)
-    if (c.fluxdbg.p && (ctx->tune[15] & 128)) {   // k_flux_scan's phases in block 0, ns: cross-sections, depths + Planck, chunk pass, hand-over, second pass, band sum
+    if (c.fluxdbg.p && ctx->set.scan_stamps) {   // k_flux_scan's phases in block 0, ns: cross-sections, depths + Planck, chunk pass, hand-over, second pass, band sum
         unsigned long long st[8] = {};
         (void)hipMemcpy(st, c.fluxdbg.p, sizeof st, hipMemcpyDeviceToHost);
         for (int q = 0; q < 4; q++) out[CS_WORK_FLUX_SCAN_NS + q] = (int64_t)(st[q + 1] - st[q]) * 10;   // (100 MHz clock)
@@ -4661,13 +4714,13 @@ int cs_fluxes_discretized_multi(cs_ctx *const *ctxs, int nctx, int64_t nnu, cons
     if (!(mp.nctx == nctx && (int64_t)mp.nu.size() == nnu && mp.gens == gens && memcmp(mp.nu.data(), nu, (size_t)nnu * sizeof(double)) == 0)) {
         if ((rc = cs_balanced_ranges(nnu, nu, ngas, nl_.data(), ln_.data(), nctx, ranges.data()))) return rc;
         // a new plan: once, inside this call, the model's partition is re-cut from what its ranges are measured to take on THIS column
-        // (cs_rebalance_ranges) -- where every context has a device to itself, so that a range's time is its own (cs_set_tuning key 15 |
-        // 32 on the first context: also on shared devices, for tests)
+        // (cs_rebalance_ranges) -- where every context has a device to itself, so that a range's time is its own (Settings::multi_recut
+        // of the first context: also on shared devices, for tests)
         calibrate = ngas > 0;
         for (int i = 0; i < nctx && calibrate; i++)
             for (int q = 0; q < i; q++)
                 if (ctxs[q]->device == ctxs[i]->device) calibrate = false;
-        if (ctxs[0]->tune[15] & 32) calibrate = ngas > 0;
+        if (ctxs[0]->set.multi_recut) calibrate = ngas > 0;
         mp.nctx = nctx;
         mp.nu.assign(nu, nu + nnu);
         mp.gens = gens;

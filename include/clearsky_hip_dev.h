@@ -35,71 +35,124 @@ int cs_set_matrix_cores(cs_ctx *ctx, int on);
  * lines changes).  Applies to every later cs_column_setup / cs_fluxes_discretized of the context. */
 int cs_set_merge(cs_ctx *ctx, int on);
 
-/* Tuning switches for A/B measurements (results do not depend on them beyond rounding; defaults from profiles/r03_notes.md):
- *   key 0: the interpolated far wings are carried to the grid inside k_voigt_edge_mx where the column has one launch group (1), or
- *          by their own launch (0, default: one launch more, the same time at C3, less with five interval levels);
- *   key 1: the matrix-core kernels also on grids too short to fill the chip with one (interval | tile, state group) per wave, through
- *          their four-waves-per-item variants (1, default; 0: such grids stay on the vector unit);
- *   key 2: the node sums of a launch group run on a side stream beside its per-point kernels -- 2 (default) always, 1 on short
- *          grids only (fewer than 16384 (tile, state) waves: a nu-shard), 0 never;
- *   key 3: distance of an interval's interpolated set from the interval, per cent of its half-width (0 = the default 30; 15..100);
- *   key 4: cs_column_run replays the step as one hipGraph (captured on the second run after anything changed launch geometry or
- *          kernel arguments; cs_column_update_state does not) instead of enqueuing its kernels one by one -- 0 (default) off, 1 on;
- *   key 5: on short grids (up to 400 tiles) the flux sweeps run one wave per (sweep, stream) of a tile (k_rt_streams) instead of one
- *          per sweep -- 1 (default), 0 off;
- *   key 6: how many interval sizes, largest first, have their matrix-core node sums shared by the four waves of a block (0 = the
- *          default, see profiles/r03_notes.md);
- *   key 7: the sub-tile cores (k_voigt_sub) and the near-line kernels run on a second side stream -- the former beside k_voigt_far,
- *          the latter beside k_voigt_edge_mx and what follows it -- adding into a plane of their own that k_rt reads together with
- *          sigma: 1 (default) on grids of 8192 .. 300000 (tile, state) waves, where it was measured to pay; 2 always; 0: on the
+/* Tuning switches for A/B measurements (results do not depend on them beyond rounding; defaults from profiles/r03_notes.md).  `key` is one
+ * of CS_TUNE_* below; the library decodes a (key, value) pair in one place (set_tuning in csrc/cs_api.hip) into a named record of settings.
+ * In ascending key order:
+ *   CS_TUNE_FUSE_APPLY (0): the interpolated far wings are carried to the grid inside k_voigt_edge_mx where the column has one launch
+ *          group (1), or by their own launch (0, default: one launch more, the same time at C3, less with five interval levels);
+ *   CS_TUNE_SMALL_MX (1): the matrix-core kernels also on grids too short to fill the chip with one (interval | tile, state group) per
+ *          wave, through their four-waves-per-item variants (1, default; 0: such grids stay on the vector unit);
+ *   CS_TUNE_NODES_STREAM (2): the node sums of a launch group run on a side stream beside its per-point kernels -- 2 (default) always,
+ *          1 on short grids only (fewer than 16384 (tile, state) waves: a nu-shard), 0 never;
+ *   CS_TUNE_MARGIN (3): distance of an interval's interpolated set from the interval, per cent of its half-width (0 = the default 30;
+ *          15..100);
+ *   CS_TUNE_GRAPH (4): cs_column_run replays the step as one hipGraph (captured on the second run after anything changed launch geometry
+ *          or kernel arguments; cs_column_update_state does not) instead of enqueuing its kernels one by one -- 0 (default) off, 1 on;
+ *   CS_TUNE_RT_STREAMS (5): on short grids (up to 400 tiles) the flux sweeps run one wave per (sweep, stream) of a tile (k_rt_streams)
+ *          instead of one per sweep -- 1 (default), 0 off;
+ *   CS_TUNE_NSPLIT_LEVELS (6): how many interval sizes, largest first, have their matrix-core node sums shared by the four waves of a
+ *          block (0 = the default, one; see profiles/r03_notes.md);
+ *   CS_TUNE_NEAR_STREAM (7): the sub-tile cores (k_voigt_sub) and the near-line kernels run on a second side stream -- the former beside
+ *          k_voigt_far, the latter beside k_voigt_edge_mx and what follows it -- adding into a plane of their own that k_rt reads together
+ *          with sigma: 1 (default) on grids of 8192 .. 300000 (tile, state) waves, where it was measured to pay; 2 always; 0: on the
  *          main stream, into sigma;
- *   key 8: a far line joins a state group's matrix-core node piece when at least this many of the group's 16 states are beyond their
- *          own series radius (the others' coefficients are masked, the vector unit sums them) -- default 7; 16 = the group's widest
- *          line decides (round 2), 1 = its narrowest;
- *   key 9: PHCO2: the pairs within 3 cm^-1 of a line (chi = 1 there: the plain Voigt profile, every near-line pair among them) go
- *          through the Voigt kernels with a 3 cm^-1 cut-off after k_phco2 (0, default), or through k_phco2's own core loop (1);
- *   key 10: PHCO2 interpolation levels: bit 0 = 64 nodes on every interval (default: 16 or 32 where a region's lines are many
- *          half-widths from the intervals of a size), bit 1 = the 64-point tiles themselves as the smallest interval size;
- *   key 11: the far pieces of an interval's matrix-core node sums (the lines beyond its parent's set: 3.8 .. 12 half-widths away on
- *          the bench grid) are summed on 32 or 16 nodes and carried to the interval's 64 (0, default), or on all 64 (1);
- *   key 12: the node sums of a level are added into the next smaller level's (a 64 x 64 matrix per interval) and only the smallest
- *          interval size is carried to the grid (k_cheb_cascade) -- 0 (default) with four or more levels in use and, on the node-sum side
- *          stream (key 2), from two levels on (it is off the critical path there), 1 always, 2 never;
- *   key 13: the vector-unit node kernel with four waves per (interval, state), a quarter of every window each -- 0 (default) on
- *          grids of fewer than 16384 (interval, state) waves (a nu-shard), 1 always, 2 never;
- *   key 14: k_voigt_edge_mx cuts a cut-off edge where the next 16-column sub-tile of the tile comes into the lines' reach and
- *          multiplies only the sub-tiles a part can reach (0, default), or all four for every line (1);
- *   key 15: the flux kernel finishes the cross-sections on chip (k_flux: the interpolated wings as a matrix product, the CIA pairs and
- *          the near-line plane are added per 64-point tile in LDS instead of by read-modify-write passes over the [K][nnu] plane, and
- *          the last block adds the band-flux partials; fluxes.jl:270-277 does depth and flux of a wavenumber in one loop body) -- 0
- *          (default) where it pays: grids of up to 1024 tiles (a nu-shard, a small column) and of 4096 tiles or more, 1 never, 2 always;
- *          | 4: the block partials are always added by k_freduce's own launch, | 8: the long-grid form with four waves per SIMD (A/B);
- *          | 16: the matrix-core piece tables with one thread per (interval | tile, state group) (k_mxzones) instead of sixteen lanes (A/B);
- *          | 256: on short grids the interval levels are NOT folded into the smallest one on the node-sum side stream (A/B);
- *          | 1024: the scan form also on grids of 1024 .. 4096 tiles (A/B: slower at 1563 tiles);
- *          | 2048: k_flux_scan forms the transmissivities of a layer chunk again in its second sweep and second pass instead of
- *          keeping them in registers (A/B; same results);
- *          | 32 (on the first context of a cs_fluxes_discretized_multi call): the partition is re-cut from measured times also when
- *          contexts share a device (tests);
- *   key 16: issue priority (s_setprio 3) for the waves of the near-line stream's kernels (k_voigt_sub, k_voigt_near), whose chains of
- *          dependent gathers otherwise lose their issue slots to the streaming kernels on the other two streams -- 0 (default) on grids
- *          of 512 tiles or more, 1 never, 2 always (bench column 2.00 -> 1.95 ms; an eighth of it 0.378 -> 0.387, hence the threshold).
- *          | 4: the two tiers of the near-line pairs in two launches (k_voigt_near<0>, <1>) also where a wave takes one tile, instead of
- *          one (k_voigt_near_both) (A/B; same results).
- *   key 19: the near-line plane of a step is cleared by a memset in front of its first kernel (1) instead of written by that kernel,
- *          k_voigt_sub (0, default: one launch and 8 B per (state, point) of writes less) (A/B; same results);
- *   key 21: the piece tables of the matrix-core kernels as blocks of k_gas_setup's launch, computing the zones they need themselves
- *          (k_gas_setup_mx) -- 0 (default) on grids below 1024 tiles, 1 never (k_mxzones16 as its own launch), 2 always (A/B; same tables);
- *   key 22: waves per 64-point tile of k_voigt_far: 1, 2 or 4 (0, default: by the number of (tile, state) waves) (A/B).
- *   key 23: the window-end lines of k_voigt_edge_mx inside the cut-off of every point of a tile at the points, masked, like the others (1)
- *          instead of on 16 Chebyshev nodes of the tile (0, default, where the grid allows: cut-off far beyond tile + smallest interval) (A/B).
- *   key 17: where the four waves of a block share every item of k_cheb_nodes_mx (short grids), the far pieces of an interval on all 64
- *          nodes (1) instead of on its level's 16 or 32, a quarter of the lines per wave (0, default) (A/B).
- *   key 18: the range-only pass of k_voigt_sub -- hand-off ranges only, no series -- 0 (default) in the waves whose octet of states the piece
- *          tables mark as unable to reach the series inside the core radius (EdgeZone::lean), 1 never (the full loop everywhere), 2 first
- *          in every wave; a wave that meets a series pair on that pass runs the full loop afterwards (A/B; same results).
- *   (key 20 is unused.)
+ *   CS_TUNE_MX_MIN_STATES (8): a far line joins a state group's matrix-core node piece when at least this many of the group's 16 states
+ *          are beyond their own series radius (the others' coefficients are masked, the vector unit sums them) -- 0 = the default 7;
+ *          16 = the group's widest line decides (round 2), 1 = its narrowest;
+ *   CS_TUNE_PH_OWN_CORE (9): PHCO2: the pairs within 3 cm^-1 of a line (chi = 1 there: the plain Voigt profile, every near-line pair among
+ *          them) go through the Voigt kernels with a 3 cm^-1 cut-off after k_phco2 (0, default), or through k_phco2's own core loop (1);
+ *   CS_TUNE_PH_NODES (10): PHCO2 interpolation levels: bit 0 = 64 nodes on every interval (default: 16 or 32 where a region's lines are
+ *          many half-widths from the intervals of a size), bit 1 = the 64-point tiles themselves as the smallest interval size;
+ *   CS_TUNE_FAR64 (11): the far pieces of an interval's matrix-core node sums (the lines beyond its parent's set: 3.8 .. 12 half-widths
+ *          away on the bench grid) are summed on 32 or 16 nodes and carried to the interval's 64 (0, default), or on all 64 (1);
+ *   CS_TUNE_CASCADE (12): the node sums of a level are added into the next smaller level's (a 64 x 64 matrix per interval) and only the
+ *          smallest interval size is carried to the grid (k_cheb_cascade) -- 0 (default) with four or more levels in use and, on the
+ *          node-sum side stream (CS_TUNE_NODES_STREAM), from two levels on (it is off the critical path there), 1 always, 2 never;
+ *   CS_TUNE_NODES_SPLIT (13): the vector-unit node kernel with four waves per (interval, state), a quarter of every window each -- 0
+ *          (default) on grids of fewer than 16384 (interval, state) waves (a nu-shard), 1 always, 2 never;
+ *   CS_TUNE_EDGE_FULL (14): k_voigt_edge_mx cuts a cut-off edge where the next 16-column sub-tile of the tile comes into the lines' reach
+ *          and multiplies only the sub-tiles a part can reach (0, default), or all four for every line (1);
+ *   CS_TUNE_FLUX (15): the flux kernel finishes the cross-sections on chip (k_flux: the interpolated wings as a matrix product, the CIA
+ *          pairs and the near-line plane are added per 64-point tile in LDS instead of by read-modify-write passes over the [K][nnu]
+ *          plane, and the last block adds the band-flux partials; fluxes.jl:270-277 does depth and flux of a wavenumber in one loop body).
+ *          The low two bits (CS_T15_FORM_MASK) choose the form: 0 (default) where it pays -- grids of up to 1024 tiles (a nu-shard, a
+ *          small column) and of 4096 tiles or more --, 1 never, 2 always.  The other bits are switches of their own, ORed on:
+ *            CS_T15_FREDUCE: the block partials are always added by k_freduce's own launch;
+ *            CS_T15_CHUNK4: the long-grid form with four waves per SIMD (A/B);
+ *            CS_T15_TABLES_ONE_THREAD: the matrix-core piece tables with one thread per (interval | tile, state group) (k_mxzones) instead
+ *              of sixteen lanes (A/B);
+ *            CS_T15_MULTI_RECUT (on the first context of a cs_fluxes_discretized_multi call): the partition is re-cut from measured times
+ *              also when contexts share a device (tests);
+ *            CS_T15_SCAN_STAMPS: block 0 of k_flux_scan stamps its phases (CS_WORK_FLUX_SCAN_NS .. of cs_column_work);
+ *            CS_T15_NO_CASCADE_ASIDE: on short grids the interval levels are NOT folded into the smallest one on the node-sum side
+ *              stream (A/B);
+ *            CS_T15_SCAN_MID: the scan form also on grids of 1024 .. 4096 tiles (A/B: slower at 1563 tiles);
+ *            CS_T15_SCAN_RECOMPUTE: k_flux_scan forms the transmissivities of a layer chunk again in its second sweep and second pass
+ *              instead of keeping them in registers (A/B; same results);
+ *   CS_TUNE_NEAR_PRIO (16): issue priority (s_setprio 3) for the waves of the near-line stream's kernels (k_voigt_sub, k_voigt_near), whose
+ *          chains of dependent gathers otherwise lose their issue slots to the streaming kernels on the other two streams -- low two bits
+ *          (CS_T16_PRIO_MASK): 0 (default) on grids of 512 tiles or more, 1 never, 2 always (bench column 2.00 -> 1.95 ms; an eighth of
+ *          it 0.378 -> 0.387, hence the threshold).  | CS_T16_NEAR_TWO_LAUNCHES: the two tiers of the near-line pairs in two launches
+ *          (k_voigt_near<0>, <1>) also where a wave takes one tile, instead of one (k_voigt_near_both) (A/B; same results);
+ *   CS_TUNE_FAR64_SHARED (17): where the four waves of a block share every item of k_cheb_nodes_mx (short grids), the far pieces of an
+ *          interval on all 64 nodes (1) instead of on its level's 16 or 32, a quarter of the lines per wave (0, default) (A/B);
+ *   CS_TUNE_SUB_LEAN (18): the range-only pass of k_voigt_sub -- hand-off ranges only, no series -- 0 (default) in the waves whose octet
+ *          of states the piece tables mark as unable to reach the series inside the core radius (EdgeZone::lean), 1 never (the full loop
+ *          everywhere), 2 first in every wave; a wave that meets a series pair on that pass runs the full loop afterwards (A/B; same
+ *          results); other values are refused;
+ *   CS_TUNE_NEAR_MEMSET (19): the near-line plane of a step is cleared by a memset in front of its first kernel (1) instead of written by
+ *          that kernel, k_voigt_sub (0, default: one launch and 8 B per (state, point) of writes less) (A/B; same results);
+ *   (key 20 is accepted and unused;)
+ *   CS_TUNE_TABLES_MERGE (21): the piece tables of the matrix-core kernels as blocks of k_gas_setup's launch, computing the zones they
+ *          need themselves (k_gas_setup_mx) -- 0 (default) on grids below 1024 tiles, 1 never (k_mxzones16 as its own launch), 2 always
+ *          (A/B; same tables);
+ *   CS_TUNE_FAR_SPLIT (22): waves per 64-point tile of k_voigt_far: 1, 2 or 4 (0, default: by the number of (tile, state) waves) (A/B);
+ *   CS_TUNE_EDGE_POINTS (23): the window-end lines of k_voigt_edge_mx inside the cut-off of every point of a tile at the points, masked,
+ *          like the others (1) instead of on 16 Chebyshev nodes of the tile (0, default, where the grid allows: cut-off far beyond tile +
+ *          smallest interval) (A/B).
  * Applies to every later cs_column_setup / cs_column_run of the context. */
+enum {
+    CS_TUNE_FUSE_APPLY = 0,
+    CS_TUNE_SMALL_MX = 1,
+    CS_TUNE_NODES_STREAM = 2,
+    CS_TUNE_MARGIN = 3,
+    CS_TUNE_GRAPH = 4,
+    CS_TUNE_RT_STREAMS = 5,
+    CS_TUNE_NSPLIT_LEVELS = 6,
+    CS_TUNE_NEAR_STREAM = 7,
+    CS_TUNE_MX_MIN_STATES = 8,
+    CS_TUNE_PH_OWN_CORE = 9,
+    CS_TUNE_PH_NODES = 10,
+    CS_TUNE_FAR64 = 11,
+    CS_TUNE_CASCADE = 12,
+    CS_TUNE_NODES_SPLIT = 13,
+    CS_TUNE_EDGE_FULL = 14,
+    CS_TUNE_FLUX = 15,
+    CS_TUNE_NEAR_PRIO = 16,
+    CS_TUNE_FAR64_SHARED = 17,
+    CS_TUNE_SUB_LEAN = 18,
+    CS_TUNE_NEAR_MEMSET = 19,
+    CS_TUNE_TABLES_MERGE = 21,
+    CS_TUNE_FAR_SPLIT = 22,
+    CS_TUNE_EDGE_POINTS = 23
+};
+/* bits of the value of CS_TUNE_FLUX */
+enum {
+    CS_T15_FORM_MASK = 3,
+    CS_T15_FREDUCE = 4,
+    CS_T15_CHUNK4 = 8,
+    CS_T15_TABLES_ONE_THREAD = 16,
+    CS_T15_MULTI_RECUT = 32,
+    CS_T15_SCAN_STAMPS = 128,
+    CS_T15_NO_CASCADE_ASIDE = 256,
+    CS_T15_SCAN_MID = 1024,
+    CS_T15_SCAN_RECOMPUTE = 2048
+};
+/* bits of the value of CS_TUNE_NEAR_PRIO */
+enum {
+    CS_T16_PRIO_MASK = 3,
+    CS_T16_NEAR_TWO_LAUNCHES = 4
+};
 int cs_set_tuning(cs_ctx *ctx, int key, int value);
 
 /* run `reps` evaluations with HIP events between the kernel classes on `stream`; ms[10] = average milliseconds per
@@ -150,30 +203,30 @@ enum {
     CS_WORK_NODES_MX_FLOPS_USEFUL = 24, /* the same for k_cheb_nodes_mx */
     CS_WORK_NODES_MX_FLOPS_ISSUED = 25,
     CS_WORK_APPLY_FLOPS = 26,       /* the node-sum -> grid contraction (k_cheb_apply_mfma, or inside k_voigt_edge_mx / k_flux_*) */
-    CS_WORK_FLUX_SCAN_NS = 27,      /* [27..31], with cs_set_tuning key 15 | 128 (0 otherwise; 100 MHz wall clock): ns block 0 of k_flux_scan spent on */
+    CS_WORK_FLUX_SCAN_NS = 27,      /* [27..31], with CS_TUNE_FLUX | CS_T15_SCAN_STAMPS (0 otherwise; 100 MHz wall clock): ns block 0 of k_flux_scan spent on */
                                     /* cross-sections, depths + Planck values, first pass over its layer chunk, hand-over of the incoming intensities; */
     CS_WORK_FLUX_SCAN_TOTAL_NS = 31,    /* and from its first instruction to the last block's store of the band fluxes */
     CS_WORK_EDGE_MX_RECORD_BYTES = 32,  /* per-(state, line) records k_voigt_edge_mx REQUESTS per launch: lines of every piece x 16 states x 32 B */
     CS_WORK_NODES_MX_RECORD_BYTES = 33, /* ... k_cheb_nodes_mx (neighbouring tiles / intervals ask for the same record again: the unique ones are K x lines in range x 32 B) */
     /* [34..39]: what the last cs_column_run (or cs_column_batch) dispatched; [34..38] for its last Voigt group (0 where it had none) */
-    CS_WORK_FAR_SPLIT = 34,         /* waves per 64-point tile of k_voigt_far (1, 2, 4; key 22) */
-    CS_WORK_TABLES = 35,            /* the matrix-core piece tables: 0 none, 1 blocks of k_gas_setup_mx, 2 k_mxzones16, 3 k_mxzones (one thread per item; key 21, key 15 | 16) */
-    CS_WORK_NEAR_PRIO = 36,         /* wave priority of the near-line kernels (0, 3; key 16) */
-    CS_WORK_STREAMS = 37,           /* side streams: 1 node sums, 2 near-line kernels (keys 2, 7) */
-    CS_WORK_NODES_SPLIT = 38,       /* 1 where k_cheb_nodes ran four waves per (interval, state) (key 13) */
+    CS_WORK_FAR_SPLIT = 34,         /* waves per 64-point tile of k_voigt_far (1, 2, 4; CS_TUNE_FAR_SPLIT) */
+    CS_WORK_TABLES = 35,            /* the matrix-core piece tables: 0 none, 1 blocks of k_gas_setup_mx, 2 k_mxzones16, 3 k_mxzones (one thread per item; CS_TUNE_TABLES_MERGE, CS_T15_TABLES_ONE_THREAD) */
+    CS_WORK_NEAR_PRIO = 36,         /* wave priority of the near-line kernels (0, 3; CS_TUNE_NEAR_PRIO) */
+    CS_WORK_STREAMS = 37,           /* side streams: 1 node sums, 2 near-line kernels (CS_TUNE_NODES_STREAM, CS_TUNE_NEAR_STREAM) */
+    CS_WORK_NODES_SPLIT = 38,       /* 1 where k_cheb_nodes ran four waves per (interval, state) (CS_TUNE_NODES_SPLIT) */
     CS_WORK_FLAGS = 39,             /* CS_DF_* of the whole step */
-    CS_WORK_SUB_LEAN_EVALS = 40,    /* the part of [16] in waves that start with the range-only pass by the piece tables (0 with key 18 = 1) */
+    CS_WORK_SUB_LEAN_EVALS = 40,    /* the part of [16] in waves that start with the range-only pass by the piece tables (0 with CS_TUNE_SUB_LEAN = 1) */
     CS_WORK_COUNT = 41
 };
 /* out[CS_WORK_FLAGS] */
 enum {
-    CS_DF_TNODES = 1,           /* window ends on the 16 tile nodes in k_voigt_edge_mx (key 23) */
-    CS_DF_NEAR_MEMSET = 2,      /* near-line plane cleared by a memset (key 19) */
-    CS_DF_RT_STREAMS = 4,       /* k_rt_streams (key 5) */
-    CS_DF_BAND_SUM = 8,         /* band sum inside the flux kernel (key 15 | 4) */
-    CS_DF_FAR64_SHARED = 16,    /* far pieces of shared items on 64 nodes (key 17) */
-    CS_DF_CHUNK4 = 32,          /* k_flux_chunk with four waves per SIMD (key 15 | 8) */
-    CS_DF_CASCADE_ASIDE = 64    /* levels folded on the node-sum side stream (key 15 | 256) */
+    CS_DF_TNODES = 1,           /* window ends on the 16 tile nodes in k_voigt_edge_mx (CS_TUNE_EDGE_POINTS = 0) */
+    CS_DF_NEAR_MEMSET = 2,      /* near-line plane cleared by a memset (CS_TUNE_NEAR_MEMSET) */
+    CS_DF_RT_STREAMS = 4,       /* k_rt_streams (CS_TUNE_RT_STREAMS) */
+    CS_DF_BAND_SUM = 8,         /* band sum inside the flux kernel (not under CS_T15_FREDUCE) */
+    CS_DF_FAR64_SHARED = 16,    /* far pieces of shared items on 64 nodes (CS_TUNE_FAR64_SHARED) */
+    CS_DF_CHUNK4 = 32,          /* k_flux_chunk with four waves per SIMD (CS_T15_CHUNK4) */
+    CS_DF_CASCADE_ASIDE = 64    /* levels folded on the node-sum side stream (not under CS_T15_NO_CASCADE_ASIDE) */
 };
 int cs_column_work(cs_ctx *ctx, int64_t *out);
 
@@ -186,8 +239,8 @@ int cs_interp_plan(int64_t nnu, const double *nu, double dnu_cut, int *interval_
  * away) and the chi-regions summed with that node count (bit 0: 3-30 cm^-1, bit 1: 30-120, bit 2: 120-cut-off).  Host only.  Returns
  * their number (at most 16; 0: every pair per point); the arrays hold `cap` entries. */
 int cs_phco2_plan(int64_t nnu, const double *nu, double dnu_cut, int cap, int *interval_sizes, int *nodes, int *regions);
-/* test hooks.  cs_phco2_plan_ctx: the same plan under the settings of `ctx` (cs_set_interp, cs_set_interp_plan, cs_set_tuning keys 3 and
- * 10) with the chi-regions of `drop` (bit 0: 3-30 cm^-1, bit 1: 30-120, bit 2: 120-cut-off) kept out of every level.
+/* test hooks.  cs_phco2_plan_ctx: the same plan under the settings of `ctx` (cs_set_interp, cs_set_interp_plan, cs_set_tuning CS_TUNE_MARGIN and
+ * CS_TUNE_PH_NODES) with the chi-regions of `drop` (bit 0: 3-30 cm^-1, bit 1: 30-120, bit 2: 120-cut-off) kept out of every level.
  * cs_phco2_wide_regions: the regions (same bits) that K states (temperature, upper bound of the Lorentz width in cm^-1) keep out of the
  * levels of a launch -- a state so wide that a zero of the profile's denominator comes within a tenth of the region's near distance of
  * the real axis.  A launch sums such a region per point. */

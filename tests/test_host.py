@@ -36,6 +36,20 @@ def test_work_layout_table_matches_the_header(cs):
     assert work == [q for q in range(cs.WORK_COUNT) if q not in (28, 29, 30)], work     # (CS_WORK_FLUX_SCAN_NS names the first of four)
 
 
+def test_tuning_key_table_matches_the_header(cs):
+    """The package's name table of the cs_set_tuning keys against the CS_TUNE_* enum of include/clearsky_hip_dev.h: keys 0 .. 23 with only
+    20 missing, and the named bits of keys 15 and 16 at the values callers have always passed as integers."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "clearsky_hip_dev.h")).read(), flags=re.S)
+    enum = {n: int(v) for n, v in re.findall(r"\b(CS_T(?:UNE|15|16)_[A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    keys = {n[len("CS_TUNE_"):]: v for n, v in enum.items() if n.startswith("CS_TUNE_")}
+    assert keys == cs.TUNING
+    assert sorted(keys.values()) == [k for k in range(24) if k != 20]
+    assert {n[len("CS_T15_"):]: v for n, v in enum.items() if n.startswith("CS_T15_")} == dict(
+        FORM_MASK=3, FREDUCE=4, CHUNK4=8, TABLES_ONE_THREAD=16, MULTI_RECUT=32, SCAN_STAMPS=128, NO_CASCADE_ASIDE=256, SCAN_MID=1024,
+        SCAN_RECOMPUTE=2048)
+    assert {n[len("CS_T16_"):]: v for n, v in enum.items() if n.startswith("CS_T16_")} == dict(PRIO_MASK=3, NEAR_TWO_LAUNCHES=4)
+
+
 def test_no_oracle_in_product():
     """The shipped path must not import, link or call anything under oracle/."""
     pkg = os.path.join(ROOT, "clearsky.jl_amd")
