@@ -79,6 +79,7 @@ struct VoigtPlan {
 struct Dispatch { int far_split, tables, near_prio, streams, nodes_split, flags; };
 // What the step being enqueued did, kept by the caller that enqueues it (run_impl, cs_column_batch) and reached by the launchers through
 // GasPass::log (NULL: nobody asks)
+struct PhPlan;
 struct StepLog {
     Dispatch disp = {};
     int near_launches = 0;      // near-line launches, all groups
@@ -92,6 +93,7 @@ struct StepLog {
         if (!pl.lor) near_launches += pl.near_both ? 1 : 2;
         line_kernel = 0;
     }
+    void phco2_group(const PhPlan &pl);   // a PHCO2 group as planned (defined below PhPlan)
 };
 
 #define HIPCHK(expr)                                                                                   \
@@ -280,6 +282,7 @@ struct ColGas {
     double cut = 25.0;
     GroupWindows w;           // the group's windows on the column's grid, widened by its largest shift at the node pressures (build_windows)
     GroupStates st;           // what the group needs per node state (upload_group_states; cs_column_update_state)
+    int ph_mask = -1;         // PHCO2: the regions those states keep out of the levels (ph_wide_regions; -1 before the first upload)
     DevBuf zones;             // [K][ntile64] Zone
     GasInterp itp;            // interpolated far wings (nlev = 0: off)
     bool ped = false;         // shape code 4: shape is SH_VOIGT and launch_pedestal follows the line sum over [w.pa, w.pb)
@@ -454,30 +457,108 @@ static void set_tuning(Settings &st, int key, int v)
 //   gas_states (cs_shape_batch, cs_shape_points,       under the context's where the call builds an interpolation view (cs_set_interp on and a
 //     cs_bake) and cs_column_batch                      shape of the Voigt family | a group with interpolation levels), else under the defaults;
 //   the inner Voigt pass of PHCO2 (line_sum_phco2)     always under the defaults.
+// What a PHCO2 group itself reads of the context does not go through GasPass::set: the six inputs of PhRules (ph_rules) reach every PHCO2
+// pass, from every entry point, with the grid (ph_set_grid).
 static const Settings kDefaultSettings;
 
-// workspace of the PHCO2 fast path (k_phco2): per-(state, line) chi factors and per-tile region windows
-// nu_lo .. grid_id: the grid of the call, set by the caller (ph_set_grid); cheb, piw, F: the interpolation levels of that grid for the
-// PHCO2 cut-off (k_phco2_nodes), rebuilt when the key (grid_id, nnu, cut) changes
-struct PhScratch {
-    DevBuf fac, win, piw, F, win3, zones3;   // win3, zones3: windows and zones of the Voigt pass over the pairs within 3 cm^-1
-    struct Dens { const void *tab; uint64_t gen, grid; bool ok; };
-    std::vector<Dens> dens;                  // check_near_density() per (table, grid), a few kept
-    double nu_lo = 0.0, nu_hi = 0.0, nu_c = 0.0, max_span = 0.0, margin = kChebMargin;
-    int itp_on = 0, itp_min = 128, itp_max = 2048, own_core = 0;   // own_core: Settings::ph_own_core
-    uint64_t grid_id = 0;
-    double lev_span[8] = {};   // widest interval of 8192 >> i points on this grid (ph_set_grid)
-    int force64 = 0;           // Settings::ph_nodes: 64 nodes for every interval (bit 0), tiles as 64-point intervals too (bit 1)
-    uint64_t builds = 0;       // how often ph_interp_ready has (re)built the levels: a captured step holds the layout of one build
-    int drop = 0;              // regions (bit r = region r + 1) the states of the coming launch keep out of the levels (ph_wide_regions)
-    // interval sizes in use (descending) and the virtual levels on them (PhVLevels); nodes [sum nI x nc], Cm[v] [nI][nc][itv]
-    struct Grid {
-        PhLevels lv; PhVLevels vl; PhFine fine;
-        int nnodes = 0, nslots = 0;
-        DevBuf nodes, Cm[CS_MAX_ALEVEL];
-    } grid;
-    uint64_t built_id = 0; int64_t built_nnu = 0; double built_cut = 0.0, built_margin = 0.0; int built_min = 0, built_max = 0, built_force = 0, built_drop = 0;
+namespace {
+// ---- the PHCO2 fast path (k_phco2) on the host: what it knows of a grid (PhGrid), what the context says about it (PhRules), the interpolation
+// levels that follow from both (PhLevelSet, ph_levels), what built levels were built for (PhKey), and the context's workspace (PhScratch).
+// How one group is run: PhPlan, below.
+
+// the grid of a call: a function of (nu, nnu, id) and nothing else (ph_grid)
+struct PhGrid {
+    uint64_t id = 0;                               // names the grid: a column's setup, or one gas_states call (0: none)
+    int64_t nnu = 0;
+    double nu_lo = 0.0, nu_hi = 0.0, nu_c = 0.0;   // first and last point, and their mean: chi is factorised about nu_c
+    double max_span = 0.0;                         // widest 64-point tile
+    double lev_span[8] = {};                       // widest interval of 8192 >> i points
 };
+static PhGrid ph_grid(const double *nu, int64_t nnu, uint64_t id)
+{
+    PhGrid g;
+    g.id = id; g.nnu = nnu;
+    g.nu_lo = nu[0]; g.nu_hi = nu[nnu - 1];
+    g.nu_c = 0.5 * (g.nu_lo + g.nu_hi);
+    for (int64_t i0 = 0; i0 < nnu; i0 += 64) g.max_span = std::max(g.max_span, nu[std::min(i0 + 63, nnu - 1)] - nu[i0]);
+    for (int i = 0; i < 8; i++) {
+        const int64_t sz = 8192 >> i;
+        double w = 0.0;
+        for (int64_t i0 = 0; i0 < nnu; i0 += sz) w = std::max(w, nu[std::min(i0 + sz - 1, nnu - 1)] - nu[i0]);
+        g.lev_span[i] = w;
+    }
+    return g;
+}
+// What the context says about PHCO2 (ph_rules); default-constructed: what cs_create sets.  PHCO2 passes follow the context for these six
+// from every entry point -- the resident column, cs_column_batch, cs_shape_batch, cs_shape_points, cs_bake -- whatever GasPass::set is.
+struct PhRules {
+    bool itp_on = true;                               // cs_set_interp
+    int itp_min = 128, itp_max = 2048;                // cs_set_interp_plan's size range
+    double margin = kDefaultSettings.margin;          // Settings::margin
+    int nodes = kDefaultSettings.ph_nodes;            // Settings::ph_nodes: 64 nodes for every interval (bit 0), tiles as 64-point intervals too (bit 1)
+    bool own_core = kDefaultSettings.ph_own_core;     // Settings::ph_own_core
+    bool operator==(const PhRules &o) const
+    {
+        return itp_on == o.itp_on && itp_min == o.itp_min && itp_max == o.itp_max && margin == o.margin && nodes == o.nodes && own_core == o.own_core;
+    }
+};
+// interval sizes in use (descending) and the virtual levels on them (PhVLevels); nnodes = sum nI x nc, nslots = sum nI over the virtual levels
+struct PhLevelSet {
+    PhLevels lv; PhVLevels vl; PhFine fine;
+    int nnodes = 0, nslots = 0;
+};
+// what a PhLevelSet follows from: the argument list of ph_levels, field by field (ph_key)
+struct PhKey {
+    uint64_t grid = 0;   // PhGrid::id (0: nothing built)
+    int64_t nnu = 0;
+    double cut = 0.0;
+    int drop = 0;        // regions (bit r = region r + 1) the states of the launch keep out of the levels (ph_wide_regions)
+    PhRules rules;
+    bool operator==(const PhKey &o) const { return grid == o.grid && nnu == o.nnu && cut == o.cut && drop == o.drop && rules == o.rules; }
+};
+static PhKey ph_key(const PhGrid &g, const PhRules &rules, double cut, int drop)
+{
+    PhKey k;
+    k.grid = g.id; k.nnu = g.nnu; k.cut = cut; k.drop = drop; k.rules = rules;
+    return k;
+}
+// The context's PHCO2 workspace.  grid, rules: of the coming launch_gas calls, set together by the caller (ph_set_grid).  fac, win: per-(state,
+// line) chi factors and per-tile region windows; win3, zones3: windows and zones of the Voigt pass over the pairs within 3 cm^-1; lev with
+// nodes [sum nI x nc], Cm[v] [nI][nc][itv], piw, F: the interpolation levels (k_phco2_nodes) as built for `key` -- ph_prepare builds them
+// again when a launch asks for another.  The scratch is one per context: two PHCO2 groups of one column whose keys differ (cut-offs,
+// region masks) rebuild the levels for each other on every step.
+struct PhScratch {
+    DevBuf fac, win, piw, F, win3, zones3;
+    PhGrid grid;
+    PhRules rules;
+    PhKey key;                 // what lev, nodes and Cm were laid out for: set only once every buffer of the levels is held, cleared when
+    PhLevelSet lev;            // a build is refused, so that equal keys always mean built tables (phco2_plan then takes lev from here)
+    DevBuf nodes, Cm[CS_MAX_ALEVEL];
+    uint64_t builds = 0;       // how often ph_prepare has (re)built the levels: a captured step holds the layout of one build
+    struct Dens { const void *tab; uint64_t gen, grid; bool ok; };
+    std::vector<Dens> dens;    // check_near_density() per (table, generation, grid), a few kept (phco2_plan is the only reader)
+};
+
+// How one PHCO2 group of a pass is run, decided before its first launch (phco2_plan: the one place that holds the rules, as voigt_plan is
+// for a Voigt group); ph_prepare reserves what the plan needs and takes back what it cannot have; line_sum_phco2 launches by it.  `key`
+// and `lev` are ph_key and ph_levels of one argument list (lev: the scratch's own where it was built for that key).  The
+// inner pass runs under kDefaultSettings, not under the context's: the open point of DESIGN.md, stated here and not decided.
+struct PhPlan {
+    bool fast = false;         // k_phco2; else k_linesum<SH_PHCO2> (line_sum_generic)
+    int drop = 7;              // regions the states of the pass keep out of the levels (ph_wide_regions; 7 where the pass has no host states)
+    bool levels = false;       // the far wings of the region-uniform lines on interpolation levels (k_phco2_nodes), `lev` of them
+    bool build = false;        // ... whose tables this launch builds first (ph_prepare: the scratch held those of another key)
+    bool clear_F = false;      // ... and whose node sums F it clears first (ph_prepare: F is new)
+    bool inner = false;        // the pairs within 3 cm^-1 through the Voigt kernels; else k_phco2's own core loop
+    int nt64 = 0;              // 64-point tiles
+    unsigned nb_zones = 0;     // blocks of the zone part of k_gas_setup
+    unsigned nb_tiles = 0, nb_itv = 0;   // blocks of k_phwin's tile part (once more for the inner pass's windows) and interval part
+    PhKey key;
+    PhLevelSet lev;
+    void no_levels() { levels = build = clear_F = false; nb_itv = 0; }
+};
+inline void StepLog::phco2_group(const PhPlan &pl) { line_kernel = pl.fast ? 2 : 1; }
+}  // namespace
 
 // what cs_fluxes_discretized_multi keeps between calls (in its first context)
 struct MultiPlan { int nctx = 0; std::vector<double> nu, wt; std::vector<uint64_t> gens; std::vector<int64_t> ranges; };
@@ -508,22 +589,18 @@ struct cs_ctx {
     DevBuf hot32;
     DevBuf tmpA, tmpB, tmpC;
 };
-void ph_set_grid(const cs_ctx *ctx, PhScratch &ph, const double *nu, int64_t nnu, uint64_t grid_id)
+static PhRules ph_rules(const cs_ctx &ctx)
 {
-    ph.nu_lo = nu[0]; ph.nu_hi = nu[nnu - 1];
-    ph.max_span = 0.0;
-    for (int64_t i0 = 0; i0 < nnu; i0 += 64) ph.max_span = std::max(ph.max_span, nu[std::min(i0 + 63, nnu - 1)] - nu[i0]);
-    ph.grid_id = grid_id;
-    ph.itp_on = ctx->interp; ph.itp_min = ctx->itp_min; ph.itp_max = ctx->itp_max;
-    ph.margin = ctx->set.margin;
-    ph.own_core = ctx->set.ph_own_core;
-    ph.force64 = ctx->set.ph_nodes;
-    for (int i = 0; i < 8; i++) {
-        const int64_t sz = 8192 >> i;
-        double w = 0.0;
-        for (int64_t i0 = 0; i0 < nnu; i0 += sz) w = std::max(w, nu[std::min(i0 + sz - 1, nnu - 1)] - nu[i0]);
-        ph.lev_span[i] = w;
-    }
+    PhRules r;
+    r.itp_on = ctx.interp != 0; r.itp_min = ctx.itp_min; r.itp_max = ctx.itp_max;
+    r.margin = ctx.set.margin; r.nodes = ctx.set.ph_nodes; r.own_core = ctx.set.ph_own_core;
+    return r;
+}
+// the grid of the coming launch_gas calls (host copy `nu`), and the context's rules with it
+static void ph_set_grid(cs_ctx *ctx, const double *nu, int64_t nnu, uint64_t grid_id)
+{
+    ctx->ph.grid = ph_grid(nu, nnu, grid_id);
+    ctx->ph.rules = ph_rules(*ctx);
 }
 
 namespace {
@@ -1150,55 +1227,53 @@ void launch_apply(hipStream_t s, const ChebApply &A, int Kpad, int64_t nnu, int 
     }
 }
 
-// PHCO2 fast path preconditions + workspace.  Returns false -> generic kernel.
-bool phco2_fast_ok(const GasTable &G, int64_t nnu, double cut, int kn, PhScratch *ph)
+// PHCO2 fast path preconditions.  Returns false -> generic kernel.
+static bool phco2_fast_ok(const GasTable &G, const PhGrid &g, double cut)
 {
-    if (cut < 130.0 || nnu < 2 || !(ph->nu_hi > ph->nu_lo)) return false;
+    if (cut < 130.0 || g.nnu < 2 || !(g.nu_hi > g.nu_lo)) return false;
     // widest near zone of any state must stay inside the chi = 1 core (|dnu| < 3 cm^-1) of its tile
-    const double amax = ((ph->nu_hi + cut) / kC) * std::sqrt(2.0 * kRgas * kTmax / G.mu_min);
+    const double amax = ((g.nu_hi + cut) / kC) * std::sqrt(2.0 * kRgas * kTmax / G.mu_min);
     if (100.0 * amax / kSqLn2 * (1.0 + 1e-6) > 2.9) return false;
-    const int nt64 = (int)((nnu + 63) / 64);
-    if ((ph->nu_hi - ph->nu_lo) / (double)(nnu - 1) * 64.0 > 5.0) return false;   // (mean tile span: wider tiles would not be faster)
-    if (!(ph->max_span <= 27.0)) return false;   // k_phco2's boundary sets hold one region boundary each: no tile wider than 30 - 3 cm^-1
+    if ((g.nu_hi - g.nu_lo) / (double)(g.nnu - 1) * 64.0 > 5.0) return false;   // (mean tile span: wider tiles would not be faster)
+    if (!(g.max_span <= 27.0)) return false;   // k_phco2's boundary sets hold one region boundary each: no tile wider than 30 - 3 cm^-1
     // the tabulated line factors exp(+-b_r (nul - nu_c)) must stay in range: b_r <= 0.0888
-    if (0.0888 * (0.5 * (ph->nu_hi - ph->nu_lo) + cut) > 600.0) return false;
-    if (ph->fac.reserve((size_t)6 * kn * G.L * sizeof(double)) != hipSuccess) return false;
-    if (ph->win.reserve((size_t)nt64 * sizeof(PhWin)) != hipSuccess) return false;
-    ph->nu_c = 0.5 * (ph->nu_lo + ph->nu_hi);
+    if (0.0888 * (0.5 * (g.nu_hi - g.nu_lo) + cut) > 600.0) return false;
     return true;
 }
-// the grid of the coming launch_gas calls (host copy `nu`), and the context's interpolation settings
+// names a grid: one per column setup and per gas_states call (PhGrid::id)
 static std::atomic<uint64_t> g_grid_counter{0};
-// interpolation levels of the PHCO2 far wings on that grid; false: none (k_phco2 sums every pair per point)
-static int ph_plan(PhScratch *ph, int64_t nnu, double cut)
+// interpolation levels of the PHCO2 far wings on that grid with the regions of `drop` (ph_wide_regions) kept out; vl.nv == 0: none (k_phco2
+// sums every pair per point).  Reads its arguments only: ph_key of the same four names what the result was formed from.
+static PhLevelSet ph_levels(const PhGrid &grid, const PhRules &rules, double cut, int drop)
 {
-    PhScratch::Grid &g = ph->grid;
+    PhLevelSet g;
+    const int64_t nnu = grid.nnu;
     memset(&g.lv, 0, sizeof g.lv);
     memset(&g.vl, 0, sizeof g.vl);
     for (int r = 0; r < 3; r++) { g.fine.off[r] = -1; g.fine.shift[r] = 0; }
     g.nnodes = g.nslots = 0;
-    if (nnu < 128) return 0;
-    const double dnu = (ph->nu_hi - ph->nu_lo) / (double)(nnu - 1);
+    if (!rules.itp_on || nnu < 128) return g;
+    const double dnu = (grid.nu_hi - grid.nu_lo) / (double)(nnu - 1);
     // (cs_set_interp_plan's limits of 128 and 2048 points are the Voigt path's; left there, the wide PHCO2 window also takes 4096 and
     //  8192 points; Settings::ph_nodes bit 1: also the tiles themselves as 64-point intervals with 16 or 32 nodes -- measured a tie at C3 size: 1.2 ms
     //  more in k_phco2_nodes, whose smallest waves are a chain of short batches, for 1.3 ms less in k_phco2)
-    const int szmax = ph->itp_max >= 2048 ? 8192 : ph->itp_max, szmin = (ph->itp_min <= 128 && (ph->force64 & 2)) ? 64 : ph->itp_min;
+    const int szmax = rules.itp_max >= 2048 ? 8192 : rules.itp_max, szmin = (rules.itp_min <= 128 && (rules.nodes & 2)) ? 64 : rules.itp_min;
     const double Dn[3] = {3.0, 30.0, 120.0}, Df[3] = {30.0, 120.0, cut};
     int need[8][3];   // per size and region: node count, 0 = not carried
     int nreal = 0, real_of[8];
     for (int i = 0; i < 8; i++) {
         const int sz = 8192 >> i;
         real_of[i] = -1;
-        if (!(sz <= szmax && sz >= szmin && 2.3 * sz * dnu <= 1.5 * cut && sz / 2 <= nnu && sz * dnu > 1e-8 * std::fabs(ph->nu_hi))) continue;
-        const double span = ph->lev_span[i], h = 0.5 * span;
+        if (!(sz <= szmax && sz >= szmin && 2.3 * sz * dnu <= 1.5 * cut && sz / 2 <= nnu && sz * dnu > 1e-8 * std::fabs(grid.nu_hi))) continue;
+        const double span = grid.lev_span[i], h = 0.5 * span;
         bool any = false;
         for (int r = 0; r < 3; r++) {
-            const double dn = std::max(Dn[r], ph->margin * h);
+            const double dn = std::max(Dn[r], rules.margin * h);
             need[i][r] = 0;
-            if ((ph->drop >> r) & 1) continue;                                  // a state too wide for this region's interpolation (ph_wide_regions)
+            if ((drop >> r) & 1) continue;                                  // a state too wide for this region's interpolation (ph_wide_regions)
             if (!(Df[r] - dn - sz * dnu >= 0.05 * (Df[r] - Dn[r]))) continue;   // (next to) nothing to hold at this size
-            const double x0 = 1.0 + std::max(Dn[r] / h, ph->margin), lr = std::log10(x0 + std::sqrt(x0 * x0 - 1.0));
-            need[i][r] = (ph->force64 & 1) ? 64 : (15.0 * lr >= 18.0 ? 16 : (31.0 * lr >= 18.0 ? 32 : 64));
+            const double x0 = 1.0 + std::max(Dn[r] / h, rules.margin), lr = std::log10(x0 + std::sqrt(x0 * x0 - 1.0));
+            need[i][r] = (rules.nodes & 1) ? 64 : (15.0 * lr >= 18.0 ? 16 : (31.0 * lr >= 18.0 ? 32 : 64));
             any = true;
         }
         if (!any) continue;
@@ -1210,7 +1285,7 @@ static int ph_plan(PhScratch *ph, int64_t nnu, double cut)
         nreal++;
     }
     g.lv.nlev = nreal;
-    if (nreal == 0) return 0;
+    if (nreal == 0) return g;
     // virtual levels; more than CS_MAX_ALEVEL of them: the regions of a size join its larger node count
     for (;;) {
         int nv = 0;
@@ -1253,16 +1328,16 @@ static int ph_plan(PhScratch *ph, int64_t nnu, double cut)
     }
     g.vl.nv = nv;
     g.vl.boff[nv] = g.nslots;
-    return nv;
+    return g;
 }
-// The node counts of ph_plan take the line centre, max(D_r, margin h) away, for the nearest singularity of a line's term.  The term's
+// The node counts of ph_levels take the line centre, max(D_r, margin h) away, for the nearest singularity of a line's term.  The term's
 // denominator x^2 + (chi y)^2 vanishes where d = nu - nul = +-i gamma chi_r(d), chi_r(d) = exp(a_r - b_r d): |d| = gamma exp(a_r - b_r Re d)
 // and arg d = pi/2 - b_r Im d.  For a narrow line these are the Lorentzian's own poles, +-i gamma beside the centre; for a wide one the
 // phase b_r Im d turns them towards the real axis -- at 25 K and 3e6 Pa (gamma = 12 cm^-1, chi up to 4.5 since B1 < 0 below 143.6 K) one
 // sits 35 cm^-1 from the centre and 20 above the axis, over the region-2 set of a 2048-point interval, whose 32 nodes then leave 5e-12
 // (measured: tests/test_gpu_phco2_line.py).  With G_r = gamma max(e^(a_r), e^(a_r - 2 b_r D_far)) bounding |d| for 0 <= Re d <= 2 D_far
 // (the larger end of a monotone function), Re d = |d| sin(b_r Im d) <= G_r sin(min(|b_r| G_r, pi/2)): a region is interpolated only while
-// that reach stays below a tenth of its near distance D_r for every state of the launch (the 18 digits ph_plan asks for keep 16 with the
+// that reach stays below a tenth of its near distance D_r for every state of the launch (the 18 digits ph_levels asks for keep 16 with the
 // distance 10 % short); else k_phco2 sums its lines per point.  Returns the regions to drop (bit r).
 int ph_wide_regions(const double *T, const double *gmax, int64_t n, double cut)
 {
@@ -1278,38 +1353,6 @@ int ph_wide_regions(const double *T, const double *gmax, int64_t n, double cut)
         }
     }
     return drop;
-}
-bool ph_interp_ready(PhScratch *ph, const double *dnu, int64_t nnu, double cut, int kn, hipStream_t s, int drop)
-{
-    if (!ph->itp_on) return false;
-    ph->drop = drop;
-    PhScratch::Grid &g = ph->grid;
-    if (!(ph->built_id == ph->grid_id && ph->built_nnu == nnu && ph->built_cut == cut && ph->built_min == ph->itp_min &&
-          ph->built_max == ph->itp_max && ph->built_margin == ph->margin && ph->built_force == ph->force64 && ph->built_drop == ph->drop)) {
-        ph->built_id = 0;
-        ph->builds++;
-        const int nv = ph_plan(ph, nnu, cut);
-        if (nv > 0) {
-            if (g.nodes.reserve((size_t)g.nnodes * sizeof(double)) != hipSuccess) return false;
-            for (int v = 0; v < nv; v++) {
-                const int rl = g.vl.rl[v], nc = g.vl.nc[v];
-                if (g.Cm[v].reserve((size_t)g.lv.nI[rl] * nc * g.lv.itv[rl] * sizeof(double)) != hipSuccess) return false;
-                CS_LAUNCH(k_cheb_setup, dim3(g.lv.nI[rl]), dim3(256), 0, s, dnu, nnu, g.lv.itv[rl], g.lv.nI[rl], nc,
-                          g.nodes.as<double>() + g.vl.noff[v], g.Cm[v].as<double>());
-            }
-            if (hipGetLastError() != hipSuccess) return false;
-        }
-        ph->built_id = ph->grid_id; ph->built_nnu = nnu; ph->built_cut = cut; ph->built_min = ph->itp_min; ph->built_max = ph->itp_max;
-        ph->built_margin = ph->margin; ph->built_force = ph->force64; ph->built_drop = ph->drop;
-    }
-    if (g.vl.nv == 0) return false;
-    if (ph->piw.reserve((size_t)g.lv.nItot * sizeof(PhIWin)) != hipSuccess) return false;
-    const size_t fb = (size_t)g.nnodes * cheb_kpad(kn) * sizeof(double);
-    if (ph->F.bytes < fb) {
-        if (ph->F.reserve(fb) != hipSuccess) return false;
-        if (hipMemsetAsync(ph->F.p, 0, ph->F.bytes, s) != hipSuccess) return false;   // padding states stay finite
-    }
-    return true;
 }
 
 // points per sub-tile of k_voigt_sub (16: 0.34 ms at C3 with every core on the 8-term series; 8: 0.22; 4: 0.22 -- what is left is not
@@ -1710,98 +1753,173 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
 
 static void launch_line_sum(hipStream_t s, const GasPass &p);
 
-// PHCO2 fast path (k_phco2): region-uniform far lines with factorised chi; needs the cut-off edges inside region 3 and the
-// near zone inside the chi = 1 core (phco2_fast_ok), else the generic kernel
-static void line_sum_phco2(hipStream_t s, const GasPass &p, PrepArgs pa, unsigned nb_prep)
+// How the PHCO2 group of this pass is run (p.ph set, the scratch's grid and rules those of the call).  Host arithmetic only: allocates
+// nothing, launches nothing; of the scratch it reads grid, rules and the levels built for the same key, and keeps the density answers.
+static PhPlan phco2_plan(const GasPass &p)
 {
     const GasTable &G = *p.G;
-    const int kn = p.kn;
-    const int64_t nnu = p.nnu, jlo = pa.jlo, jhi = pa.jhi;
-    int accumulate = p.accumulate;
-    const int nt64 = (int)((nnu + 63) / 64);
-    pa.phfac = p.ph->fac.as<double>();
-    pa.nu_c = p.ph->nu_c;
-    const ZoneArgs za = zone_args(p, false, kChebMargin, 0.0);
-    const unsigned nb_zones = (unsigned)(((int64_t)nt64 * kn + 255) / 256);
-    IzParams P;
-    memset(&P, 0, sizeof P);
-    CS_LAUNCH(k_gas_setup, dim3(nb_prep + nb_zones), dim3(256), 0, s, nb_prep, nb_zones, pa, za, P, (IZone *)nullptr);
-    const bool use_itp = ph_interp_ready(p.ph, p.dnu, nnu, p.cut, kn, s, p.h_Tk && p.h_gbound ? ph_wide_regions(p.h_Tk, p.h_gbound, kn, p.cut) : 7);
-    const PhScratch::Grid &pg = p.ph->grid;
-    PhArgs pw;
-    pw.nu = p.dnu; pw.nul = G.nu.as<double>(); pw.nnu = nnu; pw.ntile = nt64; pw.J0 = (int32_t)jlo; pw.J1 = (int32_t)jhi; pw.cut = p.cut;
-    pw.tol = 1e-9 * (std::max(std::fabs(p.ph->nu_lo), std::fabs(p.ph->nu_hi)) + p.cut + 1.0);
-    pw.out = p.ph->win.as<PhWin>();
-    PhIArgs ia;
-    memset(&ia, 0, sizeof ia);
-    if (use_itp) {
-        ia.nu = p.dnu; ia.nul = pw.nul; ia.nnu = nnu; ia.J0 = pw.J0; ia.J1 = pw.J1; ia.cut = p.cut; ia.tol = pw.tol; ia.margin = p.ph->margin;
-        ia.lv = pg.lv;
-        ia.out = p.ph->piw.as<PhIWin>();
-    }
+    const PhGrid &g = p.ph->grid;
+    const PhRules &rules = p.ph->rules;
+    PhPlan pl;
+    pl.fast = phco2_fast_ok(G, g, p.cut);
+    if (!pl.fast) return pl;
+    pl.nt64 = (int)((p.nnu + 63) / 64);
+    pl.nb_zones = (unsigned)(((int64_t)pl.nt64 * p.kn + 255) / 256);
+    pl.nb_tiles = (unsigned)((pl.nt64 + 255) / 256);
+    pl.drop = p.h_Tk && p.h_gbound ? ph_wide_regions(p.h_Tk, p.h_gbound, p.kn, p.cut) : 7;
+    pl.key = ph_key(g, rules, p.cut, pl.drop);
+    pl.lev = p.ph->key == pl.key ? p.ph->lev : ph_levels(g, rules, p.cut, pl.drop);
+    pl.levels = pl.lev.vl.nv > 0;
+    if (pl.levels) pl.nb_itv = (unsigned)((pl.lev.lv.nItot + 255) / 256);
     // the pairs within 3 cm^-1 (chi = 1: plain Voigt, every near-line pair among them) through the Voigt kernels, where their
     // near-line hand-off takes this table (check_near_density; else k_phco2's own core loop)
-    bool inner = false;
-    if (p.ranges && !p.ph->own_core) {
+    if (p.ranges && !rules.own_core) {
+        std::vector<PhScratch::Dens> &dens = p.ph->dens;
         const PhScratch::Dens *hit = nullptr;
-        for (auto &d : p.ph->dens) if (d.tab == (const void *)&G && d.gen == G.generation && d.grid == p.ph->grid_id) hit = &d;
+        for (auto &d : dens) if (d.tab == (const void *)&G && d.gen == G.generation && d.grid == g.id) hit = &d;
         if (!hit) {
-            if (p.ph->dens.size() >= 8) p.ph->dens.erase(p.ph->dens.begin());
-            p.ph->dens.push_back({(const void *)&G, G.generation, p.ph->grid_id, check_near_density(G, p.ph->nu_hi, p.ph->max_span, 3.0) == CS_OK});
-            hit = &p.ph->dens.back();
+            if (dens.size() >= 8) dens.erase(dens.begin());
+            dens.push_back({(const void *)&G, G.generation, g.id, check_near_density(G, g.nu_hi, g.max_span, 3.0) == CS_OK});
+            hit = &dens.back();
         }
-        inner = hit->ok && p.ph->win3.reserve((size_t)(nt64 + 3) * sizeof(WaveWin)) == hipSuccess &&
-                p.ph->zones3.reserve((size_t)kn * nt64 * sizeof(Zone)) == hipSuccess;
+        pl.inner = hit->ok;
+    }
+    return pl;
+}
+
+// Reserves what the plan needs on the context's scratch and, where the scratch holds the levels of another key, lays the plan's out in
+// their place (their tables are built by the launch: ph_build_levels).  The only place that takes something back from a plan for want of
+// memory, silently: without fac / win the group goes to line_sum_generic, without the level buffers k_phco2 sums every pair per point,
+// without win3 / zones3 it runs its own core loop.
+static void ph_prepare(const GasPass &p, PhPlan &pl)
+{
+    PhScratch &ph = *p.ph;
+    const int kn = p.kn;
+    if (!pl.fast) return;
+    if (ph.fac.reserve((size_t)6 * kn * p.G->L * sizeof(double)) != hipSuccess || ph.win.reserve((size_t)pl.nt64 * sizeof(PhWin)) != hipSuccess) {
+        pl = PhPlan();
+        return;
+    }
+    const bool rebuild = ph.rules.itp_on && !(ph.key == pl.key);
+    if (rebuild) {
+        ph.key = PhKey();
+        ph.builds++;
+    }
+    if (pl.levels) {
+        const size_t fb = (size_t)pl.lev.nnodes * cheb_kpad(kn) * sizeof(double);
+        bool ok = !rebuild || ph.nodes.reserve((size_t)pl.lev.nnodes * sizeof(double)) == hipSuccess;
+        for (int v = 0; rebuild && ok && v < pl.lev.vl.nv; v++) {
+            const int rl = pl.lev.vl.rl[v];
+            ok = ph.Cm[v].reserve((size_t)pl.lev.lv.nI[rl] * pl.lev.vl.nc[v] * pl.lev.lv.itv[rl] * sizeof(double)) == hipSuccess;
+        }
+        ok = ok && ph.piw.reserve((size_t)pl.lev.lv.nItot * sizeof(PhIWin)) == hipSuccess;
+        if (ok && ph.F.bytes < fb) {   // (new: cleared once, so that padding states stay finite)
+            ok = ph.F.reserve(fb) == hipSuccess;
+            pl.clear_F = ok;
+        }
+        if (!ok) pl.no_levels();
+    }
+    if (rebuild && (pl.levels || pl.lev.vl.nv == 0)) {   // every buffer held (or no level to hold): the scratch is this key's from here on
+        ph.key = pl.key;
+        ph.lev = pl.lev;
+        pl.build = pl.levels;
+    }
+    if (pl.inner)
+        pl.inner = ph.win3.reserve((size_t)(pl.nt64 + 3) * sizeof(WaveWin)) == hipSuccess && ph.zones3.reserve((size_t)kn * pl.nt64 * sizeof(Zone)) == hipSuccess;
+}
+// what ph_prepare left to the launch, behind k_gas_setup: the tables of newly laid out levels (nodes and interpolation matrices, one launch
+// per virtual level), then the one-time clear of a new F.  Either refused: no levels in this pass, and the next builds them again
+static void ph_build_levels(hipStream_t s, const GasPass &p, PhPlan &pl)
+{
+    PhScratch &ph = *p.ph;
+    const PhLevelSet &g = pl.lev;
+    for (int v = 0; pl.build && v < g.vl.nv; v++) {
+        const int rl = g.vl.rl[v], nc = g.vl.nc[v];
+        CS_LAUNCH(k_cheb_setup, dim3(g.lv.nI[rl]), dim3(256), 0, s, p.dnu, p.nnu, g.lv.itv[rl], g.lv.nI[rl], nc, ph.nodes.as<double>() + g.vl.noff[v],
+                  ph.Cm[v].as<double>());
+    }
+    if ((pl.build && hipGetLastError() != hipSuccess) || (pl.clear_F && hipMemsetAsync(ph.F.p, 0, ph.F.bytes, s) != hipSuccess)) {
+        ph.key = PhKey();
+        if (pl.clear_F) ph.F.release();   // (not cleared: the next pass takes a new one)
+        pl.no_levels();
+    }
+}
+
+// PHCO2 fast path (k_phco2): region-uniform far lines with factorised chi; needs the cut-off edges inside region 3 and the
+// near zone inside the chi = 1 core (phco2_fast_ok), else the generic kernel.  Fills the argument structs and launches by the plan.
+static void line_sum_phco2(hipStream_t s, const GasPass &p, PrepArgs pa, unsigned nb_prep, PhPlan &pl)
+{
+    const GasTable &G = *p.G;
+    const PhScratch &ph = *p.ph;
+    const int kn = p.kn, nt64 = pl.nt64;
+    const int64_t nnu = p.nnu, jlo = pa.jlo, jhi = pa.jhi;
+    int accumulate = p.accumulate;
+    pa.phfac = ph.fac.as<double>();
+    pa.nu_c = ph.grid.nu_c;
+    const ZoneArgs za = zone_args(p, false, kChebMargin, 0.0);
+    IzParams P;
+    memset(&P, 0, sizeof P);
+    CS_LAUNCH(k_gas_setup, dim3(nb_prep + pl.nb_zones), dim3(256), 0, s, nb_prep, pl.nb_zones, pa, za, P, (IZone *)nullptr);
+    if (pl.build || pl.clear_F) ph_build_levels(s, p, pl);
+    const PhLevelSet &pg = pl.lev;
+    PhArgs pw;
+    pw.nu = p.dnu; pw.nul = G.nu.as<double>(); pw.nnu = nnu; pw.ntile = nt64; pw.J0 = (int32_t)jlo; pw.J1 = (int32_t)jhi; pw.cut = p.cut;
+    pw.tol = 1e-9 * (std::max(std::fabs(ph.grid.nu_lo), std::fabs(ph.grid.nu_hi)) + p.cut + 1.0);
+    pw.out = ph.win.as<PhWin>();
+    PhIArgs ia;
+    memset(&ia, 0, sizeof ia);
+    if (pl.levels) {
+        ia.nu = p.dnu; ia.nul = pw.nul; ia.nnu = nnu; ia.J0 = pw.J0; ia.J1 = pw.J1; ia.cut = p.cut; ia.tol = pw.tol; ia.margin = ph.rules.margin;
+        ia.lv = pg.lv;
+        ia.out = ph.piw.as<PhIWin>();
     }
     WwArgs wa;
     memset(&wa, 0, sizeof wa);
-    if (inner) {
+    if (pl.inner) {
         wa.nu = p.dnu; wa.nul = pw.nul; wa.nnu = nnu; wa.ntile = nt64; wa.J0 = pw.J0; wa.J1 = pw.J1; wa.cut = 3.0;
         wa.sparse = (jhi - jlo) * 8 < nnu ? 1 : 0;
-        wa.out = p.ph->win3.as<WaveWin>();
+        wa.out = ph.win3.as<WaveWin>();
     }
-    const unsigned nb_tiles = (unsigned)((nt64 + 255) / 256), nb_itv = (unsigned)((ia.lv.nItot + 255) / 256);
-    CS_LAUNCH(k_phwin, dim3(nb_tiles + nb_itv + (inner ? nb_tiles : 0u)), dim3(256), 0, s, nb_tiles, nb_itv, pw, ia, wa);
+    CS_LAUNCH(k_phwin, dim3(pl.nb_tiles + pl.nb_itv + (pl.inner ? pl.nb_tiles : 0u)), dim3(256), 0, s, pl.nb_tiles, pl.nb_itv, pw, ia, wa);
     if (p.evg) (void)hipEventRecord(p.evg[0], s);
     const PhIWin *piw = nullptr;
     PhFine fine;
     memset(&fine, 0, sizeof fine);
-    if (use_itp) {   // far wings of the region-uniform lines: node sums, carried to the grid (sigma = base + extra + them)
+    if (pl.levels) {   // far wings of the region-uniform lines: node sums, carried to the grid (sigma = base + extra + them)
         const int Kpad = cheb_kpad(kn);
-        CS_LAUNCH(k_phco2_nodes, dim3((unsigned)pg.nslots * (unsigned)((kn + 3) / 4)), dim3(256), 0, s, pg.nodes.as<double>(), G.L, p.hot,
-                  p.ph->fac.as<double>(), p.ph->nu_c, p.ph->piw.as<PhIWin>(), pg.lv, pg.vl, kn, Kpad, p.Tk, p.cut, p.gbound, G.mu_min, G.mu_max, p.far_s,
-                  p.ph->F.as<double>());
+        CS_LAUNCH(k_phco2_nodes, dim3((unsigned)pg.nslots * (unsigned)((kn + 3) / 4)), dim3(256), 0, s, ph.nodes.as<double>(), G.L, p.hot,
+                  ph.fac.as<double>(), ph.grid.nu_c, ph.piw.as<PhIWin>(), pg.lv, pg.vl, kn, Kpad, p.Tk, p.cut, p.gbound, G.mu_min, G.mu_max, p.far_s,
+                  ph.F.as<double>());
         if (p.evg) (void)hipEventRecord(p.evg[1], s);
         ChebApply A;
         memset(&A, 0, sizeof A);
-        A.nlev = pg.vl.nv; A.ngas = 1; A.F[0] = p.ph->F.as<double>(); A.l0[0] = 0;
+        A.nlev = pg.vl.nv; A.ngas = 1; A.F[0] = ph.F.as<double>(); A.l0[0] = 0;
         for (int v = 0; v < pg.vl.nv; v++) {
             for (int r = pg.lv.itv[pg.vl.rl[v]] / 64; r > 1; r >>= 1) A.shift[v]++;
             A.ioff[v] = pg.vl.boff[v];
             A.nc[v] = pg.vl.nc[v];
             A.noff[v] = pg.vl.noff[v];
-            A.Cm[v] = pg.Cm[v].as<double>();
+            A.Cm[v] = ph.Cm[v].as<double>();
         }
         launch_apply(s, A, Kpad, nnu, kn, p.base, p.extra, p.sigma, accumulate, true);
         accumulate = 1;
         if (p.evg) (void)hipEventRecord(p.evg[2], s);
-        piw = p.ph->piw.as<PhIWin>();
+        piw = ph.piw.as<PhIWin>();
         fine = pg.fine;
     } else if (p.evg) { (void)hipEventRecord(p.evg[1], s); (void)hipEventRecord(p.evg[2], s); }
-    if (p.log) p.log->line_kernel = 2;
-    CS_LAUNCH(k_phco2, dim3((unsigned)((nt64 + 3) / 4), kn), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.cold, p.ph->fac.as<double>(), p.ph->nu_c,
-                       p.ph->win.as<PhWin>(), p.zones, nt64, p.cut, p.Tk, kn, p.base, p.extra, p.sigma, accumulate, piw, fine, inner ? 1 : 0);
+    CS_LAUNCH(k_phco2, dim3((unsigned)((nt64 + 3) / 4), kn), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.cold, ph.fac.as<double>(), ph.grid.nu_c,
+                       ph.win.as<PhWin>(), p.zones, nt64, p.cut, p.Tk, kn, p.base, p.extra, p.sigma, accumulate, piw, fine, pl.inner ? 1 : 0);
     if (p.evg) (void)hipEventRecord(p.evg[3], s);
-    if (inner) {
+    if (pl.inner) {
         const int nt4 = (nt64 + 3) / 4 * 4, per = ((nt4 / 4 + 7) / 8) * 4;   // (wave_windows' stretch length)
         GasPass in = p;   // same table, record range, states, records, grid, ranges and plane: the zones and sums of a Voigt pass with its own windows
-        in.shape = SH_VOIGT; in.cut = 3.0; in.win = p.ph->win3.as<WaveWin>(); in.xtiles = per; in.zones = p.ph->zones3.as<Zone>();
+        in.shape = SH_VOIGT; in.cut = 3.0; in.win = ph.win3.as<WaveWin>(); in.xtiles = per; in.zones = ph.zones3.as<Zone>();
         in.base = 0.0; in.extra = nullptr; in.accumulate = 1; in.evg = nullptr; in.hot32 = nullptr; in.itp = Interp(); in.set = &kDefaultSettings; in.fuse_apply = false;
         in.defer = nullptr; in.ph = nullptr; in.fork = nullptr; in.records_ready = true; in.keep = nullptr;
         in.flo = -INFINITY; in.fhi = INFINITY;   // (no K1 in this pass: nothing reads them)
         launch_line_sum(s, in);
-        if (p.log) p.log->line_kernel = 2;   // (the group's far lines were k_phco2's; the inner pass only took the pairs within 3 cm^-1)
     }
+    if (p.log) p.log->phco2_group(pl);   // (the group's far lines were k_phco2's; the inner pass only took the pairs within 3 cm^-1)
     if (p.evg) { (void)hipEventRecord(p.evg[4], s); (void)hipEventRecord(p.evg[5], s); }
 }
 
@@ -1837,8 +1955,12 @@ static void launch_line_sum(hipStream_t s, const GasPass &p)
     pa.pshift = p.pshift ? 1 : 0; pa.flo = p.flo; pa.fhi = p.fhi;
     const unsigned nb_prep = p.records_ready ? 0u : (unsigned)((jhi - jlo + 255) / 256) * (unsigned)((p.kn + CS_PREP_KC - 1) / CS_PREP_KC);   // (line block, chunk of states)
     if (p.shape == SH_VOIGT || p.shape == SH_LORENTZ) line_sum_voigt(s, p, pa, nb_prep);
-    else if (p.shape == SH_PHCO2 && !p.pshift && p.ph && phco2_fast_ok(G, p.nnu, p.cut, p.kn, p.ph)) line_sum_phco2(s, p, pa, nb_prep);
-    else line_sum_generic(s, p, pa, nb_prep);
+    else if (p.shape == SH_PHCO2 && !p.pshift && p.ph) {
+        PhPlan pl = phco2_plan(p);
+        ph_prepare(p, pl);
+        if (pl.fast) line_sum_phco2(s, p, pa, nb_prep, pl);
+        else line_sum_generic(s, p, pa, nb_prep);
+    } else line_sum_generic(s, p, pa, nb_prep);
 }
 
 // workspace of launch_pedestal for kn states of a table of L lines: p, in-block prefix and suffix sums [3][kn][L], block sums [kn][ceil(L / CS_PED_B)]
@@ -2423,7 +2545,7 @@ static int gas_states(cs_ctx *ctx, GasTable &G, const ShapeSpec &sh, double dnu_
     if (sh.pshift && (rc = shift_width(G, P, K, ds))) return rc;
     if ((rc = check_gas_states(G, K, T))) return rc;
     if (shape == SH_VOIGT && (rc = check_near_density(G, nu, nnu, dnu_cut, ds))) return rc;
-    ph_set_grid(ctx, ctx->ph, nu, nnu, ++g_grid_counter);
+    ph_set_grid(ctx, nu, nnu, ++g_grid_counter);
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     double *Z = nullptr;   // the caller's plane; NULL: a chunk buffer of our own, copied to out.host
@@ -3185,11 +3307,12 @@ int cs_column_update_state(cs_ctx *ctx, const double *T_nodes, const double *mu_
         (rc = upload(c.Tlev, T_levels, c.np, s)))
         return rc;
     for (auto &cg : c.gas) {
-        // a PHCO2 group's levels carry the regions its states allow: a captured step holds the launches of one such choice
-        const bool ph = cg.shape == SH_PHCO2 && (int)cg.st.h_T.size() == K;
-        const int was = ph ? ph_wide_regions(cg.st.h_T.data(), cg.st.h_gmax.data(), K, cg.cut) : 0;
         if ((rc = column_group_states(ctx, cg, cg.st, K, Tk.data(), c.h_Pk.data(), conc, s))) return rc;
-        if (cg.shape == SH_PHCO2 && (!ph || was != ph_wide_regions(cg.st.h_T.data(), cg.st.h_gmax.data(), K, cg.cut))) drop_graph(c);
+        if (cg.shape != SH_PHCO2) continue;
+        // a PHCO2 group's levels carry the regions its states allow: a captured step holds the launches of one such choice
+        const int mask = ph_wide_regions(cg.st.h_T.data(), cg.st.h_gmax.data(), K, cg.cut);
+        if (mask != cg.ph_mask) drop_graph(c);
+        cg.ph_mask = mask;
     }
     HIPCHK(hipStreamSynchronize(s));
     if (!c.tab.empty()) {
@@ -3266,7 +3389,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     if (c.ngas > 0 && (rc = reserve_lines(kc, maxL, c.nnu, hot, cold, &dranges, ctx->mixed ? &ctx->hot32 : nullptr, any_ped ? &dped : nullptr,
                                           vvh2 ? &dvvh : nullptr)))
         return rc;
-    if (c.has_phco2) ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id);
+    if (c.has_phco2) ph_set_grid(ctx, c.h_nu.data(), c.nnu, c.grid_id);
     for (size_t qi = 0; qi < c.gas.size(); qi++) {
         ColGas &cg = c.gas[qi];
         const size_t nt64 = (size_t)((c.nnu + 63) / 64);
@@ -3383,7 +3506,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
     if (ctx->mixed) HIPCHK(ctx->hot32.reserve(((size_t)K * c.maxL + 4) * sizeof(LineF32)));   // no-op once sized (not capturable the first time)
     ChebApply apply;
     apply.ngas = 0;
-    if (c.has_phco2) ph_set_grid(ctx, ctx->ph, c.h_nu.data(), c.nnu, c.grid_id);
+    if (c.has_phco2) ph_set_grid(ctx, c.h_nu.data(), c.nnu, c.grid_id);
     int n_itp = 0;
     for (auto &cg : c.gas) n_itp += cg.itp.nlev > 0 && !cg.vvh ? 1 : 0;   // (the groups whose node sums go into the deferred apply)
     // Settings::nodes_stream: node sums on a side stream -- 1: where the grid is short (fewer than 16384 (tile, state) waves), 2: always
@@ -3795,19 +3918,20 @@ int cs_interp_plan(int64_t nnu, const double *nu, double dnu_cut, int *interval_
     return choose_levels(nu, nnu, dnu_cut, interval_sizes);   // (default size range; a context's cs_set_interp_plan may narrow it)
 }
 
+// the virtual levels of a PhLevelSet as cs_phco2_plan reports them: (interval size, nodes, region mask) of the first `cap`; returns their number
+static int ph_levels_out(const PhLevelSet &g, int cap, int *interval_sizes, int *nodes, int *regions)
+{
+    for (int v = 0; v < std::min(g.vl.nv, cap); v++) {
+        interval_sizes[v] = g.lv.itv[g.vl.rl[v]];
+        nodes[v] = g.vl.nc[v];
+        regions[v] = g.vl.rmask[v];
+    }
+    return g.vl.nv;
+}
 int cs_phco2_plan(int64_t nnu, const double *nu, double dnu_cut, int cap, int *interval_sizes, int *nodes, int *regions)
 {
     if (!nu || nnu < 1 || !interval_sizes || !nodes || !regions || cap < 1) return fail(CS_EINVAL, "bad arguments");
-    cs_ctx defaults;          // (host data only: the default interpolation settings)
-    PhScratch ph;
-    ph_set_grid(&defaults, ph, nu, nnu, 1);
-    const int nv = ph_plan(&ph, nnu, dnu_cut);
-    for (int v = 0; v < std::min(nv, cap); v++) {
-        interval_sizes[v] = ph.grid.lv.itv[ph.grid.vl.rl[v]];
-        nodes[v] = ph.grid.vl.nc[v];
-        regions[v] = ph.grid.vl.rmask[v];
-    }
-    return nv;
+    return ph_levels_out(ph_levels(ph_grid(nu, nnu, 1), PhRules(), dnu_cut, 0), cap, interval_sizes, nodes, regions);
 }
 
 // test hooks: the plan under a context's settings (interpolation on / off, size range, margin, CS_TUNE_PH_NODES) with the regions of
@@ -3815,16 +3939,7 @@ int cs_phco2_plan(int64_t nnu, const double *nu, double dnu_cut, int cap, int *i
 int cs_phco2_plan_ctx(cs_ctx *ctx, int64_t nnu, const double *nu, double dnu_cut, int drop, int cap, int *interval_sizes, int *nodes, int *regions)
 {
     if (!ctx || !nu || nnu < 1 || !interval_sizes || !nodes || !regions || cap < 1 || drop < 0 || drop > 7) return fail(CS_EINVAL, "bad arguments");
-    PhScratch ph;
-    ph_set_grid(ctx, ph, nu, nnu, 1);
-    ph.drop = drop;
-    const int nv = ph.itp_on ? ph_plan(&ph, nnu, dnu_cut) : 0;
-    for (int v = 0; v < std::min(nv, cap); v++) {
-        interval_sizes[v] = ph.grid.lv.itv[ph.grid.vl.rl[v]];
-        nodes[v] = ph.grid.vl.nc[v];
-        regions[v] = ph.grid.vl.rmask[v];
-    }
-    return nv;
+    return ph_levels_out(ph_levels(ph_grid(nu, nnu, 1), ph_rules(*ctx), dnu_cut, drop), cap, interval_sizes, nodes, regions);
 }
 int cs_phco2_wide_regions(int K, const double *T, const double *gamma_bound, double dnu_cut)
 {

@@ -10,9 +10,9 @@ sits in every part and in both batches.
 
 The rules restated here from the sources (csrc/cs_kernels.h, csrc/cs_api.hip), as tests/test_gpu_dispatch.py restates its own:
   fast_ok        phco2_fast_ok: cut >= 130, the widest near zone inside 2.9 cm^-1, mean tile span <= 5, no tile wider than 27 cm^-1
-  levels         ph_plan: sizes 8192 .. 128 (64 with key 10 bit 1), per region the node count 16 / 32 / 64 from (nc - 1) log10 rho >= 18, the
+  levels         ph_levels: sizes 8192 .. 128 (64 with key 10 bit 1), per region the node count 16 / 32 / 64 from (nc - 1) log10 rho >= 18, the
                  virtual levels in launch order and par[] (the next larger size that carries the region).  The host test holds it to
-                 cs.phco2_plan on every grid used.  ph_plan's rule "D_far - max(D_near, margin h) - size dnu >= 5 % of the region" only
+                 cs.phco2_plan on every grid used.  ph_levels' rule "D_far - max(D_near, margin h) - size dnu >= 5 % of the region" only
                  gets easier as the size shrinks, so a region carried at one size is carried at every smaller one: par[] never jumps a size
                  on any grid (asserted; the issue's "carried at one size and skipped at the next" can only mean the next LARGER size)
   tile_win       phwin_body: the six uniform sets, four boundary sets, the core [L1, R1) with [C0, C1), and E0 / E1
@@ -30,7 +30,7 @@ A probe's form (Geometry.form) follows from them and from the settings of the ru
   ("generic",)                                   k_linesum<SH_PHCO2> (off the fast path)
 
 The hard bound is lineparam_bound(C0_GPU) with code 3's chi term; where the fast path serves a probe beyond 3 cm^-1 the term is the
-factorised form's: chi = exp(a_r -+ b_r (nu - nu_c)) x exp(+- b_r (nul - nu_c)), nu_c = (nu_1 + nu_N) / 2 (phco2_fast_ok), a_r as ph_coef
+factorised form's: chi = exp(a_r -+ b_r (nu - nu_c)) x exp(+- b_r (nul - nu_c)), nu_c = (nu_1 + nu_N) / 2 (ph_grid), a_r as ph_coef
 forms them (3 B1 | -27 B1 + 30 B2 | -27 B1 - 90 B2 + 120 B3): per coefficient B_q the multipliers of every product it enters add up
 (fact_mult), times lineparam_ref.ph_coef_abs, plus 2 ulp per exponential (chi_rounding).
 
@@ -44,7 +44,7 @@ The sharp bound (probes with s = x^2 + (chi y)^2 >= 1e3) replaces the 2e-13 Fadd
   own core loop, k_linesum        fad_re: its far branch divides (IEEE), fad_mid below s = 1e4 (1e-14, cs_faddeeva.h:7): the scalar model;
                                   the own loop takes ph_term for lines no lane of the wave has inside s < 1e4, so the larger of both
   interpolated (node forms)       U x Lambda(nc) x max_I f / f(nu), Lambda(n) = (2 / pi) ln n + 1 the Lebesgue constant of the level's own node
-                                  count, ONCE (no cascade: every level is carried to the grid by itself), plus the truncation ph_plan's rule
+                                  count, ONCE (no cascade: every level is carried to the grid by itself), plus the truncation ph_levels' rule
                                   promises, 1e-18 x max_I f / f(nu); max_I f from the 40-digit values at the interval's ends (both are probes;
                                   inside one region and side the term is monotone or has its largest value at an end: chi / d^2 with
                                   ln chi linear has no interior maximum)
@@ -74,7 +74,7 @@ CLUSTER, GHOST_STEP, GHOST_RATIO = 130, 1e-5, 1e-120
 CLUSTER_AT = (0, 1, 2, 3, 63, 64, 65)
 MAX_PROBES = 2500
 S_CROSS, S_SHARP = I.S_CROSS, I.S_SHARP
-TRUNC_NODES = 1e-18                                                # ph_plan: (nc - 1) log10 rho >= 18
+TRUNC_NODES = 1e-18                                                # ph_levels: (nc - 1) log10 rho >= 18
 
 
 def lebesgue(n):
@@ -119,7 +119,7 @@ SCALAR = Run("scalar", interp=False)
 
 
 def fast_ok(nu, cut, mu_min):
-    """phco2_fast_ok (cs_api.hip) without its allocations"""
+    """phco2_fast_ok (cs_api.hip)"""
     n = len(nu)
     if cut < 130.0 or n < 2 or not nu[-1] > nu[0]:
         return False
@@ -152,7 +152,7 @@ def wide_regions(sts_gamma, cut):
 
 
 def levels(nu, cut, interp=True, force64=0, margin=MARGIN, smin=128, smax=2048, drop=frozenset()):
-    """ph_plan (cs_api.hip): (sizes carried, largest first; virtual levels [(size, nc, regions (1-based), {region: parent size or None})] in
+    """ph_levels (cs_api.hip): (sizes carried, largest first; virtual levels [(size, nc, regions (1-based), {region: parent size or None})] in
     launch order; fine {region: smallest size that carries it or None}); drop: wide_regions of the launch's states"""
     n = len(nu)
     none = ([], [], {1: None, 2: None, 3: None})
@@ -191,7 +191,7 @@ def levels(nu, cut, interp=True, force64=0, margin=MARGIN, smin=128, smax=2048, 
                 vl.append((sz, nc, regs, {r: last[r] for r in regs}))
         for r in need[sz]:
             last[r] = sz
-    assert len(vl) <= 16                     # (CS_MAX_ALEVEL: beyond it ph_plan doubles node counts -- not restated, not reached)
+    assert len(vl) <= 16                     # (CS_MAX_ALEVEL: beyond it ph_levels doubles node counts -- not restated, not reached)
     return sizes, vl, last
 
 

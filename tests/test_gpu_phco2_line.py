@@ -31,7 +31,7 @@ sharp bound -- it keeps every term through u^2 and needs s >= 1e6 only (phco2_li
 One finding, fixed in the library.  "margin-32" first held a 25 K, 3e6 Pa state (now the case margin-32-cold): its line, just beyond 30 cm^-1
 below a 2048-point interval, came out 4.9e-12 wrong at 49 probes of that state (22 x the hard bound) with interpolation on and inside the
 bounds with it off.  gamma = 12 cm^-1 and chi up to 4.5 put a zero of the profile's denominator x^2 + (chi y)^2 -- d = +-i gamma chi(d) --
-35 cm^-1 from the centre and 20 above the real axis, over that interval, and 32 nodes cannot resolve it; ph_plan's node counts take the line
+35 cm^-1 from the centre and 20 above the real axis, over that interval, and 32 nodes cannot resolve it; ph_levels' node counts take the line
 centre for the nearest singularity.  ph_wide_regions (cs_api.hip) now keeps a region out of the levels of a launch whose states let those
 zeros reach a tenth of the region's near distance towards the real axis; such calls sum the region per point (0.373 of the sharp bound).
 The dense-table tests at 2e-11 and 5e-13 never held a state below 160 K.  The rule is cautious (its range: test_wide_states_keep_regions_out

@@ -1,5 +1,5 @@
 """Host tests of tests/phco2_line_ref.py: what tests/test_gpu_phco2_line.py presupposes of its inputs, its probes, its classification and
-its two bounds, checked without a GPU -- chi is continuous, the restated ph_plan is the library's on every grid, the grids provide the
+its two bounds, checked without a GPU -- chi is continuous, the restated ph_levels is the library's on every grid, the grids provide the
 levels asked of them, every probe sees one line, no test holds more than MAX_PROBES and none is of the underflow class, the placements
 sit where the rules put them, every evaluation form is reached by a probe with a non-zero 40-digit value, and the oracle
 (oracle/cs_oracle.c: the scalar form of the model) meets both bounds at the device's probes before the device is held to them."""
@@ -32,7 +32,7 @@ def test_chi_continuous_and_above_one_when_cold():
 
 
 def test_plans(cs, cases):
-    """the restated ph_plan is cs.phco2_plan on every grid and cut-off used, and the grids provide what the cases rely on: levels of 16, 32
+    """the restated ph_levels is cs.phco2_plan on every grid and cut-off used, and the grids provide what the cases rely on: levels of 16, 32
     and 64 nodes; every region at two or more sizes, each but the largest with the next larger size as its parent (par[] never jumps a
     size: phco2_line_ref); interval widths that differ along the geometric grid and move its node counts; no levels below 128 points,
     with interpolation off, or off the fast path"""
