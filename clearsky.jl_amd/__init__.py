@@ -14,6 +14,6 @@ from .core import (interp_plan, phco2_plan, phco2_wide_regions, MultiContext, ba
                    monochromaticfluxes_, netfluxes, nodepressures, nodevalues, opticaldepth, ozonelayer, planck,
                    pressuregrid, psatH2O, radiate, radiate_, shape_batch, stefanboltzmann, streamnodes, transmittance,
                    trapz, trapz_weights, unifyabsorbers, voigt, voigt_, voigtCKD, voigtCKD_,
-                   voigtVVH, voigtVVH_, voigtCKDVVH, voigtCKDVVH_)
+                   voigtVVH, voigtVVH_, voigtCKDVVH, voigtCKDVVH_, voigtLBL, voigtLBL_)
 
 __version__ = "0.1.0"

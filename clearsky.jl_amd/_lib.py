@@ -31,7 +31,8 @@ TUNING = {"FUSE_APPLY": 0, "SMALL_MX": 1, "NODES_STREAM": 2, "MARGIN": 3, "GRAPH
           "MX_MIN_STATES": 8, "PH_OWN_CORE": 9, "PH_NODES": 10, "FAR64": 11, "CASCADE": 12, "NODES_SPLIT": 13, "EDGE_FULL": 14, "FLUX": 15,
           "NEAR_PRIO": 16, "FAR64_SHARED": 17, "SUB_LEAN": 18, "NEAR_MEMSET": 19, "TABLES_MERGE": 21, "FAR_SPLIT": 22, "EDGE_POINTS": 23}
 SHAPES = {"voigt": 0, "lorentz": 1, "doppler": 2, "PHCO2": 3, "phco2": 3, "voigtCKD": 4, "voigtVVH": 5,
-          "voigtCKDVVH": 6}   # 4: CS_SHAPE_VOIGT_CKD, pedestal-removed Voigt; 5: CS_SHAPE_VOIGT_VVH, Van Vleck-Huber Voigt; 6: CS_SHAPE_VOIGT_CKD_VVH, both
+          "voigtCKDVVH": 6,   # 4: CS_SHAPE_VOIGT_CKD, pedestal-removed Voigt; 5: CS_SHAPE_VOIGT_VVH, Van Vleck-Huber Voigt; 6: CS_SHAPE_VOIGT_CKD_VVH, both
+          "voigtLBL": 7}      # 7: CS_SHAPE_VOIGT_LBL, code 6 at the pressure-shifted centres nul + delta_a P / P0 (needs the slot's shifts, takes no flag)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)

@@ -329,7 +329,7 @@ class Context:
         if id(sl) in self._shifted:
             return
         if getattr(sl, "source", None) is None:
-            raise ValueError("pressure_shift=True needs a line table read from a HITRAN .par file (SpectralLines(filename) or "
+            raise ValueError("pressure_shift=True and the voigtLBL shape need a line table read from a HITRAN .par file (SpectralLines(filename) or "
                              "Context.load_par): the library takes the shifts from the file")
         from .hitran import MOLPARAM, ISOINDEX
         src, kw = sl.source
@@ -398,6 +398,7 @@ class Context:
         sl = SpectralLines(dict(M=np.full(n, M, np.int16), I=iso, **a))
         self._slots[id(sl)] = (slot, sl)
         self._shifted.add(id(sl))   # (cs_gas_upload_par attached the file's own pressure shifts)
+        sl.slot_has_shifts = True   # (shape_code: no file to reload, and none needed -- the slot it is bound to holds the shifts)
         return sl
 
     def cia_slot(self, x: CIATables) -> int:
@@ -508,28 +509,39 @@ def default_context(device: int = 0) -> Context:
 # line shapes (B1)
 
 
-def shape_code(shape, pressure_shift: bool = False) -> int:
+def needs_shifts(code: int) -> bool:
+    """a shape code that reads the slot's pressure shifts: CS_SHAPE_PSHIFT on codes 0-2, or code 7 (voigtLBL), which takes no flag --
+    its table must come from a .par file (Context.slot_of(sl, shift=True))"""
+    return bool(code & CS_SHAPE_PSHIFT) or code == SHAPES["voigtLBL"]
+
+
+def shape_code(shape, pressure_shift: bool = False, sl: Optional[SpectralLines] = None) -> int:
     """The library's code of a shape name (or code), with CS_SHAPE_PSHIFT when pressure_shift: line centres at nul + delta_a P / P0
-    (include/clearsky_hip.h).  The shift applies to voigt, lorentz and doppler only; other shapes are refused here, before any device call."""
+    (include/clearsky_hip.h).  The shift applies to voigt, lorentz and doppler only; other shapes are refused here, before any device call
+    (voigtLBL among them: it is shifted as it is).  `sl`: the table the code is for -- one that is neither file-backed nor loaded by
+    Context.load_par cannot give the library its shifts and is refused here too, for the flag and for voigtLBL alike."""
     code = SHAPES[shape] if isinstance(shape, str) else int(shape)
     if pressure_shift:
         if code not in (0, 1, 2):
             raise ValueError(f"pressure_shift applies to the voigt, lorentz and doppler shapes only, not {shape!r}")
         code |= CS_SHAPE_PSHIFT
+    if sl is not None and needs_shifts(code) and getattr(sl, "source", None) is None and not getattr(sl, "slot_has_shifts", False):
+        raise ValueError("pressure_shift=True and the voigtLBL shape need a line table read from a HITRAN .par file (SpectralLines(filename) or "
+                         "Context.load_par): the library takes the shifts from the file")
     return code
 
 
 def shape_batch(sl: SpectralLines, shape, nu, T, P, Pp, dnu_cut=25.0, ctx: Optional[Context] = None, pressure_shift: bool = False):
     """sigma[k, :] = shape!(.., nu, sl, T[k], P[k], Pp[k], dnu_cut) for all states in one launch (bake's inner loop,
     gases.jl:115-126).  Returns an array of shape (K, nnu).  pressure_shift: line centres at nul + delta_a P[k] / P0."""
-    sh = shape_code(shape, pressure_shift)
+    sh = shape_code(shape, pressure_shift, sl)
     ctx = ctx or default_context()
     nu = as_f64(nu)
     T, P, Pp = (as_f64(np.atleast_1d(a)) for a in (T, P, Pp))
     Kn = len(T)
     assert len(P) == Kn and len(Pp) == Kn
     out = np.zeros((Kn, len(nu)))
-    check(lib().cs_shape_batch(ctx.handle, ctx.slot_of(sl, shift=pressure_shift), sh, float(dnu_cut), len(nu), dptr(nu), Kn, dptr(T), dptr(P),
+    check(lib().cs_shape_batch(ctx.handle, ctx.slot_of(sl, shift=needs_shifts(sh)), sh, float(dnu_cut), len(nu), dptr(nu), Kn, dptr(T), dptr(P),
                                dptr(Pp), dptr(out), len(nu)))
     return out
 
@@ -538,12 +550,12 @@ def shape_points(sl: SpectralLines, shape, nu, T, P, Pp, dnu_cut=25.0, ctx: Opti
     """The scalar-wavenumber methods shape(nu, sl, T, P, Pp, dnu_cut) (line_shapes.jl:399-405 etc.) mapped over `nu` and over
     the states: every line with |nu - nul| <= dnu_cut counts (includedlines(::Real), :12-16).  Returns (K, nnu).
     pressure_shift: line centres at nul + delta_a P[k] / P0."""
-    sh = shape_code(shape, pressure_shift)
+    sh = shape_code(shape, pressure_shift, sl)
     ctx = ctx or default_context()
     nu = as_f64(np.atleast_1d(nu))
     T, P, Pp = (as_f64(np.atleast_1d(a)) for a in (T, P, Pp))
     out = np.zeros((len(T), len(nu)))
-    check(lib().cs_shape_points(ctx.handle, ctx.slot_of(sl, shift=pressure_shift), sh, float(dnu_cut), len(nu), dptr(nu), len(T), dptr(T), dptr(P), dptr(Pp),
+    check(lib().cs_shape_points(ctx.handle, ctx.slot_of(sl, shift=needs_shifts(sh)), sh, float(dnu_cut), len(nu), dptr(nu), len(T), dptr(T), dptr(P), dptr(Pp),
                                 dptr(out), len(nu)))
     return out
 
@@ -577,6 +589,10 @@ voigtVVH_, voigtVVH = _shape_inplace("voigtVVH", 25.0)
 # pedestal-removed Van Vleck-Huber Voigt (LBLRTM's line calculation, the one MT_CKD is defined against; no reference counterpart):
 # code 5 with each resonance, direct and mirror, minus its own value at dnu_cut, max(0, .) (include/clearsky_hip.h)
 voigtCKDVVH_, voigtCKDVVH = _shape_inplace("voigtCKDVVH", 25.0)
+# LBLRTM's line calculation at pressure-shifted centres (no reference counterpart): voigtCKDVVH with every line centred at
+# nul + delta_a P / P0, both cut-offs and the mirror resonance measured from there; S, alpha, gamma from the unshifted nul.  The shifts
+# come from the table's .par file: no pressure_shift keyword (it is refused), and a table without a file is refused (include/clearsky_hip.h)
+voigtLBL_, voigtLBL = _shape_inplace("voigtLBL", 25.0)
 
 
 def faddeeva(x, y, ctx: Optional[Context] = None):
@@ -618,7 +634,7 @@ class DirectGas(AbstractGas):
     """
 
     def __init__(self, sl: SpectralLines, fC, nu, shape="voigt", dnu_cut=None, pressure_shift: bool = False):
-        shape_code(shape, pressure_shift)   # (refuses pressure_shift on a shape without it, before any device call)
+        shape_code(shape, pressure_shift, sl)   # (refuses pressure_shift on a shape without it, and a shifted shape on a table without a file, before any device call)
         self.pressure_shift = bool(pressure_shift)
         nu = np.array(nu, dtype=float)
         assert len(nu) > 0
@@ -713,7 +729,7 @@ class Gas(AbstractGas):
 
     def __init__(self, sl, fC, nu, Omega: AtmosphericDomain, shape="voigt", dnu_cut=25.0, ctx: Optional["Context"] = None,
                  keep_host_tables: bool = False, pressure_shift: bool = False, **readpar_kwargs):
-        code = shape_code(shape, pressure_shift)   # (refuses pressure_shift on a shape without it, before any device call)
+        code = shape_code(shape, pressure_shift, None if isinstance(sl, str) else sl)   # (refuses pressure_shift on a shape without it, and a shifted shape on a table without a file, before any device call)
         self.pressure_shift = bool(pressure_shift)
         if isinstance(sl, str):
             sl = SpectralLines(sl, **readpar_kwargs)
@@ -736,7 +752,7 @@ class Gas(AbstractGas):
         self.slot = self.ctx.table_slot(self)
         out = np.zeros((len(nu), Omega.nT, Omega.nP), order="F") if keep_host_tables else None
         try:
-            check(lib().cs_bake(self.ctx.handle, self.ctx.slot_of(sl, shift=pressure_shift), self.slot, code, self.dnu_cut, len(nu), dptr(nu),
+            check(lib().cs_bake(self.ctx.handle, self.ctx.slot_of(sl, shift=needs_shifts(code)), self.slot, code, self.dnu_cut, len(nu), dptr(nu),
                                 Omega.nT, dptr(as_f64(Omega.T)), Omega.nP, dptr(as_f64(Omega.P)), dptr(conc.ravel(order="F").copy()),
                                 out.ctypes.data_as(C.POINTER(C.c_double)) if out is not None else None))
         except Exception:
@@ -803,7 +819,7 @@ def opacityerror(g: Gas, i: int, N: int = 50, shape=None, pressure_shift=None):
     (the scalar-wavenumber `shape(ν, sl, T, P, C(T,P)*P)` at N*N states), the interpolated ones from cs_table_eval.  pressure_shift:
     of the exact values (None: as the gas was baked)."""
     psh = g.pressure_shift if pressure_shift is None else bool(pressure_shift)
-    shape_code(shape or g.shape, psh)
+    shape_code(shape or g.shape, psh, g.sl)
     Om = g.Omega
     T = np.linspace(Om.Tmin, Om.Tmax, N)
     P = 10.0 ** np.linspace(math.log10(Om.Pmin), math.log10(Om.Pmax), N)
@@ -1147,8 +1163,8 @@ class Column:
             if not isinstance(g_, (DirectGas, GrayGas, SemiGrayGas, Gas)):
                 raise TypeError(f"unsupported gas type {type(g_).__name__} for the HIP Discretized core")
         psh = [getattr(g_, "pressure_shift", False) for g_ in self.gases]
-        self.slots = np.array(self.ctx.slots_of([g_.sl for g_ in self.gases], psh), dtype=np.int32)
-        self.shapes = np.array([shape_code(g_.shape, p_) for g_, p_ in zip(self.gases, psh)], dtype=np.int32)
+        self.shapes = np.array([shape_code(g_.shape, p_, g_.sl) for g_, p_ in zip(self.gases, psh)], dtype=np.int32)
+        self.slots = np.array(self.ctx.slots_of([g_.sl for g_ in self.gases], [needs_shifts(int(c_)) for c_ in self.shapes]), dtype=np.int32)
         self.cuts = as_f64([g_.dnu_cut for g_ in self.gases])
         self.want_tau, self.want_M = bool(want_tau), bool(want_M)
         self._set = False

@@ -288,7 +288,7 @@ struct ColGas {
     bool ped = false;         // shape code 4: shape is SH_VOIGT and launch_pedestal follows the line sum over [w.pa, w.pb)
     bool vvh = false;         // shape code 5: shape is SH_VOIGT, the records carry S / R(nul, T) and launch_vvh follows the line sum
                               // (shape code 6: ped and vvh, and launch_vvh_ped follows it instead of both)
-    bool pshift = false;      // CS_SHAPE_PSHIFT: records centred at nul + delta_a P / P0, summed by k_linesum<shape> over windows widened by w.ds
+    bool pshift = false;      // CS_SHAPE_PSHIFT, or shape code 7: records centred at nul + delta_a P / P0, summed by k_linesum<shape> over windows widened by w.ds
     // Voigt / Lorentz groups: how the column's own cross-section stage last ran the group (sigma_impl; a batch's chunked passes run on
     // buffers of their own and leave it alone).  planned: it has, since setup -- the group's windows and zones are written, and
     // cs_column_work counts them by this plan
@@ -1412,10 +1412,10 @@ struct GasPass {
     int shape = SH_VOIGT;           // of the line sum: codes 4, 5, 6 are SH_VOIGT with ped / vvh
     int64_t jlo = 0, jhi = 0;       // only the lines some window can reach (windows are sorted: first tile's start .. last tile's end)
     double cut = 25.0;
-    bool ped = false;               // shape codes 4, 6: the pedestals of the included lines [pa, pb) come off behind the line sum
-    bool vvh = false;               // shape codes 5, 6: every Voigt kernel, over records of S / R(nul, T) (k_gas_setup*_vvh); then R(nu, T) and
+    bool ped = false;               // shape codes 4, 6, 7: the pedestals of the included lines [pa, pb) come off behind the line sum
+    bool vvh = false;               // shape codes 5, 6, 7: every Voigt kernel, over records of S / R(nul, T) (k_gas_setup*_vvh); then R(nu, T) and
     int64_t pa = 0, pb = 0, mb = 0; // the mirror term of the lines [pa, mb) (vvh_mirror_end)
-    // CS_SHAPE_PSHIFT (codes 0-2): records centred at nul + delta_a P / P0, lines whose shifted centre fails the strict pre-filter (flo, fhi)
+    // CS_SHAPE_PSHIFT (codes 0-2) and shape code 7 (with ped and vvh): records centred at nul + delta_a P / P0, lines whose shifted centre fails the strict pre-filter (flo, fhi)
     // parked.  Every kernel reads the record's centre for the values and the cut-off tests; what is decided from TABLE positions -- the
     // windows and zones of the tiles, the interval zones of the interpolated wings, J0 / J1 and the record range -- was (caller) or is
     // (zones: ZoneArgs::ds) widened by the group's largest shift ds.  Off for such groups: the fp32 wings (far_term32 reads the table
@@ -1997,6 +1997,8 @@ static void launch_vvh(hipStream_t s, const GasPass &g, const double *src)
 // shape code 6 in place of launch_vvh: k_ped_values over the included lines [pa, pb) of the S~ records, then ONE pass k_vvh_ped_finish
 // that subtracts each point's direct pedestals, adds the mirror pairs of [pa, mb) minus theirs, multiplies by R(nu, T) and writes
 // sigma = (accumulate ? sigma : base + extra) + r, then max(0, .) if clamp.  ped_ws: as launch_pedestal's.
+// Shape code 7 (g.pshift): the same k_ped_values over the shifted records, then k_vvh_ped_finish_shift, which takes each (point, state)'s
+// direct window and mirror lines from the records' own centres; the mirror tiles reach g.ds further.
 static void launch_vvh_ped(hipStream_t s, const GasPass &g, const double *src)
 {
     const GasTable &G = *g.G;
@@ -2012,10 +2014,17 @@ static void launch_vvh_ped(hipStream_t s, const GasPass &g, const double *src)
     const int64_t ntile = (g.nnu + 255) / 256;
     int64_t tm = 0;
     if (m > a) {
-        const double lim = g.cut - G.h_nu[a];
+        const double lim = g.cut - G.h_nu[a] + (g.pshift ? g.ds : 0.0);
         while (tm < ntile && g.nu[tm * 256] <= lim) tm++;
     }
     const int64_t nblk = tm * g.kn + (ntile - tm) * ((g.kn + CS_PED_KC - 1) / CS_PED_KC);
+    if (g.pshift) {   // code 7: the windows by the records' own centres (fringes of the table-position window ds wide, with room for the
+                      // rounding of nul + s and of the searches' differences)
+        CS_LAUNCH(k_vvh_ped_finish_shift, dim3((unsigned)nblk), dim3(256), 0, s, g.dnu, g.nnu, g.Tk, G.nu.as<double>(), g.hot, g.cold, G.L, a, b, a, m,
+                  g.J0, g.J1, g.cut, g.ds + 1e-9 * g.cut, g.kn, p, pre, suf, bsum, nqt, src, g.base, g.extra, g.sigma, g.accumulate, g.clamp ? 1 : 0,
+                  (int)tm);
+        return;
+    }
     CS_LAUNCH(k_vvh_ped_finish, dim3((unsigned)nblk), dim3(256), 0, s, g.dnu, g.nnu, g.Tk, G.nu.as<double>(), g.hot, g.cold, G.L, a, b, a, m, g.J0, g.J1,
               g.cut, g.kn, p, pre, suf, bsum, nqt, src, g.base, g.extra, g.sigma, g.accumulate, g.clamp ? 1 : 0, (int)tm);
 }
@@ -2023,7 +2032,7 @@ static void launch_vvh_ped(hipStream_t s, const GasPass &g, const double *src)
 // One launch group on `s`, finishing step included.  Codes 0-3: the line sum as the pass states it; code 4: launch_pedestal behind it.
 // Codes 5, 6: the bare line sum of the S / R(nul, T) records -- base 0, no extra, applied at once (no deferred apply) and without side
 // streams, into sigma itself for a group that does not accumulate, else into the spare plane -- then launch_vvh (5) or launch_vvh_ped
-// (6), which write sigma as the pass states it.
+// (6, 7), which write sigma as the pass states it.
 static void launch_gas(hipStream_t s, const GasPass &p)
 {
     if (!p.vvh) {
@@ -2041,47 +2050,53 @@ static void launch_gas(hipStream_t s, const GasPass &p)
 
 // end of the mirror lines of shape code 5 among the included lines [a, b) whose records exist: nu + nul <= cut can hold for some point
 // only where nul <= cut - nu_0 (taken a little wide here: k_vvh_finish applies the exact test).  = a on grids that start at the cut-off
-// or above, where k_vvh_finish then only scales.
-static int64_t vvh_mirror_end(const std::vector<double> &nul, int64_t a, int64_t b, double nu0, double cut)
+// or above, where k_vvh_finish then only scales.  Code 7: the centre nul + s, |s| <= ds, can reach it from table positions up to ds higher.
+static int64_t vvh_mirror_end(const std::vector<double> &nul, int64_t a, int64_t b, double nu0, double cut, double ds)
 {
     b = std::max(a, b);
-    const double lim = cut - nu0;
+    const double lim = cut - nu0 + ds;
     if (!(lim >= 0.0)) return a;
     return std::upper_bound(nul.begin() + a, nul.begin() + b, lim + 1e-9 * cut) - nul.begin();
 }
 
-// a shape code as the entry points take it -- base code 0..6, and CS_SHAPE_PSHIFT ORed onto codes 0, 1, 2 -- taken apart: codes 4, 5, 6 are
-// the Voigt line sum (line_shape), then the pedestal (ped) and / or R(nu, T) and the mirror term (vvh) behind it
+// a shape code as the entry points take it -- base code 0..7, and CS_SHAPE_PSHIFT ORed onto codes 0, 1, 2 -- taken apart: codes 4, 5, 6, 7
+// are the Voigt line sum (line_shape), then the pedestal (ped) and / or R(nu, T) and the mirror term (vvh) behind it; code 7 is code 6 at
+// the shifted centres: pshift without the flag (everything the flag does for a code-0 group, and everything code 6 does behind the sum)
 struct ShapeSpec {
     int base = 0, line_shape = SH_VOIGT;
     bool pshift = false, ped = false, vvh = false;
-    // Voigt, Lorentz, pedestal-removed Voigt, Van Vleck-Huber Voigt, both: what line_sum_voigt runs.  Its far wings can be interpolated, and
-    // gases of a column with the same code and cut-off can share one merged table
-    bool voigt_family() const { return base == SH_VOIGT || base == SH_LORENTZ || base == SH_VOIGT_CKD || base == SH_VOIGT_VVH || base == SH_VOIGT_CKD_VVH; }
+    bool flag = false;   // CS_SHAPE_PSHIFT was ORed on (pshift without it: code 7)
+    // Voigt, Lorentz, pedestal-removed Voigt, Van Vleck-Huber Voigt, both, both shifted: what line_sum_voigt runs.  Its far wings can be
+    // interpolated, and gases of a column with the same code and cut-off can share one merged table
+    bool voigt_family() const
+    {
+        return base == SH_VOIGT || base == SH_LORENTZ || base == SH_VOIGT_CKD || base == SH_VOIGT_VVH || base == SH_VOIGT_CKD_VVH || base == SH_VOIGT_LBL;
+    }
 };
 static ShapeSpec shape_spec(int code)   // (of any integer: decode_shape says which ones are shape codes)
 {
     ShapeSpec sh;
-    sh.pshift = code >= 0 && (code & CS_SHAPE_PSHIFT) != 0;
-    sh.base = sh.pshift ? (code & ~CS_SHAPE_PSHIFT) : code;
-    sh.ped = sh.base == SH_VOIGT_CKD || sh.base == SH_VOIGT_CKD_VVH;
-    sh.vvh = sh.base == SH_VOIGT_VVH || sh.base == SH_VOIGT_CKD_VVH;
+    sh.flag = code >= 0 && (code & CS_SHAPE_PSHIFT) != 0;
+    sh.base = sh.flag ? (code & ~CS_SHAPE_PSHIFT) : code;
+    sh.pshift = sh.flag || sh.base == SH_VOIGT_LBL;
+    sh.ped = sh.base == SH_VOIGT_CKD || sh.base == SH_VOIGT_CKD_VVH || sh.base == SH_VOIGT_LBL;
+    sh.vvh = sh.base == SH_VOIGT_VVH || sh.base == SH_VOIGT_CKD_VVH || sh.base == SH_VOIGT_LBL;
     sh.line_shape = (sh.ped || sh.vvh) ? SH_VOIGT : sh.base;
     return sh;
 }
-// ... any other bit, and the flag on another code, is refused
+// ... any other bit, and the flag on another code (code 7 included: it needs none and accepts none), is refused
 static int decode_shape(int code, ShapeSpec &sh)
 {
     sh = shape_spec(code);
-    if (sh.base < 0 || sh.base > SH_VOIGT_CKD_VVH) return fail(CS_EINVAL, "unknown shape %d", code);
-    if (sh.pshift && sh.base > SH_DOPPLER) return fail(CS_EINVAL, "CS_SHAPE_PSHIFT applies to shape codes 0, 1 and 2, not to %d", sh.base);
+    if (sh.base < 0 || sh.base > SH_VOIGT_LBL) return fail(CS_EINVAL, "unknown shape %d", code);
+    if (sh.flag && sh.base > SH_DOPPLER) return fail(CS_EINVAL, "CS_SHAPE_PSHIFT applies to shape codes 0, 1 and 2, not to %d", sh.base);
     return CS_OK;
 }
 // the largest pressure shift a line of G can take at pressures P[0..n): max |delta_a| x max P / P0 (every decision made from table positions
-// is widened by it).  A flagged group on a table without shifts is an error, not a shift of zero.
+// is widened by it).  A flagged or code-7 group on a table without shifts is an error, not a shift of zero.
 static int shift_width(const GasTable &G, const double *P, int64_t n, double &ds)
 {
-    if (G.h_da.empty()) return fail(CS_EINVAL, "CS_SHAPE_PSHIFT on a gas without pressure shifts (load its table with cs_gas_upload_par)");
+    if (G.h_da.empty()) return fail(CS_EINVAL, "CS_SHAPE_PSHIFT or CS_SHAPE_VOIGT_LBL on a gas without pressure shifts (load its table with cs_gas_upload_par)");
     double pmax = 0.0;
     for (int64_t k = 0; k < n; k++) pmax = std::max(pmax, std::fabs(P[k]));
     ds = G.da_max * pmax / kAtm * (1.0 + 1e-12);
@@ -2436,7 +2451,7 @@ static int build_windows(GroupWindows &w, const GasTable &G, const ShapeSpec &sh
     w.jhi = J1.back();
     w.pa = std::max(w.g0, w.jlo);
     w.pb = std::min(w.g1, w.jhi);
-    w.mb = sh.vvh ? vvh_mirror_end(G.h_nu, w.pa, w.pb, nu[0], cut) : w.pa;
+    w.mb = sh.vvh ? vvh_mirror_end(G.h_nu, w.pa, w.pb, nu[0], cut, ds) : w.pa;
     std::vector<WaveWin> win;
     w.xtiles = wave_windows(G.h_nu, w.g0, w.g1, nu, nnu, cut, win, 64, ds);
     w.nwin = (int)win.size();
@@ -3875,7 +3890,7 @@ int cs_column_counts(cs_ctx *ctx, int64_t *pair_evals, int64_t *lines_in_range)
     int64_t p = 0, l = 0;
     for (auto &g : c.ugas) {
         l += g.lines_in_range;
-        if (g.shape & CS_SHAPE_PSHIFT) {   // pairs inside the cut-off of the shifted centres, state by state
+        if (shape_spec(g.shape).pshift) {   // (the flag, or code 7) pairs inside the cut-off of the shifted centres, state by state
             if (g.pairs_all < 0) {
                 const GasTable &G = ctx->gas[g.slot];
                 std::vector<double> sh(G.h_nu.size());

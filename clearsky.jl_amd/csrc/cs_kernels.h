@@ -46,6 +46,9 @@ constexpr int SH_VOIGT_CKD = 4;
 constexpr int SH_VOIGT_VVH = 5;
 // shape code 6 (pedestal-removed Van Vleck-Huber Voigt) is code 5's line sum, then k_ped_values and k_vvh_ped_finish
 constexpr int SH_VOIGT_CKD_VVH = 6;
+// shape code 7 (LBLRTM's line calculation) is code 6 over records at the pressure-shifted centres (prep_body<true> with pa.pshift), then
+// k_ped_values and k_vvh_ped_finish_shift
+constexpr int SH_VOIGT_LBL = 7;
 
 // per-(state, line) parameters.  "hot" is what the far-wing loops read through scalar loads -- 32 bytes per line is
 // the budget at which those loops stay VALU-bound (64-byte records made them SMEM-bound: profiles/r01_notes.md);
@@ -4318,6 +4321,108 @@ __global__ __launch_bounds__(256) void k_vvh_ped_finish(const double *__restrict
             const size_t idx = o0 + j;
             const double x = v + hot[idx].nul;
             if (x > cut) break;   // (ascending lines: so are all after it)
+            const LineCold c = cold[idx];
+            s += c.A * fad_re(x * hot[idx].p1, c.y) - p[idx];
+        }
+        const double r = radiation_term(v, Tk[k]) * s;
+        const double out = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
+        sigma[o] = clamp ? fmax(out, 0.0) : out;
+    }
+}
+
+// ---- LBLRTM's line calculation at pressure-shifted centres (shape code 7, CS_SHAPE_VOIGT_LBL) ---------------------------------
+// Code 6 with every centre at c[k][l] = nul + delta_l P_k / P0 (prep_body<true> with pa.pshift: the S~ records sit at the shifted centres,
+// parked at kParked with A = 0 where the state's strict pre-filter leaves the line out; S~, alpha, gamma stay those of nul):
+//   sigma = max(0, R(nu, T) sum_l S~_l [(f_l(nu - c_l) - f_l(cut)) 1{|nu - c_l| <= cut} + (f_l(nu + c_l) - f_l(cut)) 1{nu + c_l <= cut}]).
+// k_ped_values is the same (p = A Re w(cut d, y) does not depend on the centre; a parked line has p = 0).  What moves is who is inside:
+// the direct window of a (point, state) is no run of the table, since c moves with P_k and neighbours with shifts of opposite sign
+// swap places.  With ds >= every |c - nul| of the group (the host's shift_width plus a rounding margin), the thread finds ONCE for its
+// states four table positions jA <= jB <= jC <= jD:
+//   [jB, jC)   nul in [nu - cut + ds, nu + cut - ds]: inside at every state; their pedestals are summed as k_vvh_ped_finish sums its window
+//              (in-block suffix, whole blocks, in-block prefix: never a difference of prefix sums)
+//   [jA, jB), [jC, jD)   nul within ds of an edge: tested one by one, per state, with the record's centre and the line kernels' own test
+//              !(|nu - c| > cut)
+// (cut < ds: no certain lines, [jA, jD) is all fringe.)  The mirror lines [ma, mb) -- the included lines with nul <= cut - nu_0 + ds -- are
+// not ascending in c either: every one is tested with nu + c <= cut, and no centre ends the loop; it ends at the first TABLE position with
+// nu + nul > cut + ds, beyond which no centre can pass (on tiles far from the mirror lines: at once).  A parked record fails both tests
+// (and would add p = 0).  Output, src and the block layout (tm mirror tiles, one state per block) as k_vvh_ped_finish.
+__global__ __launch_bounds__(256) void k_vvh_ped_finish_shift(const double *__restrict__ nu, int64_t nnu, const double *__restrict__ Tk,
+                                                              const double *__restrict__ nul, const LineHot *__restrict__ hot,
+                                                              const LineCold *__restrict__ cold, int64_t L, int64_t a, int64_t b, int64_t ma,
+                                                              int64_t mb, const int32_t *__restrict__ tJ0, const int32_t *__restrict__ tJ1,
+                                                              double cut, double ds, int K, const double *__restrict__ p,
+                                                              const double *__restrict__ pre, const double *__restrict__ suf,
+                                                              const double *__restrict__ bsum, int64_t nqt, const double *src, double base,
+                                                              const double *__restrict__ extra, double *sigma, int accumulate, int clamp, int tm)
+{
+    const unsigned nm = (unsigned)tm * (unsigned)K, ng = (unsigned)(K + CS_PED_KC - 1) / CS_PED_KC;
+    unsigned t;
+    int k0, k1;
+    if (blockIdx.x < nm) {
+        t = blockIdx.x / (unsigned)K;
+        k0 = (int)(blockIdx.x - t * (unsigned)K);
+        k1 = k0 + 1;
+    } else {
+        const unsigned r = blockIdx.x - nm;
+        t = (unsigned)tm + r / ng;
+        k0 = (int)(r % ng) * CS_PED_KC;
+        k1 = min(k0 + CS_PED_KC, K);
+    }
+    const int64_t i = (int64_t)t * 256 + threadIdx.x;
+    if (i >= nnu) return;
+    const double v = nu[i];
+    const int64_t wa = max(a, (int64_t)tJ0[t]), wb = max(wa, min(b, (int64_t)tJ1[t]));
+    const double out_d = cut + ds, in_d = cut - ds;   // a line's table position: beyond out_d certainly outside, within in_d certainly inside
+    int64_t lo = wa, hi = wb;
+    while (lo < hi) {   // first line with v - nul <= cut + ds
+        const int64_t m = (lo + hi) >> 1;
+        if (v - nul[m] > out_d) lo = m + 1; else hi = m;
+    }
+    const int64_t jA = lo;
+    hi = wb;
+    while (lo < hi) {   // first line with nul - v > cut + ds
+        const int64_t m = (lo + hi) >> 1;
+        if (!(nul[m] - v > out_d)) lo = m + 1; else hi = m;
+    }
+    const int64_t jD = lo;
+    int64_t jB = jA, jC = jA;   // (cut < ds: nothing is certain)
+    if (in_d >= 0.0) {
+        lo = jA; hi = jD;
+        while (lo < hi) {   // first line with v - nul <= cut - ds
+            const int64_t m = (lo + hi) >> 1;
+            if (!(v - nul[m] <= in_d)) lo = m + 1; else hi = m;
+        }
+        jB = lo;
+        hi = jD;
+        while (lo < hi) {   // first line with nul - v > cut - ds
+            const int64_t m = (lo + hi) >> 1;
+            if (nul[m] - v <= in_d) lo = m + 1; else hi = m;
+        }
+        jC = lo;
+    }
+    const int64_t b0 = jB / CS_PED_B, b1 = (max(jC, jB + 1) - 1) / CS_PED_B;
+    for (int k = k0; k < k1; k++) {
+        const size_t o0 = (size_t)k * L;
+        const double *__restrict__ bk = bsum + (size_t)k * nqt;
+        double ps = 0.0;
+        if (b0 == b1) {
+            for (int64_t j = jB; j < jC; j++) ps += p[o0 + j];
+        } else {
+            ps = suf[o0 + jB];
+            for (int64_t q = b0 + 1; q < b1; q++) ps += bk[q];
+            ps += pre[o0 + jC - 1];
+        }
+        for (int64_t j = jA; j < jB; j++)   // the lower fringe, by the state's own centres
+            if (!(fabs(v - hot[o0 + j].nul) > cut)) ps += p[o0 + j];
+        for (int64_t j = jC; j < jD; j++)   // the upper fringe
+            if (!(fabs(v - hot[o0 + j].nul) > cut)) ps += p[o0 + j];
+        const size_t o = (size_t)k * nnu + i;
+        double s = src[o] - ps;
+        for (int64_t j = ma; j < mb; j++) {
+            if (v + nul[j] > out_d) break;   // (TABLE positions ascend and c >= nul - ds: no later line can pass the test below)
+            const size_t idx = o0 + j;
+            const double x = v + hot[idx].nul;
+            if (x > cut) continue;   // (the centres are not ascending: no line's centre ends the loop)
             const LineCold c = cold[idx];
             s += c.A * fad_re(x * hot[idx].p1, c.y) - p[idx];
         }

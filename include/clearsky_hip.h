@@ -65,9 +65,23 @@ enum {
  * and at the mirror edge nu = D - nul (where code 5 steps by R S~_l f_l(D)), and sigma -> 0 as nu -> 0.  max(0, .) only absorbs
  * rounding, and is placed exactly as for code 4: B1 and cs_bake clamp the gas's own sigma; in a column, cs_column_sigma_run and
  * cs_accel_store clamp the total plane of a column holding a code-4 or code-6 gas, cs_column_run and cs_column_batch never.  Usual
- * cut-off: 25 cm^-1.  Accepted wherever a shape code is; merged only with code 6 of the same cut-off. */
+ * cut-off: 25 cm^-1.  Accepted wherever a shape code is; merged only with code 6 of the same cut-off.
+ * CS_SHAPE_VOIGT_LBL, code 6 at pressure-shifted centres (LBLRTM's line calculation as it runs: radiation term, mirror line, pedestal
+ * removal and HITRAN's air pressure shift at once): with S_l, alpha_l, gamma_l and S~_l exactly those of code 6, all from the UNSHIFTED
+ * nul (HAPI's convention, as for CS_SHAPE_PSHIFT below), c_l = nul + delta_l P / P0 (P the state's total pressure, P0 = 101325 Pa,
+ * delta_l the slot's shifts) and D = dnu_cut,
+ *     sigma(nu) = max(0, R(nu, T) sum_l S~_l [(f_l(nu - c_l) - f_l(D)) 1{|nu - c_l| <= D} + (f_l(nu + c_l) - f_l(D)) 1{nu + c_l <= D}])
+ * Both tests are inclusive and measured from the SHIFTED centre; the mirror resonance sits at -c_l.  Vector methods (cs_shape_batch,
+ * cs_bake): the strict end-point pre-filter nu_1 - D < c_l < nu_N + D, per state, on the shifted centre; scalar method
+ * (cs_shape_points): none.  With every delta = 0, or at P = 0, this is code 6.  max(0, .) is placed exactly as for code 6 (a column
+ * holding a code-4, 6 or 7 gas).  It is one shape of its own: it needs no flag and accepts none (7 | CS_SHAPE_PSHIFT is CS_EINVAL), and
+ * on a slot without shifts (one filled by cs_gas_upload) it is CS_EINVAL -- never a shift of zero.  Accepted wherever a shape code is (B1,
+ * cs_bake, the Mode D calls, resident columns in every flux form, cs_column_sigma_run, cs_column_batch, cs_accel_store, nu-shards;
+ * cs_column_counts counts its pairs inside the shifted cut-off state by state); merged only with code 7 of the same cut-off.  Its groups
+ * run first in a column like codes 5 and 6, and like a flagged group take no matrix-core pieces and no fp32 wings.  Usual cut-off:
+ * 25 cm^-1. */
 enum { CS_SHAPE_VOIGT = 0, CS_SHAPE_LORENTZ = 1, CS_SHAPE_DOPPLER = 2, CS_SHAPE_PHCO2 = 3, CS_SHAPE_VOIGT_CKD = 4, CS_SHAPE_VOIGT_VVH = 5,
-       CS_SHAPE_VOIGT_CKD_VVH = 6 };
+       CS_SHAPE_VOIGT_CKD_VVH = 6, CS_SHAPE_VOIGT_LBL = 7 };
 /* CS_SHAPE_PSHIFT, ORed onto codes 0, 1, 2: HITRAN's air pressure shift of the line centres (LBLRTM, HAPI, ARTS).  For every state
  * (T, P, Pp), with delta_l the slot's shifts (from its .par file) and P0 = 1 atm = 101325 Pa,
  *     sigma(nu) = sum_l S_l(T) f_l(nu - nul - s_l),    s_l = delta_l P / P0,
@@ -78,7 +92,7 @@ enum { CS_SHAPE_VOIGT = 0, CS_SHAPE_LORENTZ = 1, CS_SHAPE_DOPPLER = 2, CS_SHAPE_
  * The shifts come from the file: cs_gas_upload_par keeps each record's delta_a (HITRAN columns 60-67, par.jl:80,140) with the slot;
  * cs_gas_upload and cs_gas_clear drop them.
  * Accepted wherever a shape code is (B1, cs_bake, the Mode D calls, resident columns in every flux form, cs_column_sigma_run,
- * cs_column_batch, cs_accel_store, nu-shards); on codes 3-6, or with any other bit set, CS_EINVAL.  A flagged gas on a slot without
+ * cs_column_batch, cs_accel_store, nu-shards); on codes 3-7, or with any other bit set, CS_EINVAL.  A flagged gas on a slot without
  * shifts (one filled by cs_gas_upload) is CS_EINVAL -- never a shift of zero.  Flagged gases merge only with flagged gases of the same
  * base code and cut-off.  A flagged Voigt / Lorentz group keeps the vector-unit path (interpolated far wings, near-line pairs) with every
  * window and zone widened by its largest shift; it takes no matrix-core pieces and no fp32 wings under cs_set_precision mode 1 (both

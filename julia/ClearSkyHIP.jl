@@ -41,7 +41,10 @@ const CS_MAX_TABLE = 16      # opacity-table slots
 const CS_MAX_CIA = 8         # CIA slots
 const CS_MAX_ACCEL = 4       # accelerated-absorber slots
 const CS_CIA_EXTRAPOLATE, CS_CIA_SINGLES, CS_CIA_RADIATION = Cint(1), Cint(2), Cint(4)   # cia_flags (include/clearsky_hip.h)
-const SHAPES = Dict(:voigt=>0, :lorentz=>1, :doppler=>2, :PHCO2=>3, :voigtCKD=>4, :voigtVVH=>5, :voigtCKDVVH=>6)   # 4: pedestal-removed Voigt (CS_SHAPE_VOIGT_CKD), 5: Van Vleck-Huber Voigt (CS_SHAPE_VOIGT_VVH), 6: both (CS_SHAPE_VOIGT_CKD_VVH)
+const SHAPES = Dict(:voigt=>0, :lorentz=>1, :doppler=>2, :PHCO2=>3, :voigtCKD=>4, :voigtVVH=>5, :voigtCKDVVH=>6, :voigtLBL=>7)   # 4: pedestal-removed Voigt (CS_SHAPE_VOIGT_CKD), 5: Van Vleck-Huber Voigt (CS_SHAPE_VOIGT_VVH), 6: both (CS_SHAPE_VOIGT_CKD_VVH)
+# 7 (CS_SHAPE_VOIGT_LBL): code 6 at the pressure-shifted centres.  It reads the slot's shifts, so it needs a slot filled by `slotfrompar!`
+# (the library takes the shifts from the .par file); on a slot filled from a `SpectralLines` (`slot!`) the library refuses it.  There is no
+# `hipvoigtLBL!`: the reference's `SpectralLines` carries no shifts, so a `shape!(σ, ν, sl, ...)` has nothing to take them from.
 
 lasterror() = unsafe_string(ccall((:cs_last_error, LIB), Cstring, ()))
 check(rc::Cint) = rc == 0 ? nothing : error("clearsky_hip ($rc): $(lasterror())")
