@@ -1965,6 +1965,21 @@ static void launch_line_sum(hipStream_t s, const GasPass &p)
 
 // workspace of launch_pedestal for kn states of a table of L lines: p, in-block prefix and suffix sums [3][kn][L], block sums [kn][ceil(L / CS_PED_B)]
 static size_t ped_bytes(int64_t kn, int64_t L) { return (size_t)kn * ((size_t)3 * L + (L + CS_PED_B - 1) / CS_PED_B) * sizeof(double); }
+// ... and its four views
+static PedWs ped_views(double *ped_ws, int64_t kn, int64_t L)
+{
+    const size_t kl = (size_t)kn * L;
+    return {ped_ws, ped_ws + kl, ped_ws + 2 * kl, ped_ws + 3 * kl, (L + CS_PED_B - 1) / CS_PED_B};
+}
+
+// p and its in-block sums of the included lines [pa, pb) of the group's records, into ws
+static void launch_ped_values(hipStream_t s, const GasPass &g, const PedWs &ws)
+{
+    const int64_t a = g.pa, b = std::max(a, g.pb);
+    if (b <= a) return;
+    const int64_t q0 = a / CS_PED_B, q1 = (b - 1) / CS_PED_B + 1;
+    CS_LAUNCH(k_ped_values, dim3((unsigned)((q1 - q0 + 3) / 4), (unsigned)g.kn), dim3(256), 0, s, g.hot, g.cold, g.G->L, a, b, g.cut, q0, q1 - q0, ws);
+}
 
 // shape code 4 behind the group's line sum on the same stream (whose K1 left the Voigt records of these kn states in hot / cold):
 // sigma[k][i] -= sum of p[k][l] over the lines l of [pa, pb) with |nu_i - nul_l| <= cut; clamp: then max(0, .) (sigma complete).
@@ -1973,16 +1988,10 @@ static size_t ped_bytes(int64_t kn, int64_t L) { return (size_t)kn * ((size_t)3 
 static void launch_pedestal(hipStream_t s, const GasPass &g)
 {
     const GasTable &G = *g.G;
-    const int64_t nqt = (G.L + CS_PED_B - 1) / CS_PED_B, a = g.pa, b = std::max(a, g.pb);
-    const size_t kl = (size_t)g.kn * G.L;
-    double *p = g.ped_ws, *pre = p + kl, *suf = p + 2 * kl, *bsum = p + 3 * kl;
-    if (b > a) {
-        const int64_t q0 = a / CS_PED_B, q1 = (b - 1) / CS_PED_B + 1;
-        CS_LAUNCH(k_ped_values, dim3((unsigned)((q1 - q0 + 3) / 4), (unsigned)g.kn), dim3(256), 0, s, g.hot, g.cold, G.L, a, b, g.cut, q0, q1 - q0,
-                  nqt, p, pre, suf, bsum);
-    }
+    const PedWs ws = ped_views(g.ped_ws, g.kn, G.L);
+    launch_ped_values(s, g, ws);
     CS_LAUNCH(k_ped_sub, dim3((unsigned)((g.nnu + 255) / 256), (unsigned)((g.kn + CS_PED_KC - 1) / CS_PED_KC)), dim3(256), 0, s, g.dnu, g.nnu,
-              G.nu.as<double>(), G.L, a, b, g.J0, g.J1, g.cut, g.kn, p, pre, suf, bsum, nqt, g.sigma, g.clamp ? 1 : 0);
+              G.nu.as<double>(), G.L, g.pa, std::max(g.pa, g.pb), g.J0, g.J1, g.cut, g.kn, ws, g.sigma, g.clamp ? 1 : 0);
 }
 
 // shape code 5 behind the group's line sum on the same stream, which is in src (base 0, nothing else added; src may be sigma):
@@ -1997,19 +2006,14 @@ static void launch_vvh(hipStream_t s, const GasPass &g, const double *src)
 // shape code 6 in place of launch_vvh: k_ped_values over the included lines [pa, pb) of the S~ records, then ONE pass k_vvh_ped_finish
 // that subtracts each point's direct pedestals, adds the mirror pairs of [pa, mb) minus theirs, multiplies by R(nu, T) and writes
 // sigma = (accumulate ? sigma : base + extra) + r, then max(0, .) if clamp.  ped_ws: as launch_pedestal's.
-// Shape code 7 (g.pshift): the same k_ped_values over the shifted records, then k_vvh_ped_finish_shift, which takes each (point, state)'s
-// direct window and mirror lines from the records' own centres; the mirror tiles reach g.ds further.
+// Shape code 7 (g.pshift): the same k_ped_values over the shifted records, then the SHIFT form of the finish pass, which takes each
+// (point, state)'s direct window and mirror lines from the records' own centres; the mirror tiles reach g.ds further.
 static void launch_vvh_ped(hipStream_t s, const GasPass &g, const double *src)
 {
     const GasTable &G = *g.G;
-    const int64_t nqt = (G.L + CS_PED_B - 1) / CS_PED_B, a = g.pa, b = std::max(a, g.pb), m = std::min(std::max(a, g.mb), b);
-    const size_t kl = (size_t)g.kn * G.L;
-    double *p = g.ped_ws, *pre = p + kl, *suf = p + 2 * kl, *bsum = p + 3 * kl;
-    if (b > a) {
-        const int64_t q0 = a / CS_PED_B, q1 = (b - 1) / CS_PED_B + 1;
-        CS_LAUNCH(k_ped_values, dim3((unsigned)((q1 - q0 + 3) / 4), (unsigned)g.kn), dim3(256), 0, s, g.hot, g.cold, G.L, a, b, g.cut, q0, q1 - q0,
-                  nqt, p, pre, suf, bsum);
-    }
+    const int64_t a = g.pa, b = std::max(a, g.pb), m = std::min(std::max(a, g.mb), b);
+    const PedWs ws = ped_views(g.ped_ws, g.kn, G.L);
+    launch_ped_values(s, g, ws);
     // the tiles [0, tm) whose first point can reach a mirror line (nu + nul_a <= cut) get one state per block
     const int64_t ntile = (g.nnu + 255) / 256;
     int64_t tm = 0;
@@ -2018,15 +2022,12 @@ static void launch_vvh_ped(hipStream_t s, const GasPass &g, const double *src)
         while (tm < ntile && g.nu[tm * 256] <= lim) tm++;
     }
     const int64_t nblk = tm * g.kn + (ntile - tm) * ((g.kn + CS_PED_KC - 1) / CS_PED_KC);
-    if (g.pshift) {   // code 7: the windows by the records' own centres (fringes of the table-position window ds wide, with room for the
-                      // rounding of nul + s and of the searches' differences)
-        CS_LAUNCH(k_vvh_ped_finish_shift, dim3((unsigned)nblk), dim3(256), 0, s, g.dnu, g.nnu, g.Tk, G.nu.as<double>(), g.hot, g.cold, G.L, a, b, a, m,
-                  g.J0, g.J1, g.cut, g.ds + 1e-9 * g.cut, g.kn, p, pre, suf, bsum, nqt, src, g.base, g.extra, g.sigma, g.accumulate, g.clamp ? 1 : 0,
-                  (int)tm);
-        return;
-    }
-    CS_LAUNCH(k_vvh_ped_finish, dim3((unsigned)nblk), dim3(256), 0, s, g.dnu, g.nnu, g.Tk, G.nu.as<double>(), g.hot, g.cold, G.L, a, b, a, m, g.J0, g.J1,
-              g.cut, g.kn, p, pre, suf, bsum, nqt, src, g.base, g.extra, g.sigma, g.accumulate, g.clamp ? 1 : 0, (int)tm);
+    // code 7: the windows by the records' own centres (fringes of the table-position window ds wide, with room for the rounding of
+    // nul + s and of the searches' differences)
+    const double ds = g.pshift ? g.ds + 1e-9 * g.cut : 0.0;
+    CS_LAUNCH(g.pshift ? k_vvh_ped_finish<true> : k_vvh_ped_finish<false>, dim3((unsigned)nblk), dim3(256), 0, s, g.dnu, g.nnu, g.Tk,
+              G.nu.as<double>(), g.hot, g.cold, G.L, a, b, a, m, g.J0, g.J1, g.cut, ds, g.kn, ws, src, g.base, g.extra, g.sigma, g.accumulate,
+              g.clamp ? 1 : 0, (int)tm);
 }
 
 // One launch group on `s`, finishing step included.  Codes 0-3: the line sum as the pass states it; code 4: launch_pedestal behind it.

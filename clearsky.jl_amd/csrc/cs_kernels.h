@@ -47,7 +47,7 @@ constexpr int SH_VOIGT_VVH = 5;
 // shape code 6 (pedestal-removed Van Vleck-Huber Voigt) is code 5's line sum, then k_ped_values and k_vvh_ped_finish
 constexpr int SH_VOIGT_CKD_VVH = 6;
 // shape code 7 (LBLRTM's line calculation) is code 6 over records at the pressure-shifted centres (prep_body<true> with pa.pshift), then
-// k_ped_values and k_vvh_ped_finish_shift
+// k_ped_values and k_vvh_ped_finish<true>
 constexpr int SH_VOIGT_LBL = 7;
 
 // per-(state, line) parameters.  "hot" is what the far-wing loops read through scalar loads -- 32 bytes per line is
@@ -4131,22 +4131,24 @@ __global__ void k_faddeeva(int64_t n, const double *__restrict__ x, const double
     if (i < n) out[i] = fad_re(x[i], y[i]);
 }
 
-// ---- pedestal-removed Voigt (shape code 4, CS_SHAPE_VOIGT_CKD) ------------------------------------------------------------
-// sigma = sum over included lines of C S [f_V(nu - nul) - f_V(cut)].  The Voigt part is a code-0 line sum; these two kernels subtract
-// the pedestal P(nu, k) = sum_{|nu - nul| <= cut} p[k][l] behind it.  p[k][l] = A Re w(cut d, y) = C S f_V(cut; alpha, gamma) comes from
-// the Voigt records k_gas_setup just wrote (cold.A, hot.p1 = d = sqrt(ln 2)/alpha, cold.y), at the same x = cut * d the line kernels
-// reach at |nu - nul| = cut.  A window [j0, j1) is summed as head partial block + whole aligned blocks of CS_PED_B lines + tail partial
-// block, the two partial blocks read as ONE value each: the in-block suffix sum at j0 and the in-block prefix sum at j1 - 1, sums of
-// window lines only.  Never as a difference of prefix sums (over the table, or over a block): that rounding would scale with the strong
-// lines outside the window instead of with the window's own sum |p| (all p >= 0); the bound here is ~(2 + j1/64 - j0/64) eps x sum_window p.
+// ---- the finishing passes behind the Voigt line sum (shape codes 4-7) ------------------------------------------------------------
+// Code 4 subtracts pedestals (k_ped_values, k_ped_sub); code 5 adds the mirror term and multiplies by R(nu, T) (k_vvh_finish); codes 6 and
+// 7 do both in one pass (k_ped_values, k_vvh_ped_finish<SHIFT>).  Each piece they share stands once below, under its contract.
+//
+// The pedestal P(nu, k) = sum_{|nu - nul| <= cut} p[k][l]:  p[k][l] = A Re w(cut d, y) = C S f_V(cut; alpha, gamma) comes from the Voigt
+// records k_gas_setup just wrote (cold.A, hot.p1 = d = sqrt(ln 2)/alpha, cold.y), at the same x = cut * d the line kernels reach at
+// |nu - nul| = cut.  With S~ records (codes 6, 7) it is C S~ f_V(cut).
 #define CS_PED_B 64
-#define CS_PED_KC 8   // states per thread of k_ped_sub (the window search is done once for them)
+#define CS_PED_KC 8   // states per thread of k_ped_sub and k_vvh_ped_finish (the window search is done once for them)
+
+// the pedestal workspace of kn states of a table of L lines (the host's ped_views): p, its in-block prefix and suffix sums [kn][L] each,
+// and the block sums [kn][nqt], nqt = ceil(L / CS_PED_B)
+struct PedWs { double *p, *pre, *suf, *bsum; int64_t nqt; };
 
 // one wave per (aligned block q of CS_PED_B lines, state): p of the lines of [a, b) in it, their in-block prefix and suffix sums, and the
 // block's sum (0 for lines outside)
 __global__ __launch_bounds__(256) void k_ped_values(const LineHot *__restrict__ hot, const LineCold *__restrict__ cold, int64_t L, int64_t a,
-                                                    int64_t b, double cut, int64_t q0, int64_t nq, int64_t nqt, double *__restrict__ p,
-                                                    double *__restrict__ pre, double *__restrict__ suf, double *__restrict__ bsum)
+                                                    int64_t b, double cut, int64_t q0, int64_t nq, PedWs ws)
 {
     const int k = blockIdx.y;
     const int64_t q = q0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -4166,49 +4168,126 @@ __global__ __launch_bounds__(256) void k_ped_values(const LineHot *__restrict__ 
         if (lane >= d) up += u;
         if (lane + d < 64) dn += w;
     }
-    if (in) { p[idx] = v; pre[idx] = up; suf[idx] = dn; }
-    if (lane == 63) bsum[(size_t)k * nqt + q] = up;
+    if (in) { ws.p[idx] = v; ws.pre[idx] = up; ws.suf[idx] = dn; }
+    if (lane == 63) ws.bsum[(size_t)k * ws.nqt + q] = up;
 }
 
-// one thread per (point, CS_PED_KC states): sigma[k][i] -= P(nu_i, k), then max(0, .) when the plane is complete (clamp).  The window
-// [j0, j1) of [a, b) is found with the line kernels' own test !(|nu - nul| > cut) (cutline, line_shapes.jl:10), so the pedestal covers
-// exactly the lines whose Voigt term was summed; the search runs inside the 256-point tile's window [tJ0, tJ1) of the line kernels (a
-// superset of every point's), not over the whole table.
+// Window: the run [j0, j1) of the ascending table positions nul[lo, hi) that lie within d of v, by the line kernels' own test
+// !(|v - nul| > d) (cutline, line_shapes.jl:10) -- so with d = cut a pedestal covers exactly the lines whose Voigt term was summed.
+// j0 = the first line with v - nul <= d, j1 = the first after it with nul - v > d.  The callers search inside the 256-point tile's
+// window [tJ0, tJ1) of the line kernels (a superset of every point's), not over the whole table.  (Read with the comparisons turned
+// round, !(v - nul <= d) and nul - v <= d -- the natural form for code 7's inner pair, "certainly inside" -- these are the same predicates
+// for finite inputs.)
+struct PedRun { int64_t j0, j1; };
+__device__ __forceinline__ PedRun ped_window(const double *__restrict__ nul, int64_t lo, int64_t hi, double v, double d)
+{
+    const int64_t end = hi;
+    while (lo < hi) {   // first line with v - nul <= d
+        const int64_t m = (lo + hi) >> 1;
+        if (v - nul[m] > d) lo = m + 1; else hi = m;
+    }
+    const int64_t j0 = lo;
+    hi = end;
+    while (lo < hi) {   // first line with nul - v > d
+        const int64_t m = (lo + hi) >> 1;
+        if (!(nul[m] - v > d)) lo = m + 1; else hi = m;
+    }
+    return {j0, lo};
+}
+
+// Pedestal sum of the run [j0, j1) of one state (p, pre, suf: the views of PedWs, o0: the state's row in them, bk: its block sums): head
+// partial block + whole aligned blocks of CS_PED_B lines, ascending + tail partial block, the two partial blocks read as ONE value each:
+// the in-block suffix sum at j0 and the in-block prefix sum at j1 - 1, sums of window lines only.  Never as a difference of prefix sums
+// (over the table, or over a block): that rounding would scale with the strong lines outside the window instead of with the window's
+// own sum |p| (all p >= 0); the bound here is ~(2 + j1/64 - j0/64) eps x sum_window p.
+__device__ __forceinline__ double ped_sum(const double *__restrict__ p, const double *__restrict__ pre, const double *__restrict__ suf,
+                                          const double *__restrict__ bk, size_t o0, int64_t j0, int64_t j1)
+{
+    const int64_t b0 = j0 / CS_PED_B, b1 = (max(j1, j0 + 1) - 1) / CS_PED_B;   // blocks of the first and the last line of the run
+    double s = 0.0;
+    if (b0 == b1) {   // inside one block (or empty): the lines one by one
+        for (int64_t j = j0; j < j1; j++) s += p[o0 + j];
+    } else {          // suffix of the first block, whole blocks between, prefix of the last
+        s = suf[o0 + j0];
+        for (int64_t q = b0 + 1; q < b1; q++) s += bk[q];
+        s += pre[o0 + j1 - 1];
+    }
+    return s;
+}
+
+// Mirror term of one (point, state): s plus the pairs A Re w((nu + c) d, y) [- p: PED] of the lines [ma, mb), from the same records
+// (cold.A, hot.p1 = d, cold.y; c = hot.nul) as the near-line kernels, with the inclusive test nu + c <= cut.  o0: the state's row in hot, cold, p.
+// !SHIFT: the centres ascend, and the first one beyond the cut ends the loop.  SHIFT (centres c = nul + s, |s| <= ds, not ascending): every
+// line is tested, and no centre ends the loop; it ends at the first TABLE position with nu + nul > out_d = cut + ds, beyond which no centre
+// can pass (on tiles far from the mirror lines: at once).  A parked record fails the test (and would add p = 0).
+template <bool SHIFT, bool PED>
+__device__ __forceinline__ double mirror_sum(double s, double v, const LineHot *__restrict__ hot, const LineCold *__restrict__ cold,
+                                             const double *__restrict__ p, const double *__restrict__ nul, size_t o0, int64_t ma,
+                                             int64_t mb, double cut, double out_d)
+{
+    for (int64_t j = ma; j < mb; j++) {
+        if constexpr (SHIFT)
+            if (v + nul[j] > out_d) break;
+        const size_t idx = o0 + j;
+        const double x = v + hot[idx].nul;
+        if (x > cut) {
+            if constexpr (SHIFT) continue;
+            else break;   // (ascending lines: so are all after it)
+        }
+        const LineCold c = cold[idx];
+        if constexpr (PED) s += c.A * fad_re(x * hot[idx].p1, c.y) - p[idx];
+        else s += c.A * fad_re(x * hot[idx].p1, c.y);
+    }
+    return s;
+}
+
+// Output of one (point, state): sigma = (accumulate ? sigma : base + extra) + r, then max(0, .) if clamp.  The finish kernels read their
+// line sum from src, which may be sigma: no __restrict__ on either.
+__device__ __forceinline__ void finish_store(double *sigma, size_t o, int accumulate, double base, const double *__restrict__ extra, double r,
+                                             int clamp)
+{
+    const double out = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
+    sigma[o] = clamp ? fmax(out, 0.0) : out;
+}
+
+// Block layout of k_vvh_ped_finish: the first tm tiles (those whose points can reach a mirror line) one state per block, tile-major, so
+// that their loops over the mirror lines run side by side and first; every other tile CS_PED_KC states per block.  Block bx works on the
+// states [k0, k1) of tile t.
+struct FinishBlock { unsigned t; int k0, k1; };
+__device__ __forceinline__ FinishBlock finish_block(unsigned bx, int tm, int K)
+{
+    const unsigned nm = (unsigned)tm * (unsigned)K, ng = (unsigned)(K + CS_PED_KC - 1) / CS_PED_KC;
+    FinishBlock B;
+    if (bx < nm) {
+        B.t = bx / (unsigned)K;
+        B.k0 = (int)(bx - B.t * (unsigned)K);
+        B.k1 = B.k0 + 1;
+    } else {
+        const unsigned r = bx - nm;
+        B.t = (unsigned)tm + r / ng;
+        B.k0 = (int)(r % ng) * CS_PED_KC;
+        B.k1 = min(B.k0 + CS_PED_KC, K);
+    }
+    return B;
+}
+
+// ---- pedestal-removed Voigt (shape code 4, CS_SHAPE_VOIGT_CKD) ------------------------------------------------------------
+// sigma = sum over included lines of C S [f_V(nu - nul) - f_V(cut)].  The Voigt part is a code-0 line sum; k_ped_values and this kernel
+// subtract the pedestal behind it.  One thread per (point, CS_PED_KC states): sigma[k][i] -= P(nu_i, k) over the point's window of
+// [a, b), then max(0, .) when the plane is complete (clamp).
 __global__ __launch_bounds__(256) void k_ped_sub(const double *__restrict__ nu, int64_t nnu, const double *__restrict__ nul, int64_t L,
                                                  int64_t a, int64_t b, const int32_t *__restrict__ tJ0, const int32_t *__restrict__ tJ1,
-                                                 double cut, int K, const double *__restrict__ p,
-                                                 const double *__restrict__ pre, const double *__restrict__ suf, const double *__restrict__ bsum,
-                                                 int64_t nqt, double *__restrict__ sigma, int clamp)
+                                                 double cut, int K, PedWs ws, double *__restrict__ sigma, int clamp)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nnu) return;
     const double v = nu[i];
     const int64_t wa = max(a, (int64_t)tJ0[blockIdx.x]), wb = max(wa, min(b, (int64_t)tJ1[blockIdx.x]));
-    int64_t lo = wa, hi = wb;
-    while (lo < hi) {   // first line with v - nul <= cut
-        const int64_t m = (lo + hi) >> 1;
-        if (v - nul[m] > cut) lo = m + 1; else hi = m;
-    }
-    const int64_t j0 = lo;
-    hi = wb;
-    while (lo < hi) {   // first line with nul - v > cut
-        const int64_t m = (lo + hi) >> 1;
-        if (!(nul[m] - v > cut)) lo = m + 1; else hi = m;
-    }
-    const int64_t j1 = lo;
-    const int64_t b0 = j0 / CS_PED_B, b1 = (max(j1, j0 + 1) - 1) / CS_PED_B;   // blocks of the first and the last line of the window
+    const PedRun w = ped_window(nul, wa, wb, v, cut);
     const int k0 = blockIdx.y * CS_PED_KC, k1 = min(k0 + CS_PED_KC, K);
     for (int k = k0; k < k1; k++) {
         const size_t o0 = (size_t)k * L;
-        const double *__restrict__ bk = bsum + (size_t)k * nqt;
-        double s = 0.0;
-        if (b0 == b1) {   // inside one block (or empty): the lines one by one
-            for (int64_t j = j0; j < j1; j++) s += p[o0 + j];
-        } else {          // suffix of the first block, whole blocks between, prefix of the last
-            s = suf[o0 + j0];
-            for (int64_t q = b0 + 1; q < b1; q++) s += bk[q];
-            s += pre[o0 + j1 - 1];
-        }
+        const double s = ped_sum(ws.p, ws.pre, ws.suf, ws.bsum + (size_t)k * ws.nqt, o0, w.j0, w.j1);
         const size_t o = (size_t)k * nnu + i;
         const double r = sigma[o] - s;
         sigma[o] = clamp ? fmax(r, 0.0) : r;
@@ -4227,10 +4306,9 @@ __global__ __launch_bounds__(256) void k_clamp0(int64_t n, double *__restrict__ 
 // sigma = R(nu, T) sum over included lines of C S~ [f_V(nu - nul) + f_V(nu + nul)],  S~ = S / R(nul, T),  R(x, T) = x tanh(c2 x / 2T).
 // The direct term is a code-0 line sum over records that carry S~ (prep_body<true>), written into its own plane src with base 0 (or into sigma
 // itself when the group is the column's first).  One thread per (point, state) then adds the mirror term of the lines [ma, mb) -- the
-// included lines with nul <= cut - nu_0, ascending -- with the inclusive test nu + nul <= cut, and multiplies by R(nu, T_k):
+// included lines with nul <= cut - nu_0, ascending -- and multiplies by R(nu, T_k):
 //   sigma[k][i] = (accumulate ? sigma[k][i] : base + extra[k][i]) + R(nu_i, T_k) (src[k][i] + mirror).
-// The mirror pair is A Re w((nu + nul) d, y) from the same records (cold.A, hot.p1 = d, cold.y) as the near-line kernels.  R is formed
-// as nu tanh(.), which is exact to rounding for small arguments (nu -> 0: sigma -> 0).  src may be sigma (no __restrict__ on either).
+// R is formed as nu tanh(.), which is exact to rounding for small arguments (nu -> 0: sigma -> 0).
 __global__ __launch_bounds__(256) void k_vvh_finish(const double *__restrict__ nu, int64_t nnu, const double *__restrict__ Tk,
                                                     const LineHot *__restrict__ hot, const LineCold *__restrict__ cold, int64_t L,
                                                     int64_t ma, int64_t mb, double cut, const double *src, double base,
@@ -4240,196 +4318,74 @@ __global__ __launch_bounds__(256) void k_vvh_finish(const double *__restrict__ n
     if (i >= nnu) return;
     const int k = blockIdx.y;
     const double v = nu[i];
-    const size_t o = (size_t)k * nnu + i;
-    double s = src[o];
-    for (int64_t j = ma; j < mb; j++) {
-        const size_t idx = (size_t)k * L + j;
-        const double x = v + hot[idx].nul;
-        if (x > cut) break;   // (ascending lines: so are all after it)
-        const LineCold c = cold[idx];
-        s += c.A * fad_re(x * hot[idx].p1, c.y);
-    }
+    const size_t o = (size_t)k * nnu + i, o0 = (size_t)k * L;
+    const double s = mirror_sum<false, false>(src[o], v, hot, cold, nullptr, nullptr, o0, ma, mb, cut, cut);
     const double r = radiation_term(v, Tk[k]) * s;
-    sigma[o] = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
+    finish_store(sigma, o, accumulate, base, extra, r, 0);
 }
 
-// ---- pedestal-removed Van Vleck-Huber Voigt (shape code 6, CS_SHAPE_VOIGT_CKD_VVH) --------------------------------------------
+// ---- pedestal-removed Van Vleck-Huber Voigt (shape code 6, CS_SHAPE_VOIGT_CKD_VVH: SHIFT = false) ------------------------------
 // sigma = max(0, R(nu, T) sum over included lines of C S~ [(f_V(nu - nul) - f_V(cut)) 1{|nu - nul| <= cut}
 //                                                        + (f_V(nu + nul) - f_V(cut)) 1{nu + nul <= cut}]).
 // The direct Voigt part is code 5's line sum over S~ records, in src with base 0; k_ped_values then writes p[k][l] = C S~ f_V(cut) and its
 // in-block sums from those same records.  One thread per (point, CS_PED_KC states) finishes the plane in ONE pass: it finds the point's
-// direct window [j0, j1) as k_ped_sub does (once for its states) and subtracts its pedestals the same way (in-block suffix, whole blocks,
-// in-block prefix: never a difference of prefix sums), adds the mirror pairs A Re w((nu + nul) d, y) - p of the lines [ma, mb) as
-// k_vvh_finish does (inclusive test nu + nul <= cut), multiplies by R(nu, T_k) and writes
+// direct window once for its states, subtracts its pedestals, adds the mirror pairs minus p of the lines [ma, mb), multiplies by
+// R(nu, T_k) and writes
 //   sigma[k][i] = (accumulate ? sigma[k][i] : base + extra[k][i]) + r,   r = R (src - direct pedestals + mirror),  max(0, .) if clamp.
-// [ma, mb) lies inside [a, b), so every p it reads was written.  src may be sigma (no __restrict__ on either).
-// Blocks: the first tm tiles (those whose points can reach a mirror line) one state per block, tile-major, so that their loops over the
-// mirror lines run side by side and first; every other tile CS_PED_KC states per block.
-__global__ __launch_bounds__(256) void k_vvh_ped_finish(const double *__restrict__ nu, int64_t nnu, const double *__restrict__ Tk,
-                                                        const double *__restrict__ nul, const LineHot *__restrict__ hot,
-                                                        const LineCold *__restrict__ cold, int64_t L, int64_t a, int64_t b, int64_t ma,
-                                                        int64_t mb, const int32_t *__restrict__ tJ0, const int32_t *__restrict__ tJ1,
-                                                        double cut, int K, const double *__restrict__ p, const double *__restrict__ pre,
-                                                        const double *__restrict__ suf, const double *__restrict__ bsum, int64_t nqt,
-                                                        const double *src, double base, const double *__restrict__ extra, double *sigma,
-                                                        int accumulate, int clamp, int tm)
-{
-    const unsigned nm = (unsigned)tm * (unsigned)K, ng = (unsigned)(K + CS_PED_KC - 1) / CS_PED_KC;
-    unsigned t;
-    int k0, k1;
-    if (blockIdx.x < nm) {
-        t = blockIdx.x / (unsigned)K;
-        k0 = (int)(blockIdx.x - t * (unsigned)K);
-        k1 = k0 + 1;
-    } else {
-        const unsigned r = blockIdx.x - nm;
-        t = (unsigned)tm + r / ng;
-        k0 = (int)(r % ng) * CS_PED_KC;
-        k1 = min(k0 + CS_PED_KC, K);
-    }
-    const int64_t i = (int64_t)t * 256 + threadIdx.x;
-    if (i >= nnu) return;
-    const double v = nu[i];
-    const int64_t wa = max(a, (int64_t)tJ0[t]), wb = max(wa, min(b, (int64_t)tJ1[t]));
-    int64_t lo = wa, hi = wb;
-    while (lo < hi) {   // first line with v - nul <= cut
-        const int64_t m = (lo + hi) >> 1;
-        if (v - nul[m] > cut) lo = m + 1; else hi = m;
-    }
-    const int64_t j0 = lo;
-    hi = wb;
-    while (lo < hi) {   // first line with nul - v > cut
-        const int64_t m = (lo + hi) >> 1;
-        if (!(nul[m] - v > cut)) lo = m + 1; else hi = m;
-    }
-    const int64_t j1 = lo;
-    const int64_t b0 = j0 / CS_PED_B, b1 = (max(j1, j0 + 1) - 1) / CS_PED_B;
-    for (int k = k0; k < k1; k++) {
-        const size_t o0 = (size_t)k * L;
-        const double *__restrict__ bk = bsum + (size_t)k * nqt;
-        double ps = 0.0;
-        if (b0 == b1) {
-            for (int64_t j = j0; j < j1; j++) ps += p[o0 + j];
-        } else {
-            ps = suf[o0 + j0];
-            for (int64_t q = b0 + 1; q < b1; q++) ps += bk[q];
-            ps += pre[o0 + j1 - 1];
-        }
-        const size_t o = (size_t)k * nnu + i;
-        double s = src[o] - ps;
-        for (int64_t j = ma; j < mb; j++) {
-            const size_t idx = o0 + j;
-            const double x = v + hot[idx].nul;
-            if (x > cut) break;   // (ascending lines: so are all after it)
-            const LineCold c = cold[idx];
-            s += c.A * fad_re(x * hot[idx].p1, c.y) - p[idx];
-        }
-        const double r = radiation_term(v, Tk[k]) * s;
-        const double out = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
-        sigma[o] = clamp ? fmax(out, 0.0) : out;
-    }
-}
-
-// ---- LBLRTM's line calculation at pressure-shifted centres (shape code 7, CS_SHAPE_VOIGT_LBL) ---------------------------------
+// [ma, mb) lies inside [a, b), so every p it reads was written.
+//
+// ---- LBLRTM's line calculation at pressure-shifted centres (shape code 7, CS_SHAPE_VOIGT_LBL: SHIFT = true) -------------------
 // Code 6 with every centre at c[k][l] = nul + delta_l P_k / P0 (prep_body<true> with pa.pshift: the S~ records sit at the shifted centres,
 // parked at kParked with A = 0 where the state's strict pre-filter leaves the line out; S~, alpha, gamma stay those of nul):
 //   sigma = max(0, R(nu, T) sum_l S~_l [(f_l(nu - c_l) - f_l(cut)) 1{|nu - c_l| <= cut} + (f_l(nu + c_l) - f_l(cut)) 1{nu + c_l <= cut}]).
 // k_ped_values is the same (p = A Re w(cut d, y) does not depend on the centre; a parked line has p = 0).  What moves is who is inside:
 // the direct window of a (point, state) is no run of the table, since c moves with P_k and neighbours with shifts of opposite sign
 // swap places.  With ds >= every |c - nul| of the group (the host's shift_width plus a rounding margin), the thread finds ONCE for its
-// states four table positions jA <= jB <= jC <= jD:
-//   [jB, jC)   nul in [nu - cut + ds, nu + cut - ds]: inside at every state; their pedestals are summed as k_vvh_ped_finish sums its window
-//              (in-block suffix, whole blocks, in-block prefix: never a difference of prefix sums)
+// states two runs of table positions, [jA, jD) within cut + ds and inside it [jB, jC) within cut - ds:
+//   [jB, jC)   nul in [nu - cut + ds, nu + cut - ds]: inside at every state; their pedestals are one run's sum, as code 6's window
 //   [jA, jB), [jC, jD)   nul within ds of an edge: tested one by one, per state, with the record's centre and the line kernels' own test
 //              !(|nu - c| > cut)
-// (cut < ds: no certain lines, [jA, jD) is all fringe.)  The mirror lines [ma, mb) -- the included lines with nul <= cut - nu_0 + ds -- are
-// not ascending in c either: every one is tested with nu + c <= cut, and no centre ends the loop; it ends at the first TABLE position with
-// nu + nul > cut + ds, beyond which no centre can pass (on tiles far from the mirror lines: at once).  A parked record fails both tests
-// (and would add p = 0).  Output, src and the block layout (tm mirror tiles, one state per block) as k_vvh_ped_finish.
-__global__ __launch_bounds__(256) void k_vvh_ped_finish_shift(const double *__restrict__ nu, int64_t nnu, const double *__restrict__ Tk,
-                                                              const double *__restrict__ nul, const LineHot *__restrict__ hot,
-                                                              const LineCold *__restrict__ cold, int64_t L, int64_t a, int64_t b, int64_t ma,
-                                                              int64_t mb, const int32_t *__restrict__ tJ0, const int32_t *__restrict__ tJ1,
-                                                              double cut, double ds, int K, const double *__restrict__ p,
-                                                              const double *__restrict__ pre, const double *__restrict__ suf,
-                                                              const double *__restrict__ bsum, int64_t nqt, const double *src, double base,
-                                                              const double *__restrict__ extra, double *sigma, int accumulate, int clamp, int tm)
+// (cut < ds: no certain lines, [jA, jD) is all fringe.)  The mirror lines [ma, mb) are the included lines with nul <= cut - nu_0 + ds.
+// A parked record fails the fringe test (and would add p = 0).  ds is not read where !SHIFT.
+template <bool SHIFT>
+__global__ __launch_bounds__(256) void k_vvh_ped_finish(const double *__restrict__ nu, int64_t nnu, const double *__restrict__ Tk,
+                                                        const double *__restrict__ nul, const LineHot *__restrict__ hot,
+                                                        const LineCold *__restrict__ cold, int64_t L, int64_t a, int64_t b, int64_t ma,
+                                                        int64_t mb, const int32_t *__restrict__ tJ0, const int32_t *__restrict__ tJ1,
+                                                        double cut, double ds, int K, PedWs ws, const double *src, double base,
+                                                        const double *__restrict__ extra, double *sigma, int accumulate, int clamp, int tm)
 {
-    const unsigned nm = (unsigned)tm * (unsigned)K, ng = (unsigned)(K + CS_PED_KC - 1) / CS_PED_KC;
-    unsigned t;
-    int k0, k1;
-    if (blockIdx.x < nm) {
-        t = blockIdx.x / (unsigned)K;
-        k0 = (int)(blockIdx.x - t * (unsigned)K);
-        k1 = k0 + 1;
-    } else {
-        const unsigned r = blockIdx.x - nm;
-        t = (unsigned)tm + r / ng;
-        k0 = (int)(r % ng) * CS_PED_KC;
-        k1 = min(k0 + CS_PED_KC, K);
-    }
-    const int64_t i = (int64_t)t * 256 + threadIdx.x;
+    // the workspace is never the plane: a record's members cannot say __restrict__, and without this the mirror loop's wave-uniform p[j]
+    // becomes a vector load behind every store to sigma
+    __builtin_assume_separate_storage(ws.p, sigma);
+    const FinishBlock B = finish_block(blockIdx.x, tm, K);
+    const int64_t i = (int64_t)B.t * 256 + threadIdx.x;
     if (i >= nnu) return;
     const double v = nu[i];
-    const int64_t wa = max(a, (int64_t)tJ0[t]), wb = max(wa, min(b, (int64_t)tJ1[t]));
-    const double out_d = cut + ds, in_d = cut - ds;   // a line's table position: beyond out_d certainly outside, within in_d certainly inside
-    int64_t lo = wa, hi = wb;
-    while (lo < hi) {   // first line with v - nul <= cut + ds
-        const int64_t m = (lo + hi) >> 1;
-        if (v - nul[m] > out_d) lo = m + 1; else hi = m;
+    const int64_t wa = max(a, (int64_t)tJ0[B.t]), wb = max(wa, min(b, (int64_t)tJ1[B.t]));
+    // a line's table position: beyond out_d certainly outside, within in_d certainly inside
+    const double out_d = SHIFT ? cut + ds : cut, in_d = cut - ds;
+    const PedRun w = ped_window(nul, wa, wb, v, out_d);   // [jA, jD); !SHIFT: the window itself
+    PedRun c = w;                                         // [jB, jC)
+    if constexpr (SHIFT) {
+        c.j1 = c.j0;   // (cut < ds: nothing is certain)
+        if (in_d >= 0.0) c = ped_window(nul, w.j0, w.j1, v, in_d);
     }
-    const int64_t jA = lo;
-    hi = wb;
-    while (lo < hi) {   // first line with nul - v > cut + ds
-        const int64_t m = (lo + hi) >> 1;
-        if (!(nul[m] - v > out_d)) lo = m + 1; else hi = m;
-    }
-    const int64_t jD = lo;
-    int64_t jB = jA, jC = jA;   // (cut < ds: nothing is certain)
-    if (in_d >= 0.0) {
-        lo = jA; hi = jD;
-        while (lo < hi) {   // first line with v - nul <= cut - ds
-            const int64_t m = (lo + hi) >> 1;
-            if (!(v - nul[m] <= in_d)) lo = m + 1; else hi = m;
-        }
-        jB = lo;
-        hi = jD;
-        while (lo < hi) {   // first line with nul - v > cut - ds
-            const int64_t m = (lo + hi) >> 1;
-            if (nul[m] - v <= in_d) lo = m + 1; else hi = m;
-        }
-        jC = lo;
-    }
-    const int64_t b0 = jB / CS_PED_B, b1 = (max(jC, jB + 1) - 1) / CS_PED_B;
-    for (int k = k0; k < k1; k++) {
+    for (int k = B.k0; k < B.k1; k++) {
         const size_t o0 = (size_t)k * L;
-        const double *__restrict__ bk = bsum + (size_t)k * nqt;
-        double ps = 0.0;
-        if (b0 == b1) {
-            for (int64_t j = jB; j < jC; j++) ps += p[o0 + j];
-        } else {
-            ps = suf[o0 + jB];
-            for (int64_t q = b0 + 1; q < b1; q++) ps += bk[q];
-            ps += pre[o0 + jC - 1];
+        double ps = ped_sum(ws.p, ws.pre, ws.suf, ws.bsum + (size_t)k * ws.nqt, o0, c.j0, c.j1);
+        if constexpr (SHIFT) {
+            for (int64_t j = w.j0; j < c.j0; j++)   // the lower fringe, by the state's own centres
+                if (!(fabs(v - hot[o0 + j].nul) > cut)) ps += ws.p[o0 + j];
+            for (int64_t j = c.j1; j < w.j1; j++)   // the upper fringe
+                if (!(fabs(v - hot[o0 + j].nul) > cut)) ps += ws.p[o0 + j];
         }
-        for (int64_t j = jA; j < jB; j++)   // the lower fringe, by the state's own centres
-            if (!(fabs(v - hot[o0 + j].nul) > cut)) ps += p[o0 + j];
-        for (int64_t j = jC; j < jD; j++)   // the upper fringe
-            if (!(fabs(v - hot[o0 + j].nul) > cut)) ps += p[o0 + j];
         const size_t o = (size_t)k * nnu + i;
-        double s = src[o] - ps;
-        for (int64_t j = ma; j < mb; j++) {
-            if (v + nul[j] > out_d) break;   // (TABLE positions ascend and c >= nul - ds: no later line can pass the test below)
-            const size_t idx = o0 + j;
-            const double x = v + hot[idx].nul;
-            if (x > cut) continue;   // (the centres are not ascending: no line's centre ends the loop)
-            const LineCold c = cold[idx];
-            s += c.A * fad_re(x * hot[idx].p1, c.y) - p[idx];
-        }
+        const double s = mirror_sum<SHIFT, true>(src[o] - ps, v, hot, cold, ws.p, nul, o0, ma, mb, cut, out_d);
         const double r = radiation_term(v, Tk[k]) * s;
-        const double out = (accumulate ? sigma[o] : base + (extra ? extra[o] : 0.0)) + r;
-        sigma[o] = clamp ? fmax(out, 0.0) : out;
+        finish_store(sigma, o, accumulate, base, extra, r, clamp);
     }
 }
 
 }  // namespace csdev
+

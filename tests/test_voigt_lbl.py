@@ -160,6 +160,18 @@ def test_premises_of_the_device_cases(cs, O, case):
                 n25 = int(np.sum(d != d0) + np.sum(m != m0))
     assert all(v >= 1 for v in count.values()), count
     assert sum(count.values()) >= 20 and n25 >= 20, (count, n25)
+    # cut = 0.25, below the largest shift (0.375): no table position is certainly inside, every candidate is fringe.  Pairs inside by
+    # shifted centre but outside by table position, and the other way round, on both grids over the nine states (no mirror pair: both
+    # grids start at or above 0.5)
+    assert 0.25 < np.max(np.abs(da)) * max(P) / KATM
+    for grid in (V.GRID, V.EDGE_GRID):
+        V.dyadic_premise(nul, grid, da, P)
+        n_in = n_out = 0
+        for k in range(len(P)):
+            d, m, d0, m0 = V.membership(nul, da, grid, P[k], 0.25)
+            n_in += int(np.sum(d & ~d0)); n_out += int(np.sum(~d & d0))
+            assert not m.any() and not m0.any()
+        assert n_in > 0 and n_out > 0, (n_in, n_out)
     # an adjacent pair in shifted order reversed at the highest pressure, not at the lowest
     c_hi, c_lo = nul + da * max(P) / KATM, nul + da * min(P) / KATM
     assert np.any((np.diff(c_hi) < 0) & (np.diff(c_lo) > 0))

@@ -6,8 +6,9 @@ Cases (the C3 column: 1e5 nu x 60 layers, synthetic H2O + CO2 tables, Discretize
   voigt_nomerge  the same with merging off: two launch groups
   voigtVVH       H2O as code 5, CO2 as code 0: two groups (code 5 is never merged with code 0)
   voigtCKDVVH    H2O as code 6, CO2 as code 0: two groups (code 6 is never merged with code 0)
+  voigtCKD       H2O as code 4, CO2 as code 0: two groups (code 4 is never merged with code 0); the case of profiles/voigt_ckd_cost.json
 for the whole grid and its 4th 1/8 nu-shard, the median of `steps` steps after 5 warm-up steps (host wall clock around run + sync), the
-four cases' steps interleaved so that clock drift falls on all of them alike; and a 12 x 24 bake of the H2O table on the C3 grid as codes 0, 5 and 6."""
+cases' steps interleaved so that clock drift falls on all of them alike; and a 12 x 24 bake of the H2O table on the C3 grid as codes 0, 5 and 6."""
 import argparse
 import json
 import os
@@ -22,7 +23,7 @@ import clearsky_jl_amd as cs   # noqa: E402
 import workloads as W          # noqa: E402
 
 CASES = {"voigt": ("voigt", True), "voigt_nomerge": ("voigt", False), "voigtVVH": ("voigtVVH", True),
-         "voigtCKDVVH": ("voigtCKDVVH", True)}
+         "voigtCKDVVH": ("voigtCKDVVH", True), "voigtCKD": ("voigtCKD", True)}
 
 
 def column(cfg, shape, merge, nu_range=None):
