@@ -331,8 +331,8 @@ struct Column {
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int runs_since_change = 0;
-    bool graph_near_live = false, graph_sigma_partial = false;   // what the captured run left in near_live / sigma_partial / launches: a replay leaves the same
-    int graph_launches = 0;
+    bool graph_near_live = false, graph_sigma_partial = false;   // what the captured run left in near_live / sigma_partial / launches / log_last: a
+    int graph_launches = 0;                                      // replay leaves the same (cs_column_batch writes its own dispatch into log_last)
     uint64_t graph_ph_builds = 0;   // PhScratch::builds when the step was captured
     std::vector<ColTab> tab;
     std::vector<ColCia> cia;
@@ -342,10 +342,13 @@ struct Column {
     DevBuf hot, cold, sigma, sigma2, tau, Mup, Mdn, partial, F, stage, ranges;   // sigma2: the near-line plane (k_voigt_near on a side stream)
     DevBuf ped;                // launch_pedestal's workspace for K states (columns with a code-4 group)
     DevBuf vvh;                // the line sum of a code-5 group that is not the column's first, before launch_vvh (K x nnu)
+    DevBuf hot32;              // fp32 line records of mixed precision for K states (sigma_impl sizes them): the column's own, as hot and cold are --
+                               // a captured step names them, so no other entry point may move them (batches and shape calls bring their own)
     DevBuf fluxdbg;            // k_flux_scan: phase time stamps of block 0 (CS_T15_SCAN_STAMPS; cs_column_work CS_WORK_FLUX_SCAN_NS ..)
     DevBuf ticket;             // k_flux: blocks finished (the last one adds the block partials up)
     int flux_form_last = 0;      // which flux kernel the last run used (flux_form)
     StepLog log_last;            // of the last cs_column_run (cs_column_info out[6], out[7]); its disp also of the last cs_column_batch
+    StepLog graph_log;           // log_last of the captured run
     bool sigma_partial = false;  // the last run finished the cross-sections on chip (k_flux): cs_column_sigma_fetch evaluates them again, in HBM
     ChebGrid cheb;             // interpolation levels of the nu grid (nlev = 0: off)
     DevBuf chebF;              // node sums F [nItot][64][Kpad], summed over the column's gases (k_cheb_nodes accumulates)
@@ -534,7 +537,7 @@ struct PhScratch {
     PhKey key;                 // what lev, nodes and Cm were laid out for: set only once every buffer of the levels is held, cleared when
     PhLevelSet lev;            // a build is refused, so that equal keys always mean built tables (phco2_plan then takes lev from here)
     DevBuf nodes, Cm[CS_MAX_ALEVEL];
-    uint64_t builds = 0;       // how often ph_prepare has (re)built the levels: a captured step holds the layout of one build
+    uint64_t builds = 0;       // how often ph_prepare has (re)built the levels or moved fac .. zones3: a captured step holds the layout of one build
     struct Dens { const void *tab; uint64_t gen, grid; bool ok; };
     std::vector<Dens> dens;    // check_near_density() per (table, generation, grid), a few kept (phco2_plan is the only reader)
 };
@@ -586,8 +589,7 @@ struct cs_ctx {
     std::vector<std::shared_ptr<GasTable>> merged;   // merged tables (keyed by their members' (slot, generation)), least recently used first
     double far_s = 1e6;
     DevBuf reinterp;        // [64][32] then [64][16]: values at the 64 nodes of an interval from those at its 32 / 16 nodes (build_reinterp)
-    DevBuf hot32;
-    DevBuf tmpA, tmpB, tmpC;
+    DevBuf tmpA, tmpB, tmpC;   // cs_table_eval, cs_accel_eval, cs_devfn_batch: no step of the column names them
 };
 static PhRules ph_rules(const cs_ctx &ctx)
 {
@@ -1796,6 +1798,17 @@ static void ph_prepare(const GasPass &p, PhPlan &pl)
     PhScratch &ph = *p.ph;
     const int kn = p.kn;
     if (!pl.fast) return;
+    // a buffer that grows moves, and a captured step of the resident column names the old address (fac, win, win3 and zones3 grow with
+    // the states, lines and tiles of any PHCO2 pass, with or without levels): counted like a rebuild, which drops that step's graph
+    const void *const held[] = {ph.fac.p, ph.win.p, ph.piw.p, ph.F.p, ph.win3.p, ph.zones3.p};
+    struct Moved {
+        PhScratch &ph; const void *const *held;
+        ~Moved()
+        {
+            const void *const now[] = {ph.fac.p, ph.win.p, ph.piw.p, ph.F.p, ph.win3.p, ph.zones3.p};
+            for (int i = 0; i < 6; i++) if (held[i] && now[i] != held[i]) { ph.builds++; break; }
+        }
+    } moved{ph, held};
     if (ph.fac.reserve((size_t)6 * kn * p.G->L * sizeof(double)) != hipSuccess || ph.win.reserve((size_t)pl.nt64 * sizeof(PhWin)) != hipSuccess) {
         pl = PhPlan();
         return;
@@ -2570,14 +2583,14 @@ static int gas_states(cs_ctx *ctx, GasTable &G, const ShapeSpec &sh, double dnu_
     GroupStates st;        // (one member, the caller's Pp: no concentration plane)
     const GasTable *mem = &G;
     if ((rc = build_windows(w, G, sh, dnu_cut, ds, nu, nnu, strict, s)) || (rc = upload_group_states(s, st, G, &mem, 1, K, T, P, Pp))) return rc;
-    DevBuf dnu, dT, dP, hot, cold, dsig, dzones, dranges, dped;
+    DevBuf dnu, dT, dP, hot, cold, hot32, dsig, dzones, dranges, dped;
     if ((rc = upload(dnu, nu, nnu, s)) || (rc = upload(dT, T, K, s)) || (rc = upload(dP, P, K, s))) return rc;
     // bound the workspace: process the states in chunks
     const size_t per_state = (size_t)G.L * (sizeof(LineHot) + sizeof(LineCold)) +
                              (Z ? (size_t)nnu * kNearPointBytes : (size_t)nnu * (sizeof(double) + kNearPointBytes)) + (ped ? ped_bytes(1, G.L) : 0);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)K, ((size_t)4 << 30) / per_state, (size_t)65535}));   // gridDim.y limit
     const bool mixed = ctx->mixed && shape == SH_VOIGT && !sh.pshift;
-    if ((rc = reserve_lines(kc, G.L, nnu, hot, cold, &dranges, mixed ? &ctx->hot32 : nullptr, ped ? &dped : nullptr, nullptr))) return rc;
+    if ((rc = reserve_lines(kc, G.L, nnu, hot, cold, &dranges, mixed ? &hot32 : nullptr, ped ? &dped : nullptr, nullptr))) return rc;
     if (!Z) HIPCHK(dsig.reserve((size_t)kc * nnu * sizeof(double)));
     HIPCHK(dzones.reserve((size_t)kc * w.nwin * sizeof(Zone)));
     GasPass p;
@@ -2587,7 +2600,7 @@ static int gas_states(cs_ctx *ctx, GasTable &G, const ShapeSpec &sh, double dnu_
     p.pshift = sh.pshift; p.flo = strict ? nu[0] - dnu_cut : -INFINITY; p.fhi = strict ? nu[nnu - 1] + dnu_cut : INFINITY;
     p.dnu = dnu.as<double>(); p.nu = nu; p.nnu = nnu;
     p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<unsigned>(); p.ped_ws = dped.as<double>();
-    if (mixed) p.hot32 = ctx->hot32.as<LineF32>();
+    if (mixed) p.hot32 = hot32.as<LineF32>();
     p.clamp = true;   // the gas's own sigma, complete
     p.far_s = ctx->far_s; p.ph = &ctx->ph;
     ChebGrid cheb;
@@ -3180,6 +3193,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     c.merge = ctx->merge;
     c.grid_id = ++g_grid_counter;
     c.cheb.nlev = 0;
+    c.cheb.nItot = 0;    // (cs_column_work reports it: no intervals of the column this one replaces)
     if (ctx->interp) {   // interval sizes from the narrowest Voigt cut-off of the column
         double cmin = 0.0;
         for (int gi = 0; gi < ngas; gi++) {
@@ -3265,7 +3279,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
             HIPCHK(hipMemsetAsync(c.chebF.p, 0, c.chebF.bytes, s));   // padding states stay finite
         }
     }
-    // (the fp32 records of mixed precision are the context's, sized when a step first needs them: sigma_impl; the spare plane: a second code-5 group)
+    // (the fp32 records of mixed precision are sized when a step first needs them: sigma_impl; the spare plane: a second code-5 group)
     if ((rc = reserve_lines(K, c.maxL, nnu, c.hot, c.cold, ngas > 0 ? &c.ranges : nullptr, nullptr, c.any_ped ? &c.ped : nullptr,
                             c.gas.size() > 1 && c.gas[1].vvh ? &c.vvh : nullptr)))
         return rc;
@@ -3339,15 +3353,16 @@ int cs_column_update_state(cs_ctx *ctx, const double *T_nodes, const double *mu_
 }
 
 // what a launch group of the resident column fixes at setup: its table, record range and shape, the grid and its windows, and how the
-// context runs it; the callers add the states, the workspace and the output (one state set of the column | a chunk of a batch)
-static GasPass column_pass(cs_ctx *ctx, const ColGas &cg)
+// context runs it; the callers add the states, the workspace and the output (one state set of the column | a chunk of a batch).
+// hot32: the caller's fp32 records (the column's own | the batch's), used under mixed precision
+static GasPass column_pass(cs_ctx *ctx, const ColGas &cg, const DevBuf &hot32)
 {
     const Column &c = ctx->col;
     GasPass p;
     p.G = cg.tab; p.shape = cg.shape; p.cut = cg.cut; p.ped = cg.ped; p.vvh = cg.vvh; p.pshift = cg.pshift;
     pass_windows(p, cg.w);
     p.dnu = c.nu.as<double>(); p.nu = c.h_nu.data(); p.nnu = c.nnu;
-    p.hot32 = (ctx->mixed && cg.shape == SH_VOIGT) ? ctx->hot32.as<LineF32>() : nullptr;
+    p.hot32 = (ctx->mixed && cg.shape == SH_VOIGT) ? hot32.as<LineF32>() : nullptr;
     p.base = c.sigma_gray;   // (clamp stays off: the column's sigma is complete only after its last absorber)
     p.far_s = ctx->far_s; p.ph = &ctx->ph;
     return p;
@@ -3378,7 +3393,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     const double *extra = c.has_extra ? c.extra.as<double>() : nullptr;
     if (extra) return fail(CS_EINVAL, "host-evaluated sigma(nu,T,P) terms are not supported in batch mode");
     const bool shared_sigma = c.accel.slot >= 0;   // AcceleratedAbsorber: cross-sections do not depend on the thermal state (absorbers.jl:203)
-    DevBuf dped, dvvh, dTk, dPk, dmuk, dTlev, dsig, dtau, dpart, dF, dranges, dzones, dizones, dF2, dsep, dedge, hot, cold;
+    DevBuf dped, dvvh, dTk, dPk, dmuk, dTlev, dsig, dtau, dpart, dF, dranges, dzones, dizones, dF2, dsep, dedge, hot, cold, hot32;
     GroupStates st;   // of one group at all B K states: the next group's take their place
     if ((rc = upload(dTk, Tk.data(), BK, s)) || (rc = upload(dPk, Pk.data(), BK, s)) || (rc = upload(dmuk, muk.data(), BK, s)) ||
         (rc = upload(dTlev, T_levels, (size_t)B * np, s)))
@@ -3402,7 +3417,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     const size_t per_state = maxL * (sizeof(LineHot) + sizeof(LineCold) + (ctx->mixed ? sizeof(LineF32) : 0)) + (size_t)c.nnu * kNearPointBytes +
                              (any_ped ? ped_bytes(1, (int64_t)maxL) : 0) + (vvh2 ? (size_t)c.nnu * sizeof(double) : 0);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)BK, ((size_t)8 << 30) / std::max<size_t>(per_state, 1), (size_t)65535}));
-    if (c.ngas > 0 && (rc = reserve_lines(kc, maxL, c.nnu, hot, cold, &dranges, ctx->mixed ? &ctx->hot32 : nullptr, any_ped ? &dped : nullptr,
+    if (c.ngas > 0 && (rc = reserve_lines(kc, maxL, c.nnu, hot, cold, &dranges, ctx->mixed ? &hot32 : nullptr, any_ped ? &dped : nullptr,
                                           vvh2 ? &dvvh : nullptr)))
         return rc;
     if (c.has_phco2) ph_set_grid(ctx, c.h_nu.data(), c.nnu, c.grid_id);
@@ -3411,7 +3426,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
         const size_t nt64 = (size_t)((c.nnu + 63) / 64);
         if ((rc = column_group_states(ctx, cg, st, BK, Tk.data(), Pk.data(), conc, s))) return rc;
         HIPCHK(dzones.reserve((size_t)kc * nt64 * sizeof(Zone)));
-        GasPass p = column_pass(ctx, cg);
+        GasPass p = column_pass(ctx, cg, hot32);
         p.mstride = (int)BK;
         p.hot = hot.as<LineHot>(); p.cold = cold.as<LineCold>(); p.zones = dzones.as<Zone>(); p.ranges = dranges.as<unsigned>(); p.ped_ws = dped.as<double>();
         p.accumulate = qi > 0; p.spare = dvvh.as<double>();   // (a second code-5/6 group: its bare line sum goes there first)
@@ -3519,7 +3534,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
         const int64_t tot = (int64_t)K * c.nnu;
         CS_LAUNCH(k_fill, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, c.sigma_gray, extra, sig);
     }
-    if (ctx->mixed) HIPCHK(ctx->hot32.reserve(((size_t)K * c.maxL + 4) * sizeof(LineF32)));   // no-op once sized (not capturable the first time)
+    if (ctx->mixed) HIPCHK(c.hot32.reserve(((size_t)K * c.maxL + 4) * sizeof(LineF32)));   // no-op once sized (not capturable the first time)
     ChebApply apply;
     apply.ngas = 0;
     if (c.has_phco2) ph_set_grid(ctx, c.h_nu.data(), c.nnu, c.grid_id);
@@ -3540,7 +3555,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
     const bool use_fork = fk.use_nodes || fk.use_near;
     for (int gi = 0; gi < (int)c.gas.size(); gi++) {
         ColGas &cg = c.gas[gi];
-        GasPass p = column_pass(ctx, cg);
+        GasPass p = column_pass(ctx, cg, c.hot32);
         p.kn = K;
         p.Tk = c.Tk.as<double>(); p.Pk = c.Pk.as<double>(); p.scale = cg.st.conc.as<double>(); p.mstride = K;
         pass_states(p, cg.st, 0);
@@ -3647,6 +3662,11 @@ static int column_current(cs_ctx *ctx)
             return fail(CS_ESTATE, "opacity-table slot %d was baked, uploaded or cleared after cs_column_set_tables: call it again", ct.slot);
     if (c.accel.slot >= 0 && (!ctx->accel[c.accel.slot].present || ctx->accel[c.accel.slot].generation != c.accel.generation))
         return fail(CS_ESTATE, "accelerated-absorber slot %d got other knots (or was cleared) after cs_column_set_accel: call it again", c.accel.slot);
+    // ... and for the CIA pairs: their band descriptors hold the addresses of the slot's tables as cs_column_set_cia found them, and
+    // cs_cia_begin / cs_cia_clear free those
+    for (auto &cc : c.cia)
+        if (!ctx->cia[cc.slot].present || ctx->cia[cc.slot].generation != cc.generation)
+            return fail(CS_ESTATE, "CIA slot %d got other bands (or was cleared) after cs_column_set_cia: call it again", cc.slot);
     return CS_OK;
 }
 
@@ -3732,6 +3752,7 @@ int cs_column_run(cs_ctx *ctx, void *stream)
         c.near_live = c.graph_near_live;
         c.sigma_partial = c.graph_sigma_partial;
         c.launches = c.graph_launches;
+        c.log_last = c.graph_log;
         c.last_stream = s;
         return CS_OK;
     }
@@ -3750,6 +3771,7 @@ int cs_column_run(cs_ctx *ctx, void *stream)
     c.graph_near_live = c.near_live;   // (set by the captured run_impl)
     c.graph_sigma_partial = c.sigma_partial;
     c.graph_launches = c.launches;
+    c.graph_log = c.log_last;
     c.graph_ph_builds = ctx->ph.builds;
     if (hipGraphInstantiate(&c.graph_exec, g, nullptr, nullptr, 0) != hipSuccess) { c.graph_exec = nullptr; drop_graph(c); return run_impl(ctx, s, nullptr); }
     HIPCHK(hipGraphLaunch(c.graph_exec, s));

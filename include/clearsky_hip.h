@@ -321,7 +321,8 @@ int cs_column_set_tables(cs_ctx *ctx, int ntab, const int *table_slots, const do
  * (= P*concentration(g, T, P), :378-382); flags[c] = CS_CIA_EXTRAPOLATE (bit 0) | CS_CIA_SINGLES (bit 1) (:163) | CS_CIA_RADIATION
  * (bit 2: sigma += R(nu_i, T_k) (sum over bands of exp(ln k_b)) Lo^2 rho1 rho2 / rhoa with R(nu, T) = nu tanh(c2 nu / 2T) and ln k =
  * ln(C / n_ref) in cm^5 molecule^-2 per cm^-1, see cs_cia_begin); any other bit is CS_EINVAL.  Called again after
- * cs_column_update_state it re-forms the per-node inputs, R's temperatures among them. */
+ * cs_column_update_state it re-forms the per-node inputs, R's temperatures among them.  A slot refilled (cs_cia_begin / cs_cia_band) or
+ * cleared afterwards leaves the column's pairs stale: its next run or batch is CS_ESTATE until this is called again. */
 int cs_column_set_cia(cs_ctx *ctx, int ncia, const int *cia_slots, const int *flags, const double *P1, const double *P2);
 int cs_column_run(cs_ctx *ctx, void *stream);
 /* only the cross-section stage of cs_column_run: sigma[K][nnu] = Sigma(absorbers, i, T_k, P_k) for every wavenumber and node

@@ -52,6 +52,7 @@ import numpy as np
 import pytest
 
 import ckdvvh_ref as X
+import voigt_lbl_ref as V
 import workloads as W
 from conftest import HITRAN, relerr
 
@@ -141,6 +142,8 @@ def special_sigma(cs, O, spec, col, gi, x):
             import test_gpu_pressure_shift as PS
             v = PS.expected(O, g.sl, g.sl.delta_a, g.shape, x, Tk, Pk, Ck * Pk, False, g.dnu_cut)
             m = v
+        elif code == 7:
+            v, m = V.expected(cs, O, g.sl, g.sl.delta_a, x, Tk, Pk, Ck * Pk, g.dnu_cut, False)
         else:
             v, m = X.expected(cs, O, g.sl, x, Tk, Pk, Ck * Pk, g.dnu_cut, strict=False, ped=code in (4, 6), vvh=code in (5, 6))
         val[k], mag[k] = Ck * v, Ck * np.abs(m)
@@ -184,7 +187,7 @@ def sample(n):
     return np.arange(n) if n <= 3000 else np.sort(np.random.default_rng(n).choice(n, 300, replace=False))
 
 
-def vs_oracle(cs, O, spec, col, r, worst):
+def vs_oracle(cs, O, spec, col, r, worst, reference=reference):
     n = col.nnu
     idx = sample(n)
     ref, scale = reference(cs, O, spec, col, idx)
