@@ -75,6 +75,10 @@ the exact profile with rcp_nr1 (2e-15), already inside c0 of the hard bound -- a
 so code 1 is held to the hard bound alone (about 4e-15; recorded ratio 0.94).  Sharp bounds of the Voigt codes: 2.8e-14 to 4.7e-14, up to
 9e-14 at a margin of 15 per cent, against the hard 2e-13; below s = 1e3: 5e-15 to 4.5e-14.
 
+Code 7 ("col/low-lbl": the low line of "col/low-ckdvvh" with a shift, read from a .par file) takes code 6's sharp bound with the centre
+term of lineparam_bound among its rounding terms: the rounding of c = nul + delta P / P0 and of nu -+ c, times the slope of the direct and
+of the mirror profile, each weighted by its share of the sum.  Probes and crossings are placed about the state's own shifted centre.
+
 Interpolated probes.  A line is summed on the 64 Chebyshev nodes of interval I at level l where it is inside the cut-off of both ends of
 I and at least max(dA, margin h) away (izone_frame, cs_kernels.h; h the half-width, dA = 100 alpha / sqrt(ln 2), here with the line's own
 alpha <= the kernel's amax, so the set taken here contains the kernel's), at the largest such level in use.  The interpolant sum_m f(x_m)
@@ -304,6 +308,22 @@ def placements():
 
 
 LOW_CENTRE = 3.0                                    # on the grid from 0.5: nu - cut <= 0, the mirror term of codes 5 and 6 in reach
+LOW_DELTA = -0.01                                   # "col/low-lbl": the centre moves from 3.0 to 2.7 cm^-1 over the column's 1 Pa .. 3e6 Pa
+
+
+def low_shifted_table(cs, directory):
+    """one_line_table(cs, LOW_CENTRE) with the shift LOW_DELTA, written as a HITRAN 160-column file and read back (the library takes the
+    shifts from the file alone; lineparam_ref.shifted_table's layout)"""
+    path = str(directory) + "/isolated_low_shift.par"
+    with open(path, "w") as f:
+        r = (f"{2:2d}{R.ISOCHAR[0]}{LOW_CENTRE:12.6f}{1e-20:10.3E}{1.0:10.3E}{R._fx(0.07, 5, 4)}{R._fx(0.09, 5, 3)}{300.0:10.4f}"
+             f"{R._fx(0.7, 4, 2)}{R._fx(LOW_DELTA, 8, 5)}")
+        assert len(r) == 67, r
+        f.write(r + " " * 93 + "\n")
+    sl, ref = cs.SpectralLines(path), one_line_table(cs, LOW_CENTRE)
+    assert np.array_equal(sl.delta_a, [LOW_DELTA]) and all(np.array_equal(getattr(sl, n), getattr(ref, n))
+                                                           for n in ("nu", "S", "gamma_a", "gamma_s", "Epp", "na", "mu", "I"))
+    return sl
 
 
 # ---- probes -----------------------------------------------------------------------------------------------------------------------------
@@ -395,7 +415,7 @@ class Case:
                     self.lines.append((R.line_of(sl, j), None if concs is None else concs[g], CONC if fracs is None else fracs[g], g))
         self.ksel = compared(self.K) if ksel is None else list(ksel)
         self.which = which or (lambda l: self.ksel)
-        self.psh = bool(code & R.PSHIFT)
+        self.psh = R.shifts(code)      # (CS_SHAPE_PSHIFT, or code 7)
         self._build()
 
     def centre(self, k, l):
@@ -446,7 +466,7 @@ class Case:
         # codes 4, 6 at |d| = cut exactly (the grids hold such points): profile - pedestal cancels to an exact 0, rel = 0, and no relative
         # bound exists -- the device's value there is rounding of the two terms; it must be finite and >= 0 (`void`), nothing more
         self.void = np.array([f["rel"] <= 0.0 for f in self.infos]) & ((np.abs(self.nu[self.i] - [self.centre(k, l) for k, _, l in self.pr]) <= self.cut)
-                                                                         | ((self.code & ~R.PSHIFT) in (5, 6)))
+                                                                         | ((self.code & ~R.PSHIFT) in (5, 6, 7)))
         for f in self.infos:
             f["rel"] = f["rel"] if f["rel"] > 0.0 else 1.0
         self.hard = np.array([R.lineparam_bound(f, R.C0_GPU) for f in self.infos])
@@ -501,7 +521,7 @@ class Case:
             inside = abs(self.nu[i] - self.centre(k, l)) <= self.cut
             if R.lines_within(allc, self.nu[i], self.cut) != (1 if inside else 0):      # (over the lines of every gas of the case)
                 bad.append((k, i, l))
-            if any(self.lines[m][0]["nu"] + self.nu[i] <= self.cut for m in range(len(self.lines)) if m != l):
+            if any(allc[m] + self.nu[i] <= self.cut for m in range(len(self.lines)) if m != l):
                 bad.append((k, i, l))
         return bad
 
@@ -554,8 +574,8 @@ class Cases:
     """the cases by name, built on first use and kept: "batch/<placement>", "batch/low-vvh", "batch/fine" (cs_shape_batch, cs_shape_points) and
     "col/..." (a 61-state column)"""
 
-    def __init__(self, cs, shifted=None):
-        self.cs, self.shifted, self._made = cs, shifted, {}
+    def __init__(self, cs, shifted=None, low_shifted=None):
+        self.cs, self.shifted, self.low_shifted, self._made = cs, shifted, low_shifted, {}
         self.short = grid(SHORT_NU0, SHORT_DNU, SHORT_N)
         self.low = grid(LOW_NU0, SHORT_DNU, SHORT_N)
         self.four = grid(LONG_NU0, FOUR_DNU, FOUR_N)
@@ -570,7 +590,7 @@ class Cases:
 
     def names(self):
         return ([f"batch/{p}" for p in placements()] + ["batch/low-vvh", "batch/fine", "col/short", "col/short-lorentz", "col/short-ckd", "col/low-vvh",
-                "col/low-ckdvvh", "col/short-shifted", "col/short-merge", "col/four", "col/long", "col/high", "col/short-cluster",
+                "col/low-ckdvvh", "col/low-lbl", "col/short-shifted", "col/short-merge", "col/four", "col/long", "col/high", "col/short-cluster",
                 "col/four-cluster", "col/long-cluster", "col/fine", "col/fine-rep8"])
 
     def __getitem__(self, name):
@@ -615,6 +635,8 @@ class Cases:
             return one(self.low, [one_line_table(cs, LOW_CENTRE)], 5)
         if what == "low-ckdvvh":
             return one(self.low, [one_line_table(cs, LOW_CENTRE)], 6)
+        if what == "low-lbl":           # code 7: col/low-ckdvvh's line with a shift, read from a .par file (low_shifted_table)
+            return one(self.low, [self.low_shifted], R.LBL)
         if what == "short-shifted":      # lineparam_ref.shifted_table: its line at 667 cm^-1 (delta = 0.01) is the one in reach of this grid
             return Case(cs, self.short, self.plan(self.short), [self.shifted], sts, code=R.PSHIFT, concs=[CONC], which=lambda l: compared(len(sts)) if l == 3 else [])
         if what == "short-merge":        # a second gas, its one line outside the grid and more than 2 cut from the first's

@@ -1,8 +1,8 @@
 """The per-(state, line) parameter stage on the device -- prep_body of csrc/cs_kernels.h with the host tables of cs_api.hip behind it --
 one line at a time against the 40-digit values of tests/lineparam_ref.py, within its derived bound (lineparam_bound, c0 = C0_GPU):
 every isotopologue of data/molparam.json with a fit, the edge values of every line parameter under codes 0, 1, 2, 4, 5, 6 and under
-CS_SHAPE_PSHIFT on a table read from a .par file, state sets on both sides of a chunk of
-CS_PREP_KC = 8 states, and columns that fill all CS_MAX_GAS = 16 gas slots, merged and unmerged.  Tables are synthetic, with lines
+CS_SHAPE_PSHIFT and code 7 on a table read from a .par file, state sets on both sides of a chunk of
+CS_PREP_KC = 8 states, and columns that fill all CS_MAX_GAS = 16 gas slots, merged and unmerged, code 7 among the members.  Tables are synthetic, with lines
 spaced so that every probe sees exactly one line of a table (tests/test_lineparam_ref.py counts them); grids hold only the probes, so
 every call takes the short-grid forms.  Each test prints its worst error / bound."""
 import ctypes as C
@@ -11,10 +11,11 @@ import numpy as np
 import pytest
 
 import lineparam_ref as R
+from test_gpu_pressure_shift import write_par
 
 pytestmark = pytest.mark.gpu
 
-NAMES = {0: "voigt", 1: "lorentz", 2: "doppler", 4: "voigtCKD", 5: "voigtVVH", 6: "voigtCKDVVH"}
+NAMES = {0: "voigt", 1: "lorentz", 2: "doppler", 4: "voigtCKD", 5: "voigtVVH", 6: "voigtCKDVVH", 7: "voigtLBL"}
 EINVAL, ENOCHEB = -1, -3
 
 
@@ -31,7 +32,7 @@ def run_calls(cs, ctx, code, sl, sts, cut):
     psh = bool(code & R.PSHIFT)
     code &= ~R.PSHIFT
     # (pedestal codes: also 0.9 cut, and beyond the cut-off an exact 0; shifted codes: probes about the state's own shifted centre)
-    nu, pr = R.probes(lines, sts, code, cut, far=code in (4, 6), centres=R.shifted_centres(sl, sts) if psh else None)
+    nu, pr = R.probes(lines, sts, code, cut, far=code in (4, 6, R.LBL), centres=R.shifted_centres(sl, sts) if psh or code == R.LBL else None)
     want, bnd, zero = R.expected(code | (R.PSHIFT if psh else 0), sl, sts, nu, pr, cut)
     T, P, Pp = (np.array(x) for x in zip(*sts))
     k, i = np.array([p[0] for p in pr]), np.array([p[1] for p in pr])
@@ -130,6 +131,37 @@ def test_edge_parameters_pressure_shift(cs, ctx, shifted, code):
     R.check(a[3:], want[3:], bnd[3:], zero[3:], what="end-point case, vector method")
 
 
+def test_edge_parameters_voigt_lbl(cs, ctx, shifted):
+    """code 7 on the same table: K = 8 and 17 states (vacuum among them), probes about each state's own centre -- the line at 0.05 cm^-1
+    has its mirror term inside the cut-off at every probe -- also at 0.9 cut and beyond the cut-off, under lineparam_bound with its
+    centre term for the direct and the mirror profile.  Then the end-point case: the pedestal takes the whole profile off exactly on
+    the cut-off, so there the 40-digit value is 0 for both methods and the scalar method is held to the bound's absolute form"""
+    acc = [[], [], [], []]
+    for K, seed in ((8, 1), (17, 2)):
+        a, b, want, bnd, zero = run_calls(cs, ctx, R.LBL, shifted, R.states(K, seed, with_vacuum=True), R.CUT_EDGE)
+        for got in (a, b):
+            for lst, x in zip(acc, (got, want, bnd, zero)):
+                lst.append(x)
+    got, want, bnd, zero = (np.concatenate(x) for x in acc)
+    worst = R.check(got, want, bnd, zero, what="voigtLBL")
+    print(f"voigtLBL: {len(want)} probes, underflow class {100 * R.split(want[~zero])[1]:.1f} %, worst error / bound {worst:.3f}")
+    nu, sts = np.array(R.FILTER_GRID), list(R.FILTER_STATES)
+    pr = [(k, i, 5) for k in range(len(sts)) for i in range(len(nu))]
+    infos = []
+    want, bnd, zero = R.expected(R.LBL, shifted, sts, nu, pr, R.FILTER_CUT, infos=infos)
+    T, P, Pp = (np.array(x) for x in zip(*sts))
+    a = cs.shape_batch(shifted, "voigtLBL", nu, T, P, Pp, R.FILTER_CUT, ctx).ravel()
+    b = cs.shape_points(shifted, "voigtLBL", nu, T, P, Pp, R.FILTER_CUT, ctx).ravel()
+    assert np.all(zero[:3]) and np.sum(~zero) >= 3 and infos[2]["rel"] == 0.0 and infos[2]["mag"] > 0.0
+    assert np.all(a[:3] == 0.0) and np.all(b[:2] == 0.0)
+    edge = (R.U * (R.C0_GPU + R.model_terms(infos[2])) + R.FADDEEVA) * infos[2]["mag"]
+    print(f"voigtLBL, end-point case: scalar method on the cut-off {b[2]:.3e}, allowed {edge:.3e}")
+    assert 0.0 <= b[2] <= edge
+    w = max(R.check(b[3:], want[3:], bnd[3:], zero[3:], what="end-point case, scalar method"),
+            R.check(a[3:], want[3:], bnd[3:], zero[3:], what="end-point case, vector method"))
+    print(f"voigtLBL, end-point case: worst error / bound {w:.3f}")
+
+
 # ---- sixteen members ------------------------------------------------------------------------------------------------------------------
 
 SHAPES = [(4, 3, 7), (5, 5, 17)]     # (np, nlobatto, K)
@@ -212,6 +244,29 @@ def test_sixteen_members_mixed(cs):
     _compare(col, tabs, codes, cuts, "mixed line-up")
     info = col.info()
     assert info["groups"] == len(groups) and info["max_members"] == max(len(g["slots"]) for g in groups), info
+    ctx.close()
+
+
+def test_sixteen_members_with_voigt_lbl(cs, tmp_path):
+    """the mixed line-up with member 6 as code 7, its table read from a .par file with shifts of both signs: nine launch groups, the
+    code-7 member in one of its own, at K = 7 and 17 node states (arbitrary pressures: the centre term carries the rounding of
+    nu -+ c as well)"""
+    tabs = R.member_tables(cs)
+    t, da = tabs[6], np.array([0.01, -0.005, 0.25])
+    tabs[6] = cs.SpectralLines(write_par(str(tmp_path / "member6.par"), t.M, t.nu, t.S, t.gamma_a, t.gamma_s, t.Epp, t.na, da, t.I))
+    assert np.array_equal(tabs[6].delta_a, da) and np.array_equal(tabs[6].nu, t.nu) and np.array_equal(tabs[6].I, t.I) and tabs[6].M == t.M
+    nu = R.member_grid(tabs)
+    codes = [(0, 1, 4, 5)[m % 4] for m in range(16)]
+    codes[6] = R.LBL
+    cuts = [2.0 if m < 8 else 3.0 for m in range(16)]
+    ctx = cs.Context(0)
+    gases = [cs.DirectGas(tabs[m], R.member_conc(m), nu, shape=NAMES[codes[m]], dnu_cut=cuts[m]) for m in range(16)]
+    for npl, nlob, K in SHAPES:
+        col = _column(cs, ctx, gases, npl, nlob)
+        assert col.K == K
+        _compare(col, tabs, codes, cuts, f"line-up with code 7, K = {K}")
+        info = col.info()
+        assert info["groups"] == 9 and info["max_members"] == 2, info      # 4 codes x 2 cut-offs, and code 7 apart
     ctx.close()
 
 

@@ -13,7 +13,8 @@ import lineparam_ref as R
 
 @pytest.fixture(scope="module")
 def cases(cs, tmp_path_factory):
-    return I.Cases(cs, R.shifted_table(cs, tmp_path_factory.mktemp("isolated")))
+    d = tmp_path_factory.mktemp("isolated")
+    return I.Cases(cs, R.shifted_table(cs, d), I.low_shifted_table(cs, d))
 
 
 def test_grids_sit_on_the_rules(cs, cases):
@@ -60,7 +61,7 @@ def test_probes_isolated_capped_and_above_underflow(cs, cases):
             ln, C, frac, _ = c.lines[l]
             T, P = c.states[k]
             _, ga = R.widths(ln, T, P, frac * P)
-            S = float(R.intensity(ln, T, (c.code & ~R.PSHIFT) in (5, 6))[0])
+            S = float(R.intensity(ln, T, (c.code & ~R.PSHIFT) in (5, 6, 7))[0])
             assert (C or 1.0) * S * ga / (math.pi * (c.cut ** 2 + ga ** 2)) > 1e-50 > 1e200 * R.UNDERFLOW, (name, k, l)
         n += len(c.pr)
     # the clusters: ghosts within one grid step above their line, GHOST_RATIO of its strength; with the profile's largest ratio inside the
@@ -142,7 +143,7 @@ def test_rep8_core_probes(cs, cases):
         print(f"col/fine-rep8 line {l}: {core0} probes with 100 <= s < 1e3, {core1} with s < 100, in tiles {met}")
 
 
-@pytest.mark.parametrize("name", ["batch/mid-tile", "batch/between-tiles-1024", "batch/low-vvh", "batch/fine", "col/fine-rep8"])
+@pytest.mark.parametrize("name", ["batch/mid-tile", "batch/between-tiles-1024", "batch/low-vvh", "batch/fine", "col/fine-rep8", "col/low-lbl"])
 def test_oracle_meets_both_bounds(cs, O, cases, name):
     """the oracle at the device's probes: within lineparam_bound(C0_ORACLE) everywhere, and within the sharp bound of the scalar form (no
     reciprocal terms: its divisions are IEEE; below s = 1e4 faddeeva_ref.bound(x, y, "scalar") per probe, the line core included) -- the

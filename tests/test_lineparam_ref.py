@@ -8,6 +8,7 @@ import pytest
 
 import ckdvvh_ref as CK
 import lineparam_ref as R
+import voigt_lbl_ref as V
 
 ORACLE_SHAPE = {0: "voigt", 1: "lorentz", 2: "doppler"}
 
@@ -23,6 +24,12 @@ def oracle_sigma(cs, O, code, nu, sl, T, P, Pp, cut):
         for l in range(len(sl.nu)):
             out += O.shape_bang(ORACLE_SHAPE[code & ~R.PSHIFT], np.asarray(nu) - sl.delta_a[l] * P / R.KATM, CK.tilde(cs, sl, T, l, l + 1, scale=False),
                                 T, P, Pp, cut, strict_ends=False)
+        return out
+    if code == R.LBL:     # voigt_lbl_ref.expected, the composite the device's code-7 tests use, on one-line tables
+        out = np.zeros(len(nu))
+        for l in range(len(sl.nu)):
+            one = V.subset(sl, np.arange(len(sl.nu)) == l)
+            out += V.expected(cs, O, one, sl.delta_a[l:l + 1], nu, T, P, Pp, cut, strict=False)[0]
         return out
     ped, vvh = code in (4, 6), code in (5, 6)
     nu = np.asarray(nu, float)
@@ -50,7 +57,7 @@ def calls(cs, shifted=None):
     if shifted is not None:
         for K, seed in ((8, 1), (17, 2)):
             out.append((shifted, R.states(K, seed), R.CUT_EDGE, (17,)))
-            out.append((shifted, R.states(K, seed, with_vacuum=True), R.CUT_EDGE, (16, 18)))
+            out.append((shifted, R.states(K, seed, with_vacuum=True), R.CUT_EDGE, (16, 18, R.LBL)))
     for sl, K, seed in R.edge_tables(cs):
         out.append((sl, R.states(K, seed), R.CUT_EDGE, (1,)))
         out.append((sl, R.states(K, seed, with_vacuum=True), R.CUT_EDGE, (0, 2, 4, 5, 6)))
@@ -68,7 +75,7 @@ def measured(cs, O, shifted):
     for sl, sts, cut, codes in calls(cs, shifted):
         lines = [R.line_of(sl, l) for l in range(len(sl.nu))]
         for code in codes:
-            nu, pr = R.probes(lines, sts, code & ~R.PSHIFT, cut, far=code in (4, 6), centres=R.shifted_centres(sl, sts) if code & R.PSHIFT else None)
+            nu, pr = R.probes(lines, sts, code & ~R.PSHIFT, cut, far=code in (4, 6, R.LBL), centres=R.shifted_centres(sl, sts) if R.shifts(code) else None)
             infos = []
             want, bnd, zero = R.expected(code, sl, sts, nu, pr, cut, c0=R.C0_ORACLE, infos=infos)
             got = np.zeros(len(pr))
@@ -157,9 +164,9 @@ def test_probes_isolate_one_line(cs, shifted):
     for sl, sts, cut, codes in calls(cs, shifted):
         lines = [R.line_of(sl, l) for l in range(len(sl.nu))]
         for code in codes:
-            psh = bool(code & R.PSHIFT)
+            psh = R.shifts(code)
             cen = R.shifted_centres(sl, sts) if psh else [list(sl.nu)] * len(sts)
-            nu, pr = R.probes(lines, sts, code & ~R.PSHIFT, cut, far=code in (4, 6), centres=cen if psh else None)
+            nu, pr = R.probes(lines, sts, code & ~R.PSHIFT, cut, far=code in (4, 6, R.LBL), centres=cen if psh else None)
             assert len(nu) <= 600 and np.all(np.diff(nu) > 0) and nu[0] > 0
             for k, i, l in pr:
                 inside = abs(nu[i] - cen[k][l]) <= cut

@@ -5,7 +5,10 @@ they count.  If one of them changes, the GPU tests may no longer cross a chunk b
 import os
 import re
 
+import numpy as np
+
 import test_gpu_state_chunks as SC
+import voigt_lbl_ref as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "clearsky.jl_amd", "csrc")
@@ -104,3 +107,43 @@ def test_rule_arithmetic():
             assert N % step == 0
             kc, b = SC.boundaries(rule, N, L, n, **kw)
             assert len(b) == 2 and b == [kc, 2 * kc]
+
+
+def test_shifted_cases_cross_chunks_and_see_their_shifts():
+    """the shifted cases of test_gpu_state_chunks.py, without a GPU: every one makes three chunks with a ragged last one (boundaries():
+    with 10 % fewer bytes per state too); the largest pressure, so the largest shift ds, belongs to no state of the first chunk; the
+    compared rows are exact in fp64 (the premise of the 1e-11 bar); and among them membership by shifted centre differs from membership
+    by table position for the direct and the mirror terms, and the strict pre-filter keeps a line in one row that it drops in another"""
+    t = SC.shifted_lines()
+    nul, da, nu = t["nu"], t["delta_a"], SC.GRID_DY
+    L = len(nul)
+    assert 300_000 < L <= SC.NLINES and np.all(nul * 64 == np.round(nul * 64)) and np.all(da * 32 == np.round(da * 32))
+    assert np.max(np.abs(da)) == 0.1875 and np.mean(np.diff(nul + da * 2.0) < 0) > 0.01      # neighbours swap their order at 2 atm
+    for code, cut in SC.SHIFT_CASES:
+        ped = code == 7
+        c = SC.shift_case(code, cut)
+        assert c.b0 == [c.kc, 2 * c.kc] and c.kc == SC.chunk_size("shape", c.n, L, len(nu), ped=ped)
+        assert np.max(c.P[:c.kc]) == 0.5 * SC.KATM and np.max(c.P) == 2.0 * SC.KATM and all(c.P[k0] == 2.0 * SC.KATM for k0 in c.b0)
+        assert 0.1875 * 2.0 == 0.375 and (cut == 0.25) == (cut < 0.375)
+        assert {0, c.n - 1, c.kc - 1, c.kc, 2 * c.kc - 1, 2 * c.kc} <= set(c.rows) and sum(c.P[k] >= 0.25 * SC.KATM for k in c.rows) >= 4
+        a, b = np.searchsorted(nul, [max(0.0, nu[0] - cut - 1.0), nu[-1] + cut + 1.0])       # (_reach)
+        V.dyadic_premise(nul[a:b], nu, da[a:b], np.unique(c.P[c.rows]))
+        direct = mirror = any_mirror = False
+        keep = []
+        for k in c.rows:
+            d, m, d0, m0 = V.membership(nul[a:b], da[a:b], nu, c.P[k], cut)
+            direct, mirror, any_mirror = direct or bool(np.any(d != d0)), mirror or bool(np.any(m != m0)), any_mirror or bool(np.any(m | m0))
+            cen = nul[a:b] + da[a:b] * c.P[k] / SC.KATM
+            keep.append((cen > nu[0] - cut) & (cen < nu[-1] + cut))
+        keep = np.array(keep)
+        assert direct, (code, cut)
+        assert np.any(keep.any(axis=0) & ~keep.all(axis=0)), (code, cut)
+        if code == 7:   # (the flagged codes 0-2 have no mirror term; at cut 0.25 < nu_1 no mirror line exists on this grid)
+            assert mirror == any_mirror == (cut > nu[0]), (code, cut)
+    for code in SC.BAKE_SHIFT_CASES:
+        nP, n, kc, b0 = SC.bake_sizes(code)
+        assert n == SC.NT_BAKE * nP and b0 == [kc, 2 * kc] and kc == SC.chunk_size("bake", n, L, len(nu), ped=code == 7)
+    for code, kw in [(c_, {}) for c_, _ in SC.COLUMN_SHIFT_CASES] + [(7, dict(vvh2=True))]:
+        B, kc, b0 = SC.column_sizes(code, **kw)
+        assert b0 == [kc, 2 * kc] and any(k0 % SC.NP_COL for k0 in b0)
+        assert kc == SC.chunk_size("column", B * SC.NP_COL, L, len(nu), ped=code == 7, **kw)

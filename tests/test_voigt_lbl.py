@@ -134,6 +134,46 @@ def test_restatement_vs_40_digits(cs, O, case, capsys):
     assert worst < 1e-12 and wf < 1e-12, (worst, wf)
 
 
+def test_sigma_isolated_code_7_is_sigma_line(cs, case):
+    """lineparam_ref.sigma_isolated(7, ...), the reference of the per-line harnesses, equals voigt_lbl_ref.sigma_line as floats: at the
+    shifted centre, inside, at both direct edges and the mirror edge, and beyond, every state of the device cases, and on the golden
+    H2O file's shifts at an arbitrary pressure; its bound's centre term is there exactly where a term hangs on a shifted centre"""
+    T, P, Pp = V.states()
+    n = 0
+    for cut in (1.0, 25.0):
+        for l in (0, 3, 41, len(case.nu) - 1):
+            line = LP.line_of(case, l)
+            assert line["delta"] == case.delta_a[l]
+            for k in range(len(T)):
+                c = case.nu[l] + case.delta_a[l] * P[k] / KATM
+                for x in (c, c + 0.25, c - 0.5, c + cut, c - cut, cut - c, c + cut + 0.25, cut - c - 0.25, cut - c + 0.25, 0.5, 64.5):
+                    if x <= 0.0:
+                        continue
+                    a, sc = V.sigma_line(x, line, T[k], P[k], Pp[k], cut, C=0.37)
+                    b, _, info = LP.sigma_isolated(7, x, line, T[k], P[k], Pp[k], cut, C=0.37)
+                    assert a == b, (cut, l, k, x, a, b)
+                    assert info["voigt"] and info["planck_T"] == 0.0 and (0.0 <= info["rel"] <= 1.0)
+                    # dyadic: nothing but the centre's own rounding, and that only with a shift and a term in reach
+                    # (at x = c the direct profile's slope is 0)
+                    if not (sc > 0.0 and case.delta_a[l] * P[k] != 0.0):
+                        assert info["centre"] == 0.0, (cut, l, k, x)
+                    elif x != c:
+                        assert info["centre"] > 0.0, (cut, l, k, x)
+                    n += 1
+    h2o = cs.SpectralLines(os.path.join(HITRAN, "H2O.par"), numin=0.0, numax=150.0)
+    Tq, Pq, Ppq = 251.3, 87654.3, 1234.5
+    for l in (1, 5, 12, 30):
+        line = LP.line_of(h2o, l)
+        c = h2o.nu[l] + h2o.delta_a[l] * Pq / KATM
+        for x in (c + 0.013, c - 0.4, c + 24.9, 25.0 - c - 0.01, 0.37):
+            if x > 0.0:
+                a, sc = V.sigma_line(x, line, Tq, Pq, Ppq, 25.0)
+                b, _, info = LP.sigma_isolated(7, x, line, Tq, Pq, Ppq, 25.0)
+                assert a == b and (info["centre"] > 0.0) == (sc > 0.0), (l, x)
+                n += 1
+    assert n > 500
+
+
 def test_premises_of_the_device_cases(cs, O, case):
     """Conditions the device cases rest on, on the reference alone"""
     nul, da, nu = case.nu, case.delta_a, V.GRID

@@ -6,7 +6,8 @@ shared by tests/test_voigt_lbl.py (host) and tests/test_gpu_voigt_lbl.py (device
 with c_l = nul + s_l, s_l = delta_l P / P0, and S~_l, alpha_l, gamma_l from the unshifted nul.
 
 `sigma_line` is ONE line at 40 digits: the code-6 branch of lineparam_ref.sigma_isolated restated with d = nu - (nul + s), the mirror
-test and argument nu + nul + s, and S~, alpha, gamma from nul (that function asserts against shifted codes above 2).
+test and argument nu + nul + s, and S~, alpha, gamma from nul.  lineparam_ref.sigma_isolated(7, ...) is the same value with the terms
+of its rounding bound beside it (test_voigt_lbl.py holds the two equal as floats); the per-line harnesses use that one.
 
 `expected` is many lines through the oracle, by the identity the CS_SHAPE_PSHIFT tests use, extended for the mirror: line l's direct
 term is the code-6 direct term on the grid nu - s_l, its mirror term the code-6 mirror term on the grid nu + s_l.  So for each distinct
