@@ -239,6 +239,7 @@ class Context:
         self._slots = {}   # id(sl) -> (slot, sl)
         self._shifted = set()   # id(sl) of the slots whose pressure shifts are attached (cs_gas_upload_par)
         self._next = 0
+        self._returned = []   # slots taken for a file that was then refused (load_par): handed out again before _next moves on
         self._tables = {}  # id(Gas) -> slot
         self._free_tables = list(range(CS_MAX_TABLE))
 
@@ -367,6 +368,8 @@ class Context:
                     self._shifted.discard(old)
                     return self._slots.pop(old)[0]
             raise ClearSkyHIPError(-1, f"all {CS_MAX_GAS} gas slots hold tables of the current call")
+        if self._returned:   # (slots a refused load_par gave back)
+            return self._returned.pop()
         slot = self._next
         self._next += 1
         return slot
@@ -387,9 +390,13 @@ class Context:
         cheb = as_f64(mp.cheb_table())
         slot = self._take_slot()
         L = C.c_int64()
-        check(lib().cs_gas_upload_par(self._h, slot, filename.encode(), float(numin), float(min(numax, 1e300)), float(Scut),
-                                      keep.ctypes.data_as(C.POINTER(C.c_int)), len(keep), int(maxlines), int(M), dptr(mu), len(mu),
-                                      ncheb.ctypes.data_as(C.POINTER(C.c_int32)), dptr(cheb), C.byref(L)))
+        try:
+            check(lib().cs_gas_upload_par(self._h, slot, filename.encode(), float(numin), float(min(numax, 1e300)), float(Scut),
+                                          keep.ctypes.data_as(C.POINTER(C.c_int)), len(keep), int(maxlines), int(M), dptr(mu), len(mu),
+                                          ncheb.ctypes.data_as(C.POINTER(C.c_int32)), dptr(cheb), C.byref(L)))
+        except ClearSkyHIPError:
+            self._returned.append(slot)   # (a refused file -- malformed, filtered to nothing, another molecule -- costs the context no slot)
+            raise
         n = L.value
         a = {k: np.zeros(n) for k in ("nu", "S", "gamma_a", "gamma_s", "Epp", "na")}
         iso = np.zeros(n, dtype=np.int16)

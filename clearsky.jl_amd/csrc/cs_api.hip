@@ -25,6 +25,7 @@
 #include "../../include/clearsky_hip.h"
 #include "../../include/clearsky_hip_dev.h"
 #include "cs_kernels.h"
+#include "cs_par.h"
 
 using namespace csdev;
 
@@ -4525,92 +4526,65 @@ struct MappedFile {
     }
 };
 
-// record length incl. line terminator: 160 characters + "\n" or "\r\n"
-int par_layout(const MappedFile &f, size_t &stride, int64_t &n)
-{
-    const char *nl = (const char *)memchr(f.p, '\n', f.len);
-    stride = nl ? (size_t)(nl - f.p) + 1 : f.len;
-    const size_t body = (stride >= 2 && f.p[stride - 2] == '\r') ? stride - 2 : (nl ? stride - 1 : stride);
-    if (body != 160) return fail(CS_EINVAL, "expected 160-character HITRAN records, found %zu", body);
-    n = (int64_t)((f.len + (nl ? 0 : 1)) / stride);
-    if ((size_t)n * stride < f.len && f.len - (size_t)n * stride >= 160) n++;  // last record without a terminator
-    return CS_OK;
-}
-
-double field(const char *s, int a, int b)   // columns a..b (1-based, inclusive), like parse(Float64, line[a:b])
-{
-    char buf[32];
-    const int w = b - a + 1;
-    memcpy(buf, s + a - 1, w);
-    buf[w] = 0;
-    return strtod(buf, nullptr);
-}
+// a mapped .par file and the offsets of its records (cs_par.h: the layout half of the validity rule); refusals say what first, the file
+// name after it, where a long path cannot push the record and field out of the message
+struct ParFile {
+    MappedFile f;
+    std::vector<size_t> off;
+    int open(const char *fn)
+    {
+        int rc = f.open_ro(fn);
+        if (rc) return rc;
+        std::string err;
+        if (!cs_par::index_records(f.p, f.len, off, err)) return fail(CS_EINVAL, "%s (%s)", err.c_str(), fn);
+        return CS_OK;
+    }
+    int64_t n() const { return (int64_t)off.size(); }
+    int parse(const char *fn, const cs_par::Arrays &o) const   // (the field half)
+    {
+        std::string err;
+        if (!cs_par::parse_records(f.p, off, o, err)) return fail(CS_EINVAL, "%s (%s)", err.c_str(), fn);
+        return CS_OK;
+    }
+};
 }  // namespace
 
 int cs_par_count(const char *filename, int64_t *n)
 {
     if (!filename || !n) return fail(CS_EINVAL, "bad arguments");
-    MappedFile f;
-    int rc = f.open_ro(filename);
+    ParFile pf;
+    int rc = pf.open(filename);
     if (rc) return rc;
-    size_t stride;
-    return par_layout(f, stride, *n);
+    *n = pf.n();
+    return CS_OK;
 }
 
 int cs_par_parse(const char *filename, int64_t n, int16_t *M, char *I, double *nu, double *S, double *A, double *gamma_a,
                  double *gamma_s, double *Epp, double *na, double *delta_a)
 {
     if (!filename) return fail(CS_EINVAL, "bad arguments");
-    MappedFile f;
-    int rc = f.open_ro(filename);
+    ParFile pf;
+    int rc = pf.open(filename);
     if (rc) return rc;
-    size_t stride;
-    int64_t cnt;
-    if ((rc = par_layout(f, stride, cnt))) return rc;
-    if (cnt != n) return fail(CS_EINVAL, "file holds %lld records, caller expects %lld", (long long)cnt, (long long)n);
-    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)std::thread::hardware_concurrency(), 32, n / 20000}));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nth; t++)
-        th.emplace_back([&, t]() {
-            for (int64_t i = n * t / nth; i < n * (t + 1) / nth; i++) {
-                const char *r = f.p + (size_t)i * stride;   // columns: par.jl:131-140
-                M[i] = (int16_t)field(r, 1, 2);
-                I[i] = r[2];
-                nu[i] = field(r, 4, 15);
-                S[i] = field(r, 16, 25);
-                A[i] = field(r, 26, 35);
-                gamma_a[i] = field(r, 36, 40);
-                gamma_s[i] = field(r, 41, 45);
-                Epp[i] = field(r, 46, 55);
-                na[i] = field(r, 56, 59);
-                delta_a[i] = field(r, 60, 67);
-            }
-        });
-    for (auto &x : th) x.join();
-    return CS_OK;
+    if (pf.n() != n) return fail(CS_EINVAL, "file holds %lld records, caller expects %lld", (long long)pf.n(), (long long)n);
+    return pf.parse(filename, {M, I, {nu, S, A, gamma_a, gamma_s, Epp, na, delta_a}});
 }
 
-// ISOINDEX, par.jl:6-13: '1'..'9' -> 1..9, '0' -> 10, 'A'..'Z' -> 11..36; 0 = not an isotopologue character
-static int iso_index(char c)
-{
-    if (c >= '1' && c <= '9') return c - '0';
-    if (c == '0') return 10;
-    if (c >= 'A' && c <= 'Z') return 11 + (c - 'A');
-    return 0;
-}
+using cs_par::iso_index;
 
 int cs_gas_upload_par(cs_ctx *ctx, int slot, const char *filename, double numin, double numax, double Scut, const int *iso_keep,
                       int n_iso_keep, int64_t maxlines, int M_expected, const double *mu_table, int niso, const int32_t *ncheb,
                       const double *cheb, int64_t *L_out)
 {
     if (!ctx || !filename || !mu_table || !ncheb || !cheb || niso < 1) return fail(CS_EINVAL, "bad arguments");
-    int64_t n = 0;
     int rc;
-    if ((rc = cs_par_count(filename, &n))) return rc;
+    ParFile pf;   // a file that breaks the rule is refused here, before the slot is touched: the table it holds stays as it was
+    if ((rc = pf.open(filename))) return rc;
+    const int64_t n = pf.n();
     std::vector<int16_t> M(n);
     std::vector<char> I(n);
     std::vector<double> nu(n), S(n), A(n), ga(n), gs(n), Epp(n), na(n), da(n);
-    if ((rc = cs_par_parse(filename, n, M.data(), I.data(), nu.data(), S.data(), A.data(), ga.data(), gs.data(), Epp.data(), na.data(), da.data())))
+    if ((rc = pf.parse(filename, {M.data(), I.data(), {nu.data(), S.data(), A.data(), ga.data(), gs.data(), Epp.data(), na.data(), da.data()}})))
         return rc;
     // par.jl:153-175: wavenumber range, intensity cut, isotopologue list
     std::vector<int64_t> keep;

@@ -5,6 +5,7 @@ data table src/hitran/molparam.jl (extracted to data/molparam.json by tools/gen_
 """
 import json
 import os
+import re
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -73,6 +74,20 @@ def readpar(filename: str, numin: float = 0.0, numax: float = np.inf, Scut: floa
     Filters (nu range, intensity cut, isotopologues, strongest `maxlines`) and the final stable sort by wavenumber
     follow par.jl:153-191.  Returns a dict of numpy arrays keyed M, I (characters), nu, S, A, gamma_a, gamma_s, Epp,
     na, delta_a.
+
+    A valid file, by the same rule in the native parser (cs_par_parse, include/clearsky_hip.h) and here (native=False):
+      - a record ends at LF; one CR directly before that LF belongs to the terminator, record by record; the last record may lack
+        a terminator; lines of whitespace only are allowed at the very end of the file and nowhere else;
+      - every record has exactly 160 characters -- a stump at the end, a blank line in the middle, a 159- or 161-character record
+        are refused with the 1-based record number and the length found;
+      - nu, S, A, gamma_a, gamma_s, Epp, na, delta_a (columns 4-15, 16-25, 26-35, 36-40, 41-45, 46-55, 56-59, 60-67): blanks trimmed on
+        both sides, the whole remainder a plain decimal literal (optional sign, digits with an optional point, optional e/E exponent
+        with optional sign) with a finite value; M (columns 1-2) an integer literal; column 3 one of 1-9, 0, A-Z.  Blank fields,
+        '#' fill, "1.234-100", D exponents, hex floats, nan/inf, underscores and trailing junk are refused with record number and
+        field name, the first such field in file order of the lowest such record.
+    A refused file raises ValueError here and ClearSkyHIPError from the native parser (the reference's parse(Float64, ...)
+    throws on every one of these fields, par.jl:127-152).  Accepted values are correctly rounded: float() of the trimmed field, bit for bit, in
+    both readers, whatever the locale.
     """
     if not filename.endswith(".par"):
         raise AssertionError("expected file with .par extension, downloaded from https://hitran.org/lbl/")
@@ -80,23 +95,55 @@ def readpar(filename: str, numin: float = 0.0, numax: float = np.inf, Scut: floa
     if par is not None:
         return _filter_sort(par, len(par["nu"]), numin, numax, Scut, I, maxlines)
     with open(filename, "rb") as f:
-        raw = f.read().split(b"\n")
-    raw = [ln.rstrip(b"\r") for ln in raw if len(ln.strip()) > 0]
+        raw = _records(f.read())
     N = len(raw)
     par = dict(M=np.zeros(N, np.int16), I=np.empty(N, "U1"), nu=np.zeros(N), S=np.zeros(N), A=np.zeros(N),
                gamma_a=np.zeros(N), gamma_s=np.zeros(N), Epp=np.zeros(N), na=np.zeros(N), delta_a=np.zeros(N))
     for i, ln in enumerate(raw):
-        par["M"][i] = int(ln[0:2])
+        par["M"][i] = _field(ln, i, "M", 1, 2, _INTEGER, int)
+        if chr(ln[2]) not in ISOINDEX:
+            raise ValueError(f"record {i + 1}: field I (columns 3-3) = {ln[2:3]!r} is not an isotopologue character (1-9, 0, A-Z)")
         par["I"][i] = chr(ln[2])
-        par["nu"][i] = float(ln[3:15])
-        par["S"][i] = float(ln[15:25])
-        par["A"][i] = float(ln[25:35])
-        par["gamma_a"][i] = float(ln[35:40])
-        par["gamma_s"][i] = float(ln[40:45])
-        par["Epp"][i] = float(ln[45:55])
-        par["na"][i] = float(ln[55:59])
-        par["delta_a"][i] = float(ln[59:67])
+        for name, a, b in _COLUMNS:
+            par[name][i] = _field(ln, i, name, a, b, _DECIMAL, float)
     return _filter_sort(par, N, numin, numax, Scut, I, maxlines)
+
+
+# the numeric fields in file order: columns a..b (1-based, inclusive), par.jl:133-140
+_COLUMNS = (("nu", 4, 15), ("S", 16, 25), ("A", 26, 35), ("gamma_a", 36, 40), ("gamma_s", 41, 45), ("Epp", 46, 55), ("na", 56, 59),
+            ("delta_a", 60, 67))
+_DECIMAL = re.compile(rb"[+-]?(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]+)?")
+_INTEGER = re.compile(rb"[+-]?[0-9]+")
+
+
+def _records(data: bytes) -> list:
+    """The layout half of readpar's rule: the 160-character records of a file's bytes, without their terminators."""
+    out, pos = [], 0
+    while pos < len(data):
+        nl = data.find(b"\n", pos)
+        end = len(data) if nl < 0 else nl
+        ln = data[pos:end]
+        if nl >= 0 and ln.endswith(b"\r"):
+            ln = ln[:-1]
+        if len(ln) != 160:
+            if not data[pos:].strip(b" \t\n\v\f\r"):
+                break   # blank lines at the end of the file
+            raise ValueError(f"record {len(out) + 1} has {len(ln)} characters, a HITRAN .par record has 160")
+        out.append(ln)
+        pos = end + 1
+    if not out:
+        raise ValueError("the file holds no records")
+    return out
+
+
+def _field(ln, i, name, a, b, literal, convert):
+    """The field half: columns a..b of record i (0-based), blanks trimmed, the whole remainder a literal with a finite value."""
+    txt = ln[a - 1:b].strip(b" ")
+    v = convert(txt) if literal.fullmatch(txt) else np.inf
+    if not np.isfinite(v):
+        kind = "an integer literal" if convert is int else "a finite plain decimal literal"
+        raise ValueError(f"record {i + 1}: field {name} (columns {a}-{b}) = {ln[a - 1:b]!r} is not {kind}")
+    return v
 
 
 def _readpar_native(filename):

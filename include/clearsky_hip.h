@@ -349,6 +349,23 @@ int cs_column_update_state(cs_ctx *ctx, const double *T_nodes, const double *mu_
  *   cs_par_count : number of records in the file
  *   cs_par_parse : fills the caller's arrays of length n (= cs_par_count): M (molecule number), I (isotopologue character),
  *                  nu, S, A, gamma_a, gamma_s, Epp, na, delta_a
+ * A valid file (the Python mirror readpar(native=False) holds the same rule and agrees on every accept-or-refuse decision):
+ *   - Terminator: a record ends at LF; one CR directly before that LF belongs to the terminator.  This is decided record by record
+ *     (LF and CRLF may mix, as in two downloads concatenated); the last record may lack a terminator.
+ *   - Blank lines (whitespace only) are allowed at the very end of the file, nowhere else.
+ *   - Length: every record has exactly 160 characters.  A stump at the end of the file, a blank line in the middle, a 159- or
+ *     161-character record are refused: "record <1-based number> has <length> characters".  cs_par_count applies this layout rule too,
+ *     so it counts no file that cs_par_parse would refuse for its layout.
+ *   - Numeric fields nu, S, A, gamma_a, gamma_s, Epp, na, delta_a (columns 4-15, 16-25, 26-35, 36-40, 41-45, 46-55, 56-59, 60-67;
+ *     par.jl:133-140): blanks trimmed on both sides, the whole remainder a plain decimal literal -- optional sign, digits with an
+ *     optional point, optional e/E exponent with optional sign -- whose value is finite.  M (columns 1-2) is an integer literal,
+ *     column 3 an isotopologue character 1-9, 0, A-Z.  Blank fields, '#' fill, an exponent without its letter (Fortran's "1.234-100"),
+ *     D exponents, hex floats, nan/inf, underscores and trailing junk are refused: "record <number>: field <name> ...", for the
+ *     lowest such record of the file (whichever thread met it) and its first such field in file order.
+ *   - Accepted values are correctly rounded (bit-equal to Python's float() of the trimmed field) and do not depend on the locale.
+ * Every refusal is CS_EINVAL.  A file refused for its layout leaves the caller's arrays untouched; one refused for a field leaves
+ * unspecified values in elements 0 .. n-1 (the threads have written what they got to) and nothing outside them.  cs_gas_upload_par
+ * refuses such a file before it touches the slot: the table the slot held stays usable.
  */
 int cs_par_count(const char *filename, int64_t *n);
 int cs_par_parse(const char *filename, int64_t n, int16_t *M, char *I, double *nu, double *S, double *A, double *gamma_a,

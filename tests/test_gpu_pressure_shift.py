@@ -18,6 +18,7 @@ import pytest
 
 import workloads as W
 from conftest import HITRAN, relerr
+from par_files import write_par
 
 pytestmark = pytest.mark.gpu
 
@@ -49,30 +50,6 @@ def expected(O, sl, da, base, nu, T, P, Pp, strict, cut=CUT):
     for s in np.unique(s_l[near]):
         out += O.shape_bang(base, nu - s, subset(sl, near & (s_l == s)), T, P, Pp, cut, strict_ends=strict)
     return out
-
-
-def _fx(x, w, dec):
-    """x in a fixed field of w characters with dec decimals (HITRAN drops the leading zero where the field needs it: .0927, -.23)"""
-    r = f"{x:.{dec}f}"
-    if len(r) > w:
-        r = r.replace("0.", ".", 1)
-    assert len(r) <= w, (x, w)
-    return r.rjust(w)
-
-
-ISOCHAR = {1: "1", 2: "2", 3: "3", 4: "4", 5: "5", 6: "6", 7: "7", 8: "8", 9: "9", 10: "0", 11: "A", 12: "B"}
-
-
-def write_par(path, M, nu, S, ga, gs, Epp, na, da, iso=None):
-    """a HITRAN 160-column file of these lines (par.jl:131-149 layout); read back through the parser, its values are the table's"""
-    iso = np.ones(len(nu), int) if iso is None else iso
-    with open(path, "w") as f:
-        for j in range(len(nu)):
-            r = (f"{M:2d}{ISOCHAR[int(iso[j])]}{nu[j]:12.6f}{S[j]:10.3E}{1.0:10.3E}{_fx(ga[j], 5, 4)}{_fx(gs[j], 5, 3)}{Epp[j]:10.4f}"
-                 f"{_fx(na[j], 4, 2)}{_fx(da[j], 8, 5)}")
-            assert len(r) == 67, r
-            f.write(r + " " * 93 + "\n")
-    return str(path)
 
 
 def with_delta(cs, tmp, name, sl, da):
