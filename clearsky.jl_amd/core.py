@@ -1180,32 +1180,33 @@ class Column:
             self._setup()
 
     # -- closures -> arrays ---------------------------------------------------------------------------------------
-    def _state(self, fT, fmu):
+    def _node_inputs(self, fT, fmu):
+        """What a profile (fT, fmu) fixes at the column's nodes -- Tn, mun, Tlev, Tk, muk, then conc [ngas, K], conc_tab [ntab, K] and
+        cia_P1, cia_P2 [ncia, K] in Fortran order -- for the resident column (_state) or one member of a batch (run_batch)"""
         nlob = self.core.nlobatto
-        self.Tn, self.mun = lobattoevaluations(self.P, fT, fmu, nlob)
-        self.Tlev = as_f64([fT(p) for p in self.P])          # planckevaluations, discretized.jl:51
-        self.Tk = nodevalues(self.Tn, nlob)
-        self.muk = nodevalues(self.mun, nlob)
-        ng = len(self.gases)
-        conc = np.zeros((ng, self.K), order="F")
-        for gi, g_ in enumerate(self.gases):
-            for k in range(self.K):
-                conc[gi, k] = g_.fC(self.Tk[k], self.Pk[k])
-        self.conc = conc
-        ct = np.zeros((len(self.baked), self.K), order="F")
-        for ti, g_ in enumerate(self.baked):
-            for k in range(self.K):
-                ct[ti, k] = g_.fC(self.Tk[k], self.Pk[k])
-        self.conc_tab = ct
-        nc = len(self.U.cia)
-        self.cia_P1 = np.zeros((nc, self.K), order="F")
-        self.cia_P2 = np.zeros((nc, self.K), order="F")
-        for ci, x in enumerate(self.U.cia):
+        Tn, mun = lobattoevaluations(self.P, fT, fmu, nlob)
+        Tlev = as_f64([fT(p) for p in self.P])               # planckevaluations, discretized.jl:51
+        Tk, muk = nodevalues(Tn, nlob), nodevalues(mun, nlob)
+
+        def at_nodes(fs, partial=False):      # f(T_k, P_k) of every member and node; partial: the partial pressure, times P_k
+            a = np.zeros((len(fs), self.K), order="F")
+            for i, f in enumerate(fs):
+                for k in range(self.K):
+                    a[i, k] = f(Tk[k], self.Pk[k]) * (self.Pk[k] if partial else 1.0)
+            return a
+
+        conc = at_nodes([g_.fC for g_ in self.gases])
+        conc_tab = at_nodes([g_.fC for g_ in self.baked])
+        for x in self.U.cia:
             if isinstance(x, Continuum):
-                x.check_temperatures(self.Tk)
-            for k in range(self.K):
-                self.cia_P1[ci, k] = self.Pk[k] * x.g1.concentration(self.Tk[k], self.Pk[k])   # cia…jl:378-382
-                self.cia_P2[ci, k] = self.Pk[k] * x.g2.concentration(self.Tk[k], self.Pk[k])
+                x.check_temperatures(Tk)
+        P1 = at_nodes([x.g1.concentration for x in self.U.cia], partial=True)      # cia…jl:378-382
+        P2 = at_nodes([x.g2.concentration for x in self.U.cia], partial=True)
+        return Tn, mun, Tlev, Tk, muk, conc, conc_tab, P1, P2
+
+    def _state(self, fT, fmu):
+        (self.Tn, self.mun, self.Tlev, self.Tk, self.muk, self.conc, self.conc_tab, self.cia_P1,
+         self.cia_P2) = self._node_inputs(fT, fmu)
         semi = [g_ for g_ in self.U.gas if isinstance(g_, SemiGrayGas)]
         if self.U.fun or semi:
             ex = np.zeros((self.K, self.nnu))
@@ -1287,8 +1288,7 @@ class Column:
         (whose cross-sections are shared by all B states, as in jacobian!); function absorbers cannot be batched."""
         self._ensure_resident()
         B = len(Ts)
-        nlob = self.core.nlobatto
-        nn = nlob * self.nl
+        nn = self.core.nlobatto * self.nl
         ng, nt, nc = len(self.gases), len(self.baked), len(self.U.cia)
         Tn_all, mun_all = np.zeros((B, nn)), np.zeros((B, nn))
         Tlev_all = np.zeros((B, self.np))
@@ -1296,29 +1296,13 @@ class Column:
         ctab_all = np.zeros((B, max(nt, 1) * self.K))
         P1_all, P2_all = np.zeros((B, max(nc, 1) * self.K)), np.zeros((B, max(nc, 1) * self.K))
         for b in range(B):
-            fT = formprofile(self.P, Ts[b])
             mu_b = mus if (mus is None or np.ndim(mus) == 0) else mus[b]
             fmu = formprofile(self.P, mu_b) if mu_b is not None else self._fmu
-            Tn, mun = lobattoevaluations(self.P, fT, fmu, nlob)
-            Tk = nodevalues(Tn, nlob)
+            Tn, mun, Tlev_all[b], _, _, *members = self._node_inputs(formprofile(self.P, Ts[b]), fmu)
             Tn_all[b], mun_all[b] = Tn.ravel(order="F"), mun.ravel(order="F")
-            Tlev_all[b] = [fT(p) for p in self.P]
-            for arr, members, n in ((conc_all, self.gases, ng), (ctab_all, self.baked, nt)):
-                if n:
-                    cc = np.zeros((n, self.K), order="F")
-                    for gi, g_ in enumerate(members):
-                        for k in range(self.K):
-                            cc[gi, k] = g_.fC(Tk[k], self.Pk[k])
-                    arr[b] = cc.ravel(order="F")
-            if nc:
-                p1, p2 = np.zeros((nc, self.K), order="F"), np.zeros((nc, self.K), order="F")
-                for ci, x in enumerate(self.U.cia):
-                    if isinstance(x, Continuum):
-                        x.check_temperatures(Tk)
-                    for k in range(self.K):
-                        p1[ci, k] = self.Pk[k] * x.g1.concentration(Tk[k], self.Pk[k])      # cia…jl:378-382
-                        p2[ci, k] = self.Pk[k] * x.g2.concentration(Tk[k], self.Pk[k])
-                P1_all[b], P2_all[b] = p1.ravel(order="F"), p2.ravel(order="F")
+            for rows, a in zip((conc_all, ctab_all, P1_all, P2_all), members):
+                if a.size:
+                    rows[b] = a.ravel(order="F")
         Fup, Fdn = np.zeros((B, self.np)), np.zeros((B, self.np))
         check(lib().cs_column_batch(self.ctx.handle, B, dptr(Tn_all), dptr(mun_all), dptr(Tlev_all), dptr(conc_all),
                                     dptr(ctab_all) if nt else None, dptr(P1_all) if nc else None, dptr(P2_all) if nc else None,

@@ -183,12 +183,6 @@ struct TableDev {
     DevBuf Z;  // [nT*nP][nnu] ln sigma
 };
 
-struct ColTab {
-    int slot = 0;
-    uint64_t generation = 0;   // of the table slot the weights were formed for
-    DevBuf W, conc;  // [M][K], [K]
-};
-
 // AcceleratedAbsorber (absorbers.jl:114-203): ln sigma on pressure knots, per wavenumber
 struct AccelDev {
     bool present = false;
@@ -198,11 +192,6 @@ struct AccelDev {
     int nk = 0;
     std::vector<double> lnP, nu;   // knots (ascending), wavenumbers
     DevBuf L;                      // [nk][nnu]
-};
-struct ColAccel {
-    int slot = -1;                 // -1: none
-    uint64_t generation = 0;       // of the accelerated-absorber slot the cells were formed for
-    DevBuf cell, x, xa, xb;        // per node: knot interval and the three abscissae of the LinearInterpolator formula
 };
 
 struct CiaBandHost {
@@ -214,18 +203,6 @@ struct CiaDev {
     uint64_t generation = 0;   // bumped whenever the slot's bands change (a resident column's per-grid tables belong to one generation)
     std::vector<CiaBandHost> bands;
     int filled = 0;
-};
-struct ColCia {
-    int slot = 0, flags = 0;
-    DevBuf bands, st, rho1, rho2, rhoa;
-    DevBuf Tr;            // CS_CIA_RADIATION: [K] node temperatures, where R(nu, T_k) is formed (upload_cia_states)
-    DevBuf fac;           // k_cia_tab: [K] Lo^2 rho1 rho2 / rhoa
-    DevBuf tab, toff;     // k_cia_tab: ln k of every band at the temperature of every node state, [toff[b] + k * nb + c]
-    DevBuf tband, cell, fx;   // k_flux: per 64-point tile the bands that reach it [ntile][CS_CIA_ACT] (-1: none), and per (slot, wavenumber)
-                              // the sample cell of that band (-1: outside it) and the position in the cell -- the grid's, not the state's
-    uint64_t generation = 0;  // of the CIA slot these per-grid tables were built from
-    int nband = 0;
-    int max_overlap = 0;  // bands of this object reaching one 64-point tile of the column's grid, at most (k_flux holds CS_CIA_ACT)
 };
 
 // interpolated far wings: interval levels of a nu grid (descending interval size; intervals of all levels form one list)
@@ -261,6 +238,39 @@ struct GroupStates {
     DevBuf gmax;              // [N] max Lorentz width over the members (gamma_bound; Voigt fast path)
     std::vector<double> h_T, h_gmax;   // host copies of T and gmax [N] (ph_wide_regions: which chi-regions these states let PHCO2 interpolate)
     DevBuf lrt, qref;         // state_tables(): [N], [N][niso]
+};
+// ... and a table, a CIA pair, the accelerated absorber's knots (one builder and one launcher each): the column's own records, a batch's, the context's
+struct TabStates { DevBuf W, conc; };                    // table_states: weights [nT * nP][N] and concentrations [N]
+struct CiaStates { DevBuf st, rho1, rho2, rhoa, Tr; };   // cia_states: CiaState [nband][N]; the pair's densities [amagat] and the air's [cm^-3],
+                                                         // [N] each; Tr: CS_CIA_RADIATION only, the temperatures [N], where R(nu, T) is formed
+struct AccelStates { DevBuf cell, x, xa, xb; };          // accel_states: knot interval and the three abscissae of the LinearInterpolator formula, [N] each
+
+struct ColTab {
+    int slot = 0;
+    uint64_t generation = 0;   // of the table slot the weights were formed for
+    TabStates st;              // at the K node states
+};
+struct ColAccel {
+    int slot = -1;             // -1: none
+    uint64_t generation = 0;   // of the accelerated-absorber slot the cells were formed for
+    AccelStates st;            // at the K node pressures
+};
+// what a CIA pair fixes on the column's grid, whatever the states (cia_grid; kept while the column names the same slots and generations)
+struct CiaGrid {
+    DevBuf bands;             // CiaBand [nband]: the addresses and sizes of the slot's band tables
+    DevBuf fac;               // k_cia_tab: [K] Lo^2 rho1 rho2 / rhoa
+    DevBuf tab, toff;         // k_cia_tab: ln k of every band at the temperature of every node state, [toff[b] + k * nb + c]
+    DevBuf tband, cell, fx;   // k_flux: per 64-point tile the bands that reach it [ntile][CS_CIA_ACT] (-1: none), and per (slot, wavenumber)
+                              // the sample cell of that band (-1: outside it) and the position in the cell
+    int nband = 0;
+    int maxnb = 0;            // samples of the longest band (k_cia_tab's grid)
+    int max_overlap = 0;      // bands of this object reaching one 64-point tile of the column's grid, at most (k_flux holds CS_CIA_ACT)
+};
+struct ColCia {
+    int slot = 0, flags = 0;
+    uint64_t generation = 0;  // of the CIA slot the per-grid part was built from
+    CiaGrid grid;
+    CiaStates st;             // at the K node states
 };
 
 // a gas of the column as the caller named it (conc is laid out [ngas, K] over these)
@@ -590,7 +600,8 @@ struct cs_ctx {
     std::vector<std::shared_ptr<GasTable>> merged;   // merged tables (keyed by their members' (slot, generation)), least recently used first
     double far_s = 1e6;
     DevBuf reinterp;        // [64][32] then [64][16]: values at the 64 nodes of an interval from those at its 32 / 16 nodes (build_reinterp)
-    DevBuf tmpA, tmpB, tmpC;   // cs_table_eval, cs_accel_eval, cs_devfn_batch: no step of the column names them
+    DevBuf tmpA, tmpB, tmpC;   // cs_devfn_batch, cs_faddeeva_batch (A, B); the output of those and of cs_table_eval, cs_accel_eval (C) ...
+    TabStates tmpTab; AccelStates tmpAccel;   // ... which evaluate at one state of their own: no step of the column names any of these
 };
 static PhRules ph_rules(const cs_ctx &ctx)
 {
@@ -782,7 +793,7 @@ int flux_form(const cs_ctx *ctx, const Column &c, size_t *shmem, int *nblk, int 
 {
     if (ctx->set.flux_form == 1 || !c.tab.empty() || c.gas.empty()) return 0;   // (baked tables are added between wings and CIA pairs: own pass)
     for (auto &cc : c.cia)
-        if (cc.max_overlap > CS_CIA_ACT) return 0;
+        if (cc.grid.max_overlap > CS_CIA_ACT) return 0;
     const int np = c.np, ns = c.nstream, K = c.K;
     const size_t lim = 160 * 1024 - 4096;
     const int nt64_ = (int)((c.nnu + 63) / 64);
@@ -2715,13 +2726,14 @@ int cs_table_clear(cs_ctx *ctx, int table_slot)
 #ifndef CS_TABLE_NSUB
 #define CS_TABLE_NSUB 2
 #endif
-static int launch_table_eval(hipStream_t s, const double *Z, int M, int64_t nnu, const double *W, int K, const double *conc, double *sigma)
+static int launch_table_eval(hipStream_t s, const TableDev &tb, const TabStates &st, int K, double *sigma)
 {
-    const int nt64 = (int)((nnu + 63) / 64);
+    const int nt64 = (int)((tb.nnu + 63) / 64);
     const int nst = (K + 15) / 16, nsg = (nst + CS_TABLE_NSUB - 1) / CS_TABLE_NSUB;
     const int64_t nblk = (int64_t)((nt64 + 3) / 4) * nsg;
     if (nblk > 0x7fffffffLL) return fail(CS_EINVAL, "too many (tile, state) blocks for the opacity-table kernel");
-    CS_LAUNCH(k_table_eval_mfma<CS_TABLE_NSUB>, dim3((unsigned)nblk), dim3(256), 0, s, Z, M, nnu, nt64, W, K, conc, sigma);
+    CS_LAUNCH(k_table_eval_mfma<CS_TABLE_NSUB>, dim3((unsigned)nblk), dim3(256), 0, s, tb.Z.as<double>(), tb.nT * tb.nP, tb.nnu, nt64,
+              st.W.as<double>(), K, st.conc.as<double>(), sigma);
     return CS_OK;
 }
 
@@ -2745,6 +2757,18 @@ static int table_weights(const TableDev &tb, int K, const double *Tk, const doub
     return CS_OK;
 }
 
+// what table tb needs at N states (T, P): its weights, and element idx of every state's row of conc [N][stride] (NULL: 1 at every state)
+static int table_states(hipStream_t s, const TableDev &tb, int64_t N, const double *T, const double *P, const double *conc, int stride, int idx,
+                        TabStates &st)
+{
+    std::vector<double> W, cc(N, 1.0);
+    int rc;
+    if ((rc = table_weights(tb, (int)N, T, P, W))) return rc;
+    if (conc && (rc = gather_conc(conc, idx, stride, N, cc.data()))) return rc;
+    if ((rc = upload(st.W, W.data(), W.size(), s))) return rc;
+    return upload(st.conc, cc.data(), N, s);   // (from pageable memory: both copies have left the host vectors on return)
+}
+
 int cs_table_eval(cs_ctx *ctx, int table_slot, double T, double P, int64_t i0, int64_t n, double *sigma_out)
 {
     if (!ctx || table_slot < 0 || table_slot >= CS_MAX_TABLE || !ctx->tab[table_slot].present) return fail(CS_EINVAL, "table slot is empty");
@@ -2752,15 +2776,11 @@ int cs_table_eval(cs_ctx *ctx, int table_slot, double T, double P, int64_t i0, i
     if (i0 < 0 || n < 1 || i0 + n > tb.nnu) return fail(CS_EINVAL, "wavenumber range out of bounds");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    std::vector<double> W;
     int rc;
-    if ((rc = table_weights(tb, 1, &T, &P, W))) return rc;
-    const int M = tb.nT * tb.nP;
-    const double one = 1.0;
-    if ((rc = upload(ctx->tmpA, W.data(), M, s)) || (rc = upload(ctx->tmpB, &one, 1, s))) return rc;
+    if ((rc = table_states(s, tb, 1, &T, &P, nullptr, 0, 0, ctx->tmpTab))) return rc;
     HIPCHK(ctx->tmpC.reserve((size_t)tb.nnu * sizeof(double)));
     HIPCHK(hipMemsetAsync(ctx->tmpC.p, 0, (size_t)tb.nnu * sizeof(double), s));
-    if ((rc = launch_table_eval(s, tb.Z.as<double>(), M, tb.nnu, ctx->tmpA.as<double>(), 1, ctx->tmpB.as<double>(), ctx->tmpC.as<double>()))) return rc;
+    if ((rc = launch_table_eval(s, tb, ctx->tmpTab, 1, ctx->tmpC.as<double>()))) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(sigma_out, ctx->tmpC.as<double>() + i0, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -2770,17 +2790,11 @@ int cs_table_eval(cs_ctx *ctx, int table_slot, double T, double P, int64_t i0, i
 static int upload_tables(cs_ctx *ctx, const double *conc_tab)
 {
     Column &c = ctx->col;
-    hipStream_t s = ctx->stream;
     const int nt = (int)c.tab.size();
-    std::vector<double> W, cc(c.K);
     int rc;
-    for (int t = 0; t < nt; t++) {
-        TableDev &tb = ctx->tab[c.tab[t].slot];
-        if ((rc = table_weights(tb, c.K, c.h_Tk.data(), c.h_Pk.data(), W))) return rc;
-        if ((rc = gather_conc(conc_tab, t, nt, c.K, cc.data()))) return rc;
-        if ((rc = upload(c.tab[t].W, W.data(), W.size(), s)) || (rc = upload(c.tab[t].conc, cc.data(), c.K, s))) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(s));
+    for (int t = 0; t < nt; t++)
+        if ((rc = table_states(ctx->stream, ctx->tab[c.tab[t].slot], c.K, c.h_Tk.data(), c.h_Pk.data(), conc_tab, nt, t, c.tab[t].st))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return CS_OK;
 }
 
@@ -2848,37 +2862,35 @@ int cs_cia_clear(cs_ctx *ctx, int cia_slot)
 }
 
 // per-state inputs of a CIA pair: temperature cells of every band + number densities (cia(k,T,Pa,P1,P2), :295-303).
-// Kn states with temperatures T, air pressures Pa and partial pressures P1/P2 (element k at P[idx + stride*k]); results go to the
-// given device buffers (a column's own, or a batch's).  An object flagged CS_CIA_RADIATION also gets the temperatures themselves (dT):
-// R(nu, T_k) follows the node states like everything else here
-static int upload_cia_states(cs_ctx *ctx, int slot, int flags, int Kn, const double *T, const double *Pa, const double *P1,
-                             const double *P2, int stride, int idx, DevBuf &dst, DevBuf &d1, DevBuf &d2, DevBuf &da, DevBuf &dT)
+// K states with temperatures T, air pressures Pa and partial pressures P1/P2 (element k at P[idx + stride*k]).  An object flagged
+// CS_CIA_RADIATION also gets the temperatures themselves (Tr): R(nu, T_k) follows the node states like everything else here
+static int cia_states(hipStream_t s, const CiaDev &cd, int flags, int K, const double *T, const double *Pa, const double *P1, const double *P2,
+                      int stride, int idx, CiaStates &out)
 {
-    CiaDev &cd = ctx->cia[slot];
-    const int K = Kn, nband = (int)cd.bands.size();
+    const int nband = (int)cd.bands.size();
     const bool extrap = flags & CS_CIA_EXTRAPOLATE, singles = flags & CS_CIA_SINGLES;
     std::vector<CiaState> st((size_t)nband * K);
     for (int b = 0; b < nband; b++) {
         const std::vector<double> &Tg = cd.bands[b].T;
         const int nt = (int)Tg.size();
         for (int k = 0; k < K; k++) {
-            CiaState s;
-            s.use = 0; s.jT = 0; s.fT = 0.0;
+            CiaState q;
+            q.use = 0; q.jT = 0; q.fT = 0.0;
             const double Tk = T[k];
             if (nt == 1) {
-                s.use = singles ? 1 : 0;
+                q.use = singles ? 1 : 0;
             } else {
                 double Te = Tk;
-                if (Tk >= Tg.front() && Tk <= Tg.back()) s.use = 1;                       // :258
-                else if (extrap) { s.use = 1; Te = Tk > Tg.back() ? Tg.back() : Tg.front(); }  // :261-263
-                if (s.use) {
+                if (Tk >= Tg.front() && Tk <= Tg.back()) q.use = 1;                       // :258
+                else if (extrap) { q.use = 1; Te = Tk > Tg.back() ? Tg.back() : Tg.front(); }  // :261-263
+                if (q.use) {
                     int j = (int)(std::upper_bound(Tg.begin(), Tg.end(), Te) - Tg.begin()) - 1;
                     j = std::min(std::max(j, 0), nt - 2);
-                    s.jT = j;
-                    s.fT = (Te - Tg[j]) / (Tg[j + 1] - Tg[j]);
+                    q.jT = j;
+                    q.fT = (Te - Tg[j]) / (Tg[j + 1] - Tg[j]);
                 }
             }
-            st[(size_t)b * K + k] = s;
+            st[(size_t)b * K + k] = q;
         }
     }
     std::vector<double> r1(K), r2(K), ra(K);
@@ -2887,29 +2899,97 @@ static int upload_cia_states(cs_ctx *ctx, int slot, int flags, int Kn, const dou
         r2[k] = (P2[idx + (size_t)stride * k] / kAtm) * (273.15 / T[k]);
         ra[k] = 1e-6 * Pa[k] / (kKb * T[k]);                               // molecules/cm^3, :300
     }
-    hipStream_t s = ctx->stream;
     int rc;
-    if ((rc = upload(dst, st.data(), st.size(), s)) || (rc = upload(d1, r1.data(), K, s)) ||
-        (rc = upload(d2, r2.data(), K, s)) || (rc = upload(da, ra.data(), K, s)) ||
-        ((flags & CS_CIA_RADIATION) && (rc = upload(dT, T, K, s))))
+    if ((rc = upload(out.st, st.data(), st.size(), s)) || (rc = upload(out.rho1, r1.data(), K, s)) ||
+        (rc = upload(out.rho2, r2.data(), K, s)) || (rc = upload(out.rhoa, ra.data(), K, s)) ||
+        ((flags & CS_CIA_RADIATION) && (rc = upload(out.Tr, T, K, s))))
         return rc;
     HIPCHK(hipStreamSynchronize(s));   // the host vectors are locals
     return CS_OK;
 }
-// k_cia over Kn states with the given per-state inputs (a column's own, or a batch's); an object flagged CS_CIA_RADIATION runs k_cia<true>
-static void launch_cia(hipStream_t s, Column &c, ColCia &cc, DevBuf &st, DevBuf &d1, DevBuf &d2, DevBuf &da, DevBuf &dT, int Kn, double *sig)
+// k_cia of pair cc over Kn states with the per-state inputs st (the column's own, or a batch's); an object flagged CS_CIA_RADIATION runs k_cia<true>
+static void launch_cia(hipStream_t s, const Column &c, const ColCia &cc, const CiaStates &st, int Kn, double *sig)
 {
+    const CiaGrid &g = cc.grid;
     if (cc.flags & CS_CIA_RADIATION)
-        CS_LAUNCH(k_cia<true>, dim3((unsigned)c.ntile), dim3(256), 0, s, cc.nband, cc.bands.as<CiaBand>(), st.as<CiaState>(), c.nu.as<double>(),
-                  c.nnu, Kn, d1.as<double>(), d2.as<double>(), da.as<double>(), dT.as<double>(), sig);
+        CS_LAUNCH(k_cia<true>, dim3((unsigned)c.ntile), dim3(256), 0, s, g.nband, g.bands.as<CiaBand>(), st.st.as<CiaState>(), c.nu.as<double>(),
+                  c.nnu, Kn, st.rho1.as<double>(), st.rho2.as<double>(), st.rhoa.as<double>(), st.Tr.as<double>(), sig);
     else
-        CS_LAUNCH(k_cia<false>, dim3((unsigned)c.ntile), dim3(256), 0, s, cc.nband, cc.bands.as<CiaBand>(), st.as<CiaState>(), c.nu.as<double>(),
-                  c.nnu, Kn, d1.as<double>(), d2.as<double>(), da.as<double>(), (const double *)nullptr, sig);
+        CS_LAUNCH(k_cia<false>, dim3((unsigned)c.ntile), dim3(256), 0, s, g.nband, g.bands.as<CiaBand>(), st.st.as<CiaState>(), c.nu.as<double>(),
+                  c.nnu, Kn, st.rho1.as<double>(), st.rho2.as<double>(), st.rhoa.as<double>(), (const double *)nullptr, sig);
 }
-static int upload_cia_state(cs_ctx *ctx, ColCia &cc, const double *P1, const double *P2, int stride, int idx)
+// the pair as the flux kernel and k_cia_tab take it
+static CiaPairDev cia_pair(const ColCia &cc)
 {
-    Column &c = ctx->col;
-    return upload_cia_states(ctx, cc.slot, cc.flags, c.K, c.h_Tk.data(), c.h_Pk.data(), P1, P2, stride, idx, cc.st, cc.rho1, cc.rho2, cc.rhoa, cc.Tr);
+    const CiaGrid &g = cc.grid;
+    CiaPairDev pd;
+    pd.nband = g.nband; pd.bands = g.bands.as<CiaBand>(); pd.st = cc.st.st.as<CiaState>(); pd.tab = g.tab.as<double>();
+    pd.toff = g.toff.as<int64_t>(); pd.rho1 = cc.st.rho1.as<double>(); pd.rho2 = cc.st.rho2.as<double>(); pd.rhoa = cc.st.rhoa.as<double>();
+    pd.tband = g.tband.as<int32_t>(); pd.cell = g.cell.as<int32_t>(); pd.fx = g.fx.as<double>();
+    pd.nslot = std::min(std::max(g.max_overlap, 1), (int)CS_CIA_ACT);
+    pd.fac = g.fac.as<double>();
+    pd.Tr = (cc.flags & CS_CIA_RADIATION) ? cc.st.Tr.as<double>() : nullptr;
+    return pd;
+}
+
+// what the bands of slot cd fix on the column's grid: the band descriptors; for k_flux, room for ln k at every state's temperature, per
+// tile the bands that reach it and per wavenumber its cell in each
+static int cia_grid(cs_ctx *ctx, const CiaDev &cd, CiaGrid &g)
+{
+    const Column &c = ctx->col;
+    const int nt64 = (int)((c.nnu + 63) / 64);
+    g = CiaGrid();
+    g.nband = (int)cd.bands.size();
+    std::vector<CiaBand> hb(g.nband);
+    std::vector<int64_t> toff(g.nband);
+    int64_t tot = 0;
+    for (int b = 0; b < g.nband; b++) {
+        hb[b].nu = cd.bands[b].dnu.as<double>();
+        hb[b].lnk = cd.bands[b].dlnk.as<double>();
+        hb[b].nb = (int)cd.bands[b].nu.size();
+        hb[b].nt = (int)cd.bands[b].T.size();
+        toff[b] = tot;
+        tot += (int64_t)c.K * hb[b].nb;
+        g.maxnb = std::max(g.maxnb, hb[b].nb);
+    }
+    std::vector<int32_t> tband((size_t)nt64 * CS_CIA_ACT, -1);
+    for (int ti = 0; ti < nt64; ti++) {
+        const double vlo = c.h_nu[(int64_t)ti * 64], vhi = c.h_nu[std::min<int64_t>((int64_t)ti * 64 + 63, c.nnu - 1)];
+        int n = 0;
+        for (int b = 0; b < g.nband; b++)
+            if (cd.bands[b].nu.front() <= vhi && cd.bands[b].nu.back() >= vlo) {
+                if (n < CS_CIA_ACT) tband[(size_t)ti * CS_CIA_ACT + n] = b;
+                n++;
+            }
+        g.max_overlap = std::max(g.max_overlap, n);
+    }
+    const int nslot = std::min(std::max(g.max_overlap, 1), (int)CS_CIA_ACT);
+    std::vector<int32_t> cell((size_t)nslot * c.nnu, -1);
+    std::vector<double> fx((size_t)nslot * c.nnu, 0.0);
+    for (int ti = 0; ti < nt64; ti++)
+        for (int q = 0; q < nslot; q++) {
+            const int b = tband[(size_t)ti * CS_CIA_ACT + q];
+            if (b < 0) continue;
+            const std::vector<double> &v = cd.bands[b].nu;
+            for (int64_t i = (int64_t)ti * 64; i < std::min<int64_t>((int64_t)ti * 64 + 64, c.nnu); i++) {
+                const double x = c.h_nu[i];
+                if (!(v.front() <= x && x <= v.back())) continue;      // Phi.G.xa <= nu <= Phi.G.xb, :255
+                int lo = 0, hi = (int)v.size() - 1;                      // cell with v[lo] <= x < v[lo + 1] (the last one for x == v.back()): k_cia's search
+                while (hi - lo > 1) { const int m = (lo + hi) >> 1; if (v[m] <= x) lo = m; else hi = m; }
+                cell[(size_t)q * c.nnu + i] = lo;
+                fx[(size_t)q * c.nnu + i] = (x - v[lo]) / (v[lo + 1] - v[lo]);
+            }
+        }
+    hipStream_t s = ctx->stream;
+    int rc;
+    if ((rc = upload(g.bands, hb.data(), hb.size(), s)) || (rc = upload(g.toff, toff.data(), toff.size(), s)) ||
+        (rc = upload(g.tband, tband.data(), tband.size(), s)) || (rc = upload(g.cell, cell.data(), cell.size(), s)) ||
+        (rc = upload(g.fx, fx.data(), fx.size(), s)))
+        return rc;
+    HIPCHK(g.tab.reserve((size_t)tot * sizeof(double)));
+    HIPCHK(g.fac.reserve((size_t)c.K * sizeof(double)));
+    HIPCHK(hipStreamSynchronize(s));   // (the host vectors are locals)
+    return CS_OK;
 }
 
 int cs_column_set_cia(cs_ctx *ctx, int ncia, const int *cia_slots, const int *flags, const double *P1, const double *P2)
@@ -2918,92 +2998,40 @@ int cs_column_set_cia(cs_ctx *ctx, int ncia, const int *cia_slots, const int *fl
     if (ncia < 0 || ncia > CS_MAX_CIA) return fail(CS_EINVAL, "ncia out of range");
     Column &c = ctx->col;
     HIPCHK(hipSetDevice(ctx->device));
-    for (int t = 0; t < ncia; t++)
-        if (cia_slots[t] < 0 || cia_slots[t] >= CS_MAX_CIA || !ctx->cia[cia_slots[t]].present) {
-            c.cia.clear();
-            return fail(CS_EINVAL, "CIA slot %d is empty", cia_slots[t]);
-        }
-    for (int t = 0; t < ncia && flags; t++)
-        if (flags[t] & ~(CS_CIA_EXTRAPOLATE | CS_CIA_SINGLES | CS_CIA_RADIATION)) {
-            c.cia.clear();
-            return fail(CS_EINVAL, "CIA flags %d: only CS_CIA_EXTRAPOLATE, CS_CIA_SINGLES and CS_CIA_RADIATION are defined", flags[t]);
-        }
-    // what depends on the grid and the tables alone (band descriptors, sample cells of every wavenumber) is kept while the pairs named
-    // are the ones the column already holds: an RCM loop re-sets its pairs on every call for the partial pressures only
-    bool same = (int)c.cia.size() == ncia;
-    for (int t = 0; t < ncia && same; t++)
-        same = c.cia[t].slot == cia_slots[t] && c.cia[t].generation == ctx->cia[cia_slots[t]].generation;
-    if (!same) {
-        drop_graph(c);
-        c.cia.clear();
-        c.cia.resize(ncia);
-    }
-    int rc;
-    const int nt64 = (int)((c.nnu + 63) / 64);
-    for (int t = 0; t < ncia; t++) {
-        ColCia &cc = c.cia[t];
-        cc.slot = cia_slots[t];
-        const int fl = flags ? flags[t] : 0;
-        if (same && ((fl ^ cc.flags) & CS_CIA_RADIATION)) drop_graph(c);   // (the captured launches name the kernels of the other kind)
-        cc.flags = fl;
-        CiaDev &cd = ctx->cia[cc.slot];
+    const int res = [&]() -> int {   // one way out: whatever fails in here, the column is left without pairs
+        for (int t = 0; t < ncia; t++)
+            if (cia_slots[t] < 0 || cia_slots[t] >= CS_MAX_CIA || !ctx->cia[cia_slots[t]].present)
+                return fail(CS_EINVAL, "CIA slot %d is empty", cia_slots[t]);
+        for (int t = 0; t < ncia && flags; t++)
+            if (flags[t] & ~(CS_CIA_EXTRAPOLATE | CS_CIA_SINGLES | CS_CIA_RADIATION))
+                return fail(CS_EINVAL, "CIA flags %d: only CS_CIA_EXTRAPOLATE, CS_CIA_SINGLES and CS_CIA_RADIATION are defined", flags[t]);
+        // what depends on the grid and the tables alone (cia_grid) is kept while the pairs named are the ones the column already holds: an
+        // RCM loop re-sets its pairs on every call for the partial pressures only
+        bool same = (int)c.cia.size() == ncia;
+        for (int t = 0; t < ncia && same; t++)
+            same = c.cia[t].slot == cia_slots[t] && c.cia[t].generation == ctx->cia[cia_slots[t]].generation;
         if (!same) {
-            cc.generation = cd.generation;
-            cc.nband = (int)cd.bands.size();
-            std::vector<CiaBand> hb(cc.nband);
-            for (int b = 0; b < cc.nband; b++) {
-                hb[b].nu = cd.bands[b].dnu.as<double>();
-                hb[b].lnk = cd.bands[b].dlnk.as<double>();
-                hb[b].nb = (int)cd.bands[b].nu.size();
-                hb[b].nt = (int)cd.bands[b].T.size();
-            }
-            // k_flux: room for ln k at every state's temperature; per tile the bands that reach it; per wavenumber its cell in each
-            std::vector<int64_t> toff(cc.nband);
-            int64_t tot = 0;
-            for (int b = 0; b < cc.nband; b++) { toff[b] = tot; tot += (int64_t)c.K * hb[b].nb; }
-            std::vector<int32_t> tband((size_t)nt64 * CS_CIA_ACT, -1);
-            cc.max_overlap = 0;
-            for (int ti = 0; ti < nt64; ti++) {
-                const double vlo = c.h_nu[(int64_t)ti * 64], vhi = c.h_nu[std::min<int64_t>((int64_t)ti * 64 + 63, c.nnu - 1)];
-                int n = 0;
-                for (int b = 0; b < cc.nband; b++)
-                    if (cd.bands[b].nu.front() <= vhi && cd.bands[b].nu.back() >= vlo) {
-                        if (n < CS_CIA_ACT) tband[(size_t)ti * CS_CIA_ACT + n] = b;
-                        n++;
-                    }
-                cc.max_overlap = std::max(cc.max_overlap, n);
-            }
-            const int nslot = std::min(std::max(cc.max_overlap, 1), (int)CS_CIA_ACT);
-            std::vector<int32_t> cell((size_t)nslot * c.nnu, -1);
-            std::vector<double> fx((size_t)nslot * c.nnu, 0.0);
-            for (int ti = 0; ti < nt64; ti++)
-                for (int q = 0; q < nslot; q++) {
-                    const int b = tband[(size_t)ti * CS_CIA_ACT + q];
-                    if (b < 0) continue;
-                    const std::vector<double> &g = cd.bands[b].nu;
-                    for (int64_t i = (int64_t)ti * 64; i < std::min<int64_t>((int64_t)ti * 64 + 64, c.nnu); i++) {
-                        const double v = c.h_nu[i];
-                        if (!(g.front() <= v && v <= g.back())) continue;      // Phi.G.xa <= nu <= Phi.G.xb, :255
-                        int lo = 0, hi = (int)g.size() - 1;                      // cell with g[lo] <= v < g[lo + 1] (the last one for v == g.back()): k_cia's search
-                        while (hi - lo > 1) { const int m = (lo + hi) >> 1; if (g[m] <= v) lo = m; else hi = m; }
-                        cell[(size_t)q * c.nnu + i] = lo;
-                        fx[(size_t)q * c.nnu + i] = (v - g[lo]) / (g[lo + 1] - g[lo]);
-                    }
-                }
-            if ((rc = upload(cc.bands, hb.data(), hb.size(), ctx->stream)) || (rc = upload(cc.toff, toff.data(), toff.size(), ctx->stream)) ||
-                (rc = upload(cc.tband, tband.data(), tband.size(), ctx->stream)) || (rc = upload(cc.cell, cell.data(), cell.size(), ctx->stream)) ||
-                (rc = upload(cc.fx, fx.data(), fx.size(), ctx->stream))) {
-                c.cia.clear();
-                return rc;
-            }
-            HIPCHK(cc.tab.reserve((size_t)tot * sizeof(double)));
-            HIPCHK(cc.fac.reserve((size_t)c.K * sizeof(double)));
-            HIPCHK(hipStreamSynchronize(ctx->stream));   // (the host vectors are locals)
+            drop_graph(c);
+            c.cia.clear();
+            c.cia.resize(ncia);
         }
-        if ((rc = upload_cia_state(ctx, cc, P1, P2, ncia, t))) { c.cia.clear(); return rc; }
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return CS_OK;
+        int rc;
+        for (int t = 0; t < ncia; t++) {
+            ColCia &cc = c.cia[t];
+            const CiaDev &cd = ctx->cia[cia_slots[t]];
+            const int fl = flags ? flags[t] : 0;
+            if (same && ((fl ^ cc.flags) & CS_CIA_RADIATION)) drop_graph(c);   // (the captured launches name the kernels of the other kind)
+            cc.slot = cia_slots[t];
+            cc.flags = fl;
+            cc.generation = cd.generation;
+            if (!same && (rc = cia_grid(ctx, cd, cc.grid))) return rc;
+            if ((rc = cia_states(ctx->stream, cd, fl, c.K, c.h_Tk.data(), c.h_Pk.data(), P1, P2, ncia, t, cc.st))) return rc;
+        }
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return CS_OK;
+    }();
+    if (res) c.cia.clear();
+    return res;
 }
 
 static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLog *log, bool *near_plane_live = nullptr, FluxFuse *fuse = nullptr);
@@ -3048,12 +3076,13 @@ int cs_accel_clear(cs_ctx *ctx, int accel_slot)
     return CS_OK;
 }
 
-// knot interval and abscissae of LinearInterpolator(lnP, y, NoBoundaries())(x): the cell of x clamped to the end cells (extrapolation)
-static void accel_cells(const AccelDev &ad, int K, const double *P, std::vector<int32_t> &cell, std::vector<double> &x,
-                        std::vector<double> &xa, std::vector<double> &xb)
+// what the knots of ad need at N pressures: knot interval and abscissae of LinearInterpolator(lnP, y, NoBoundaries())(x), the cell of x
+// clamped to the end cells (extrapolation)
+static int accel_states(hipStream_t s, const AccelDev &ad, int N, const double *P, AccelStates &st)
 {
-    cell.resize(K); x.resize(K); xa.resize(K); xb.resize(K);
-    for (int k = 0; k < K; k++) {
+    std::vector<int32_t> cell(N);
+    std::vector<double> x(N), xa(N), xb(N);
+    for (int k = 0; k < N; k++) {
         x[k] = std::log(P[k]);
         int i = (int)(std::upper_bound(ad.lnP.begin(), ad.lnP.end(), x[k]) - ad.lnP.begin()) - 1;
         i = std::min(std::max(i, 0), ad.nk - 2);
@@ -3061,6 +3090,15 @@ static void accel_cells(const AccelDev &ad, int K, const double *P, std::vector<
         xa[k] = ad.lnP[i];
         xb[k] = ad.lnP[i + 1];
     }
+    int rc;
+    if ((rc = upload(st.cell, cell.data(), N, s)) || (rc = upload(st.x, x.data(), N, s)) || (rc = upload(st.xa, xa.data(), N, s))) return rc;
+    return upload(st.xb, xb.data(), N, s);   // (from pageable memory: the copies have left the host vectors on return)
+}
+// sigma[k][nu] = base (+ extra[k][nu]) + exp of the ln P-interpolated ln sigma, at N states (absorbers.jl:203)
+static void launch_accel(hipStream_t s, const AccelDev &ad, const AccelStates &st, int N, double base, const double *extra, double *sigma)
+{
+    CS_LAUNCH(k_accel_eval, dim3((unsigned)((ad.nnu + 255) / 256), N), dim3(256), 0, s, ad.L.as<double>(), ad.nnu, N, st.cell.as<int32_t>(),
+              st.x.as<double>(), st.xa.as<double>(), st.xb.as<double>(), base, extra, sigma);
 }
 
 int cs_accel_eval(cs_ctx *ctx, int accel_slot, double P, int64_t i0, int64_t n, double *sigma_out)
@@ -3071,17 +3109,10 @@ int cs_accel_eval(cs_ctx *ctx, int accel_slot, double P, int64_t i0, int64_t n, 
     if (!(P > 0)) return fail(CS_EINVAL, "pressure must be positive");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    std::vector<int32_t> cell;
-    std::vector<double> x, xa, xb;
-    accel_cells(ad, 1, &P, cell, x, xa, xb);
-    DevBuf dc, dx, da, db;
     int rc;
-    if ((rc = upload(dc, cell.data(), 1, s)) || (rc = upload(dx, x.data(), 1, s)) || (rc = upload(da, xa.data(), 1, s)) ||
-        (rc = upload(db, xb.data(), 1, s)))
-        return rc;
+    if ((rc = accel_states(s, ad, 1, &P, ctx->tmpAccel))) return rc;
     HIPCHK(ctx->tmpC.reserve((size_t)ad.nnu * sizeof(double)));
-    CS_LAUNCH(k_accel_eval, dim3((unsigned)((ad.nnu + 255) / 256), 1), dim3(256), 0, s, ad.L.as<double>(), ad.nnu, 1, dc.as<int32_t>(),
-                       dx.as<double>(), da.as<double>(), db.as<double>(), 0.0, (const double *)nullptr, ctx->tmpC.as<double>());
+    launch_accel(s, ad, ctx->tmpAccel, 1, 0.0, nullptr, ctx->tmpC.as<double>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(sigma_out, ctx->tmpC.as<double>() + i0, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -3100,15 +3131,9 @@ int cs_column_set_accel(cs_ctx *ctx, int accel_slot)
     AccelDev &ad = ctx->accel[accel_slot];
     if (ad.nnu != c.nnu || !std::equal(ad.nu.begin(), ad.nu.end(), c.h_nu.begin())) return fail(CS_EINVAL, "wavenumber grids differ");
     HIPCHK(hipSetDevice(ctx->device));
-    std::vector<int32_t> cell;
-    std::vector<double> x, xa, xb;
-    accel_cells(ad, c.K, c.h_Pk.data(), cell, x, xa, xb);
     int rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = upload(c.accel.cell, cell.data(), c.K, s)) || (rc = upload(c.accel.x, x.data(), c.K, s)) ||
-        (rc = upload(c.accel.xa, xa.data(), c.K, s)) || (rc = upload(c.accel.xb, xb.data(), c.K, s)))
-        return rc;
-    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = accel_states(ctx->stream, ad, c.K, c.h_Pk.data(), c.accel.st))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     c.accel.slot = accel_slot;
     c.accel.generation = ad.generation;
     return CS_OK;
@@ -3396,6 +3421,7 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     const bool shared_sigma = c.accel.slot >= 0;   // AcceleratedAbsorber: cross-sections do not depend on the thermal state (absorbers.jl:203)
     DevBuf dped, dvvh, dTk, dPk, dmuk, dTlev, dsig, dtau, dpart, dF, dranges, dzones, dizones, dF2, dsep, dedge, hot, cold, hot32;
     GroupStates st;   // of one group at all B K states: the next group's take their place
+    TabStates tst; CiaStates cst;   // ... and of one table, of one CIA pair
     if ((rc = upload(dTk, Tk.data(), BK, s)) || (rc = upload(dPk, Pk.data(), BK, s)) || (rc = upload(dmuk, muk.data(), BK, s)) ||
         (rc = upload(dTlev, T_levels, (size_t)B * np, s)))
         return rc;
@@ -3461,37 +3487,20 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     }
     // baked gases of the column at all B*K states: the Gas functor fC(T,P)*exp(Phi(T, ln P)) (gases.jl:85,278) -- what RCM holds
     // inside its AcceleratedAbsorber (radiative_convective.jl:6-103)
-    if (!shared_sigma && !c.tab.empty()) {
-        const int nt = (int)c.tab.size();
-        std::vector<double> W, ct(BK);
-        DevBuf dW, dct;
-        for (int t = 0; t < nt; t++) {
-            TableDev &tb = ctx->tab[c.tab[t].slot];
-            if ((rc = table_weights(tb, (int)BK, Tk.data(), Pk.data(), W))) return rc;
-            if ((rc = gather_conc(conc_tab, t, nt, BK, ct.data()))) return rc;
-            if ((rc = upload(dW, W.data(), W.size(), s)) || (rc = upload(dct, ct.data(), BK, s))) return rc;
-            const int M = tb.nT * tb.nP;
-            if ((rc = launch_table_eval(s, tb.Z.as<double>(), M, c.nnu, dW.as<double>(), (int)BK, dct.as<double>(), sig))) return rc;
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(s));   // W/ct host and device buffers are reused by the next table
-        }
+    const int nt = shared_sigma ? 0 : (int)c.tab.size(), nc = shared_sigma ? 0 : (int)c.cia.size();
+    for (int t = 0; t < nt; t++) {
+        const TableDev &tb = ctx->tab[c.tab[t].slot];
+        if ((rc = table_states(s, tb, BK, Tk.data(), Pk.data(), conc_tab, nt, t, tst))) return rc;
+        if ((rc = launch_table_eval(s, tb, tst, (int)BK, sig))) return rc;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));   // the record is reused by the next table
     }
-    if (!shared_sigma && !c.cia.empty()) {
-        const int nc = (int)c.cia.size();
-        DevBuf dst, d1, d2, da, dT;
-        std::vector<double> p1(BK), p2(BK);
-        for (int t = 0; t < nc; t++) {
-            ColCia &ci = c.cia[t];
-            for (int b = 0; b < B; b++)
-                for (int k = 0; k < K; k++) {
-                    p1[(size_t)b * K + k] = cia_P1[(size_t)b * nc * K + t + (size_t)nc * k];
-                    p2[(size_t)b * K + k] = cia_P2[(size_t)b * nc * K + t + (size_t)nc * k];
-                }
-            if ((rc = upload_cia_states(ctx, ci.slot, ci.flags, (int)BK, Tk.data(), Pk.data(), p1.data(), p2.data(), 1, 0, dst, d1, d2, da, dT))) return rc;
-            launch_cia(s, c, ci, dst, d1, d2, da, dT, (int)BK, sig);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(s));
-        }
+    // its CIA pairs: the partial pressures of pair t at state b K + k are element t + nc (b K + k) of the caller's [B][nc * K] rows
+    for (int t = 0; t < nc; t++) {
+        if ((rc = cia_states(s, ctx->cia[c.cia[t].slot], c.cia[t].flags, (int)BK, Tk.data(), Pk.data(), cia_P1, cia_P2, nc, t, cst))) return rc;
+        launch_cia(s, c, c.cia[t], cst, (int)BK, sig);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
     }
     if (bg.streams) log.disp.flags |= CS_DF_RT_STREAMS;
     c.log_last.disp = log.disp;
@@ -3528,9 +3537,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
     double *sig = c.sigma.as<double>();
     const double *extra = c.has_extra ? c.extra.as<double>() : nullptr;
     if (c.accel.slot >= 0) {   // AcceleratedAbsorber: exp of the ln P-interpolated ln sigma (absorbers.jl:203)
-        AccelDev &ad = ctx->accel[c.accel.slot];
-        CS_LAUNCH(k_accel_eval, dim3((unsigned)c.ntile, K), dim3(256), 0, s, ad.L.as<double>(), c.nnu, K, c.accel.cell.as<int32_t>(),
-                           c.accel.x.as<double>(), c.accel.xa.as<double>(), c.accel.xb.as<double>(), c.sigma_gray, extra, sig);
+        launch_accel(s, ctx->accel[c.accel.slot], c.accel.st, K, c.sigma_gray, extra, sig);   // (its grid is the column's: cs_column_set_accel)
     } else if (c.gas.empty()) {
         const int64_t tot = (int64_t)K * c.nnu;
         CS_LAUNCH(k_fill, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, tot, c.sigma_gray, extra, sig);
@@ -3610,26 +3617,15 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
                              fuse ? &fuse->A : nullptr);
         if (fuse) fuse->apply = 1;
     }
-    for (auto &t : c.tab) {  // baked gases: sigma += fC * exp(Phi(T, ln P))
-        TableDev &tb = ctx->tab[t.slot];
-        int rc2;
-        if ((rc2 = launch_table_eval(s, tb.Z.as<double>(), tb.nT * tb.nP, c.nnu, t.W.as<double>(), K, t.conc.as<double>(), sig))) return rc2;
-    }
+    for (auto &t : c.tab)  // baked gases: sigma += fC * exp(Phi(T, ln P))
+        if (const int rc2 = launch_table_eval(s, ctx->tab[t.slot], t.st, K, sig)) return rc2;
     for (auto &cc : c.cia) {  // CIA pairs
         if (fuse) {   // the temperature half of the interpolation per (band, state, sample); k_flux does the rest per point
-            CiaPairDev &pd = fuse->cia[fuse->ncia++];
-            pd.nband = cc.nband; pd.bands = cc.bands.as<CiaBand>(); pd.st = cc.st.as<CiaState>(); pd.tab = cc.tab.as<double>();
-            pd.toff = cc.toff.as<int64_t>(); pd.rho1 = cc.rho1.as<double>(); pd.rho2 = cc.rho2.as<double>(); pd.rhoa = cc.rhoa.as<double>();
-            pd.tband = cc.tband.as<int32_t>(); pd.cell = cc.cell.as<int32_t>(); pd.fx = cc.fx.as<double>();
-            pd.nslot = std::min(std::max(cc.max_overlap, 1), (int)CS_CIA_ACT);
-            pd.fac = cc.fac.as<double>();
-            pd.Tr = (cc.flags & CS_CIA_RADIATION) ? cc.Tr.as<double>() : nullptr;
-            int maxnb = 0;
-            for (auto &b : ctx->cia[cc.slot].bands) maxnb = std::max(maxnb, (int)b.nu.size());
-            CS_LAUNCH(k_cia_tab, dim3((unsigned)((maxnb + 255) / 256), (unsigned)K, (unsigned)cc.nband), dim3(256), 0, s, pd, K);
+            const CiaPairDev &pd = fuse->cia[fuse->ncia++] = cia_pair(cc);
+            CS_LAUNCH(k_cia_tab, dim3((unsigned)((cc.grid.maxnb + 255) / 256), (unsigned)K, (unsigned)cc.grid.nband), dim3(256), 0, s, pd, K);
             continue;
         }
-        launch_cia(s, c, cc, cc.st, cc.rho1, cc.rho2, cc.rhoa, cc.Tr, K, sig);
+        launch_cia(s, c, cc, cc.st, K, sig);
     }
     fork_join(&fk, s);
     c.near_live = false;
@@ -3651,22 +3647,24 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
 static int column_current(cs_ctx *ctx)
 {
     Column &c = ctx->col;
+    // the slot still holds what the column formed its windows, weights, cells or per-grid tables from
+    auto slot_current = [](const auto &sl, uint64_t generation) { return sl.present && sl.generation == generation; };
     for (auto &ug : c.ugas)
-        if (!ctx->gas[ug.slot].present || ctx->gas[ug.slot].generation != ug.generation) {
+        if (!slot_current(ctx->gas[ug.slot], ug.generation)) {
             c.ready = false;
             return fail(CS_ESTATE, "gas slot %d was re-uploaded or cleared after cs_column_setup", ug.slot);
         }
     // the same for the opacity tables and the accelerated absorber the column names by slot: its weights [nT * nP][K] / knot cells were
     // formed for the (T, P) grid / knots the slot held at cs_column_set_tables / cs_column_set_accel
     for (auto &ct : c.tab)
-        if (!ctx->tab[ct.slot].present || ctx->tab[ct.slot].generation != ct.generation)
+        if (!slot_current(ctx->tab[ct.slot], ct.generation))
             return fail(CS_ESTATE, "opacity-table slot %d was baked, uploaded or cleared after cs_column_set_tables: call it again", ct.slot);
-    if (c.accel.slot >= 0 && (!ctx->accel[c.accel.slot].present || ctx->accel[c.accel.slot].generation != c.accel.generation))
+    if (c.accel.slot >= 0 && !slot_current(ctx->accel[c.accel.slot], c.accel.generation))
         return fail(CS_ESTATE, "accelerated-absorber slot %d got other knots (or was cleared) after cs_column_set_accel: call it again", c.accel.slot);
     // ... and for the CIA pairs: their band descriptors hold the addresses of the slot's tables as cs_column_set_cia found them, and
     // cs_cia_begin / cs_cia_clear free those
     for (auto &cc : c.cia)
-        if (!ctx->cia[cc.slot].present || ctx->cia[cc.slot].generation != cc.generation)
+        if (!slot_current(ctx->cia[cc.slot], cc.generation))
             return fail(CS_ESTATE, "CIA slot %d got other bands (or was cleared) after cs_column_set_cia: call it again", cc.slot);
     return CS_OK;
 }

@@ -76,6 +76,56 @@ def test_set_cia_flags(cs, monkeypatch):
     assert one.x.radiation and not one.x.extrapolate and one.x.singles      # one temperature: a single range, evaluated at every T
 
 
+def test_batch_rows_are_the_states_own_arrays(cs, monkeypatch):
+    """Row b of what run_batch hands to cs_column_batch -- [B][n K], member t of node k at t + n k -- is what _state leaves for profile b
+    in conc, conc_tab, cia_P1 and cia_P2 (Column._node_inputs forms both), with two members of every kind whose values depend on T"""
+    import ctypes as C
+    from clearsky_jl_amd import core
+    nu = np.linspace(10.0, 60.0, 11)
+    seen = {}
+
+    real = core.lib()
+
+    class FakeLib:
+        def cs_column_batch(self, h, B, Tn, mun, Tlev, conc, ctab, P1, P2, Fup, Fdn):
+            for name, p in (("conc", conc), ("conc_tab", ctab), ("cia_P1", P1), ("cia_P2", P2)):
+                seen[name] = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_double)), shape=(B, 2 * 9)).copy()
+            return 0
+
+        def __getattr__(self, name):      # (the host-only helpers: cs_lobattonodes)
+            assert name == "cs_lobattonodes", name
+            return getattr(real, name)
+
+    class FakeCtx:
+        handle = None
+
+        def slots_of(self, tables, shifts=None):
+            return [0] * len(tables)
+    ctx = FakeCtx()
+    sl = {f: cs.SpectralLines.synthetic(m, 20, 3, 5000.0, 5100.0) for f, m in (("H2O", 1), ("CO2", 2))}
+    direct = [cs.DirectGas(sl["H2O"], lambda T, P: 0.02 * (T / 250.0), nu), cs.DirectGas(sl["CO2"], lambda T, P: 0.3 + 1e-4 * T, nu)]
+    baked = []
+    for f in (lambda T, P: 0.1 + 2e-4 * T, lambda T, P: 0.5 * (200.0 / T)):      # two baked gases without a bake: what a Column reads of them
+        g = object.__new__(cs.Gas)
+        g.ctx, g.fC, g.nu, g.formula, g.Omega = ctx, f, nu, "N2", cs.AtmosphericDomain((100.0, 500.0), 2, (1.0, 2e5), 2)
+        baked.append(g)
+    pairs = [cs.CIATables(R.band(5.0, 70.0, 7, R.TS, 1, sym)) for sym in ("H2O-CO2", "CO2-H2O")]
+    P = cs.pressuregrid(100.0, 1e5, 5)
+    Ts = [np.linspace(200.0, 300.0, 5), np.linspace(260.0, 240.0, 5), np.full(5, 280.0)]
+    monkeypatch.setattr(core, "lib", lambda: FakeLib())
+    col = cs.Column(P, 9.8, Ts[0], 0.029, 0.0, 0.0, *direct, *baked, *pairs, core=cs.Discretized(4, 3), ctx=ctx, _setup=False, _warn=False)
+    assert col.K == 9 and (len(col.gases), len(col.baked), len(col.U.cia)) == (2, 2, 2)
+    ctx._resident = col
+    col.run_batch(Ts)
+    for b, T in enumerate(Ts):
+        col._state(core.formprofile(P, T), col._fmu)
+        for name in ("conc", "conc_tab", "cia_P1", "cia_P2"):
+            a = getattr(col, name)
+            assert a.shape == (2, 9) and a.flags.f_contiguous and not np.array_equal(a[0], a[1]), name
+            assert np.array_equal(seen[name][b], a.ravel(order="F")), (name, b)
+    assert not np.array_equal(seen["cia_P1"][0], seen["cia_P1"][1]) and not np.array_equal(seen["cia_P1"], seen["cia_P2"])
+
+
 @pytest.mark.parametrize("kind", ["self", "foreign"])
 def test_unit_mapping(cs, kind):
     """Continuum(nu, T, P) against x1 R C n2 / n_ref at table samples and temperatures (where ln C is a knot value).  The CIA functor

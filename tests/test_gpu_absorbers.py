@@ -5,7 +5,8 @@
     baked gases, gray gases, CIA objects and functions, with the scalar-wavenumber line-shape semantics (line_shapes.jl:12-16);
   * AcceleratedAbsorber + update! (absorbers.jl:114-207): knots, ln P interpolation, floatmin clamp, a column and a batch over it
     (what RCM does: radiative_convective.jl:95,113,154-171);
-  * cs_column_batch with baked Gas objects and CIA pairs as members.
+  * cs_column_batch with baked Gas objects and CIA pairs as members; and the strided member rows it reads in place, on two synthetic
+    tables and two synthetic CIA objects (1e-11: tables of 15 and 12 knots, no line sums).
 Tolerances: 1e-11 vs the oracle's line sums, 1e-10 where the numpy opacity-table restatement is involved.
 """
 import math
@@ -207,3 +208,84 @@ def test_batch_with_baked_gas_and_cia_vs_oracle(cs, O, lines):
     with pytest.raises(AssertionError):
         cs.checkpressures(U, 3.0, 1e5)
     ctx.close()
+
+
+# ---- the member rows of a batch, read in place: [B][n K] rows, member t of state (b, k) at t + n (b K + k) --------------------------------
+
+class _Strided:
+    """Two uploaded tables and two CIA objects on grid(200) with no line-by-line gas: np = 7, nlobatto = 3 -> K = 13, and B = 3 profiles
+    are 39 states (past one 32-state block of the table kernel, no multiple of 16).  The tables' concentrations differ and depend on T;
+    so do the pairs' partners (CO2-CO2: f0, f0; CO2-CH4, flagged extrapolate: f0, f1).  Everything here is host arithmetic."""
+    NP, NLOB, NS, G, MU = 7, 3, 4, 9.8, 0.044
+
+    def __init__(self, cs):
+        import tabulated_ref as R
+        self.fC = (lambda T, P: 0.55 + 1e-3 * (T - 250.0)), (lambda T, P: 0.08 * (300.0 / T) ** 2)
+        self.nu = R.grid(200)
+        self.P = cs.pressuregrid(50.0, 1e5, self.NP)
+        self.Pk = cs.nodepressures(self.P, self.NLOB)
+        self.Om = [cs.AtmosphericDomain((150.0, 420.0), 3, (3.0, 2e5), 5), cs.AtmosphericDomain((150.0, 420.0), 4, (3.0, 2e5), 3)]
+        self.Z = [R.table_values(self.nu, 3, 5, -66.0, -52.0), R.table_values(self.nu, 4, 3, -68.0, -54.0)[::-1].copy()]
+        self.cia = [R.overlap_set(3), R.band(self.nu[0] - 1.0, self.nu[-1] + 1.0, 23, R.TS[1:4], 7, "CO2-CH4")
+                    + R.band(self.nu[30], self.nu[150], 9, R.TS[:3], 8, "CO2-CH4")]
+        self.extrap = (False, True)
+        self.Ts = [np.linspace(190.0, 330.0, self.NP), np.linspace(240.0, 300.0, self.NP) - 5.0, np.linspace(170.0, 400.0, self.NP)]
+
+    def nodes(self, cs, T):
+        fT = cs.formprofile(self.P, T)
+        Tn, mun = cs.lobattoevaluations(self.P, fT, cs.formprofile(self.P, self.MU), self.NLOB)
+        return Tn, mun, np.array([fT(p) for p in self.P]), cs.nodevalues(Tn, self.NLOB)
+
+    def oracle(self, cs, O, T, swap_tables=False, swap_pairs=False):
+        """band fluxes and optical depths of profile T; swap_tables: the two tables' concentrations exchanged; swap_pairs: the two pairs'
+        partial pressures exchanged -- what a batch that read another member's element of a row would compute"""
+        Tn, mun, Tlev, Tk = self.nodes(cs, T)
+        f0, f1 = self.fC
+        conc = (f1, f0) if swap_tables else (f0, f1)
+        part = ((f0, f1), (f0, f0)) if swap_pairs else ((f0, f0), (f0, f1))
+        extra = np.zeros((len(Tk), len(self.nu)))
+        for k, (t, p) in enumerate(zip(Tk, self.Pk)):
+            for Om, Z, f in zip(self.Om, self.Z, conc):
+                extra[k] += f(t, p) * O.table_sigma(Z, Om.T, Om.P, t, p)
+            for d, ex, (fa, fb) in zip(self.cia, self.extrap, part):
+                extra[k] += O.cia_sigma(d, self.nu, t, p, p * fa(t, p), p * fb(t, p), extrapolate=ex)
+        return O.fluxes_discretized(self.nu, self.P, self.G, self.NLOB, Tn, mun, Tlev, [], [], [], np.zeros((0, len(Tk))), sigma_extra=extra,
+                                    nstream=self.NS)
+
+    def column(self, cs, lines, ctx, T):
+        from test_gpu_table_eval import _table_gas
+        gases = [_table_gas(cs, ctx, lines, self.nu, Om, Z, f, name) for Om, Z, f, name in zip(self.Om, self.Z, self.fC, ("CO2", "CH4"))]
+        xs = [cs.CIATables(d, extrapolate=ex) for d, ex in zip(self.cia, self.extrap)]
+        return cs.Column(self.P, self.G, T, self.MU, 0.0, 0.0, *gases, *xs, core=cs.Discretized(self.NS, self.NLOB), ctx=ctx, _warn=False)
+
+
+def test_batch_reads_strided_member_rows(cs, O, lines):
+    """run_batch(Ts) of the _Strided column against three update(T); run(); fetch() on a fresh context and against the oracle fed the numpy
+    restatements of both tables and both pairs: 1e-11 of the largest upward flux, for both.  Before any device result is looked at, from
+    the oracle alone: more than half of every profile's layers lie above the 1e-6 optical-depth floor, and the fluxes with the two tables'
+    concentrations exchanged, and with the two pairs' partial pressures exchanged, are at least 1e-8 of the largest flux away"""
+    m = _Strided(cs)
+    refs = [m.oracle(cs, O, T) for T in m.Ts]
+    for b, (T, r) in enumerate(zip(m.Ts, refs)):
+        share = float((r["tau"] > 1e-6).mean())
+        away = [max(np.max(np.abs(q[k] - r[k])) for k in ("Fup", "Fdn")) / r["Fup"].max()
+                for q in (m.oracle(cs, O, T, swap_tables=True), m.oracle(cs, O, T, swap_pairs=True))]
+        print(f"  profile {b}: layers above the floor {share:.2f}; tables exchanged {away[0]:.2e}, pairs exchanged {away[1]:.2e}")
+        assert share > 0.5 and min(away) >= 1e-8, (b, share, away)
+    ctx, ctx2 = cs.Context(0), cs.Context(0)
+    try:
+        col = m.column(cs, lines, ctx, m.Ts[0])
+        assert col.K == 13 and len(col.gases) == 0 and col.conc_tab.shape == (2, 13) and col.cia_P1.shape == (2, 13)
+        Bu, Bd = col.run_batch(m.Ts)
+        one = m.column(cs, lines, ctx2, m.Ts[1])
+        for b, (T, r) in enumerate(zip(m.Ts, refs)):
+            one.update(T)
+            one.run()
+            Fu, Fd = one.fetch()
+            top = r["Fup"].max()
+            e1 = max(np.max(np.abs(Bu[b] - Fu)), np.max(np.abs(Bd[b] - Fd))) / top
+            e2 = max(np.max(np.abs(Bu[b] - r["Fup"])), np.max(np.abs(Bd[b] - r["Fdn"]))) / top
+            print(f"  profile {b}: batch against single run {e1:.2e}, against the oracle {e2:.2e}")
+            assert e1 < 1e-11 and e2 < 1e-11, (b, e1, e2)
+    finally:
+        ctx.close(); ctx2.close()

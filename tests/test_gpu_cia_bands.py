@@ -412,7 +412,7 @@ def test_resident_update_set_again_and_reupload(cs, O, lines, tune, form):
 
 @pytest.mark.parametrize("which,extrap", [("overlap4", False), ("temperatures", True), ("temperatures", False)])
 def test_run_batch(cs, O, lines, which, extrap):
-    """cs_column_batch evaluates the pairs at B K = 76 states through its own code (upload_cia_states over B K, the unfused k_cia): per
+    """cs_column_batch evaluates the pairs at B K = 76 states through its own code (cia_states over B K, the unfused k_cia): per
     profile against the reference.  A batch returns band fluxes only, so they are what is compared (1e-11 of the largest); every profile
     must have a good share of its layers above the optical-depth floor, or the fluxes would not depend on the bands"""
     nu = R.grid(200)

@@ -224,7 +224,7 @@ def test_update_to_a_far_profile(cs, O, lines, tune, form):
 # ---- 6: batches ---------------------------------------------------------------------------------------------------------------------
 
 def test_run_batch(cs, O, lines):
-    """cs_column_batch forms R at B K states through upload_cia_states: three profiles against three single runs and the reference"""
+    """cs_column_batch forms R at B K states through cia_states: three profiles against three single runs and the reference"""
     which, np_, nlob = "low", 7, 3
     nu = CR.grid(which, 200)
     data = CR.bands_for(which, nu, seed=1, symbol=SYMBOL[which])
