@@ -76,6 +76,24 @@ struct VoigtPlan {
     unsigned nb_zones, nb_iz, nb_sep, nb_edge;   // blocks of the zone, interval-zone and piece-table parts of the setup launches
 };
 
+// the flux kernel instances (NS: the column's stream count): k_rt<NS, true>; k_rt<NS, false>; k_rt_streams<NS>; k_flux_scan<NS, 5>; k_flux_scan<NS, 0>; k_flux_chunk3<NS>; k_flux_chunk<NS>
+enum FluxKern { FK_RT_UD, FK_RT, FK_RT_STREAMS, FK_SCAN5, FK_SCAN, FK_CHUNK3, FK_CHUNK };
+// How the flux stage of a step is run: everything that follows from sizes, settings and what the column holds (flux_plan, the one place
+// that holds the rules).  launch_flux launches by it, a column keeps the plan of its last run, and cs_column_info and cs_column_work read that.
+// One plan, stored at setup and completed at run: cs_column_setup stores the k_rt part (form 0, and how long `partial` must be) under the
+// settings of that moment; every run hands it back to flux_plan, which keeps that part and decides under the settings of the run whether a fused
+// form takes its place.  A batch asks for the k_rt part of its B columns.  What depends on the state of the step -- side streams, cascade, `rad` -- is not in here.
+struct FluxPlan {
+    int form;                   // 0 = k_rt / k_rt_streams reading finished cross-sections from HBM, 3 = k_flux_scan (short grids), 2 = k_flux_chunk (long grids)
+    FluxKern kern, rt_kern;     // the instance that runs; the one form 0 runs, fixed at setup (FK_RT_STREAMS: a short grid for sigma_impl, too)
+    int nt64, tiles;            // 64-point tiles; k_rt: tiles per block
+    int nblk, threads; size_t shmem;   // blocks (per column), threads, dynamic LDS
+    bool band_sum; int nfreduce;       // the last blocks of the kernel to finish add the block partials (FluxFuse::ticket); else k_freduce adds nfreduce per column (0: not launched)
+    bool need_tau;              // the kernel writes the layer optical depths whether the caller wants them or not
+    size_t npartial, gpartial;  // rows of 2 np partials `partial` must hold, and the row where the group sums start
+    int flags;                  // the CS_DF_* of the flux stage
+};
+
 // which forms a step dispatched (cs_column_work CS_WORK_FAR_SPLIT ..): the fields of its last Voigt group, the flags (CS_DF_*) of the whole step
 struct Dispatch { int far_split, tables, near_prio, streams, nodes_split, flags; };
 // What the step being enqueued did, kept by the caller that enqueues it (run_impl, cs_column_batch) and reached by the launchers through
@@ -307,16 +325,13 @@ struct ColGas {
     bool planned = false;
 };
 
-// k_rt launch geometry (rt_geometry)
-struct RtGeom { bool ud, streams; int tiles, nblk, threads; size_t shmem; };   // streams: k_rt_streams (one wave per stream and sweep)
-
 struct Column {
     double *F_dst = nullptr;   // cs_column_set_flux_dst: caller-owned device memory the band fluxes [2 np] are written to (NULL: the column's own F)
     double *flux_out() { return F_dst ? F_dst : F.as<double>(); }
     bool ready = false;
     int64_t nnu = 0;
     int np = 0, nl = 0, nlob = 0, K = 0, nstream = 0, ngas = 0, ntile = 0;
-    RtGeom rtg = {};
+    FluxPlan flux = {}, flux_last = {};   // the setup-time part of the flux plan (flux_plan); the plan the last cs_column_run ran by
     bool want_tau = false, want_M = false, has_extra = false, has_S = false, has_alb = false;
     bool default_wts = false;  // trapezoid weights of the column's own grid (not a shard of a larger one)
     int64_t g_nnu = 0, g_start = 0;      // set by cs_fluxes_discretized_multi: this column is points [g_start, g_start + nnu) of a grid of
@@ -357,7 +372,6 @@ struct Column {
                                // a captured step names them, so no other entry point may move them (batches and shape calls bring their own)
     DevBuf fluxdbg;            // k_flux_scan: phase time stamps of block 0 (CS_T15_SCAN_STAMPS; cs_column_work CS_WORK_FLUX_SCAN_NS ..)
     DevBuf ticket;             // k_flux: blocks finished (the last one adds the block partials up)
-    int flux_form_last = 0;      // which flux kernel the last run used (flux_form)
     StepLog log_last;            // of the last cs_column_run (cs_column_info out[6], out[7]); its disp also of the last cs_column_batch
     StepLog graph_log;           // log_last of the captured run
     bool sigma_partial = false;  // the last run finished the cross-sections on chip (k_flux): cs_column_sigma_fetch evaluates them again, in HBM
@@ -714,30 +728,6 @@ void launch_linesum_shape(int shape, dim3 grid, hipStream_t s, const double *nu,
     }
 }
 
-// k_rt launch geometry: up/down split (two waves per 64-point tile) while the grid has fewer than ~4 waves per SIMD,
-// tiles per block so that the grid still covers the chip
-RtGeom rt_geometry(int64_t nnu, int np, int ncol, int ns = 0, bool allow_streams = false)
-{
-    RtGeom g;
-    const int64_t nwave = (nnu + 63) / 64 * ncol;
-    g.ud = nwave < 4096;
-    g.streams = false;
-    g.tiles = g.ud ? (nnu >= 65536 ? 2 : 1) : (nnu >= 65536 ? 4 : 1);
-    g.nblk = (int)((nnu + (int64_t)g.tiles * 64 - 1) / ((int64_t)g.tiles * 64));
-    g.threads = g.tiles * 64 * (g.ud ? 2 : 1);
-    g.shmem = ((size_t)2 * np * g.tiles + (g.ud ? (size_t)g.tiles * 64 : 0)) * sizeof(double);
-    // short grids: the sweeps are latency chains -- one wave per (sweep, stream) of a tile instead of one per sweep (k_rt_streams): 1/8
-    // of C3 (196 tiles) 0.061 -> 0.046 ms, C2 (157) 0.042 -> 0.033; from ~400 tiles on the two-wave form is as fast or faster (1/4 of
-    // C3 0.082 vs 0.085, 1/2 0.087 vs 0.126: ten waves per tile stop fitting beside each other)
-    const size_t sh2 = ((size_t)(2 * np - 1) * 64 + (size_t)4 * ns * 64 + (size_t)2 * np + 64) * sizeof(double);   // Planck + optical depths + exchange
-    if (allow_streams && g.ud && g.tiles == 1 && nwave <= 400 && ns >= 2 && ns <= 8 && sh2 <= 160 * 1024 - 4096) {
-        g.streams = true;
-        g.threads = 2 * ns * 64;
-        g.shmem = sh2;
-    }
-    return g;
-}
-
 // what every flux launch passes (host only; the kernels keep their argument lists, pointer by pointer)
 struct FluxArgs {
     const RtParams *p;
@@ -772,85 +762,104 @@ void launch_flux_kernel(Kern kern, dim3 grid, int threads, size_t shmem, const F
               rest...);
 }
 
-// the sweeps over finished cross-sections (form 0): B columns of a batch, sigma2 = the near-line plane (NULL: none)
-void launch_rt(const RtGeom &g, int B, const FluxArgs &a, size_t sig_bstride = 0, const double *sigma2 = nullptr)
-{
-    with_nstream(a.p->nstream, [&](auto ns) {
-        constexpr int NS = decltype(ns)::value;
-        const dim3 grid(g.nblk, B);
-        if (g.streams) {
-            if constexpr (NS >= 2 && NS <= 8) launch_flux_kernel(k_rt_streams<NS>, grid, g.threads, g.shmem, a, sig_bstride, sigma2);
-        } else if (g.ud)
-            launch_flux_kernel(k_rt<NS, true>, grid, g.threads, g.shmem, a, sig_bstride, sigma2);
-        else
-            launch_flux_kernel(k_rt<NS, false>, grid, g.threads, g.shmem, a, sig_bstride, sigma2);
-    });
-}
+// what flux_plan decides from, besides the settings: sizes; baked tables, launch groups, a CIA pair with more than CS_CIA_ACT bands over one tile; the device
+struct FluxFacts { int64_t nnu; int np, nlob, K, nstream; bool tables, gases, cia_overlap, gfx950; };   // (a step's choice of form alone reads the last four)
 
-// which form of the flux kernel a step of the resident column uses: 0 = k_rt / k_rt_streams reading finished cross-sections from HBM,
-// 3 = k_flux_scan (short grids), 2 = k_flux_chunk (long grids)
-int flux_form(const cs_ctx *ctx, const Column &c, size_t *shmem, int *nblk, int *threads)
+// The flux stage of a step (FluxPlan).  setup = NULL: the k_rt part for B columns, under these settings (cs_column_setup with B = 1;
+// cs_column_batch); else the step of the resident column whose k_rt part is *setup, completed under these settings (run_impl).
+// k_rt launch geometry: up/down split (two waves per 64-point tile) while the grid has fewer than ~4 waves per SIMD,
+// tiles per block so that the grid still covers the chip
+static FluxPlan flux_plan(const Settings &set, const FluxFacts &f, int B, const FluxPlan *setup)
 {
-    if (ctx->set.flux_form == 1 || !c.tab.empty() || c.gas.empty()) return 0;   // (baked tables are added between wings and CIA pairs: own pass)
-    for (auto &cc : c.cia)
-        if (cc.grid.max_overlap > CS_CIA_ACT) return 0;
-    const int np = c.np, ns = c.nstream, K = c.K;
-    const size_t lim = 160 * 1024 - 4096;
-    const int nt64_ = (int)((c.nnu + 63) / 64);
+    const int np = f.np, ns = f.nstream, nt64 = (int)((f.nnu + 63) / 64);
+    const size_t lim = 160 * 1024 - 4096;   // dynamic LDS of one block
+    if (!setup) {
+        FluxPlan g = {};
+        const int64_t nwave = (int64_t)nt64 * B; const bool ud = nwave < 4096;
+        g.kern = ud ? FK_RT_UD : FK_RT; g.nt64 = nt64;
+        g.tiles = ud ? (f.nnu >= 65536 ? 2 : 1) : (f.nnu >= 65536 ? 4 : 1);
+        g.nblk = (int)((f.nnu + (int64_t)g.tiles * 64 - 1) / ((int64_t)g.tiles * 64));
+        g.threads = g.tiles * 64 * (ud ? 2 : 1);
+        g.shmem = ((size_t)2 * np * g.tiles + (ud ? (size_t)g.tiles * 64 : 0)) * sizeof(double);
+        // short grids: the sweeps are latency chains -- one wave per (sweep, stream) of a tile instead of one per sweep (k_rt_streams): 1/8
+        // of C3 (196 tiles) 0.061 -> 0.046 ms, C2 (157) 0.042 -> 0.033; from ~400 tiles on the two-wave form is as fast or faster (1/4 of
+        // C3 0.082 vs 0.085, 1/2 0.087 vs 0.126: ten waves per tile stop fitting beside each other)
+        const size_t sh2 = ((size_t)(2 * np - 1) * 64 + (size_t)4 * ns * 64 + (size_t)2 * np + 64) * sizeof(double);   // Planck + optical depths + exchange
+        if (set.rt_streams && ud && g.tiles == 1 && nwave <= 400 && ns >= 2 && ns <= 8 && sh2 <= lim) {
+            g.kern = FK_RT_STREAMS; g.flags = CS_DF_RT_STREAMS; g.threads = 2 * ns * 64; g.shmem = sh2;
+        }
+        g.rt_kern = g.kern; g.nfreduce = g.nblk;
+        // a batch: the block partials of its B columns; the resident column: room for every form (one block per tile at most) + k_flux's group sums
+        g.gpartial = (size_t)nt64; g.npartial = B > 1 ? (size_t)B * g.nblk : g.gpartial + 512 / CS_FLUX_GROUP;
+        return g;
+    }
+    FluxPlan pl = *setup;
+    if (set.flux_form == 1 || f.tables || !f.gases || f.cia_overlap) return pl;   // (baked tables are added between wings and CIA pairs: own pass)
+    const bool streams = pl.rt_kern == FK_RT_STREAMS, ud = pl.rt_kern != FK_RT;
     // the scan form: grids of up to 1024 tiles -- with a chunk's transmissivities in registers it beats the separate kernels on a half
     // (846 tiles: 1.10 -> 1.08 ms) and a quarter (407 tiles: 0.677 -> 0.610) of the bench column, not on the whole (1563 tiles: 1.94 ->
     // 1.99) -- and, under Settings::scan_mid, every grid in k_rt's two-waves-per-tile regime (A/B)
     // (Settings::flux_form = 2, `always`, keeps the chunked form on mid-size grids: tests)
-    const bool scan_ok = c.rtg.streams || (c.rtg.ud && ns >= 2 && ns <= 8 && nt64_ >= 1 && ((nt64_ <= 1024 && ctx->set.flux_form != 2) || ctx->set.scan_mid));
-    if (scan_ok) {
+    if (streams || (ud && ns >= 2 && ns <= 8 && nt64 >= 1 && ((nt64 <= 1024 && set.flux_form != 2) || set.scan_mid))) {
         // the sweeps as a scan over layer chunks: five layers per wave where 12 waves reach (their transmissivities stay in registers,
         // k_flux_scan<NS, 5>), whole waves per SIMD (4, 8 or 12: ten waves of six layers load two SIMDs with three waves and two with two)
-        const int nw = std::min(12, std::max(4, 4 * ((c.nl + 19) / 20)));
-        const size_t sh = ((size_t)K * 64 + (size_t)(2 * np - 1) * 64 + (size_t)2 * (ns + 1) * 64 + (size_t)2 * np) * sizeof(double);
-        if (sh > lim) return 0;
-        *shmem = sh; *nblk = nt64_; *threads = nw * 64;
-        return 3;
+        const int nw = std::min(12, std::max(4, 4 * ((np - 1 + 19) / 20))), per = (np - 1 + nw - 1) / nw;
+        pl.shmem = ((size_t)f.K * 64 + (size_t)(2 * np - 1) * 64 + (size_t)2 * (ns + 1) * 64 + (size_t)2 * np) * sizeof(double);
+        pl.form = 3; pl.nblk = nt64; pl.threads = nw * 64;
+        // a chunk of up to 5 layers (60 layers over 12 waves) keeps its transmissivities in registers between the sweeps and passes
+        // (seven streams and up: the 5 x NS values no longer fit beside the rest at three waves per SIMD)
+        pl.kern = ns <= 6 && per <= 5 && !set.scan_recompute ? FK_SCAN5 : FK_SCAN;
+    } else {
+        // long grids: where k_rt runs one wave per tile for both sweeps (>= 4096 tiles) the chunked form saves the passes over the plane; in
+        // between (the bench column at full size: 1563 tiles, two waves per tile) the separate kernels are as fast (profiles/r04_notes.md)
+        if (set.flux_form != 2 && ud) return pl;
+        const int nw = 4, R = 16 + f.nlob - 1;
+        pl.shmem = ((size_t)2 * np * nw + (size_t)nw * R * 64) * sizeof(double);
+        pl.form = 2; pl.nblk = (nt64 + nw - 1) / nw; pl.threads = nw * 64;
+        pl.kern = set.chunk4 ? FK_CHUNK : FK_CHUNK3;
+        // the chunked form always writes the layer optical depths (its upward sweep reads them back): into the caller's plane or scratch
+        pl.need_tau = true;   // (forms 0 and 3 keep the optical depths in LDS unless the caller wants them)
     }
-    // long grids: where k_rt runs one wave per tile for both sweeps (>= 4096 tiles) the chunked form saves the passes over the plane; in
-    // between (the bench column at full size: 1563 tiles, two waves per tile) the separate kernels are as fast (profiles/r04_notes.md)
-    const int nt64 = (int)((c.nnu + 63) / 64);
-    if (ctx->set.flux_form != 2 && c.rtg.ud) return 0;
-    const int nw = 4, R = 16 + c.nlob - 1;
-    const size_t sh = ((size_t)2 * np * nw + (size_t)nw * R * 64) * sizeof(double);
-    if (sh > lim) return 0;
-    *shmem = sh; *nblk = (nt64 + nw - 1) / nw; *threads = nw * 64;
-    return 2;
+    if (pl.shmem > lim) return *setup;
+    // up to 512 blocks the last ones to finish add the block partials (two stages of 16 and <= 32 terms); longer grids keep k_freduce
+    pl.band_sum = pl.nblk <= 512 && !set.freduce_always && f.gfx950; pl.nfreduce = pl.band_sum ? 0 : pl.nblk;
+    pl.flags = (pl.band_sum ? CS_DF_BAND_SUM : 0) | (pl.kern == FK_CHUNK ? CS_DF_CHUNK4 : 0);
+    return pl;
 }
 
-// the fused forms (flux_form 3 and 2).  rad: the column holds a CIA object flagged CS_CIA_RADIATION (kernels that can form R(nu, T_k);
+// the flux kernel a plan names, for B columns.  The k_rt forms read finished cross-sections, sigma2 = the near-line plane (NULL: none);
+// the fused forms (3 and 2) take *f.  rad: the column holds a CIA object flagged CS_CIA_RADIATION (kernels that can form R(nu, T_k);
 // every other column runs the ones it always ran)
-void launch_flux(int form, size_t shmem, int nblk, int threads, const FluxArgs &a, const FluxFuse &f, bool rad, bool three_waves, bool scan_recompute)
+static int launch_flux(const FluxPlan &pl, int B, const FluxArgs &a, size_t sig_bstride, const double *sigma2, const FluxFuse *f = nullptr, bool rad = false)
 {
-    with_nstream(a.p->nstream, [&](auto ns) {
-        constexpr int NS = decltype(ns)::value;
-        auto go = [&](auto radc) {
-            constexpr bool RAD = decltype(radc)::value;
-            const int ntile = (int)((a.nnu + 63) / 64);
-            if (form == 3) {
-                if constexpr (NS >= 2 && NS <= 8) {
-                    // a chunk of up to 5 layers (60 layers over 12 waves) keeps its transmissivities in registers between the sweeps and passes
-                    const int nw = threads / 64, per = (a.p->np - 1 + nw - 1) / nw;
-                    if constexpr (NS <= 6) {   // (seven streams and up: the 5 x NS values no longer fit beside the rest at three waves per SIMD)
-                        if (per <= 5 && !scan_recompute) {
-                            launch_flux_kernel(k_flux_scan<NS, 5, RAD>, dim3(nblk), threads, shmem, a, f);
-                            return;
-                        }
-                    }
-                    launch_flux_kernel(k_flux_scan<NS, 0, RAD>, dim3(nblk), threads, shmem, a, f);
+    bool launched = false;
+    auto go = [&](auto kern, const auto &... rest) { launch_flux_kernel(kern, dim3(pl.nblk, B), pl.threads, pl.shmem, a, rest...); launched = true; };
+    if (pl.form == 0)
+        with_nstream(a.p->nstream, [&](auto ns) {
+            constexpr int NS = decltype(ns)::value;
+            switch (pl.kern) {
+            case FK_RT_STREAMS: if constexpr (NS >= 2 && NS <= 8) go(k_rt_streams<NS>, sig_bstride, sigma2); break;
+            case FK_RT_UD: go(k_rt<NS, true>, sig_bstride, sigma2); break;
+            case FK_RT: go(k_rt<NS, false>, sig_bstride, sigma2); break;
+            default: break;
+            }
+        });
+    else   // (a second pass over the stream counts: the instances keep their places in the code object)
+        with_nstream(a.p->nstream, [&](auto ns) {
+            constexpr int NS = decltype(ns)::value;
+            auto fused = [&](auto radc) {
+                constexpr bool RAD = decltype(radc)::value;
+                switch (pl.kern) {
+                case FK_SCAN5: if constexpr (NS >= 2 && NS <= 6) go(k_flux_scan<NS, 5, RAD>, *f); break;
+                case FK_SCAN: if constexpr (NS >= 2 && NS <= 8) go(k_flux_scan<NS, 0, RAD>, *f); break;
+                case FK_CHUNK3: go(k_flux_chunk3<NS, RAD>, *f, pl.nt64); break;
+                case FK_CHUNK: go(k_flux_chunk<NS, RAD>, *f, pl.nt64); break;
+                default: break;
                 }
-            } else if (three_waves)
-                launch_flux_kernel(k_flux_chunk3<NS, RAD>, dim3(nblk), threads, shmem, a, f, ntile);
-            else
-                launch_flux_kernel(k_flux_chunk<NS, RAD>, dim3(nblk), threads, shmem, a, f, ntile);
-        };
-        if (rad) go(std::true_type{});
-        else go(std::false_type{});
-    });
+            };
+            rad ? fused(std::true_type{}) : fused(std::false_type{});
+        });
+    return launched ? CS_OK : fail(CS_EINVAL, "internal: no flux kernel instance %d for %d streams", (int)pl.kern, a.p->nstream);
 }
 
 // includedlines(::Vector) line_shapes.jl:18-22 -> [g0, g1) ; strict = 0 keeps every line (scalar-nu method :12-16)
@@ -3034,7 +3043,7 @@ int cs_column_set_cia(cs_ctx *ctx, int ncia, const int *cia_slots, const int *fl
     return res;
 }
 
-static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLog *log, bool *near_plane_live = nullptr, FluxFuse *fuse = nullptr);
+static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLog *log, bool *near_plane_live = nullptr, FluxFuse *fuse = nullptr, const FluxPlan *fpl = nullptr);
 static int column_current(cs_ctx *ctx);
 
 // ---- AcceleratedAbsorber (absorbers.jl:114-203) -------------------------------------------------------------------------
@@ -3165,7 +3174,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     hipStream_t s = ctx->stream;
     c.nnu = nnu; c.np = np; c.nl = np - 1; c.nlob = nlobatto; c.K = (np - 1) * (nlobatto - 1) + 1;
     c.nstream = nstream; c.ngas = ngas; c.ntile = (int)((nnu + 255) / 256);
-    c.rtg = rt_geometry(nnu, np, 1, nstream, ctx->set.rt_streams);
+    c.flux = flux_plan(ctx->set, {nnu, np, nlobatto, c.K, nstream}, 1, nullptr);
     c.want_tau = want_tau != 0; c.want_M = want_M != 0;
     c.g = g; c.sigma_gray = sigma_gray; c.theta_s = theta_s;
     const int K = c.K, nl = c.nl;
@@ -3320,7 +3329,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         HIPCHK(c.Mup.reserve((size_t)np * nnu * sizeof(double)));
         HIPCHK(c.Mdn.reserve((size_t)np * nnu * sizeof(double)));
     }
-    HIPCHK(c.partial.reserve(((size_t)std::max<int64_t>(c.rtg.nblk, (nnu + 63) / 64) + 512 / CS_FLUX_GROUP) * 2 * np * sizeof(double)));   // (one block per tile at most) + k_flux's group sums
+    HIPCHK(c.partial.reserve(c.flux.npartial * 2 * np * sizeof(double)));
     HIPCHK(c.F.reserve((size_t)2 * np * sizeof(double)));
     HIPCHK(hipStreamSynchronize(s));
     c.ready = true;  // state upload below needs the sizes
@@ -3425,9 +3434,9 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
     if ((rc = upload(dTk, Tk.data(), BK, s)) || (rc = upload(dPk, Pk.data(), BK, s)) || (rc = upload(dmuk, muk.data(), BK, s)) ||
         (rc = upload(dTlev, T_levels, (size_t)B * np, s)))
         return rc;
-    const RtGeom bg = rt_geometry(c.nnu, np, B, c.nstream, ctx->set.rt_streams);
+    const FluxPlan bg = flux_plan(ctx->set, {c.nnu, np, c.nlob, K, c.nstream}, B, nullptr);
     if (!shared_sigma) HIPCHK(dsig.reserve((size_t)BK * c.nnu * sizeof(double)));
-    HIPCHK(dpart.reserve((size_t)B * bg.nblk * 2 * np * sizeof(double)));
+    HIPCHK(dpart.reserve(bg.npartial * 2 * np * sizeof(double)));
     HIPCHK(dF.reserve((size_t)B * 2 * np * sizeof(double)));
     double *sig = shared_sigma ? c.sigma.as<double>() : dsig.as<double>();
     StepLog log;
@@ -3502,13 +3511,13 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
     }
-    if (bg.streams) log.disp.flags |= CS_DF_RT_STREAMS;
+    log.disp.flags |= bg.flags;
     c.log_last.disp = log.disp;
     const FluxArgs fa = {&c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, sig, dmuk.as<double>(), c.P.as<double>(), dTlev.as<double>(),
                          c.has_S ? c.S_toa.as<double>() : nullptr, c.has_alb ? c.albedo.as<double>() : nullptr,
                          nullptr, nullptr, nullptr, dpart.as<double>(), s};   // batches return band fluxes only: no tau stored
-    launch_rt(bg, B, fa, shared_sigma ? 0 : (size_t)K * c.nnu);
-    CS_LAUNCH(k_freduce, dim3(2 * np, B), dim3(256), 0, s, dpart.as<double>(), bg.nblk, 2 * np, dF.as<double>());
+    if ((rc = launch_flux(bg, B, fa, shared_sigma ? 0 : (size_t)K * c.nnu, nullptr))) return rc;
+    CS_LAUNCH(k_freduce, dim3(2 * np, B), dim3(256), 0, s, dpart.as<double>(), bg.nfreduce, 2 * np, dF.as<double>());
     HIPCHK(hipGetLastError());
     std::vector<double> F((size_t)B * 2 * np);
     HIPCHK(hipMemcpyAsync(F.data(), dF.p, F.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -3525,8 +3534,8 @@ int cs_column_batch(cs_ctx *ctx, int B, const double *T_nodes, const double *mu_
 // near_plane_live: NULL = the cross-sections themselves are the result (the near-line plane is folded into sigma before returning);
 // else the caller (run_impl) hands both planes to k_rt and is told here whether the second one is in use this step
 // fuse != NULL: the interpolated wings are not carried to the grid and the CIA pairs are not added here -- *fuse says what the flux
-// kernel still has to add (k_flux; near_plane_live must be given too: the near-line plane is not folded in either)
-static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLog *log, bool *near_plane_live, FluxFuse *fuse)
+// kernel still has to add (k_flux; near_plane_live must be given too: the near-line plane is not folded in either), and *fpl is the step's flux plan
+static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLog *log, bool *near_plane_live, FluxFuse *fuse, const FluxPlan *fpl)
 {
     Column &c = ctx->col;
     const int K = c.K;
@@ -3590,7 +3599,7 @@ static int sigma_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev, int &e, StepLo
     bool cascaded_aside = false;
     ChebApply carried;   // what a cascade on the side stream leaves to carry to the grid
     const int nl_itp = apply.ngas == 1 ? apply.nlev - apply.l0[0] : 0;
-    const bool short_aside = fuse && c.rtg.streams;
+    const bool short_aside = fuse && fpl->rt_kern == FK_RT_STREAMS;
     // long grids: where the cascade is in use anyway (four levels and up) it runs on the node-sum stream as well, beside the per-point
     // kernels, instead of between them and the flux kernel (BASELINE configs[4]: four launches, 0.32 ms of the main stream)
     // ... and with the node sums on a side stream the cascade is off the step's critical path whatever the number of levels: that stream
@@ -3679,44 +3688,32 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
     StepLog log;
     c.last_stream = s;
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
-    bool near_live = false;
-    size_t fsh = 0;
-    int fblk = 0, fthr = 0;
-    const int form = flux_form(ctx, c, &fsh, &fblk, &fthr);
+    bool near_live = false, overlap = false, rad = false;
+    for (auto &cc : c.cia) overlap = overlap || cc.grid.max_overlap > CS_CIA_ACT;
+    const FluxPlan pl = flux_plan(ctx->set, {c.nnu, c.np, c.nlob, c.K, c.nstream, !c.tab.empty(), !c.gas.empty(), overlap, ctx->gfx950}, 1, &c.flux);
     FluxFuse fuse;
     memset(&fuse, 0, sizeof fuse);
-    if ((rc = sigma_impl(ctx, s, ev, e, &log, &near_live, form ? &fuse : nullptr))) return rc;
+    if ((rc = sigma_impl(ctx, s, ev, e, &log, &near_live, pl.form ? &fuse : nullptr, &pl))) return rc;
     c.near_live = near_live;
-    c.sigma_partial = form != 0;
-    c.flux_form_last = form;
+    c.sigma_partial = pl.form != 0;
+    c.flux_last = pl;
+    log.disp.flags |= pl.flags;
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
-    FluxArgs fa = {&c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, sig, c.muk.as<double>(), c.P.as<double>(), c.Tlev.as<double>(),
-                   c.has_S ? c.S_toa.as<double>() : nullptr, c.has_alb ? c.albedo.as<double>() : nullptr,
-                   c.want_tau ? c.tau.as<double>() : nullptr, c.want_M ? c.Mup.as<double>() : nullptr, c.want_M ? c.Mdn.as<double>() : nullptr,
-                   c.partial.as<double>(), s};
-    bool reduced = false;
-    if (form) {
-        fuse.sigma2 = near_live ? c.sigma2.as<double>() : nullptr;
-        fuse.F = c.flux_out();
-        // up to 512 blocks the last ones to finish add the block partials (two stages of 16 and <= 32 terms); longer grids keep k_freduce
-        fuse.ticket = (fblk <= 512 && !ctx->set.freduce_always && ctx->gfx950) ? c.ticket.as<unsigned>() : nullptr;
-        fuse.gpartial = c.partial.as<double>() + (size_t)std::max<int64_t>(c.rtg.nblk, (c.nnu + 63) / 64) * 2 * c.np;
-        reduced = fuse.ticket != nullptr;
-        if (reduced) log.disp.flags |= CS_DF_BAND_SUM;
-        if (form == 2 && ctx->set.chunk4) log.disp.flags |= CS_DF_CHUNK4;
-        if (ctx->set.scan_stamps && c.fluxdbg.reserve((8 + 2 * (size_t)fblk + 32) * sizeof(unsigned long long)) == hipSuccess) fuse.dbg = c.fluxdbg.as<unsigned long long>();
-        // the chunked form always writes the layer optical depths (its upward sweep reads them back): into the caller's plane or scratch
-        if (form == 2) fa.tau = c.tau.as<double>();   // (forms 0 and 3 keep the optical depths in LDS unless the caller wants them)
-        bool rad = false;
+    const FluxArgs fa = {&c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, sig, c.muk.as<double>(), c.P.as<double>(), c.Tlev.as<double>(),
+                         c.has_S ? c.S_toa.as<double>() : nullptr, c.has_alb ? c.albedo.as<double>() : nullptr,
+                         c.want_tau || pl.need_tau ? c.tau.as<double>() : nullptr, c.want_M ? c.Mup.as<double>() : nullptr, c.want_M ? c.Mdn.as<double>() : nullptr,
+                         c.partial.as<double>(), s};
+    const double *sigma2 = near_live ? c.sigma2.as<double>() : nullptr;
+    if (pl.form) {
+        fuse.sigma2 = sigma2; fuse.F = c.flux_out();
+        fuse.ticket = pl.band_sum ? c.ticket.as<unsigned>() : nullptr;
+        fuse.gpartial = c.partial.as<double>() + pl.gpartial * 2 * c.np;
+        if (ctx->set.scan_stamps && c.fluxdbg.reserve((8 + 2 * (size_t)pl.nblk + 32) * sizeof(unsigned long long)) == hipSuccess) fuse.dbg = c.fluxdbg.as<unsigned long long>();
         for (int t = 0; t < fuse.ncia; t++) rad = rad || fuse.cia[t].Tr != nullptr;
-        launch_flux(form, fsh, fblk, fthr, fa, fuse, rad, !ctx->set.chunk4, ctx->set.scan_recompute);
-    } else {
-        if (c.rtg.streams) log.disp.flags |= CS_DF_RT_STREAMS;
-        launch_rt(c.rtg, 1, fa, 0, near_live ? c.sigma2.as<double>() : nullptr);
     }
+    if ((rc = launch_flux(pl, 1, fa, 0, sigma2, &fuse, rad))) return rc;
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
-    if (!reduced)
-        CS_LAUNCH(k_freduce, dim3(2 * c.np), dim3(256), 0, s, c.partial.as<double>(), form ? fblk : c.rtg.nblk, 2 * c.np, c.flux_out());
+    if (pl.nfreduce) CS_LAUNCH(k_freduce, dim3(2 * c.np), dim3(256), 0, s, c.partial.as<double>(), pl.nfreduce, 2 * c.np, c.flux_out());
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
     c.launches = g_nlaunch;
     c.log_last = log;
@@ -3943,7 +3940,7 @@ int cs_column_info(cs_ctx *ctx, int64_t *out)
     out[1] = c.launches;
     for (auto &g : c.gas) { out[2] += g.tab->L; out[4] = std::max<int64_t>(out[4], (int64_t)g.mem.size()); }
     out[3] = c.merge;
-    out[5] = c.flux_form_last;
+    out[5] = c.flux_last.form;
     out[6] = c.log_last.near_launches;
     out[7] = c.log_last.line_kernel;
     return CS_OK;
@@ -4289,8 +4286,8 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
         (void)hipMemcpy(st, c.fluxdbg.p, sizeof st, hipMemcpyDeviceToHost);
         for (int q = 0; q < 4; q++) out[CS_WORK_FLUX_SCAN_NS + q] = (int64_t)(st[q + 1] - st[q]) * 10;   // (100 MHz clock)
         out[CS_WORK_FLUX_SCAN_TOTAL_NS] = (int64_t)(st[7] - st[0]) * 10;   // block 0's first instruction to the last block's last word
-        if (getenv("CS_FLUX_DBG") && c.flux_form_last == 3) {   // every block's start and end (k_flux_scan), relative to the earliest start
-            const size_t nb = (size_t)(c.nnu + 63) / 64;
+        if (getenv("CS_FLUX_DBG") && c.flux_last.form == 3) {   // every block's start and end (k_flux_scan), relative to the earliest start
+            const size_t nb = (size_t)c.flux_last.nblk;
             if (c.fluxdbg.bytes >= (8 + 2 * nb + 32) * sizeof(unsigned long long)) {
                 std::vector<unsigned long long> bs(2 * nb + 32);
                 (void)hipMemcpy(bs.data(), (const char *)c.fluxdbg.p + 8 * sizeof(unsigned long long), (2 * nb + 32) * sizeof(unsigned long long), hipMemcpyDeviceToHost);

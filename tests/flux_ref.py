@@ -59,7 +59,7 @@ doubles are correctly rounded on both sides (hipcc -O3 and gcc -O3, no fast-math
          layer recurrence (it is linear), so its sensitivities are those above; its own roundings are A's products (per - 1), the
          chunk from zero (never more than the chunk from X >= 0) and the final multiply-add (2): at every chunk boundary
          e_X += u (per A X + 2 X').  The beam's Ms A_s likewise: per u Ms'.  `bounds(..., per=)` adds them; per = layers per wave,
-         read from launch_flux / flux_form (scan_per below).
+         read from flux_plan (scan_per below).
   underflow  a result below the normal range is rounded absolutely: 2^-1074 per operation.  Operations that can reach an element:
          per (stream, layer) 15 -- stream_tr (product, exp), sweep_step's 1/(tau m) product, layerplanck_inv (1 - t, B1 - B2, four
          products, two sums), stream_step (product, sum), W_k I_k and its addition -- in two sweeps (M+ sees the downward one through
@@ -220,12 +220,12 @@ def mp_fluxes(nu, P, g, muk, Tlev, sigma, S_toa, albedo, theta_s, ws, m, W, dps=
 # ---- the bound ----------------------------------------------------------------------------------------------------------------
 
 def scan_waves(nl):
-    """flux_form (cs_api.hip): waves of the scan form"""
+    """flux_plan (cs_api.hip): waves of the scan form"""
     return min(12, max(4, 4 * ((nl + 19) // 20)))
 
 
 def scan_per(nl):
-    """launch_flux: layers per wave of the scan form"""
+    """flux_plan: layers per wave of the scan form"""
     return -(-nl // scan_waves(nl))
 
 

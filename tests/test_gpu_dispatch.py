@@ -183,7 +183,7 @@ RULES = [
 ]
 # Not in the table: sep_in_use / edge_in_use (mx_big at 2048 (interval, group) and 1024 (tile, group) blocks) decide nothing by
 # default -- cs_set_tuning key 1 = 1 keeps the matrix-core kernels on short grids -- and key 1 = 0 is compared in test_gpu_merge;
-# rt_geometry's 65536-point rule only changes k_rt's tiles per block (not reported; the grids of the scan rule sit on it).
+# flux_plan's 65536-point rule only changes k_rt's tiles per block (not reported; the grids of the scan rule sit on it).
 
 
 def _grids(rule):

@@ -7,8 +7,8 @@ k_flux_chunk3 spills, so the instances are not copies of the tested ones.  Every
 compares with the oracle at the suite's tolerances (sigma and tau 1e-11 relative, M+- 1e-11 of their maximum plus
 conftest.source_rounding_bound, F+- 1e-11 of max F+; columns with a CIA pair 1e-10, as test_gpu_flux_fused) and with a second form:
 bitwise where an existing test documents identical results, else test_gpu_merge._close(..., 5e-13, 1e-12).  Forms are forced only by the
-existing cs_set_tuning keys (5, 15 and its bits 2, 8, 2048).  Grid-size rules are taken from their formulas in cs_api.hip (rt_geometry,
-flux_form, launch_flux), so a moved threshold fails here instead of leaving a form unrun.
+existing cs_set_tuning keys (5, 15 and its bits 2, 8, 2048).  Grid-size rules are taken from their formulas in cs_api.hip (flux_plan),
+so a moved threshold fails here instead of leaving a form unrun.
 
 Inputs: HITRAN CO2 fixture line by line, a gray term, a stellar beam (theta_s = 0.6), an albedo function; a CIA pair (CO2-CO2) in part
 of the cases; 2577-point grids (41 tiles, a last tile of 17 points) unless a rule needs another.
@@ -26,7 +26,7 @@ of the cases; 2577-point grids (41 tiles, a last tile of 17 points) unless a rul
   k_flux_chunk3<NS>             key 15 = 2, key 5 = 0                               1-16     test_stream_sweep
   k_flux_chunk<NS>              key 15 = 2 | 8, key 5 = 0                           1-16     test_stream_sweep
 
-  (Key 15 = 2 alone keeps the scan form wherever k_rt_streams could run -- flux_form takes rt_geometry's `streams` as scan_ok -- so on
+  (Key 15 = 2 alone keeps the scan form wherever k_rt_streams could run -- flux_plan takes the setup-time k_rt_streams choice as reason enough for the scan -- so on
   these short grids key 5 = 0 goes with it.)
 
   nlobatto 2..16, NS = 4: the scan form, k_flux_chunk3, k_rt<4, true> and the batch k_rt<4, false> (test_lobatto_sweep); K mod 16 takes
@@ -38,8 +38,8 @@ of the cases; 2577-point grids (41 tiles, a last tile of 17 points) unless a rul
   with CS_EINVAL by cs_column_setup, cs_fluxes_discretized and cs_fluxes_discretized_members (test_orders_outside_the_abi_refused).
 
 Instances that no input reaches: k_flux_scan<NS, 5> for NS 7, 8 and k_flux_scan / k_rt_streams for NS 1, 9..16 are not instantiated
-(`if constexpr` in launch_flux / launch_rt); flux_form returns 3 and rt_geometry sets `streams` only for 2 <= NS <= 8, which
-test_stream_sweep asserts for every NS outside that range (those branches would launch nothing).
+(`if constexpr` in launch_flux); flux_plan names form 3 and k_rt_streams only for 2 <= NS <= 8, which
+test_stream_sweep asserts for every NS outside that range (launch_flux would refuse such a plan with CS_EINVAL).
 """
 import functools
 import os
@@ -58,7 +58,7 @@ from test_gpu_merge import _close
 pytestmark = pytest.mark.gpu
 
 RT_STREAMS, CHUNK4 = DISPATCH_FLAGS["RT_STREAMS"], DISPATCH_FLAGS["CHUNK4"]   # Column.work()["dispatch"]["flags"]
-LIM = 160 * 1024 - 4096                          # LDS the flux forms may take (flux_form, rt_geometry)
+LIM = 160 * 1024 - 4096                          # LDS the flux forms may take (flux_plan)
 N_SHORT = 64 * 40 + 17                           # 41 tiles, ragged last tile
 THETA_S, FS, GRAY = 0.6, 0.4, 5e-27
 CS_EINVAL = -1
@@ -85,11 +85,11 @@ def _K(np_, nlob):
 
 
 # the grid-size rules, copied from cs_api.hip
-def _ud(n, B=1):                                 # rt_geometry: two waves per tile below 4096 (tile, column) waves
+def _ud(n, B=1):                                 # flux_plan: two waves per tile below 4096 (tile, column) waves
     return _tiles(n) * B < 4096
 
 
-def _streams_sh(np_, ns):                        # rt_geometry: k_rt_streams' LDS
+def _streams_sh(np_, ns):                        # flux_plan: k_rt_streams' LDS
     return ((2 * np_ - 1) * 64 + 4 * ns * 64 + 2 * np_ + 64) * 8
 
 
@@ -97,7 +97,7 @@ def _rt_streams(n, np_, ns, key5=1):
     return bool(key5) and _ud(n) and _tiles(n) <= 400 and 2 <= ns <= 8 and _streams_sh(np_, ns) <= LIM
 
 
-def _scan_nw(nl):                                # flux_form: waves of the scan form
+def _scan_nw(nl):                                # flux_plan: waves of the scan form
     return min(12, max(4, 4 * ((nl + 19) // 20)))
 
 
@@ -105,12 +105,12 @@ def _scan_sh(np_, nlob, ns):
     return (_K(np_, nlob) * 64 + (2 * np_ - 1) * 64 + 2 * (ns + 1) * 64 + 2 * np_) * 8
 
 
-def _scan_per(np_):                              # launch_flux: layers per wave
+def _scan_per(np_):                              # flux_plan: layers per wave
     nl = np_ - 1
     return -(-nl // _scan_nw(nl))
 
 
-def _chunk_sh(np_, nlob):                        # flux_form: the chunk form, four waves, R = 16 + nlob - 1 ring rows each
+def _chunk_sh(np_, nlob):                        # flux_plan: the chunk form, four waves, R = 16 + nlob - 1 ring rows each
     return (2 * np_ * 4 + 4 * (16 + nlob - 1) * 64) * 8
 
 

@@ -17,10 +17,10 @@ kernels, 2 chunk, 3 scan; work()["dispatch"]["flags"]: RT_STREAMS, CHUNK4), as t
   k_flux_chunk<NS>     key 15 = 2 | 8, key 5 = 0                        1-16     stream_sweep, lobatto, boundaries
   k_rt<NS, false>      Column.run_batch, tiles x B >= 4096              1-16     batch (band fluxes of four members; B - 1: k_rt<NS, true>)
 Every form is reached with the host-evaluated term.  What a run reports tells the forms apart, not the template instances of one
-form: k_flux_scan<NS, 5> from <NS, 0> and k_rt<NS, true> from <NS, false> are inferred from the rules of launch_flux and rt_geometry
+form: k_flux_scan<NS, 5> from <NS, 0> and k_rt<NS, true> from <NS, false> are inferred from the rules of flux_plan
 (restated in flux_ref.scan_per and in test_batch) and from key 15 | 2048, as in tests/test_gpu_flux_orders.py.  Grid: 64 x 2 + 17 = 145 points (three tiles, a ragged last one), all compared.
 One reference per (NS, nlobatto, np, inputs), shared by the forms (flux_ref.reference).  The scan form's bound carries the roundings of
-forming A I + B per chunk (bounds(per=)); per comes from flux_ref.scan_per, the formula of launch_flux.
+forming A I + B per chunk (bounds(per=)); per comes from flux_ref.scan_per, the formula of flux_plan.
 
 Band sum.  For every form that returns planes, on test_gpu_flux_orders' 2577-point grid with its CO2 lines (41 blocks, 3 groups of
 CS_FLUX_GROUP): |F - fsum(w_j M_j)| <= (n + 2) u sum |w_j M_j| per level, with M the run's own planes and n the longest chain of
@@ -232,7 +232,7 @@ def test_batch(ns):
     """Column.run_batch on a gray column, tiles x B at the 4096 rule (k_rt<NS, false>) and one below it (k_rt<NS, true>): the band
     fluxes of members 0, 1, the middle one and B - 1 against sum_j w_j M_j of the reference over all 145 points, within
     sum_j w_j bound_j + (n + 2) u sum_j |w_j M_j|, n = 17 (k_rt).  Which of the two instances runs is inferred from the rule of
-    rt_geometry (restated here: fewer than 4096 (tile, column) waves -> two waves per tile), not reported by the library; the run only
+    flux_plan (restated here: fewer than 4096 (tile, column) waves -> two waves per tile), not reported by the library; the run only
     reports that k_rt_streams did not take it.  The column's own run hands back the gray plane bitwise"""
     cs = clearsky_jl_amd
     nlob, np_, sig = 2, 7, 3e-27
