@@ -53,7 +53,7 @@ enum { TABLES_NONE = 0, TABLES_MERGED = 1, TABLES_LANES16 = 2, TABLES_ONE_THREAD
 // place that holds the rules).  line_sum_voigt launches by it, a column keeps the plan of its last run and cs_column_work counts from it.
 // What depends on the state of the step -- the side streams, who clears the near-line plane, the fused apply -- is not in here.
 struct VoigtPlan {
-    bool lor;                   // the Lorentz body (no near-line tiers, no matrix cores)
+    bool lor;                   // the Lorentz body and the Lorentz series of the matrix-core pieces (no near-line tiers, no sub-tile cores, no 8-term tier)
     int nt64, ngrp;             // 64-point tiles; groups of 16 states
     int q0, ishift;             // first interval in use; tile -> interval of the smallest size (both 0 without interpolated wings)
     int near_prio;              // wave priority of k_voigt_sub / k_voigt_near (0, 3)
@@ -1385,24 +1385,24 @@ constexpr int CS_SUBW = 8;
 // tile gains 0.12 ms with them, the HITRAN fixtures at 0.4-0.7 lose)
 constexpr int CS_EDGE_DENS = 4;
 
-// matrix-core node sums (k_cheb_nodes_mx): fp64 Voigt only, and by default only where there are enough (interval, state group)
+// matrix-core node sums (k_cheb_nodes_mx): fp64 Voigt and Lorentz, and by default only where there are enough (interval, state group)
 // blocks to fill the chip -- on a short grid (a nu-shard) the one-state-per-wave vector kernel has the shorter critical path
 // (1/8 of C3: 0.17 vs 0.25 ms)
 static bool mx_big(int nblocks, int kn, int min_blocks) { return (int64_t)nblocks * ((kn + 15) / 16) >= min_blocks; }
 // `small`: Settings::small_mx -- short grids too, through the variants that share one (interval | tile, group) between the four
 // waves of a block (k_cheb_nodes_mx with every level split, k_voigt_edge_mx<4>)
-static bool sep_in_use(bool have_sep, bool always, int nblocks_intervals, int kn, bool lor, bool mixed, bool small = false)
+static bool sep_in_use(bool have_sep, bool always, int nblocks_intervals, int kn, bool mixed, bool small = false)
 {
     (void)mixed;   // (the mixed-precision variant keeps the matrix-core pieces in fp64: only the vector bodies beyond far_s go to fp32)
-    return have_sep && !lor && (always || small || mx_big(nblocks_intervals, kn, 2048));
+    return have_sep && (always || small || mx_big(nblocks_intervals, kn, 2048));
 }
 // the per-point pieces (k_voigt_edge_mx: one wave per (tile, state group), no reduction) pay on shorter grids -- 1/4 of C3 (1564
 // waves): far 0.42 -> 0.36 ms; 1/8: 0.261 -> 0.244 ms, which the extra zone launch eats -- but only on tables dense enough to give
 // a wave more than a few steps (C5's HITRAN fixtures: far 3.94 -> 4.01 ms with them; its synthetic O3 table: step 10.63 -> 10.51)
-static bool edge_in_use(bool have_edge, bool always, int ntiles, int kn, bool lor, bool mixed, int64_t lines_in_range, bool small = false)
+static bool edge_in_use(bool have_edge, bool always, int ntiles, int kn, bool mixed, int64_t lines_in_range, bool small = false)
 {
     (void)mixed;
-    return have_edge && !lor && (always || ((small || mx_big(ntiles, kn, 1024)) && lines_in_range >= (int64_t)ntiles * CS_EDGE_DENS));
+    return have_edge && (always || ((small || mx_big(ntiles, kn, 1024)) && lines_in_range >= (int64_t)ntiles * CS_EDGE_DENS));
 }
 
 // Short grids (a nu-shard): the kernels no longer fill the chip, a step is a chain of launch tails -- and the node sums (F) and the
@@ -1508,7 +1508,7 @@ template <bool MIX, bool LOR, bool EDGE> static FarKernel far_kernel_split(int s
 }
 static FarKernel far_kernel(bool mixed, int split, bool lor, bool edge)
 {
-    if (lor) return far_kernel_split<false, true, false>(split);
+    if (lor) return edge ? far_kernel_split<false, true, true>(split) : far_kernel_split<false, true, false>(split);
     if (mixed) return edge ? far_kernel_split<true, false, true>(split) : far_kernel_split<true, false, false>(split);
     return edge ? far_kernel_split<false, false, true>(split) : far_kernel_split<false, false, false>(split);
 }
@@ -1537,8 +1537,8 @@ static VoigtPlan voigt_plan(const GasPass &p)
         pl.nb_iz = (unsigned)(((int64_t)nq * kn + 255) / 256);
         // what the matrix cores take of the interpolated sets and of the window ends (not of a shifted group: GasPass::pshift)
         if (!p.pshift) {
-            pl.use_sep = sep_in_use(itp.sep != nullptr, st.matrix_nodes == 2, nq, kn, pl.lor, mixed, st.small_mx);
-            pl.use_edge = edge_in_use(itp.edge != nullptr, st.matrix_nodes == 2, pl.nt64, kn, pl.lor, mixed, nlines, st.small_mx);
+            pl.use_sep = sep_in_use(itp.sep != nullptr, st.matrix_nodes == 2, nq, kn, mixed, st.small_mx);
+            pl.use_edge = edge_in_use(itp.edge != nullptr, st.matrix_nodes == 2, pl.nt64, kn, mixed, nlines, st.small_mx);
         }
         // short grids: four waves per (interval, state) (Settings::nodes_split: 0 = below 16384 waves, 1 = always, 2 = never)
         pl.nsplit4 = st.nodes_split == 1 || (st.nodes_split == 0 && (int64_t)nq * kn < 16384);
@@ -1553,7 +1553,7 @@ static VoigtPlan voigt_plan(const GasPass &p)
             for (int l = 0; l < itp.nlev; l++) pl.nfar[l] = itp.nfar[l] > 0 ? itp.nfar[l] : CS_NC;
         }
     }
-    pl.core = pl.use_edge && st.matrix_core;
+    pl.core = pl.use_edge && st.matrix_core && !pl.lor;   // (a Lorentz group takes no cores: the lines within the 4-term radius of a tile stay with k_voigt_far's exact body)
     // The piece tables per (interval | tile, state group) need the zones -- which their sixteen-lanes-per-item form computes itself, as
     // blocks of the SAME launch (k_gas_setup_mx); the one-thread-per-item form reads them, a launch of its own behind k_gas_setup
     if (pl.use_sep || pl.use_edge) {
@@ -1627,6 +1627,7 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
     if (pl.tables != TABLES_NONE) {
         sa.nodes = itp.nodes; sa.nul = G.nu.as<double>(); sa.gbound = p.gbound; sa.Tk = p.Tk; sa.iz = itp.iz; sa.out = itp.sep;
         sa.nItot = itp.nItot; sa.q0 = pl.q0; sa.K = kn; sa.ngrp = pl.ngrp; sa.mu_min = G.mu_min; sa.cut = p.cut; sa.min_states = p.set->mx_min_states;
+        sa.lorentz = ea.lorentz = pl.lor ? 1 : 0;
         ea.nu = p.dnu; ea.nul = G.nu.as<double>(); ea.gbound = p.gbound; ea.Tk = p.Tk; ea.win = p.win; ea.zones = p.zones;
         ea.iz = itp.iz + itp.ioff[itp.nlev - 1]; ea.out = itp.edge; ea.nnu = nnu; ea.ntile = nt64; ea.K = kn; ea.ngrp = pl.ngrp;
         ea.nI = itp.nItot; ea.ishift = pl.ishift;
@@ -1677,7 +1678,7 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
             for (int l = 0; l < itp.nlev; l++) { mf.ioff[l] = itp.ioff[l]; mf.nfar[l] = pl.nfar[l]; }
             mf.ioff[itp.nlev] = itp.nItot;
             mf.R = pl.far_R ? itp.R : nullptr;
-            CS_LAUNCH(k_cheb_nodes_mx, dim3(pl.nblk_mx), dim3(256), 0, s, itp.nodes, G.L, p.hot, itp.sep, itp.nItot, q0, pl.nsplit, kn,
+            CS_LAUNCH(pl.lor ? k_cheb_nodes_mx<true> : k_cheb_nodes_mx<false>, dim3(pl.nblk_mx), dim3(256), 0, s, itp.nodes, G.L, p.hot, itp.sep, itp.nItot, q0, pl.nsplit, kn,
                                itp.Kpad, pl.ngrp, itp.F, itp.iz, mf);
         }
         if (s != sm) {
@@ -1766,7 +1767,8 @@ static void line_sum_voigt(hipStream_t s, const GasPass &p, const PrepArgs &pa, 
     if (use_edge) {
         if (fuse) fork_join(p.fork, s);   // (it reads F)
         const unsigned ntx = pl.edge_big ? (unsigned)((nt64 + 3) / 4) : (unsigned)nt64;
-        CS_LAUNCH(pl.edge_big ? k_voigt_edge_mx<1> : k_voigt_edge_mx<4>, dim3(ntx, (unsigned)pl.ngrp), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.win,
+        const auto edge_kernel = pl.lor ? (pl.edge_big ? k_voigt_edge_mx<1, true> : k_voigt_edge_mx<4, true>) : (pl.edge_big ? k_voigt_edge_mx<1> : k_voigt_edge_mx<4>);
+        CS_LAUNCH(edge_kernel, dim3(ntx, (unsigned)pl.ngrp), dim3(256), 0, s, p.dnu, nnu, G.L, p.hot, p.win,
                   itp.edge, nt64, kn, p.cut, p.sigma, fuse ? 1 : 0, Afuse, itp.Kpad, G.nu.as<double>(), pl.edge_phases,
                   pl.tnodes ? itp.tnodes : (const double *)nullptr, pl.edge_big ? itp.tC : (const double *)nullptr);
     }

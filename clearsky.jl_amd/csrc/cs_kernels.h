@@ -782,7 +782,8 @@ __device__ __forceinline__ IZone izone_compute(const IzParams &P, const ZoneArgs
     }
     // this state's radius of the 4-term series in 1/dnu^2 (sepzones_body takes the group's pieces from these)
     const double R4 = [&] {
-        const double amax = ((vhi + cut) / kC) * vth / sqrt(mu_min), gb = gbound[k];
+        // (a Lorentz profile: its own geometric series, no Doppler width in the radius)
+        const double amax = a.lorentz ? 0.0 : ((vhi + cut) / kC) * vth / sqrt(mu_min), gb = gbound[k];
         return sep_radii(gb, amax).r4;
     }();
     // own Z0, Z1 (set stays dZ away), M0, M1 (4-term zone), Q0, Q1 (3-term zone), parent's Z0, Z1, series radius: ten searches side by side
@@ -954,7 +955,7 @@ __global__ __launch_bounds__(256) void k_cheb_nodes(const double *__restrict__ n
     const IZone z = iz[(size_t)k * nItot + T];
     const FarK c = load_fark();
     int sa[4] = {z.P0, z.Z0, z.Z1, z.P3}, sb[4] = {z.P0, z.Z0, z.Z1, z.P3};   // (no matrix-core pieces: empty ones at the window ends)
-    if (!LOR && sep) {   // (also in the mixed-precision variant: what the matrix cores take stays fp64 -- they beat the fp32 vector bodies)
+    if (sep) {   // (also in the mixed-precision variant: what the matrix cores take stays fp64 -- they beat the fp32 vector bodies; Lorentz alike)
         const SepZone sz = sep[(size_t)(k >> 4) * nItot + T];
         // of the group's piece the matrix cores sum, for THIS state, only the lines beyond its own series radius (IZone::S0, S1): the
         // rest of the piece stays here
@@ -1011,27 +1012,38 @@ typedef double v4f64_sep __attribute__((ext_vector_type(4)));
 // one step of the matrix-core sums: 4 lines x 64 columns (nodes or points) x 16 states.  The lane's record as (state lr, line lq)
 // gives the NT coefficients (A operands) and, as (column lr, line lq), the line position; vn[st] = the lane's column of sub-tile
 // st.  MASK: w = 0 beyond the cut-off (line_shapes.jl:10).  4 NT matrix instructions.
-template <int NT, int MASK, int NST = 4, int ST0 = 0, int NA = 4>   // MASK 1: w = 0 beyond the cut-off; 2: also inside the radius rin (those pairs are k_voigt_sub's)
+// LOR: the lane's record is the Lorentz one, {nul, gamma^2, C S gamma/pi} (prep_body), and the series the geometric one of the profile
+// itself: p2 w / (1 + gamma^2 w) = p2 sum_n (-gamma^2)^n w^(n+1) -- a_0 = p2, a_n = -gamma^2 a_(n-1).  It alternates, so NT terms leave less
+// than (gamma^2 w)^NT: kSepEps at sep_radii(gamma, 0).  3 and 4 terms, MASK 0 and 1 only (a Lorentz group has no cores: edge_pieces)
+template <int NT, int MASK, int NST = 4, int ST0 = 0, int NA = 4, bool LOR = false>   // MASK 1: w = 0 beyond the cut-off; 2: also inside the radius rin (those pairs are k_voigt_sub's)
 __device__ __forceinline__ void sep_step(v4f64_sep (&acc)[NA], const double (&vn)[NA], const LineHot &h, bool valid, double cut, double rin = 0.0)
 {   // the NST sub-tiles of 16 columns from ST0 on (4: a 64-point tile or the 64 nodes of an interval; 1, 2: a far piece on 16 or 32
     // nodes; 1 .. 3 from either end: a cut-off edge whose far lines reach only the first or last columns of the tile)
     static_assert(ST0 + NST <= NA, "sub-tile range");
-    const double id2 = rcp_nr1(h.p1 * h.p1);
-    const double y2 = h.p2;
-    // a_n = (A y / sqrt(pi)) c_n(y^2) / d^(2n), c_n from tools/voigt_series.py (exact rationals, all representable)
+    static_assert(!LOR || (NT <= 4 && MASK != 2), "the Lorentz series has no 8-term tier and no cores");
     double a[NT];
-    double Cn = valid ? h.p3 * id2 : 0.0;
-    a[0] = Cn;
-    Cn *= id2; a[1] = Cn * (1.5 - y2);
-    Cn *= id2; a[2] = Cn * __builtin_fma(y2, y2 - 5.0, 3.75);
-    if (NT >= 4) { Cn *= id2; a[3] = Cn * __builtin_fma(y2, __builtin_fma(y2, 10.5 - y2, -26.25), 13.125); }
-    if (NT == 8) {
-        Cn *= id2; a[4] = Cn * __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, y2 - 18.0, 94.5), -157.5), 59.0625);
-        Cn *= id2; a[5] = Cn * __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, 27.5 - y2, -247.5), 866.25), -1082.8125), 324.84375);
-        Cn *= id2; a[6] = Cn * __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, y2 - 39.0, 536.25), -3217.5), 8445.9375),
-                                                               -8445.9375), 2111.484375);
-        Cn *= id2; a[7] = Cn * __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, 52.5 - y2, -1023.75), 9384.375),
-                                                                                          -42229.6875), 88682.34375), -73901.953125), 15836.1328125);
+    if constexpr (LOR) {
+        const double mg2 = -h.p1;
+        a[0] = valid ? h.p2 : 0.0;
+#pragma unroll
+        for (int n = 1; n < NT; n++) a[n] = mg2 * a[n - 1];
+    } else {
+        const double id2 = rcp_nr1(h.p1 * h.p1);
+        const double y2 = h.p2;
+        // a_n = (A y / sqrt(pi)) c_n(y^2) / d^(2n), c_n from tools/voigt_series.py (exact rationals, all representable)
+        double Cn = valid ? h.p3 * id2 : 0.0;
+        a[0] = Cn;
+        Cn *= id2; a[1] = Cn * (1.5 - y2);
+        Cn *= id2; a[2] = Cn * __builtin_fma(y2, y2 - 5.0, 3.75);
+        if (NT >= 4) { Cn *= id2; a[3] = Cn * __builtin_fma(y2, __builtin_fma(y2, 10.5 - y2, -26.25), 13.125); }
+        if (NT == 8) {
+            Cn *= id2; a[4] = Cn * __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, y2 - 18.0, 94.5), -157.5), 59.0625);
+            Cn *= id2; a[5] = Cn * __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, 27.5 - y2, -247.5), 866.25), -1082.8125), 324.84375);
+            Cn *= id2; a[6] = Cn * __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, y2 - 39.0, 536.25), -3217.5), 8445.9375),
+                                                                   -8445.9375), 2111.484375);
+            Cn *= id2; a[7] = Cn * __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, __builtin_fma(y2, 52.5 - y2, -1023.75), 9384.375),
+                                                                                              -42229.6875), 88682.34375), -73901.953125), 15836.1328125);
+        }
     }
     // w = 1 / dnu^2 of the NST sub-tiles.  Where no dnu can vanish (MASK 0, 1: the lines of these pieces are at least a series radius
     // from every column) the reciprocals of two or four sub-tiles come from ONE reciprocal of their product -- 1/a = b/(ab) -- 10 resp.
@@ -1089,7 +1101,7 @@ __device__ __forceinline__ void sep_step(v4f64_sep (&acc)[NA], const double (&vn
 // matrix instructions of step t and waited for after them
 // [jlo_ok, jhi_ok): the lines of the run this LANE's state takes part in (its coefficients are zero for the others: a state whose own
 // series radius excludes a line of the group's piece leaves it to the vector-unit kernel)
-template <int NT, int MASK, int NST = 4, int ST0 = 0, int NA = 4>
+template <int NT, int MASK, int NST = 4, int ST0 = 0, int NA = 4, bool LOR = false>
 __device__ __forceinline__ void sep_run(v4f64_sep (&acc)[NA], const double (&vn)[NA], const LineHot *__restrict__ hk, int ja, int jb, bool asc,
                                         int lq, double cut, double rin = 0.0, int jlo_ok = -0x7fffffff, int jhi_ok = 0x7fffffff)
 {
@@ -1102,7 +1114,7 @@ __device__ __forceinline__ void sep_run(v4f64_sep (&acc)[NA], const double (&vn)
     for (int t = 0; t < nst; t++) {
         const LineHot nxt = rec(t + 1);      // (past the end: a harmless re-read of an end record, never used)
         __builtin_amdgcn_sched_barrier(0);   // keep the load here: the scheduler would sink it behind the matrix instructions
-        sep_step<NT, MASK, NST, ST0, NA>(acc, vn, cur, ok(t), cut, rin);
+        sep_step<NT, MASK, NST, ST0, NA, LOR>(acc, vn, cur, ok(t), cut, rin);
         __builtin_amdgcn_sched_barrier(0);   // ... and the wait for it there
         cur = nxt;
     }
@@ -1113,6 +1125,7 @@ struct SepArgs {
     const IZone *iz;
     SepZone *out;
     int nItot, q0, K, ngrp;
+    int lorentz;      // a Lorentz group (ZoneArgs::lorentz): the series radii at alpha = 0
     int min_states;   // a line joins a group's matrix-core piece when at least this many of its states are beyond their series radius
     double mu_min, cut;
 };
@@ -1138,9 +1151,10 @@ template <int W, class T, class Op> __device__ __forceinline__ T redW(T v, Op op
 }
 template <int W> __device__ __forceinline__ int bcastW(int v, int lane) { return W == 1 ? v : __shfl(v, lane, W); }   // lane's v, to every lane of the item
 // the series radii of a state for the lines a column up to vhi can see: its Lorentz-width bound, the Doppler width at the upper end of the window
-__device__ __forceinline__ SepRadii state_radii(double vhi, double cut, double Tk, double mu_min, double gb)
+// (lorentz: the radii of the profile's own geometric series -- alpha = 0)
+__device__ __forceinline__ SepRadii state_radii(double vhi, double cut, double Tk, double mu_min, double gb, bool lorentz)
 {
-    const double amax = ((vhi + cut) / kC) * sqrt(2.0 * kRgas * Tk) / sqrt(mu_min);
+    const double amax = lorentz ? 0.0 : ((vhi + cut) / kC) * sqrt(2.0 * kRgas * Tk) / sqrt(mu_min);
     return sep_radii(gb, amax);
 }
 
@@ -1214,7 +1228,7 @@ __device__ __forceinline__ void sepzones_body(unsigned bid, const SepArgs &a, co
         s0v[j] = G.S0; s1v[j] = G.S1;           // (a group's missing tail states never count)
         if (kk >= ns) continue;
         const IZone z = RC ? izone_compute(*ip, *za, k, T) : a.iz[(size_t)k * a.nItot + T];
-        const SepState s = sep_state(z, state_radii(vhi, a.cut, a.Tk[k], a.mu_min, a.gbound[k]).r3);
+        const SepState s = sep_state(z, state_radii(vhi, a.cut, a.Tk[k], a.mu_min, a.gbound[k], a.lorentz).r3);
         sep_fold(G, s);
         s0v[j] = s.S0; s1v[j] = s.S1;
         if (kk == ns - 1) { E0 = z.E0; E1 = z.E1; }
@@ -1268,7 +1282,7 @@ __device__ __forceinline__ void sepzones_body(unsigned bid, const SepArgs &a, co
 // fixed 64 x n matrix in the interval's own coordinate (R: [64][32] then [64][16], built by the host in extended precision), one more
 // small matrix product per (interval, state group) -- and F, the apply kernel and everything after them never know.
 struct MxFar { int nlev, ioff[CS_MAX_LEVEL + 1], nfar[CS_MAX_LEVEL]; const double *R; };   // nfar[l]: 16, 32 or 64 (= as before); R = NULL: 64 everywhere
-template <int NST>
+template <int NST, bool LOR = false>
 __device__ __forceinline__ void mx_far_pieces(v4f64_sep (&acc)[4], const SepZone &z, const LineHot *__restrict__ hk, double vlo, double vhi,
                                               int lr, int lq, int S0k, int S1k, const double *__restrict__ R, double (*__restrict__ tr)[CS_MX_PITCH],
                                               int wq = 0, int nq = 1)
@@ -1292,12 +1306,12 @@ __device__ __forceinline__ void mx_far_pieces(v4f64_sep (&acc)[4], const SepZone
         af[st] = v4f64_sep{0.0, 0.0, 0.0, 0.0};
     }
     if (z.b[0] > z.a[0]) {   // left of the interval, ascending: the 3-term part (the far end) first
-        if (z.m[0] > z.a[0]) { mine(z.a[0], z.m[0], true, ja, jb); sep_run<3, 0, NST, 0, NST>(af, vf, hk, ja, jb, true, lq, 0.0, 0.0, -0x7fffffff, S0k); }
-        if (z.b[0] > z.m[0]) { mine(z.m[0], z.b[0], true, ja, jb); sep_run<4, 0, NST, 0, NST>(af, vf, hk, ja, jb, true, lq, 0.0, 0.0, -0x7fffffff, S0k); }
+        if (z.m[0] > z.a[0]) { mine(z.a[0], z.m[0], true, ja, jb); sep_run<3, 0, NST, 0, NST, LOR>(af, vf, hk, ja, jb, true, lq, 0.0, 0.0, -0x7fffffff, S0k); }
+        if (z.b[0] > z.m[0]) { mine(z.m[0], z.b[0], true, ja, jb); sep_run<4, 0, NST, 0, NST, LOR>(af, vf, hk, ja, jb, true, lq, 0.0, 0.0, -0x7fffffff, S0k); }
     }
     if (z.b[3] > z.a[3]) {   // right of it, descending
-        if (z.b[3] > z.m[3]) { mine(z.m[3], z.b[3], false, ja, jb); sep_run<3, 0, NST, 0, NST>(af, vf, hk, ja, jb, false, lq, 0.0, 0.0, S1k); }
-        if (z.m[3] > z.a[3]) { mine(z.a[3], z.m[3], false, ja, jb); sep_run<4, 0, NST, 0, NST>(af, vf, hk, ja, jb, false, lq, 0.0, 0.0, S1k); }
+        if (z.b[3] > z.m[3]) { mine(z.m[3], z.b[3], false, ja, jb); sep_run<3, 0, NST, 0, NST, LOR>(af, vf, hk, ja, jb, false, lq, 0.0, 0.0, S1k); }
+        if (z.m[3] > z.a[3]) { mine(z.a[3], z.m[3], false, ja, jb); sep_run<4, 0, NST, 0, NST, LOR>(af, vf, hk, ja, jb, false, lq, 0.0, 0.0, S1k); }
     }
     // acc[state][m] += sum_j af[state][j] R[m][j]: af goes through LDS from the D layout (state 4r + lq, node lr) to the A layout
     // (state lr, node lq of a group of four)
@@ -1321,6 +1335,7 @@ __device__ __forceinline__ void mx_far_pieces(v4f64_sep (&acc)[4], const SepZone
 // (waves_per_eu: left alone the allocator puts the 32 accumulator registers into AGPRs but carries them around the loop's back edge in VGPRs
 //  -- 32 v_accvgpr_write + 32 v_accvgpr_read per 4-line step, 64 of the step's 144 vector instructions, round 5's reading of the ISA; with
 //  the register budget of three waves per SIMD it keeps them in VGPRs, as k_voigt_edge_mx has had since round 3)
+template <bool LOR = false>   // LOR: a Lorentz group -- its records and series (sep_step), everything else as for Voigt
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_cheb_nodes_mx(const double *__restrict__ nodes, int64_t L, const LineHot *__restrict__ hot,
                                                        const SepZone *__restrict__ sep, int nItot, int q0, int nsplit, int K, int Kpad,
                                                        int ngrp, double *__restrict__ F, const IZone *__restrict__ iz, MxFar far)
@@ -1371,8 +1386,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             const int nf = far.nfar[l];
             if (nf < CS_NC && (z.b[0] > z.a[0] || z.b[3] > z.a[3])) {
                 const double vhi = nodes[(size_t)T * CS_NC], vlo = nodes[(size_t)T * CS_NC + CS_NC - 1];
-                if (nf == 16) mx_far_pieces<1>(acc, z, hk, vlo, vhi, lr, lq, S0k, S1k, far.R, part[wv], split ? wv : 0, split ? 4 : 1);
-                else mx_far_pieces<2>(acc, z, hk, vlo, vhi, lr, lq, S0k, S1k, far.R, part[wv], split ? wv : 0, split ? 4 : 1);
+                if (nf == 16) mx_far_pieces<1, LOR>(acc, z, hk, vlo, vhi, lr, lq, S0k, S1k, far.R, part[wv], split ? wv : 0, split ? 4 : 1);
+                else mx_far_pieces<2, LOR>(acc, z, hk, vlo, vhi, lr, lq, S0k, S1k, far.R, part[wv], split ? wv : 0, split ? 4 : 1);
                 far_done = true;
             }
         }
@@ -1382,11 +1397,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             if (z.b[p] <= z.a[p] || (far_done && (p == 0 || p == 3))) continue;
             int ja, jb;
             if (asc) {
-                if (z.m[p] > z.a[p]) { quarter(z.a[p], z.m[p], true, ja, jb); sep_run<3, 0>(acc, vn, hk, ja, jb, true, lq, 0.0, 0.0, -0x7fffffff, S0k); }
-                if (z.b[p] > z.m[p]) { quarter(z.m[p], z.b[p], true, ja, jb); sep_run<4, 0>(acc, vn, hk, ja, jb, true, lq, 0.0, 0.0, -0x7fffffff, S0k); }
+                if (z.m[p] > z.a[p]) { quarter(z.a[p], z.m[p], true, ja, jb); sep_run<3, 0, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, true, lq, 0.0, 0.0, -0x7fffffff, S0k); }
+                if (z.b[p] > z.m[p]) { quarter(z.m[p], z.b[p], true, ja, jb); sep_run<4, 0, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, true, lq, 0.0, 0.0, -0x7fffffff, S0k); }
             } else {
-                if (z.b[p] > z.m[p]) { quarter(z.m[p], z.b[p], false, ja, jb); sep_run<3, 0>(acc, vn, hk, ja, jb, false, lq, 0.0, 0.0, S1k); }
-                if (z.m[p] > z.a[p]) { quarter(z.a[p], z.m[p], false, ja, jb); sep_run<4, 0>(acc, vn, hk, ja, jb, false, lq, 0.0, 0.0, S1k); }
+                if (z.b[p] > z.m[p]) { quarter(z.m[p], z.b[p], false, ja, jb); sep_run<3, 0, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, false, lq, 0.0, 0.0, S1k); }
+                if (z.m[p] > z.a[p]) { quarter(z.a[p], z.m[p], false, ja, jb); sep_run<4, 0, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, false, lq, 0.0, 0.0, S1k); }
             }
         }
         if (!split) {   // D[state 4r + lq][node 16 st + lr] straight into F
@@ -1755,7 +1770,8 @@ struct EdgeArgs {
     const IZone *iz;      // lowest interpolation level, or NULL
     EdgeZone *out;        // [ngrp][ntile]
     int64_t nnu;
-    int ntile, K, ngrp, nI, ishift, core;   // core: sub-tile treatment of the window core where it pays (k_voigt_sub)
+    int ntile, K, ngrp, nI, ishift, core;   // core: sub-tile treatment of the window core where it pays (k_voigt_sub); never for a Lorentz group
+    int lorentz;                            // a Lorentz group (ZoneArgs::lorentz): the series radii at alpha = 0
     double mu_min, cut, core4;              // core4: the core takes the 4-term series where its radius is below core4 x the tile's span
     double mu_max;                          // heaviest molecule of the table (sub_series_free)
 };
@@ -1854,7 +1870,7 @@ __device__ __forceinline__ void edgezones_body(unsigned bid, const EdgeArgs &a, 
         const Zone z = RC ? zone_compute(*za, k, t) : a.zones[(size_t)k * a.ntile + t];
         const FarCovered c = !a.iz ? far_covered(z)
                              : far_covered(z, RC ? izone_compute(*ip, *za, k, ip->ioff[ip->nlev - 1] + (t >> a.ishift)) : a.iz[(size_t)k * a.nI + (t >> a.ishift)], w);
-        edge_fold(G, edge_state(z, c, state_radii(vhi, a.cut, a.Tk[k], a.mu_min, a.gbound[k])));
+        edge_fold(G, edge_state(z, c, state_radii(vhi, a.cut, a.Tk[k], a.mu_min, a.gbound[k], a.lorentz)));
     }
     edge_group<W>(G);
     int sr[4];
@@ -1925,7 +1941,8 @@ __global__ __launch_bounds__(256) void k_gas_setup_mx_vvh(unsigned nb_prep, unsi
 // SPLIT = 4 (short grids: a nu-shard of a multi-GPU run has a few hundred tiles, i.e. fewer (tile, group) waves than the chip has
 // SIMDs, each a chain of a hundred dependent load -> matrix steps): the four waves of a block share ONE (tile, group), every piece
 // cut into four runs of lines as in k_cheb_nodes_mx, partial sums added through LDS in wave order (bitwise repeatable).
-template <int SPLIT>
+// LOR: a Lorentz group -- its records and series (sep_step); it has no cores (edge_pieces is never asked for one)
+template <int SPLIT, bool LOR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_voigt_edge_mx(const double *__restrict__ nu, int64_t nnu, int64_t L, const LineHot *__restrict__ hot,
                                                        const WaveWin *__restrict__ win, const EdgeZone *__restrict__ edge, int ntile, int K,
                                                        double cut, double *__restrict__ sigma, int fuse, ChebApply A, int Kpad,
@@ -2043,10 +2060,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         v4f64_sep af[1] = {v4f64_sep{0.0, 0.0, 0.0, 0.0}};
         const double vf[1] = {tnodes[(size_t)tile * 16 + lr]};
         if (ndL) {
-            if (e.far3 & 1) sep_run<3, 0, 1, 0, 1>(af, vf, hk, J[3], e.eL, true, lq, 0.0); else sep_run<4, 0, 1, 0, 1>(af, vf, hk, J[3], e.eL, true, lq, 0.0);
+            if (e.far3 & 1) sep_run<3, 0, 1, 0, 1, LOR>(af, vf, hk, J[3], e.eL, true, lq, 0.0); else sep_run<4, 0, 1, 0, 1, LOR>(af, vf, hk, J[3], e.eL, true, lq, 0.0);
         }
         if (ndR) {
-            if (e.far3 & 2) sep_run<3, 0, 1, 0, 1>(af, vf, hk, e.eR, U[3], false, lq, 0.0); else sep_run<4, 0, 1, 0, 1>(af, vf, hk, e.eR, U[3], false, lq, 0.0);
+            if (e.far3 & 2) sep_run<3, 0, 1, 0, 1, LOR>(af, vf, hk, e.eR, U[3], false, lq, 0.0); else sep_run<4, 0, 1, 0, 1, LOR>(af, vf, hk, e.eR, U[3], false, lq, 0.0);
         }
         // acc[state][point] += sum_m af[state][m] tC[tile][m][point]: af goes through LDS from the D layout (state 4r + lq, node lr) to the A
         // layout (state lr, node lq of a group of four), as in mx_far_pieces
@@ -2066,48 +2083,50 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     if (phL) {
         const int p0 = w.W0;
         if (e.far3 & 1) {
-            sep_run<3, 1, 1, 0>(acc, vn, hk, p0, J[0], true, lq, cut);
-            sep_run<3, 1, 2, 0>(acc, vn, hk, J[0], J[1], true, lq, cut);
-            sep_run<3, 1, 3, 0>(acc, vn, hk, J[1], J[2], true, lq, cut);
-            sep_run<3, 1, 4, 0>(acc, vn, hk, J[2], J[3], true, lq, cut);
+            sep_run<3, 1, 1, 0, 4, LOR>(acc, vn, hk, p0, J[0], true, lq, cut);
+            sep_run<3, 1, 2, 0, 4, LOR>(acc, vn, hk, J[0], J[1], true, lq, cut);
+            sep_run<3, 1, 3, 0, 4, LOR>(acc, vn, hk, J[1], J[2], true, lq, cut);
+            sep_run<3, 1, 4, 0, 4, LOR>(acc, vn, hk, J[2], J[3], true, lq, cut);
         } else {
-            sep_run<4, 1, 1, 0>(acc, vn, hk, p0, J[0], true, lq, cut);
-            sep_run<4, 1, 2, 0>(acc, vn, hk, J[0], J[1], true, lq, cut);
-            sep_run<4, 1, 3, 0>(acc, vn, hk, J[1], J[2], true, lq, cut);
-            sep_run<4, 1, 4, 0>(acc, vn, hk, J[2], J[3], true, lq, cut);
+            sep_run<4, 1, 1, 0, 4, LOR>(acc, vn, hk, p0, J[0], true, lq, cut);
+            sep_run<4, 1, 2, 0, 4, LOR>(acc, vn, hk, J[0], J[1], true, lq, cut);
+            sep_run<4, 1, 3, 0, 4, LOR>(acc, vn, hk, J[1], J[2], true, lq, cut);
+            sep_run<4, 1, 4, 0, 4, LOR>(acc, vn, hk, J[2], J[3], true, lq, cut);
         }
     } else {
         run(w.W0, e.eL, true, ja, jb);
-        if (e.far3 & 1) sep_run<3, 1>(acc, vn, hk, ja, jb, true, lq, cut); else sep_run<4, 1>(acc, vn, hk, ja, jb, true, lq, cut);
+        if (e.far3 & 1) sep_run<3, 1, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, true, lq, cut); else sep_run<4, 1, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, true, lq, cut);
     }
     if (e.mL1 > e.mL0) {
-        run(e.mL0, e.mL3, true, ja, jb); sep_run<3, 1>(acc, vn, hk, ja, jb, true, lq, cut);
-        run(e.mL3, e.mL1, true, ja, jb); sep_run<4, 1>(acc, vn, hk, ja, jb, true, lq, cut);
+        run(e.mL0, e.mL3, true, ja, jb); sep_run<3, 1, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, true, lq, cut);
+        run(e.mL3, e.mL1, true, ja, jb); sep_run<4, 1, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, true, lq, cut);
     }
     if (phR) {
         const int p1 = w.W1;
         if (e.far3 & 2) {
-            sep_run<3, 1, 1, 3>(acc, vn, hk, U[2], p1, false, lq, cut);
-            sep_run<3, 1, 2, 2>(acc, vn, hk, U[1], U[2], false, lq, cut);
-            sep_run<3, 1, 3, 1>(acc, vn, hk, U[0], U[1], false, lq, cut);
-            sep_run<3, 1, 4, 0>(acc, vn, hk, U[3], U[0], false, lq, cut);
+            sep_run<3, 1, 1, 3, 4, LOR>(acc, vn, hk, U[2], p1, false, lq, cut);
+            sep_run<3, 1, 2, 2, 4, LOR>(acc, vn, hk, U[1], U[2], false, lq, cut);
+            sep_run<3, 1, 3, 1, 4, LOR>(acc, vn, hk, U[0], U[1], false, lq, cut);
+            sep_run<3, 1, 4, 0, 4, LOR>(acc, vn, hk, U[3], U[0], false, lq, cut);
         } else {
-            sep_run<4, 1, 1, 3>(acc, vn, hk, U[2], p1, false, lq, cut);
-            sep_run<4, 1, 2, 2>(acc, vn, hk, U[1], U[2], false, lq, cut);
-            sep_run<4, 1, 3, 1>(acc, vn, hk, U[0], U[1], false, lq, cut);
-            sep_run<4, 1, 4, 0>(acc, vn, hk, U[3], U[0], false, lq, cut);
+            sep_run<4, 1, 1, 3, 4, LOR>(acc, vn, hk, U[2], p1, false, lq, cut);
+            sep_run<4, 1, 2, 2, 4, LOR>(acc, vn, hk, U[1], U[2], false, lq, cut);
+            sep_run<4, 1, 3, 1, 4, LOR>(acc, vn, hk, U[0], U[1], false, lq, cut);
+            sep_run<4, 1, 4, 0, 4, LOR>(acc, vn, hk, U[3], U[0], false, lq, cut);
         }
     } else {
         run(e.eR, w.W1, false, ja, jb);
-        if (e.far3 & 2) sep_run<3, 1>(acc, vn, hk, ja, jb, false, lq, cut); else sep_run<4, 1>(acc, vn, hk, ja, jb, false, lq, cut);
+        if (e.far3 & 2) sep_run<3, 1, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, false, lq, cut); else sep_run<4, 1, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, false, lq, cut);
     }
     if (e.mR1 > e.mR0) {
-        run(e.mR3, e.mR1, false, ja, jb); sep_run<3, 1>(acc, vn, hk, ja, jb, false, lq, cut);
-        run(e.mR0, e.mR3, false, ja, jb); sep_run<4, 1>(acc, vn, hk, ja, jb, false, lq, cut);
+        run(e.mR3, e.mR1, false, ja, jb); sep_run<3, 1, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, false, lq, cut);
+        run(e.mR0, e.mR3, false, ja, jb); sep_run<4, 1, 4, 0, 4, LOR>(acc, vn, hk, ja, jb, false, lq, cut);
     }
-    if (e.cR > e.cL) {   // the core: pairs at least R apart
-        run(e.cL, e.cR, true, ja, jb);
-        if (e.far3 & 4) sep_run<8, 2>(acc, vn, hk, ja, jb, true, lq, cut, e.R); else sep_run<4, 2>(acc, vn, hk, ja, jb, true, lq, cut, e.R);
+    if constexpr (!LOR) {
+        if (e.cR > e.cL) {   // the core: pairs at least R apart
+            run(e.cL, e.cR, true, ja, jb);
+            if (e.far3 & 4) sep_run<8, 2>(acc, vn, hk, ja, jb, true, lq, cut, e.R); else sep_run<4, 2>(acc, vn, hk, ja, jb, true, lq, cut, e.R);
+        }
     }
     if (SPLIT == 1) {
 #pragma unroll

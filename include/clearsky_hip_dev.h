@@ -22,7 +22,10 @@ int cs_set_interp_plan(cs_ctx *ctx, int first_level, int size_min, int size_max)
 
 /* Far lines on the matrix cores: where the 4-term series in 1/dnu^2 holds to 1e-15 relative for every state of a group of 16
  * (|dnu| >= 74.99 sqrt(gamma^2 + 4.33 alpha^2)), the node sums of the interpolated far wings and the window ends of the
- * per-point sum -- cut-off edges included, as a mask (K2e) -- are matrix products on v_mfma_f64_16x16x4.  on = 1 (default):
+ * per-point sum -- cut-off edges included, as a mask (K2e) -- are matrix products on v_mfma_f64_16x16x4.  A Lorentz group (shape code 1)
+ * takes the same path with the geometric series of its own profile, 3 or 4 terms in 1/dnu^2 from |dnu| >= 316.3 gamma resp. 74.99 gamma
+ * on; it has no sub-tile cores and no 8-term tier (the lines nearer than that stay with k_voigt_far's exact body), and under
+ * CS_SHAPE_PSHIFT it keeps the vector unit like every shifted group.  on = 1 (default):
  * where the grid has enough (interval | tile, state group) blocks to fill the chip; 2: always; 0: everything on the vector
  * unit; | 4 keeps the tile-wide near-zone pass where the default hands the core of a window to 16-point sub-tiles (k_voigt_sub).
  * Same results to rounding (tests/test_gpu_interp.py). */
