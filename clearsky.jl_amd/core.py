@@ -1062,15 +1062,17 @@ class Discretized:
     """core/shared.jl:55-66 -- and julia/ClearSkyHIP.jl's HIPDiscretized, whose extra field it carries: `fluxpack` says what
     radiate_ (radiate!, fluxes.jl:357-383) brings back.  "full": tau, M+, M- and the band fluxes, as the reference fills its FluxPack;
     "bands": Fup, Fdn, Fnet only -- all heating! reads (radiative_convective.jl:109-144) -- tau, M+, M- stay in HBM (NULL across the
-    ABI: no 146 MB copy per call at 1e5 x 60) and keep whatever the FluxPack held."""
+    ABI: no 146 MB copy per call at 1e5 x 60) and keep whatever the FluxPack held.  "edges": the band fluxes and the boundary spectra
+    M+, M- at the top and the bottom level (rows 0 and np-1 of F.Mup, F.Mdn) -- a resident column in the edges mode (Column(want_M=
+    "edges")): the planes are never allocated, 2 nnu doubles per spectrum come back; tau and the inner rows keep what the FluxPack held."""
 
     def __init__(self, nstream: int = 5, nlobatto: int = 2, fluxpack: str = "full"):
-        if fluxpack not in ("full", "bands"):
-            raise ValueError(f"fluxpack must be 'full' or 'bands', not {fluxpack!r}")
+        if fluxpack not in ("full", "bands", "edges"):
+            raise ValueError(f"fluxpack must be 'full', 'bands' or 'edges', not {fluxpack!r}")
         self.nstream, self.nlobatto, self.fluxpack = int(nstream), int(nlobatto), fluxpack
 
     def __repr__(self):
-        return f"Discretized(nstream={self.nstream}, nlobatto={self.nlobatto}" + (", fluxpack='bands')" if self.fluxpack == "bands" else ")")
+        return f"Discretized(nstream={self.nstream}, nlobatto={self.nlobatto}" + (f", fluxpack={self.fluxpack!r})" if self.fluxpack != "full" else ")")
 
 
 HIPDiscretized = Discretized     # the name of the core type in julia/ClearSkyHIP.jl
@@ -1103,6 +1105,49 @@ def checkstreams(n):
 # ----------------------------------------------------------------------------------------------------------------
 # whole-column evaluation (B3)
 
+# include/clearsky_hip.h, CS_M_*: what a resident column keeps of M+, M- (the `want_M` of cs_column_setup)
+M_NONE, M_PLANES, M_EDGES, M_TILES = 0, 1, 2, 3
+TILE = 64      # points per tile of the tiles mode: one wave of the flux kernels
+
+
+def m_mode(want_M) -> int:
+    """Column's want_M (False | True | "edges" | "tiles") as the CS_M_* value"""
+    if isinstance(want_M, str):
+        if want_M not in ("edges", "tiles"):
+            raise ValueError(f"want_M must be False, True, 'edges' or 'tiles', not {want_M!r}")
+        return M_EDGES if want_M == "edges" else M_TILES
+    return M_PLANES if want_M else M_NONE
+
+
+def tile_ranges(nnu: int):
+    """[(j0, j1), ...]: the points [j0, j1) of every 64-point tile of an nnu-point grid (or nu_range shard, counted from its first
+    point); the last tile may be ragged.  Column t of Column.tile_fluxes() sums these points.  Host only."""
+    nnu = int(nnu)
+    if nnu < 1:
+        raise ValueError("a grid has at least one point")
+    return [(j0, min(j0 + TILE, nnu)) for j0 in range(0, nnu, TILE)]
+
+
+def band_fluxes(Fup_t, Fdn_t, tile_edges):
+    """Whole tiles summed into bands: band b = tiles [tile_edges[b], tile_edges[b+1]) of Column.tile_fluxes()' arrays [np, ntile].
+    Returns (Fup_b, Fdn_b) of shape [np, nbands].  The tile sums carry the column's global trapezoid weights, so the bands of a full
+    partition add up to Fup, Fdn.  Edges that are not ascending tile indices in 0 .. ntile are refused (a band cannot cut a tile:
+    points inside one were never kept apart).  Host only."""
+    Fup_t, Fdn_t = np.asarray(Fup_t, float), np.asarray(Fdn_t, float)
+    if Fup_t.ndim != 2 or Fup_t.shape != Fdn_t.shape:
+        raise ValueError(f"expected two [np, ntile] arrays, got shapes {Fup_t.shape} and {Fdn_t.shape}")
+    ntile = Fup_t.shape[1]
+    e = np.asarray(tile_edges)
+    if e.ndim != 1 or len(e) < 2:
+        raise ValueError("tile_edges needs at least two entries")
+    if not (np.issubdtype(e.dtype, np.integer) or np.all(e == np.floor(e))):
+        raise ValueError("tile_edges must be tile indices (integers): a band is a sum of whole 64-point tiles")
+    e = e.astype(np.int64)
+    if e[0] < 0 or e[-1] > ntile or np.any(np.diff(e) <= 0):
+        raise ValueError(f"tile_edges must ascend strictly within 0 .. {ntile}")
+    out = [np.stack([np.array([math.fsum(row[a:b]) for row in F]) for a, b in zip(e[:-1], e[1:])], axis=1) for F in (Fup_t, Fdn_t)]
+    return out[0], out[1]
+
 
 class Column:
     """A column resident in HBM: inputs uploaded once, evaluated any number of times (cs_column_* in the C ABI).
@@ -1111,12 +1156,19 @@ class Column:
     lobattoevaluations (T, mu at Lobatto nodes), T at the levels for Planck, fC at the nodes, fS(nu), fa(nu).
     `nu_range=(j0, j1)` restricts the device work to a contiguous shard of the grid with the global trapezoid
     weights, so shards' Fup/Fdn simply add (multi-GPU).
+    `want_M`: False (band fluxes only), True (the planes M+, M- [np, nnu]), "edges" (M+, M- at level 0 = TOA and level np-1 only,
+    [2, nnu]: edge_spectra) or "tiles" (sum of w_j M[level, j] over every 64-point tile, [np, ntile]: tile_fluxes); the two reduced
+    modes never allocate the planes.
     """
 
     def __init__(self, P, g, T, mu, fS, fa, *absorbers, core: Optional[Discretized] = None, theta_s: float = 0.841,
-                 want_tau: bool = True, want_M: bool = True, nu_range=None, ctx: Optional[Context] = None, _setup: bool = True,
+                 want_tau: bool = True, want_M=True, nu_range=None, ctx: Optional[Context] = None, _setup: bool = True,
                  _warn: bool = True):
         core = core or Discretized()
+        mode = m_mode(want_M)
+        if mode in (M_EDGES, M_TILES) and isinstance(ctx, MultiContext):
+            raise TypeError("a MultiContext cannot carry want_M='edges' or 'tiles': cs_fluxes_discretized_multi takes no mode (its M "
+                            "pointers mean planes or nothing); use one Context per shard with nu_range")
         U, nu, nnu = unifyabsorbers(absorbers)
         self.accel = U if isinstance(U, AcceleratedAbsorber) else None
         if self.accel is not None:
@@ -1173,7 +1225,9 @@ class Column:
         self.shapes = np.array([shape_code(g_.shape, p_, g_.sl) for g_, p_ in zip(self.gases, psh)], dtype=np.int32)
         self.slots = np.array(self.ctx.slots_of([g_.sl for g_ in self.gases], [needs_shifts(int(c_)) for c_ in self.shapes]), dtype=np.int32)
         self.cuts = as_f64([g_.dnu_cut for g_ in self.gases])
-        self.want_tau, self.want_M = bool(want_tau), bool(want_M)
+        self.want_tau, self.want_M = bool(want_tau), (want_M if mode in (M_EDGES, M_TILES) else bool(want_M))
+        self.m_mode = mode
+        self.ntile = -(-self.nnu // TILE)
         self._set = False
         self._state(fT, fmu)
         if _setup:
@@ -1230,7 +1284,7 @@ class Column:
             dptr(self.Tlev), len(self.gases), ip(self.slots), ip(self.shapes), dptr(self.cuts) if len(self.cuts) else None,
             dptr(self.conc.ravel(order="F").copy()) if self.conc.size else None, self.sigma_gray,
             dptr(self.sigma_extra) if self.sigma_extra is not None else None, dptr(self.S_toa), dptr(self.albedo),
-            self.theta_s, self.core.nstream, int(self.want_tau), int(self.want_M)))
+            self.theta_s, self.core.nstream, int(self.want_tau), self.m_mode))
         if self.baked:
             slots = np.array([g_.slot for g_ in self.baked], dtype=np.int32)
             check(lib().cs_column_set_tables(self.ctx.handle, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int)),
@@ -1383,17 +1437,19 @@ class Column:
                                   flags=out[39]))
 
     def fetch(self, tau=None, Mup=None, Mdn=None):
-        """Copy results to host.  Returns (Fup, Fdn); fills the optional Fortran-order matrices in place."""
+        """Copy results to host.  Returns (Fup, Fdn); fills the optional Fortran-order matrices in place.  Mup, Mdn are what the
+        column's want_M says: [np, nnu] planes, [2, nnu] edge spectra (row 0 = TOA, row 1 = level np-1) or [np, ntile] tile sums."""
         self._require_resident("fetch")
         Fup, Fdn = np.zeros(self.np), np.zeros(self.np)
         bufs = []
         ptrs = []
-        for a, rows in ((tau, self.nl), (Mup, self.np), (Mdn, self.np)):
+        mshape = {M_EDGES: (2, self.nnu), M_TILES: (self.np, self.ntile)}.get(self.m_mode, (self.np, self.nnu))
+        for a, shape in ((tau, (self.nl, self.nnu)), (Mup, mshape), (Mdn, mshape)):
             if a is None:
                 ptrs.append(None)
                 bufs.append(None)
                 continue
-            assert a.shape == (rows, self.nnu), f"expected shape {(rows, self.nnu)}, got {a.shape}"
+            assert a.shape == shape, f"expected shape {shape}, got {a.shape}"
             b = a if (a.flags["F_CONTIGUOUS"] and a.dtype == np.float64) else np.zeros(a.shape, order="F")
             bufs.append(b)
             ptrs.append(b.ctypes.data_as(C.POINTER(C.c_double)))
@@ -1402,6 +1458,25 @@ class Column:
             if a is not None and b is not a:
                 a[...] = b
         return Fup, Fdn
+
+    def edge_spectra(self):
+        """(Mup, Mdn), each [2, nnu]: the outgoing and the back-radiation spectra of a want_M="edges" column -- row 0 = level 0 (TOA),
+        row 1 = level np-1 (surface) -- at full spectral resolution"""
+        if self.m_mode != M_EDGES:
+            raise TypeError(f"edge_spectra needs a column set up with want_M='edges' (this one: want_M={self.want_M!r})")
+        Mup, Mdn = np.zeros((2, self.nnu), order="F"), np.zeros((2, self.nnu), order="F")
+        self.fetch(Mup=Mup, Mdn=Mdn)
+        return Mup, Mdn
+
+    def tile_fluxes(self):
+        """(Fup_t, Fdn_t), each [np, ntile]: sum of w_j M[level, j] over the points of every 64-point tile (tile_ranges(nnu)) of a
+        want_M="tiles" column, w_j the column's (global trapezoid) weights: band fluxes and heating rates at 64-point resolution
+        (band_fluxes sums whole tiles)"""
+        if self.m_mode != M_TILES:
+            raise TypeError(f"tile_fluxes needs a column set up with want_M='tiles' (this one: want_M={self.want_M!r})")
+        Fu, Fd = np.zeros((self.np, self.ntile), order="F"), np.zeros((self.np, self.ntile), order="F")
+        self.fetch(Mup=Fu, Mdn=Fd)
+        return Fu, Fd
 
     def sigma_nodes(self):
         """Total cross-section at the nodes, shape (K, nnu) (test hook)."""
@@ -1508,9 +1583,19 @@ hipfluxes, hipnetfluxes = fluxes, netfluxes
 
 def radiate_(F: FluxPack, core: Discretized, P, g, T, mu, fS, fa, *absorbers, theta_s=0.841, ctx=None):
     """radiate!(F, core, P, g, T, mu, fS, fa, absorbers...) fluxes.jl:357-383"""
+    pack = getattr(core, "fluxpack", "full")
+    if pack == "edges" and isinstance(ctx, MultiContext):
+        raise TypeError("fluxpack='edges' needs one Context: a MultiContext has no way to carry the mode (cs_fluxes_discretized_multi "
+                        "takes none; its M pointers mean planes or nothing)")
     U, nu, nnu = unifyabsorbers(absorbers)
     assert F.size == (len(P), nnu), "size of FluxPack does not match number of pressure or wavenumber coordinates"
-    if getattr(core, "fluxpack", "full") == "bands":     # F+, F-, Fnet from the device's intF!; tau, M+, M- neither copied nor touched
+    if pack == "edges":     # resident column in the edges mode, run, fetch: the boundary rows of M+, M- and the band fluxes; the rest untouched
+        col = Column(P, g, T, mu, fS, fa, U, core=core, theta_s=theta_s, want_tau=False, want_M="edges", ctx=ctx)
+        col.run()
+        Mup, Mdn = np.zeros((2, nnu), order="F"), np.zeros((2, nnu), order="F")
+        Fup, Fdn = col.fetch(Mup=Mup, Mdn=Mdn)
+        F.Mup[0], F.Mup[-1], F.Mdn[0], F.Mdn[-1] = Mup[0], Mup[1], Mdn[0], Mdn[1]
+    elif pack == "bands":     # F+, F-, Fnet from the device's intF!; tau, M+, M- neither copied nor touched
         Fup, Fdn = _b3(P, g, T, mu, fS, fa, (U,), core, theta_s, ctx, None, None, None)
     else:
         Fup, Fdn = _b3(P, g, T, mu, fS, fa, (U,), core, theta_s, ctx, F.tau, F.Mup, F.Mdn)

@@ -332,7 +332,12 @@ struct Column {
     int64_t nnu = 0;
     int np = 0, nl = 0, nlob = 0, K = 0, nstream = 0, ngas = 0, ntile = 0;
     FluxPlan flux = {}, flux_last = {};   // the setup-time part of the flux plan (flux_plan); the plan the last cs_column_run ran by
-    bool want_tau = false, want_M = false, has_extra = false, has_S = false, has_alb = false;
+    bool want_tau = false, has_extra = false, has_S = false, has_alb = false;
+    int want_M = CS_M_NONE;    // what Mup / Mdn hold (CS_M_*): nothing, the planes [np][nnu], the boundary levels [2][nnu], tile sums [np][m_ntile()]
+    int64_t m_ntile() const { return (nnu + 63) / 64; }
+    // rows and row length of Mup / Mdn in the column's mode (kernel layout: level-major)
+    int m_rows() const { return want_M == CS_M_EDGES ? 2 : np; }
+    int64_t m_cols() const { return want_M == CS_M_TILES ? m_ntile() : nnu; }
     bool default_wts = false;  // trapezoid weights of the column's own grid (not a shard of a larger one)
     int64_t g_nnu = 0, g_start = 0;      // set by cs_fluxes_discretized_multi: this column is points [g_start, g_start + nnu) of a grid of
     double g_left = 0.0, g_right = 0.0;  // g_nnu points, with these neighbours left and right (what its trapezoid weights depend on)
@@ -3177,13 +3182,15 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     c.nnu = nnu; c.np = np; c.nl = np - 1; c.nlob = nlobatto; c.K = (np - 1) * (nlobatto - 1) + 1;
     c.nstream = nstream; c.ngas = ngas; c.ntile = (int)((nnu + 255) / 256);
     c.flux = flux_plan(ctx->set, {nnu, np, nlobatto, c.K, nstream}, 1, nullptr);
-    c.want_tau = want_tau != 0; c.want_M = want_M != 0;
+    c.want_tau = want_tau != 0;
+    c.want_M = want_M == CS_M_NONE || want_M == CS_M_EDGES || want_M == CS_M_TILES ? want_M : CS_M_PLANES;   // (any other non-zero value: planes)
     c.g = g; c.sigma_gray = sigma_gray; c.theta_s = theta_s;
     const int K = c.K, nl = c.nl;
     // quadrature rules
     RtParams &rt = c.rt;
     memset(&rt, 0, sizeof rt);
     rt.np = np; rt.nlobatto = nlobatto; rt.K = K; rt.nstream = nstream;
+    rt.mmode = c.want_M; rt.mtile = (int)c.m_ntile();   // (level_out: what the flux kernels store through the M pointers)
     rt.C = 1e-4 * kNa / g;
     rt.cos_ts = std::cos(theta_s);
     c.h_xs.assign(nlobatto, 0.0);
@@ -3327,9 +3334,10 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         HIPCHK(c.ticket.reserve((size_t)(1 + 512 / CS_FLUX_GROUP) * sizeof(unsigned)));
         HIPCHK(hipMemsetAsync(c.ticket.p, 0, c.ticket.bytes, s));
     }
-    if (c.want_M) {
-        HIPCHK(c.Mup.reserve((size_t)np * nnu * sizeof(double)));
-        HIPCHK(c.Mdn.reserve((size_t)np * nnu * sizeof(double)));
+    if (c.want_M) {   // by mode: [np][nnu], [2][nnu] or [np][ntile] -- the planes only for a column that asked for them
+        const size_t mbytes = (size_t)c.m_rows() * (size_t)c.m_cols() * sizeof(double);
+        HIPCHK(c.Mup.reserve(mbytes));
+        HIPCHK(c.Mdn.reserve(mbytes));
     }
     HIPCHK(c.partial.reserve(c.flux.npartial * 2 * np * sizeof(double)));
     HIPCHK(c.F.reserve((size_t)2 * np * sizeof(double)));
@@ -3868,8 +3876,9 @@ int cs_column_fetch(cs_ctx *ctx, int64_t nnu, int np, double *tau, double *Mup, 
     if (tau && !c.want_tau) return fail(CS_ESTATE, "column was set up without want_tau");
     if (tau && (rc = fetch_transposed(ctx, c.tau.as<double>(), c.nl, c.nnu, tau))) return rc;
     if ((Mup || Mdn) && !c.want_M) return fail(CS_ESTATE, "column was set up without want_M");
-    if (Mup && (rc = fetch_transposed(ctx, c.Mup.as<double>(), c.np, c.nnu, Mup))) return rc;
-    if (Mdn && (rc = fetch_transposed(ctx, c.Mdn.as<double>(), c.np, c.nnu, Mdn))) return rc;
+    // by the column's mode: [np, nnu] planes, [2, nnu] boundary spectra or [np, ntile] tile sums, column-major (level fastest) all three
+    if (Mup && (rc = fetch_transposed(ctx, c.Mup.as<double>(), c.m_rows(), c.m_cols(), Mup))) return rc;
+    if (Mdn && (rc = fetch_transposed(ctx, c.Mdn.as<double>(), c.m_rows(), c.m_cols(), Mdn))) return rc;
     if (Fup) HIPCHK(hipMemcpyAsync(Fup, c.flux_out(), c.np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (Fdn) HIPCHK(hipMemcpyAsync(Fdn, c.flux_out() + c.np, c.np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -4325,7 +4334,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
 //  = 0 and accel_slot = -1 for a column without them)
 static bool column_matches(cs_ctx *ctx, int64_t nnu, const double *nu, int np, const double *P, double g, int nlobatto, int ngas,
                            const int *gas_slots, const int *shapes, const double *dnu_cuts, double sigma_gray, double theta_s,
-                           int nstream, bool want_tau, bool want_M, int64_t g_nnu = 0, int64_t g_start = 0, double g_left = 0.0, double g_right = 0.0,
+                           int nstream, bool want_tau, int want_M, int64_t g_nnu = 0, int64_t g_start = 0, double g_left = 0.0, double g_right = 0.0,
                            int ntab = 0, const int *table_slots = nullptr, int ncia = 0, const int *cia_slots = nullptr, int accel_slot = -1)
 {
     const Column &c = ctx->col;
@@ -4338,7 +4347,7 @@ static bool column_matches(cs_ctx *ctx, int64_t nnu, const double *nu, int np, c
         if (c.cia[t].slot != cia_slots[t]) return false;
     if (c.nnu != nnu || c.np != np || c.nlob != nlobatto || c.nstream != nstream || c.ngas != ngas) return false;
     if (c.g != g || c.sigma_gray != sigma_gray || c.theta_s != theta_s) return false;
-    if (c.want_tau != want_tau || c.want_M != want_M) return false;
+    if (c.want_tau != want_tau || c.want_M != want_M) return false;   // (modes compared: an edges or tiles column is no planes column -- its M buffers are smaller)
     if (c.merge != ctx->merge) return false;
     for (int gi = 0; gi < ngas; gi++) {
         const UserGas &cg = c.ugas[gi];
@@ -4379,7 +4388,7 @@ int cs_fluxes_discretized_members(cs_ctx *ctx, int64_t nnu, const double *nu, in
     // column of the previous call resident and refresh only what a call can change -- node states, fS, fa, sigma_extra, and the
     // per-node inputs of the tables / CIA pairs / accelerated absorber it names
     if (column_matches(ctx, nnu, nu, np, P, g, nlobatto, ngas, gas_slots, shapes, dnu_cuts, sigma_gray, theta_s, nstream,
-                       tau != nullptr, Mup || Mdn, 0, 0, 0.0, 0.0, ntab, table_slots, ncia, cia_slots, accel_slot)) {
+                       tau != nullptr, (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE, 0, 0, 0.0, 0.0, ntab, table_slots, ncia, cia_slots, accel_slot)) {
         Column &c = ctx->col;
         HIPCHK(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
@@ -4397,7 +4406,7 @@ int cs_fluxes_discretized_members(cs_ctx *ctx, int64_t nnu, const double *nu, in
     } else {
         rc = cs_column_setup(ctx, nnu, nu, nullptr, np, P, g, nlobatto, T_nodes, mu_nodes, T_levels, ngas, gas_slots,
                              shapes, dnu_cuts, conc, sigma_gray, sigma_extra, S_toa, albedo, theta_s, nstream,
-                             tau != nullptr, (Mup || Mdn) ? 1 : 0);
+                             tau != nullptr, (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE);
         if (rc) return rc;
         if (ntab > 0 && (rc = cs_column_set_tables(ctx, ntab, table_slots, conc_tab))) return rc;
     }
@@ -4883,7 +4892,7 @@ int cs_fluxes_discretized_multi(cs_ctx *const *ctxs, int nctx, int64_t nnu, cons
         const double gl = a > 0 ? nu[a - 1] : 0.0, gr = a + n < nnu ? nu[a + n] : 0.0;
         int r;
         if (column_matches(ctx, n, nu + a, np, P, g, nlobatto, ngas, gas_slots, shapes, dnu_cuts, sigma_gray, theta_s, nstream, tau != nullptr,
-                           Mup || Mdn, nnu, a, gl, gr)) {
+                           (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE, nnu, a, gl, gr)) {
             Column &c = ctx->col;
             hipStream_t s = ctx->stream;
             r = hipSetDevice(ctx->device) == hipSuccess ? CS_OK : fail(CS_EHIP, "hipSetDevice(%d) failed", ctx->device);
@@ -4898,7 +4907,7 @@ int cs_fluxes_discretized_multi(cs_ctx *const *ctxs, int nctx, int64_t nnu, cons
         } else {
             r = cs_column_setup(ctx, n, nu + a, wt.data() + a, np, P, g, nlobatto, T_nodes, mu_nodes, T_levels, ngas, gas_slots, shapes, dnu_cuts,
                                 conc, sigma_gray, sigma_extra ? ex.data() : nullptr, S_toa ? S_toa + a : nullptr, albedo ? albedo + a : nullptr,
-                                theta_s, nstream, tau != nullptr, (Mup || Mdn) ? 1 : 0);
+                                theta_s, nstream, tau != nullptr, (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE);
             if (!r) { ctx->col.g_nnu = nnu; ctx->col.g_start = a; ctx->col.g_left = gl; ctx->col.g_right = gr; }
         }
         if (prev[i] >= 0) {

@@ -2959,6 +2959,7 @@ __device__ __forceinline__ double layerplanck_inv(double B1, double B2, double i
 
 struct RtParams {
     int np, nlobatto, K, nstream;
+    int mmode, mtile;   // what level_out leaves in the M pointers: CS_M_PLANES / CS_M_EDGES / CS_M_TILES (0: no M pointers); 64-point tiles of the grid
     double C;        // 1e-4*Na/g, fluxes.jl:259
     double cos_ts;   // cos(theta_s)
     double ws[16];   // Lobatto weights on [0,1]
@@ -3066,13 +3067,25 @@ __device__ __forceinline__ double sweep_step(const RtParams &p, double t, double
 // surface: Lambertian reflection of the downward flux + Planck emission, discretized.jl:309-310
 __device__ __forceinline__ double surface_intensity(double Md, double fa, double Bs) { return Md * fa / kPi + Bs; }
 
-// what radiate! returns at a level: the tile's share of the band flux into its slot of `red` (lane 0), the flux itself into the
-// caller's plane if there is one
-__device__ __forceinline__ void level_out(const RtLane &L, double M, double *red_slot, double *plane, int level, int64_t nnu)
+// what radiate! returns at a level: the tile's share of the band flux into its slot of `red` (lane 0), and into the caller's plane, if
+// there is one, what the column's mode (p.mmode, wave-uniform) keeps of the flux itself: the flux at every level, [np][nnu]
+// (CS_M_PLANES); at level 0 and level np - 1 only, [2][nnu] (CS_M_EDGES); or the tile's share again, [np][mtile] (CS_M_TILES: the very
+// value that goes to `red`, so the tile sums of a level add up to its band flux as the blocks' partial sums do)
+__device__ __forceinline__ void level_out(const RtParams &p, const RtLane &L, double M, double *red_slot, double *plane, int level, int64_t nnu)
 {
     const double r = wave_sum(L.w * M);
     if (L.lane == 0) *red_slot = r;
-    if (plane && L.live) plane[(size_t)level * nnu + L.j] = M;
+    if (!plane) return;
+    // ONE predicated store whatever the mode -- row, row length, shift, lane mask and value are wave-uniform selects -- as the planes
+    // alone had it: a branch per mode cost k_rt<9..10> a wave per SIMD and 54 chunk instances 4 to 16 bytes of scratch
+    // (profiles/reduced_spectra_notes.md)
+    const bool edges = p.mmode == CS_M_EDGES, tiles = p.mmode == CS_M_TILES;
+    const int row = edges ? (level ? 1 : 0) : level;
+    const bool level_ok = !edges || level == 0 || level == p.np - 1;
+    const size_t base = (size_t)row * (size_t)(tiles ? (int64_t)p.mtile : nnu);
+    const int sh = tiles ? 6 : 0, lmask = tiles ? 63 : 0;   // tiles: lane 0 alone (live there = the tile is one of the grid's), at j / 64
+    const double v = tiles ? r : M;
+    if (L.live && level_ok && (L.lane & lmask) == 0) plane[base + (size_t)(L.j >> sh)] = v;
 }
 
 // (agent-scope accesses of the block partials: the note above flux_last_block_reduce)
@@ -3147,7 +3160,7 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p, const double *__restrict
         double Ms = c * L.fS;                    // M-[1] = c*fS(nu), discretized.jl:299
         Md = Ms;
         Bprev = planck(L.v, Tlev[0]);
-        level_out(L, Md, &red[(np + 0) * nw + wv], Mdn, 0, nnu);
+        level_out(p, L, Md, &red[(np + 0) * nw + wv], Mdn, 0, nnu);
         double sg_next = sg(nlob - 1);   // end node of layer 0; later layers are fetched one layer ahead
         for (int i = 0; i < nl; i++) {
             const double dP = P[i + 1] - P[i];
@@ -3163,7 +3176,7 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p, const double *__restrict
             if (S_toa) Ms *= exp(-t / c);   // (wave-uniform; without a stellar beam Ms stays 0)
             Md += Ms;
             Bprev = Bnext;
-            level_out(L, Md, &red[(np + i + 1) * nw + wv], Mdn, i + 1, nnu);
+            level_out(p, L, Md, &red[(np + i + 1) * nw + wv], Mdn, i + 1, nnu);
         }
         if (UD && albedo) xch[wv * 64 + lane] = Md;
     }
@@ -3174,7 +3187,7 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p, const double *__restrict
             Md = albedo ? xch[wv * 64 + lane] : 0.0;
         }
         const double Is = surface_intensity(Md, L.fa, Bprev);
-        level_out(L, Is * kPi, &red[(np - 1) * nw + wv], Mup, np - 1, nnu);
+        level_out(p, L, Is * kPi, &red[(np - 1) * nw + wv], Mup, np - 1, nnu);
 #pragma unroll
         for (int k = 0; k < NS; k++) I[k] = Is;
         double Bhi = Bprev;  // B at level i+1
@@ -3204,7 +3217,7 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p, const double *__restrict
             const double Blo = planck(L.v, Tlev[i]);
             const double Mu = sweep_step<NS, TR_EXP>(p, t, 1.0 / t, Bhi, Blo, I, nullptr, nullptr);
             Bhi = Blo;
-            level_out(L, Mu, &red[i * nw + wv], Mup, i, nnu);
+            level_out(p, L, Mu, &red[i * nw + wv], Mup, i, nnu);
         }
     }
     __syncthreads();
@@ -3267,11 +3280,11 @@ __global__ __launch_bounds__(2 * NS * 64) void k_rt_streams(RtParams p, const do
     };
     double I = 0.0, Ms = c * L.fS;
     // ---- downward sweep (the up-waves run their own sweep in the same loop when nothing ties them to this one)
-    if (!up && k == 0) level_out(L, Ms, &red[np + 0], Mdn, 0, nnu);   // level 0: M-[1] = c fS(nu), discretized.jl:299
+    if (!up && k == 0) level_out(p, L, Ms, &red[np + 0], Mdn, 0, nnu);   // level 0: M-[1] = c fS(nu), discretized.jl:299
     double Iu = 0.0;
     if (up && !serial) {   // surface: Planck emission only (no reflected part without an albedo), discretized.jl:309-310
         Iu = Blev[(size_t)(np - 1) * 64 + lane];
-        if (k == 0) level_out(L, Iu * kPi, &red[np - 1], Mup, np - 1, nnu);
+        if (k == 0) level_out(p, L, Iu * kPi, &red[np - 1], Mup, np - 1, nnu);
     }
     for (int s = 0; s < nl; s++) {
         const int buf = s & 1;
@@ -3290,10 +3303,10 @@ __global__ __launch_bounds__(2 * NS * 64) void k_rt_streams(RtParams p, const do
             const double M = stream_sum(buf, up ? 1 : 0);
             if (!up) {
                 const double Md = M + Ms;
-                level_out(L, Md, &red[np + s + 1], Mdn, s + 1, nnu);
+                level_out(p, L, Md, &red[np + s + 1], Mdn, s + 1, nnu);
                 if (serial && s == nl - 1) msurf[lane] = Md;
             } else {
-                level_out(L, M, &red[nl - 1 - s], Mup, nl - 1 - s, nnu);
+                level_out(p, L, M, &red[nl - 1 - s], Mup, nl - 1 - s, nnu);
             }
         }
     }
@@ -3301,7 +3314,7 @@ __global__ __launch_bounds__(2 * NS * 64) void k_rt_streams(RtParams p, const do
         __syncthreads();
         if (up) {
             Iu = surface_intensity(msurf[lane], L.fa, Blev[(size_t)(np - 1) * 64 + lane]);
-            if (k == 0) level_out(L, Iu * kPi, &red[np - 1], Mup, np - 1, nnu);
+            if (k == 0) level_out(p, L, Iu * kPi, &red[np - 1], Mup, np - 1, nnu);
         }
         for (int s = 0; s < nl; s++) {
             const int buf = s & 1, i = nl - 1 - s;
@@ -3310,7 +3323,7 @@ __global__ __launch_bounds__(2 * NS * 64) void k_rt_streams(RtParams p, const do
                 *slot(buf, 1, k) = Wk * Iu;
             }
             __syncthreads();
-            if (up && k == 0) level_out(L, stream_sum(buf, 1), &red[i], Mup, i, nnu);
+            if (up && k == 0) level_out(p, L, stream_sum(buf, 1), &red[i], Mup, i, nnu);
         }
     }
     __syncthreads();
@@ -3872,13 +3885,13 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
         double Md = sweep_step<NS, TR_UP>(p, t, it, B(i), B(i + 1), Id, &trv[q], nullptr);
         if (S_toa) Ms *= KEPT ? trs[q] : exp(-t / c);
         Md += Ms;
-        level_out(L, Md, &red[np + i + 1], Mdn, i + 1, nnu);
+        level_out(p, L, Md, &red[np + i + 1], Mdn, i + 1, nnu);
     };
     auto levels_up = [&](int i, int q) __attribute__((always_inline)) {
         double t, it;
         depth(i, q, t, it);
         const double Mu = sweep_step<NS, TR_UP>(p, t, it, B(i + 1), B(i), Iu, &trv[q], nullptr);
-        level_out(L, Mu, &red[i], Mup, i, nnu);
+        level_out(p, L, Mu, &red[i], Mup, i, nnu);
     };
 #pragma unroll
     for (int k = 0; k < NS; k++) { Ad[k] = 1.0; Bd[k] = 0.0; Au[k] = 1.0; Bu[k] = 0.0; }
@@ -3911,7 +3924,7 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
         const double Is = surface_intensity(Md, L.fa, B(np - 1));
 #pragma unroll
         for (int k = 0; k < NS; k++) *X(1, k) = Is;
-        level_out(L, Is * kPi, &red[np - 1], Mup, np - 1, nnu);
+        level_out(p, L, Is * kPi, &red[np - 1], Mup, np - 1, nnu);
     };
     if (!serial && wave == NW - 1) surface(0.0);   // (no reflected part: both sweeps travel in the same steps below)
     for (int s = 0; s < NW; s++) {
@@ -3947,7 +3960,7 @@ __global__ __launch_bounds__(768) void k_flux_scan(RtParams p, const double *__r
     }
     flux_stamp(f, 4);
     // ---- phase 3
-    if (wave == 0) level_out(L, Ms, &red[np + 0], Mdn, 0, nnu);   // level 0 of the downward flux
+    if (wave == 0) level_out(p, L, Ms, &red[np + 0], Mdn, 0, nnu);   // level 0 of the downward flux
     if constexpr (KEPT) {
 #pragma unroll
         for (int q = 0; q < PER; q++) {
@@ -4055,7 +4068,7 @@ __device__ __forceinline__ void flux_chunk_body(const RtParams &p, const double 
     double Ms = c * L.fS;                 // M-[1] = c*fS(nu), discretized.jl:299
     double Md = Ms;
     double Bprev = planck(v, Tlev[0]);
-    level_out(L, Md, &red[(np + 0) * nw + wv], Mdn, 0, nnu);
+    level_out(p, L, Md, &red[(np + 0) * nw + wv], Mdn, 0, nnu);
     for (int i = 0; i < nl; i++) {
         const int ke = (i + 1) * (nlob - 1);
         while (ke >= chunk_next) load_chunk();      // (wave-uniform)
@@ -4067,11 +4080,11 @@ __device__ __forceinline__ void flux_chunk_body(const RtParams &p, const double 
         if (S_toa) Ms *= exp(-t / c);   // (wave-uniform; without a stellar beam Ms stays 0)
         Md += Ms;
         Bprev = Bnext;
-        level_out(L, Md, &red[(np + i + 1) * nw + wv], Mdn, i + 1, nnu);
+        level_out(p, L, Md, &red[(np + i + 1) * nw + wv], Mdn, i + 1, nnu);
     }
     {
         const double Is = surface_intensity(Md, L.fa, Bprev);
-        level_out(L, Is * kPi, &red[(np - 1) * nw + wv], Mup, np - 1, nnu);
+        level_out(p, L, Is * kPi, &red[(np - 1) * nw + wv], Mup, np - 1, nnu);
 #pragma unroll
         for (int k = 0; k < NS; k++) I[k] = Is;
         double Bhi = Bprev;  // B at level i+1
@@ -4082,7 +4095,7 @@ __device__ __forceinline__ void flux_chunk_body(const RtParams &p, const double 
             const double Blo = planck(v, Tlev[i]);
             const double Mu = sweep_step<NS, TR_EXP>(p, t, 1.0 / t, Bhi, Blo, I, nullptr, nullptr);
             Bhi = Blo;
-            level_out(L, Mu, &red[i * nw + wv], Mup, i, nnu);
+            level_out(p, L, Mu, &red[i * nw + wv], Mup, i, nnu);
         }
     }
     __syncthreads();

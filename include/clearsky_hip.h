@@ -302,11 +302,31 @@ int cs_rebalance_ranges(int64_t nnu, const double *nu, int ngas, const int64_t *
  *                    results stay in HBM;
  *   cs_column_flux_ptr  device address of [2*np] doubles (Fup then Fdn) for an in-place RCCL all-reduce;
  *   cs_column_fetch  synchronises and copies results to host (NULL = skip), layouts as in cs_fluxes_discretized; nnu and np
- *                    are the sizes the caller's buffers were allocated for -- CS_ESTATE if the resident column differs
- *                    (a context holds ONE resident column; a later cs_column_setup replaces it);
+ *                    are the sizes of the COLUMN the caller means (in every mode of want_M) -- CS_ESTATE if the resident column
+ *                    differs (a context holds ONE resident column; a later cs_column_setup replaces it);
  *   cs_column_sigma_fetch  copies the total cross-section at the nodes, [nnu, K] nu-fastest (test hook), same size check;
  *   cs_column_counts line-shape evaluations of one run (sum over nu, node, gas of lines inside the cut-off).
+ *
+ * `want_M` of cs_column_setup says what the column keeps of the monochromatic fluxes M+, M- and, with that, what cs_column_fetch
+ * writes through its Mup / Mdn pointers (both column-major, level fastest; Mup or Mdn of a CS_M_NONE column is CS_ESTATE):
+ *   CS_M_NONE   nothing: the band fluxes only;
+ *   CS_M_PLANES the planes, [np, nnu], as cs_fluxes_discretized returns them (every non-zero value that is none of the two below
+ *               means this one);
+ *   CS_M_EDGES  M+ and M- at the top and the bottom level only, at full spectral resolution: [2, nnu], row 0 = level 0 = TOA (M+ there
+ *               is the outgoing spectrum), row 1 = level np - 1 (M- there is the back-radiation spectrum) -- 2 nnu doubles each;
+ *   CS_M_TILES  per level and 64-point tile t = points [64 t, min(64 t + 64, nnu)) of the column, sum_j w_j M[level, j], w = the
+ *               column's weights (`wts`, or the trapezoid weights of `nu`): [np, ntile], ntile = (nnu + 63) / 64 -- np ntile doubles
+ *               each.  A band whose ends fall on tile boundaries is a sum of columns of this array; all its columns add up to the
+ *               band fluxes Fup / Fdn (to rounding: the same terms, added in another order), and the tiles of nu-shards cut at
+ *               multiples of 64 points are the tiles of the whole grid.
+ * In the last two modes the [np, nnu] planes are never allocated.  The host-pointer entry points (cs_fluxes_discretized, _members,
+ * _multi) know planes or nothing -- their M pointers are [np, nnu] -- and never re-use a resident column of another mode;
+ * cs_column_batch returns band fluxes only, whatever the mode.
  */
+#define CS_M_NONE 0
+#define CS_M_PLANES 1
+#define CS_M_EDGES 2
+#define CS_M_TILES 3
 int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wts, int np, const double *P,
                     double g, int nlobatto, const double *T_nodes, const double *mu_nodes, const double *T_levels,
                     int ngas, const int *gas_slots, const int *shapes, const double *dnu_cuts, const double *conc,
@@ -333,8 +353,12 @@ int cs_column_flux_ptr(cs_ctx *ctx, double **dF);
 /* asynchronously copy the [2*np] band fluxes (Fup then Fdn) into caller-owned DEVICE memory on `stream` */
 int cs_column_flux_to(cs_ctx *ctx, double *dst_device, void *stream);
 /* from now on the resident column WRITES its [2*np] band fluxes into caller-owned device memory (a buffer a collective reduces in place,
- * a tensor of the host framework) instead of its own -- no copy per step; NULL: back to its own.  Holds until the next cs_column_setup.
- * cs_column_flux_ptr / cs_column_fetch / cs_column_flux_to read from wherever the fluxes are. */
+ * a tensor of the host framework) instead of its own -- no copy per step; NULL: back to its own.  The destination is DROPPED by every
+ * cs_column_setup (also the one inside a host-pointer call that does not re-use the resident column): the column writes into its own
+ * buffer again until this is called again -- a caller that sets a column up anew names the destination anew, or its collective reduces
+ * stale memory.  cs_column_flux_ptr / cs_column_fetch / cs_column_flux_to follow the destination: they read from wherever the fluxes
+ * are, so after an in-place all-reduce cs_column_fetch returns the reduced sums, not this column's own.  The pointer is the caller's:
+ * it must stay valid, on the context's device, until it is replaced. */
 int cs_column_set_flux_dst(cs_ctx *ctx, double *dst_device);
 int cs_column_fetch(cs_ctx *ctx, int64_t nnu, int np, double *tau, double *Mup, double *Mdn, double *Fup, double *Fdn);
 int cs_column_sigma_fetch(cs_ctx *ctx, int64_t nnu, int K, double *sigma);

@@ -842,6 +842,58 @@ function hipnetfluxes(P::AbstractVector{<:Real}, g::Real, T, μ, 𝒻S, 𝒻a, a
     return F⁺ .- F⁻
 end
 
+# Reduced spectra of one column, without the M planes [np, nν] ever existing: a resident column whose `want_M` is CS_M_EDGES (2) or
+# CS_M_TILES (3) [include/clearsky_hip.h], run, fetch.
+#   kind = :edges  ->  F⁺, F⁻, M⁺, M⁻ with M⁺, M⁻ [2, nν]: row 1 = level 1 (TOA: the outgoing spectrum is M⁺[1,:]), row 2 = level np
+#                      (the back-radiation spectrum is M⁻[2,:]);
+#   kind = :tiles  ->  F⁺, F⁻, F⁺ₜ, F⁻ₜ with F±ₜ [np, ⌈nν/64⌉]: Σ wⱼ M[level, j] over each 64-point tile, wⱼ the trapezoid weights of
+#                      ν -- any band whose ends fall on tile boundaries is a sum of columns, and all columns add up to F⁺, F⁻.
+# One device (core.ngpu is not looked at: cs_fluxes_discretized_multi takes no mode); members as hipcolumn! takes them.
+function hipspectra(kind::Symbol, P::AbstractVector{<:Real}, g::Real, T, μ, 𝒻S, 𝒻a, absorbers...; core::HIPDiscretized=HIPDiscretized(),
+                    θₛ::Real=0.841)
+    kind in (:edges, :tiles) || error("kind must be :edges or :tiles, not :$kind")
+    𝒜, ν, nν = ClearSky.unifyabsorbers(absorbers)
+    𝒜 isa AcceleratedAbsorber && error("hipspectra takes the absorbers themselves, not an AcceleratedAbsorber")
+    𝒻T, 𝒻μ = formprofiles(P, T, μ)
+    nstream, nlobatto = core.nstream, core.nlobatto
+    @assert issorted(P) "pressure coordinates must be in ascending order (sorted)"
+    Tn, μn = lobattoevaluations(P, 𝒻T, 𝒻μ, nlobatto)
+    Tn = Matrix{Float64}(Tn); μn = Matrix{Float64}(μn)
+    Tlev = Float64[𝒻T(p) for p in P]
+    hipcheckpressures(𝒜, P[end], P[1])
+    checkstreams(nstream); checkazimuth(θₛ)
+    np = length(P)
+    Pv = collect(Float64, P)
+    Pk, Tk = nodestates(Pv, Tn, nlobatto)
+    ctx = context(0)
+    m = members(ctx, 𝒜, Tk, Pk)
+    Stoa = Float64[𝒻S(x) for x in ν]; alb = Float64[𝒻a(x) for x in ν]
+    νv = collect(Float64, ν)
+    mode = kind == :edges ? 2 : 3                       # CS_M_EDGES, CS_M_TILES
+    rows, cols = kind == :edges ? (2, nν) : (np, cld(nν, 64))
+    M⁺ = Matrix{Float64}(undef, rows, cols); M⁻ = Matrix{Float64}(undef, rows, cols)
+    F⁺ = Vector{Float64}(undef, np); F⁻ = Vector{Float64}(undef, np)
+    extra = m.extra
+    GC.@preserve νv Pv Tn μn Tlev m extra Stoa alb M⁺ M⁻ F⁺ F⁻ begin
+        check(ccall((:cs_column_setup, LIB), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Float64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Float64, Cint, Cint, Cint),
+            ctx.handle, nν, νv, C_NULL, np, Pv, Float64(g), nlobatto, Tn, μn, Tlev, length(m.slots), m.slots, m.shapes, m.cuts, m.conc,
+            m.σgray, extra === nothing ? C_NULL : pointer(extra), Stoa, alb, Float64(θₛ), nstream, 0, mode))
+        isempty(m.tslots) || check(ccall((:cs_column_set_tables, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Float64}),
+            ctx.handle, length(m.tslots), m.tslots, m.conctab))
+        isempty(m.cslots) || check(ccall((:cs_column_set_cia, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}),
+            ctx.handle, length(m.cslots), m.cslots, m.cflags, m.P₁, m.P₂))
+        check(ccall((:cs_column_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.handle, C_NULL))
+        # nnu and np are the COLUMN's sizes (the size check); M⁺, M⁻ are filled by the column's mode: [2, nν] or [np, ⌈nν/64⌉]
+        check(ccall((:cs_column_fetch, LIB), Cint,
+            (Ptr{Cvoid}, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            ctx.handle, nν, np, C_NULL, M⁺, M⁻, F⁺, F⁻))
+    end
+    return F⁺, F⁻, M⁺, M⁻
+end
+
 # jacobian! [radiative_convective.jl:154-171] as ONE device batch: the band fluxes of B temperature profiles on the column of the
 # last monochromaticfluxes! call of this thread's context (same grid, levels and members).  Ts[b] is whatever `T` was in that call
 # (vector at the levels or a function of P).  Returns F⁺, F⁻ as [np, B].
@@ -882,6 +934,6 @@ function batchfluxes(core::HIPDiscretized, P::AbstractVector{<:Real}, Ts::Abstra
 end
 
 export HIPDiscretized, DirectGas, HIPGas, HIPCIA, Continuum, hipvoigt!, hiplorentz!, hipdoppler!, hipPHCO2!, hipvoigtCKD!, hipvoigtVVH!, hipvoigtCKDVVH!, hipbake!, hipshapepoints, batchfluxes,
-       hipfluxes, hipnetfluxes
+       hipfluxes, hipnetfluxes, hipspectra
 
 end # module
