@@ -13,7 +13,7 @@ from .core import (interp_plan, phco2_plan, phco2_wide_regions, MultiContext, ba
                    lobattoevaluations, lobattonodes, logrange, lorentz, lorentz_, monochromaticfluxes,
                    monochromaticfluxes_, netfluxes, nodepressures, nodevalues, opticaldepth, ozonelayer, planck,
                    pressuregrid, psatH2O, radiate, radiate_, shape_batch, stefanboltzmann, streamnodes, transmittance,
-                   tile_ranges, band_fluxes, trapz, trapz_weights, unifyabsorbers, voigt, voigt_, voigtCKD, voigtCKD_,
+                   tile_ranges, band_fluxes, band_transmittance, tau_mode, trapz, trapz_weights, unifyabsorbers, voigt, voigt_, voigtCKD, voigtCKD_,
                    voigtVVH, voigtVVH_, voigtCKDVVH, voigtCKDVVH_, voigtLBL, voigtLBL_)
 
 __version__ = "0.1.0"

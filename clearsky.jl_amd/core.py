@@ -1108,6 +1108,8 @@ def checkstreams(n):
 # include/clearsky_hip.h, CS_M_*: what a resident column keeps of M+, M- (the `want_M` of cs_column_setup)
 M_NONE, M_PLANES, M_EDGES, M_TILES = 0, 1, 2, 3
 TILE = 64      # points per tile of the tiles mode: one wave of the flux kernels
+# CS_TAU_*: what it keeps of the optical depths (the `want_tau` of cs_column_setup)
+TAU_NONE, TAU_LAYERS, TAU_TOTAL, TAU_TILES = 0, 1, 2, 3
 
 
 def m_mode(want_M) -> int:
@@ -1117,6 +1119,15 @@ def m_mode(want_M) -> int:
             raise ValueError(f"want_M must be False, True, 'edges' or 'tiles', not {want_M!r}")
         return M_EDGES if want_M == "edges" else M_TILES
     return M_PLANES if want_M else M_NONE
+
+
+def tau_mode(want_tau) -> int:
+    """Column's want_tau (False | True | "total" | "tiles") as the CS_TAU_* value"""
+    if isinstance(want_tau, str):
+        if want_tau not in ("total", "tiles"):
+            raise ValueError(f"want_tau must be False, True, 'total' or 'tiles', not {want_tau!r}")
+        return TAU_TOTAL if want_tau == "total" else TAU_TILES
+    return TAU_LAYERS if want_tau else TAU_NONE
 
 
 def tile_ranges(nnu: int):
@@ -1149,6 +1160,16 @@ def band_fluxes(Fup_t, Fdn_t, tile_edges):
     return out[0], out[1]
 
 
+def band_transmittance(Tt, tile_edges):
+    """Band transmission functions from Column.tile_transmittance()'s [np, ntile]: band b = tiles [tile_edges[b], tile_edges[b+1]), its
+    transmittance to space at level i = the sum of row i over the band's tiles divided by the same sum of row 0 (the tiles' weights:
+    row 0 is sum_j w_j).  Returns [np, nband]; differences between levels are band weighting functions.  The argument checks are
+    band_fluxes' (a band is a sum of whole 64-point tiles).  Host only."""
+    Tt = np.asarray(Tt, float)
+    S, _ = band_fluxes(Tt, Tt, tile_edges)
+    return S / S[0][None, :]
+
+
 class Column:
     """A column resident in HBM: inputs uploaded once, evaluated any number of times (cs_column_* in the C ABI).
 
@@ -1159,13 +1180,20 @@ class Column:
     `want_M`: False (band fluxes only), True (the planes M+, M- [np, nnu]), "edges" (M+, M- at level 0 = TOA and level np-1 only,
     [2, nnu]: edge_spectra) or "tiles" (sum of w_j M[level, j] over every 64-point tile, [np, ntile]: tile_fluxes); the two reduced
     modes never allocate the planes.
+    `want_tau`: False, True (the layer depths [np-1, nnu], floored at 1e-6 as the sweeps use them), "total" (the slant optical depth of
+    the whole column at theta_s, [nnu], unfloored: column_depth -- opticaldepth of fluxes.jl:68-97) or "tiles" (sum of w_j exp(-D_i(nu_j))
+    over every 64-point tile, D_i the slant depth above level i, [np, ntile]: tile_transmittance); the last two never allocate the layer
+    plane, run the separate flux kernels, and are also filled by sigma_run() alone.
     """
 
     def __init__(self, P, g, T, mu, fS, fa, *absorbers, core: Optional[Discretized] = None, theta_s: float = 0.841,
-                 want_tau: bool = True, want_M=True, nu_range=None, ctx: Optional[Context] = None, _setup: bool = True,
+                 want_tau=True, want_M=True, nu_range=None, ctx: Optional[Context] = None, _setup: bool = True,
                  _warn: bool = True):
         core = core or Discretized()
-        mode = m_mode(want_M)
+        mode, tmode = m_mode(want_M), tau_mode(want_tau)
+        if tmode in (TAU_TOTAL, TAU_TILES) and isinstance(ctx, MultiContext):
+            raise TypeError("a MultiContext cannot carry want_tau='total' or 'tiles': cs_fluxes_discretized_multi takes no mode (its tau "
+                            "pointer means layers or nothing); use one Context per shard with nu_range")
         if mode in (M_EDGES, M_TILES) and isinstance(ctx, MultiContext):
             raise TypeError("a MultiContext cannot carry want_M='edges' or 'tiles': cs_fluxes_discretized_multi takes no mode (its M "
                             "pointers mean planes or nothing); use one Context per shard with nu_range")
@@ -1225,8 +1253,9 @@ class Column:
         self.shapes = np.array([shape_code(g_.shape, p_, g_.sl) for g_, p_ in zip(self.gases, psh)], dtype=np.int32)
         self.slots = np.array(self.ctx.slots_of([g_.sl for g_ in self.gases], [needs_shifts(int(c_)) for c_ in self.shapes]), dtype=np.int32)
         self.cuts = as_f64([g_.dnu_cut for g_ in self.gases])
-        self.want_tau, self.want_M = bool(want_tau), (want_M if mode in (M_EDGES, M_TILES) else bool(want_M))
-        self.m_mode = mode
+        self.want_tau = want_tau if tmode in (TAU_TOTAL, TAU_TILES) else bool(want_tau)
+        self.want_M = want_M if mode in (M_EDGES, M_TILES) else bool(want_M)
+        self.m_mode, self.tau_mode = mode, tmode
         self.ntile = -(-self.nnu // TILE)
         self._set = False
         self._state(fT, fmu)
@@ -1284,7 +1313,7 @@ class Column:
             dptr(self.Tlev), len(self.gases), ip(self.slots), ip(self.shapes), dptr(self.cuts) if len(self.cuts) else None,
             dptr(self.conc.ravel(order="F").copy()) if self.conc.size else None, self.sigma_gray,
             dptr(self.sigma_extra) if self.sigma_extra is not None else None, dptr(self.S_toa), dptr(self.albedo),
-            self.theta_s, self.core.nstream, int(self.want_tau), self.m_mode))
+            self.theta_s, self.core.nstream, self.tau_mode, self.m_mode))
         if self.baked:
             slots = np.array([g_.slot for g_ in self.baked], dtype=np.int32)
             check(lib().cs_column_set_tables(self.ctx.handle, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int)),
@@ -1438,13 +1467,15 @@ class Column:
 
     def fetch(self, tau=None, Mup=None, Mdn=None):
         """Copy results to host.  Returns (Fup, Fdn); fills the optional Fortran-order matrices in place.  Mup, Mdn are what the
-        column's want_M says: [np, nnu] planes, [2, nnu] edge spectra (row 0 = TOA, row 1 = level np-1) or [np, ntile] tile sums."""
+        column's want_M says: [np, nnu] planes, [2, nnu] edge spectra (row 0 = TOA, row 1 = level np-1) or [np, ntile] tile sums; tau what
+        its want_tau says: [np-1, nnu] layer depths, [1, nnu] column depths or [np, ntile] tile transmittances."""
         self._require_resident("fetch")
         Fup, Fdn = np.zeros(self.np), np.zeros(self.np)
         bufs = []
         ptrs = []
         mshape = {M_EDGES: (2, self.nnu), M_TILES: (self.np, self.ntile)}.get(self.m_mode, (self.np, self.nnu))
-        for a, shape in ((tau, (self.nl, self.nnu)), (Mup, mshape), (Mdn, mshape)):
+        tshape = {TAU_TOTAL: (1, self.nnu), TAU_TILES: (self.np, self.ntile)}.get(self.tau_mode, (self.nl, self.nnu))
+        for a, shape in ((tau, tshape), (Mup, mshape), (Mdn, mshape)):
             if a is None:
                 ptrs.append(None)
                 bufs.append(None)
@@ -1477,6 +1508,25 @@ class Column:
         Fu, Fd = np.zeros((self.np, self.ntile), order="F"), np.zeros((self.np, self.ntile), order="F")
         self.fetch(Mup=Fu, Mdn=Fd)
         return Fu, Fd
+
+    def column_depth(self):
+        """[nnu]: the slant optical depth D(nu) = sum_i tau_i / cos(theta_s) of the whole column of a want_tau="total" column, after run()
+        or sigma_run() -- dDepth's unfloored layer sums (discretized.jl:92-134), accumulated on the device"""
+        if self.tau_mode != TAU_TOTAL:
+            raise TypeError(f"column_depth needs a column set up with want_tau='total' (this one: want_tau={self.want_tau!r})")
+        D = np.zeros((1, self.nnu), order="F")
+        self.fetch(tau=D)
+        return D[0].copy()
+
+    def tile_transmittance(self):
+        """[np, ntile]: sum of w_j exp(-D_i(nu_j)) over the points of every 64-point tile (tile_ranges(nnu)) of a want_tau="tiles" column,
+        D_i the slant optical depth between the top and level i, w_j the column's (global trapezoid) weights; row 0 is sum w_j
+        (band_transmittance divides by it)"""
+        if self.tau_mode != TAU_TILES:
+            raise TypeError(f"tile_transmittance needs a column set up with want_tau='tiles' (this one: want_tau={self.want_tau!r})")
+        Tt = np.zeros((self.np, self.ntile), order="F")
+        self.fetch(tau=Tt)
+        return Tt
 
     def sigma_nodes(self):
         """Total cross-section at the nodes, shape (K, nnu) (test hook)."""
@@ -1615,26 +1665,13 @@ def radiate(P, g, T, mu, fS, fa, *absorbers, core: Optional[Discretized] = None,
 
 def opticaldepth(P, g, T, mu, theta, *absorbers, nlobatto: int = 4, ctx=None):
     """opticaldepth(P::Vector, g, T, mu, theta, absorbers...; nlobatto=4) fluxes.jl:68-97: total slant optical depth per
-    wavenumber via dDepth (discretized.jl:92-134, no 1e-6 floor).  The node cross-sections come from the device; the
-    O(nnu*K) Lobatto sum is done here."""
+    wavenumber via dDepth (discretized.jl:92-134, no 1e-6 floor).  A want_tau="total" column at theta_s = theta: the cross-section
+    stage and k_depth, no sweep; nnu doubles come back."""
     assert 0 <= theta < math.pi / 2, "azimuth angle θ must be ∈ [0,π/2)"
     P = np.sort(as_f64(P))
-    col = Column(P, g, T, mu, None, None, *absorbers, core=Discretized(5, nlobatto), want_tau=False, want_M=False, ctx=ctx)
+    col = Column(P, g, T, mu, None, None, *absorbers, core=Discretized(5, nlobatto), theta_s=theta, want_tau="total", want_M=False, ctx=ctx)
     col.sigma_run()
-    sig = col.sigma_nodes()
-    Cc = 1e-4 * K.Na / g
-    _, ws = lobattonodes(nlobatto)
-    m = 1 / math.cos(theta)
-    beta = Cc * (sig / col.muk[:, None])
-    tau = np.zeros(col.nnu)
-    nl = len(P) - 1
-    for i in range(nl):
-        dP = P[i + 1] - P[i]
-        ti = np.zeros(col.nnu)
-        for n in range(nlobatto):
-            ti = ti + (dP * ws[n]) * beta[i * (nlobatto - 1) + n]
-        tau = tau + ti * m
-    return tau
+    return col.column_depth()
 
 
 def transmittance(*args, **kw):

@@ -332,7 +332,9 @@ struct Column {
     int64_t nnu = 0;
     int np = 0, nl = 0, nlob = 0, K = 0, nstream = 0, ngas = 0, ntile = 0;
     FluxPlan flux = {}, flux_last = {};   // the setup-time part of the flux plan (flux_plan); the plan the last cs_column_run ran by
-    bool want_tau = false, has_extra = false, has_S = false, has_alb = false;
+    bool has_extra = false, has_S = false, has_alb = false;
+    int want_tau = CS_TAU_NONE;   // what cs_column_fetch's tau is (CS_TAU_*): nothing, the layer depths [nl][nnu] (tau), or k_depth's product (depth): D [nnu], tile sums [np][m_ntile()]
+    bool depth_mode() const { return want_tau == CS_TAU_TOTAL || want_tau == CS_TAU_TILES; }
     int want_M = CS_M_NONE;    // what Mup / Mdn hold (CS_M_*): nothing, the planes [np][nnu], the boundary levels [2][nnu], tile sums [np][m_ntile()]
     int64_t m_ntile() const { return (nnu + 63) / 64; }
     // rows and row length of Mup / Mdn in the column's mode (kernel layout: level-major)
@@ -370,7 +372,7 @@ struct Column {
     ColAccel accel;
     std::vector<double> h_Tk;
     DevBuf nu, wts, P, Pk, Tk, muk, Tlev, extra, S_toa, albedo;
-    DevBuf hot, cold, sigma, sigma2, tau, Mup, Mdn, partial, F, stage, ranges;   // sigma2: the near-line plane (k_voigt_near on a side stream)
+    DevBuf hot, cold, sigma, sigma2, tau, depth, Mup, Mdn, partial, F, stage, ranges;   // sigma2: the near-line plane (k_voigt_near on a side stream)
     DevBuf ped;                // launch_pedestal's workspace for K states (columns with a code-4 group)
     DevBuf vvh;                // the line sum of a code-5 group that is not the column's first, before launch_vvh (K x nnu)
     DevBuf hot32;              // fp32 line records of mixed precision for K states (sigma_impl sizes them): the column's own, as hot and cold are --
@@ -768,7 +770,7 @@ void launch_flux_kernel(Kern kern, dim3 grid, int threads, size_t shmem, const F
 }
 
 // what flux_plan decides from, besides the settings: sizes; baked tables, launch groups, a CIA pair with more than CS_CIA_ACT bands over one tile; the device
-struct FluxFacts { int64_t nnu; int np, nlob, K, nstream; bool tables, gases, cia_overlap, gfx950; };   // (a step's choice of form alone reads the last four)
+struct FluxFacts { int64_t nnu; int np, nlob, K, nstream; bool tables, gases, cia_overlap, gfx950; int tau_mode; };   // (a step's choice of form alone reads the last five)
 
 // The flux stage of a step (FluxPlan).  setup = NULL: the k_rt part for B columns, under these settings (cs_column_setup with B = 1;
 // cs_column_batch); else the step of the resident column whose k_rt part is *setup, completed under these settings (run_impl).
@@ -800,6 +802,7 @@ static FluxPlan flux_plan(const Settings &set, const FluxFacts &f, int B, const 
     }
     FluxPlan pl = *setup;
     if (set.flux_form == 1 || f.tables || !f.gases || f.cia_overlap) return pl;   // (baked tables are added between wings and CIA pairs: own pass)
+    if (f.tau_mode == CS_TAU_TOTAL || f.tau_mode == CS_TAU_TILES) return pl;   // (k_depth reads the finished cross-sections from HBM: the fused forms never write them)
     const bool streams = pl.rt_kern == FK_RT_STREAMS, ud = pl.rt_kern != FK_RT;
     // the scan form: grids of up to 1024 tiles -- with a chunk's transmissivities in registers it beats the separate kernels on a half
     // (846 tiles: 1.10 -> 1.08 ms) and a quarter (407 tiles: 0.677 -> 0.610) of the bench column, not on the whole (1563 tiles: 1.94 ->
@@ -3182,7 +3185,7 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
     c.nnu = nnu; c.np = np; c.nl = np - 1; c.nlob = nlobatto; c.K = (np - 1) * (nlobatto - 1) + 1;
     c.nstream = nstream; c.ngas = ngas; c.ntile = (int)((nnu + 255) / 256);
     c.flux = flux_plan(ctx->set, {nnu, np, nlobatto, c.K, nstream}, 1, nullptr);
-    c.want_tau = want_tau != 0;
+    c.want_tau = want_tau == CS_TAU_NONE || want_tau == CS_TAU_TOTAL || want_tau == CS_TAU_TILES ? want_tau : CS_TAU_LAYERS;   // (any other non-zero value: layers)
     c.want_M = want_M == CS_M_NONE || want_M == CS_M_EDGES || want_M == CS_M_TILES ? want_M : CS_M_PLANES;   // (any other non-zero value: planes)
     c.g = g; c.sigma_gray = sigma_gray; c.theta_s = theta_s;
     const int K = c.K, nl = c.nl;
@@ -3329,7 +3332,10 @@ int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wt
         return rc;
     HIPCHK(c.sigma.reserve((size_t)K * nnu * sizeof(double)));
     if (any_voigt) HIPCHK(c.sigma2.reserve((size_t)K * nnu * sizeof(double)));
-    HIPCHK(c.tau.reserve((size_t)nl * nnu * sizeof(double)));   // the caller's output, or k_flux_chunk's scratch between its two sweeps
+    // the caller's output, or k_flux_chunk's scratch between its two sweeps; a column in a depth mode runs form 0 and stores no layer depths:
+    // k_depth's product instead, [nnu] or [np][ntile]
+    if (!c.depth_mode()) HIPCHK(c.tau.reserve((size_t)nl * nnu * sizeof(double)));
+    else HIPCHK(c.depth.reserve((c.want_tau == CS_TAU_TOTAL ? (size_t)nnu : (size_t)np * (size_t)c.m_ntile()) * sizeof(double)));
     if (!c.ticket.p) {
         HIPCHK(c.ticket.reserve((size_t)(1 + 512 / CS_FLUX_GROUP) * sizeof(unsigned)));
         HIPCHK(hipMemsetAsync(c.ticket.p, 0, c.ticket.bytes, s));
@@ -3688,6 +3694,15 @@ static int column_current(cs_ctx *ctx)
     return CS_OK;
 }
 
+// the column's slant optical depth, or its per-tile transmittances to space (CS_TAU_TOTAL / CS_TAU_TILES), from the cross-section plane as the
+// call in progress leaves it: one wave per 64-point tile
+static void launch_depth(Column &c, hipStream_t s, const double *sigma2)
+{
+    const int64_t nt64 = c.m_ntile();
+    CS_LAUNCH(k_depth, dim3((unsigned)((nt64 + 3) / 4)), dim3(256), 0, s, c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, c.sigma.as<double>(), sigma2,
+              c.muk.as<double>(), c.P.as<double>(), c.want_tau, c.depth.as<double>());
+}
+
 // enqueue one evaluation; when ev != NULL an event is recorded between the kernel classes (ev must hold 7 * (launch groups) + 4)
 static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
 {
@@ -3700,7 +3715,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
     bool near_live = false, overlap = false, rad = false;
     for (auto &cc : c.cia) overlap = overlap || cc.grid.max_overlap > CS_CIA_ACT;
-    const FluxPlan pl = flux_plan(ctx->set, {c.nnu, c.np, c.nlob, c.K, c.nstream, !c.tab.empty(), !c.gas.empty(), overlap, ctx->gfx950}, 1, &c.flux);
+    const FluxPlan pl = flux_plan(ctx->set, {c.nnu, c.np, c.nlob, c.K, c.nstream, !c.tab.empty(), !c.gas.empty(), overlap, ctx->gfx950, c.want_tau}, 1, &c.flux);
     FluxFuse fuse;
     memset(&fuse, 0, sizeof fuse);
     if ((rc = sigma_impl(ctx, s, ev, e, &log, &near_live, pl.form ? &fuse : nullptr, &pl))) return rc;
@@ -3711,7 +3726,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
     const FluxArgs fa = {&c.rt, c.nu.as<double>(), c.wts.as<double>(), c.nnu, sig, c.muk.as<double>(), c.P.as<double>(), c.Tlev.as<double>(),
                          c.has_S ? c.S_toa.as<double>() : nullptr, c.has_alb ? c.albedo.as<double>() : nullptr,
-                         c.want_tau || pl.need_tau ? c.tau.as<double>() : nullptr, c.want_M ? c.Mup.as<double>() : nullptr, c.want_M ? c.Mdn.as<double>() : nullptr,
+                         c.want_tau == CS_TAU_LAYERS || pl.need_tau ? c.tau.as<double>() : nullptr, c.want_M ? c.Mup.as<double>() : nullptr, c.want_M ? c.Mdn.as<double>() : nullptr,
                          c.partial.as<double>(), s};
     const double *sigma2 = near_live ? c.sigma2.as<double>() : nullptr;
     if (pl.form) {
@@ -3725,6 +3740,7 @@ static int run_impl(cs_ctx *ctx, hipStream_t s, hipEvent_t *ev)
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
     if (pl.nfreduce) CS_LAUNCH(k_freduce, dim3(2 * c.np), dim3(256), 0, s, c.partial.as<double>(), pl.nfreduce, 2 * c.np, c.flux_out());
     if (ev) HIPCHK(hipEventRecord(ev[e++], s));
+    if (c.depth_mode()) launch_depth(c, s, sigma2);   // (form 0: sig is finished, the near-line pairs in it or beside it)
     c.launches = g_nlaunch;
     c.log_last = log;
     HIPCHK(hipGetLastError());
@@ -3736,7 +3752,16 @@ int cs_column_sigma_run(cs_ctx *ctx, void *stream)
     if (!ctx || !ctx->col.ready) return fail(CS_ESTATE, "cs_column_setup has not been called");
     HIPCHK(hipSetDevice(ctx->device));
     int e = 0;
-    return sigma_impl(ctx, stream ? (hipStream_t)stream : ctx->stream, nullptr, e, nullptr);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const int rc = sigma_impl(ctx, s, nullptr, e, nullptr);
+    if (rc) return rc;
+    Column &c = ctx->col;
+    if (c.depth_mode()) {   // the depths of the plane this call completed (near-line pairs folded in, clamped where a pedestal came off)
+        launch_depth(c, s, nullptr);
+        c.last_stream = s;
+        HIPCHK(hipGetLastError());
+    }
+    return CS_OK;
 }
 
 int cs_column_run(cs_ctx *ctx, void *stream)
@@ -3874,7 +3899,10 @@ int cs_column_fetch(cs_ctx *ctx, int64_t nnu, int np, double *tau, double *Mup, 
     HIPCHK(hipStreamSynchronize(ctx->stream));
     int rc;
     if (tau && !c.want_tau) return fail(CS_ESTATE, "column was set up without want_tau");
-    if (tau && (rc = fetch_transposed(ctx, c.tau.as<double>(), c.nl, c.nnu, tau))) return rc;
+    // by the column's mode: [np - 1, nnu] layer depths, [nnu] slant depths of the whole column or [np, ntile] tile transmittances
+    if (tau && c.want_tau == CS_TAU_LAYERS && (rc = fetch_transposed(ctx, c.tau.as<double>(), c.nl, c.nnu, tau))) return rc;
+    if (tau && c.want_tau == CS_TAU_TOTAL) HIPCHK(hipMemcpyAsync(tau, c.depth.p, (size_t)c.nnu * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (tau && c.want_tau == CS_TAU_TILES && (rc = fetch_transposed(ctx, c.depth.as<double>(), c.np, c.m_ntile(), tau))) return rc;
     if ((Mup || Mdn) && !c.want_M) return fail(CS_ESTATE, "column was set up without want_M");
     // by the column's mode: [np, nnu] planes, [2, nnu] boundary spectra or [np, ntile] tile sums, column-major (level fastest) all three
     if (Mup && (rc = fetch_transposed(ctx, c.Mup.as<double>(), c.m_rows(), c.m_cols(), Mup))) return rc;
@@ -4334,7 +4362,7 @@ int cs_column_work(cs_ctx *ctx, int64_t *out)
 //  = 0 and accel_slot = -1 for a column without them)
 static bool column_matches(cs_ctx *ctx, int64_t nnu, const double *nu, int np, const double *P, double g, int nlobatto, int ngas,
                            const int *gas_slots, const int *shapes, const double *dnu_cuts, double sigma_gray, double theta_s,
-                           int nstream, bool want_tau, int want_M, int64_t g_nnu = 0, int64_t g_start = 0, double g_left = 0.0, double g_right = 0.0,
+                           int nstream, int want_tau, int want_M, int64_t g_nnu = 0, int64_t g_start = 0, double g_left = 0.0, double g_right = 0.0,
                            int ntab = 0, const int *table_slots = nullptr, int ncia = 0, const int *cia_slots = nullptr, int accel_slot = -1)
 {
     const Column &c = ctx->col;
@@ -4347,7 +4375,7 @@ static bool column_matches(cs_ctx *ctx, int64_t nnu, const double *nu, int np, c
         if (c.cia[t].slot != cia_slots[t]) return false;
     if (c.nnu != nnu || c.np != np || c.nlob != nlobatto || c.nstream != nstream || c.ngas != ngas) return false;
     if (c.g != g || c.sigma_gray != sigma_gray || c.theta_s != theta_s) return false;
-    if (c.want_tau != want_tau || c.want_M != want_M) return false;   // (modes compared: an edges or tiles column is no planes column -- its M buffers are smaller)
+    if (c.want_tau != want_tau || c.want_M != want_M) return false;   // (modes compared: an edges or tiles column is no planes column -- its M buffers are smaller -- and a total or tiles column holds no layer depths)
     if (c.merge != ctx->merge) return false;
     for (int gi = 0; gi < ngas; gi++) {
         const UserGas &cg = c.ugas[gi];
@@ -4388,7 +4416,7 @@ int cs_fluxes_discretized_members(cs_ctx *ctx, int64_t nnu, const double *nu, in
     // column of the previous call resident and refresh only what a call can change -- node states, fS, fa, sigma_extra, and the
     // per-node inputs of the tables / CIA pairs / accelerated absorber it names
     if (column_matches(ctx, nnu, nu, np, P, g, nlobatto, ngas, gas_slots, shapes, dnu_cuts, sigma_gray, theta_s, nstream,
-                       tau != nullptr, (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE, 0, 0, 0.0, 0.0, ntab, table_slots, ncia, cia_slots, accel_slot)) {
+                       tau ? CS_TAU_LAYERS : CS_TAU_NONE, (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE, 0, 0, 0.0, 0.0, ntab, table_slots, ncia, cia_slots, accel_slot)) {
         Column &c = ctx->col;
         HIPCHK(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
@@ -4406,7 +4434,7 @@ int cs_fluxes_discretized_members(cs_ctx *ctx, int64_t nnu, const double *nu, in
     } else {
         rc = cs_column_setup(ctx, nnu, nu, nullptr, np, P, g, nlobatto, T_nodes, mu_nodes, T_levels, ngas, gas_slots,
                              shapes, dnu_cuts, conc, sigma_gray, sigma_extra, S_toa, albedo, theta_s, nstream,
-                             tau != nullptr, (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE);
+                             tau ? CS_TAU_LAYERS : CS_TAU_NONE, (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE);
         if (rc) return rc;
         if (ntab > 0 && (rc = cs_column_set_tables(ctx, ntab, table_slots, conc_tab))) return rc;
     }
@@ -4891,7 +4919,7 @@ int cs_fluxes_discretized_multi(cs_ctx *const *ctxs, int nctx, int64_t nnu, cons
         }
         const double gl = a > 0 ? nu[a - 1] : 0.0, gr = a + n < nnu ? nu[a + n] : 0.0;
         int r;
-        if (column_matches(ctx, n, nu + a, np, P, g, nlobatto, ngas, gas_slots, shapes, dnu_cuts, sigma_gray, theta_s, nstream, tau != nullptr,
+        if (column_matches(ctx, n, nu + a, np, P, g, nlobatto, ngas, gas_slots, shapes, dnu_cuts, sigma_gray, theta_s, nstream, tau ? CS_TAU_LAYERS : CS_TAU_NONE,
                            (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE, nnu, a, gl, gr)) {
             Column &c = ctx->col;
             hipStream_t s = ctx->stream;
@@ -4907,7 +4935,7 @@ int cs_fluxes_discretized_multi(cs_ctx *const *ctxs, int nctx, int64_t nnu, cons
         } else {
             r = cs_column_setup(ctx, n, nu + a, wt.data() + a, np, P, g, nlobatto, T_nodes, mu_nodes, T_levels, ngas, gas_slots, shapes, dnu_cuts,
                                 conc, sigma_gray, sigma_extra ? ex.data() : nullptr, S_toa ? S_toa + a : nullptr, albedo ? albedo + a : nullptr,
-                                theta_s, nstream, tau != nullptr, (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE);
+                                theta_s, nstream, tau ? CS_TAU_LAYERS : CS_TAU_NONE, (Mup || Mdn) ? CS_M_PLANES : CS_M_NONE);
             if (!r) { ctx->col.g_nnu = nnu; ctx->col.g_start = a; ctx->col.g_left = gl; ctx->col.g_right = gr; }
         }
         if (prev[i] >= 0) {

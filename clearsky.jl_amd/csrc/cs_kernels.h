@@ -3375,6 +3375,63 @@ __global__ __launch_bounds__(256) void k_fold(int64_t n, double *__restrict__ si
     if (i < n) sigma[i] += sigma2[i];
 }
 
+// opticaldepth / transmittance of the one-shot interface (fluxes.jl:68-109) from the finished cross-section plane sigma[K][nnu] (+ sigma2,
+// the near-line plane, where the step kept it apart: sg(k) as in k_rt): dDepth (discretized.jl:92-134) -- the layer sum layer_depth
+// forms, WITHOUT its floor, times m = 1 / cos(theta_s), accumulated from the top: D_0 = 0, D_{i+1} = D_i + tau_i m.  One lane per
+// wavenumber, one wave per 64-point tile (rt_lane: ragged last tile, weight 0 past the end), no barrier, no LDS.  The lane walks the
+// nodes in order -- each (node, nu) is read once, a layer's end node opens the next layer -- eight node rows in flight at a time (a
+// row is a coalesced 512-byte load of the wave; the walk itself is a chain of K multiply-adds).
+//   CS_TAU_TOTAL  out[nnu] = D_{np-1}
+//   CS_TAU_TILES  out[np][ntile] = sum over the tile of w_j exp(-D_i(nu_j)), from lane 0 (the library's exp: 1 ulp); no per-point value is stored
+// Reads RtParams (C, ws, cos_ts) and the flux kernels' helpers; changes neither.
+__global__ __launch_bounds__(256) void k_depth(RtParams p, const double *__restrict__ nu, const double *__restrict__ wts, int64_t nnu,
+                                               const double *__restrict__ sigma, const double *__restrict__ sigma2,
+                                               const double *__restrict__ muk, const double *__restrict__ P, int mode, double *__restrict__ out)
+{
+    const int64_t ntile = (nnu + 63) / 64;
+    const int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (tile >= ntile) return;   // (wave-uniform)
+    const RtLane L = rt_lane(tile, true, nnu, nu, wts, nullptr, nullptr);
+    const int nlob = p.nlobatto, K = p.K;
+    const bool tiles = mode == CS_TAU_TILES;
+    auto sg = [&](int k) { const size_t idx = (size_t)k * nnu + L.jj; return sigma2 ? sigma[idx] + sigma2[idx] : sigma[idx]; };   // node k
+    auto level = [&](int i, double D) {   // transmittance to space of level i, summed over the tile
+        if (!tiles) return;
+        const double r = wave_sum(L.w * exp(-D));
+        if (L.lane == 0) out[(size_t)i * ntile + tile] = r;
+    };
+    const double m = 1.0 / p.cos_ts;   // (correctly rounded; theta_s < pi / 2)
+    double D = 0.0, ti = 0.0, dP = P[1] - P[0];
+    int i = 0, n = 0;   // layer and node within it of the node being added
+    level(0, D);
+    for (int k0 = 0; k0 < K; k0 += 8) {
+        double s[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) s[q] = sg(min(k0 + q, K - 1));
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int k = k0 + q;
+            if (k >= K) break;
+            const double b = node_beta(p.C, s[q], muk[k]);
+            if (k == 0) {
+                ti = (dP * p.ws[0]) * b;
+                continue;
+            }
+            n++;
+            ti += (dP * p.ws[n]) * b;
+            if (n < nlob - 1) continue;
+            D += ti * m;   // the layer is complete: tau_i m onto the depth above it
+            level(++i, D);
+            if (k < K - 1) {   // its end node is the first node of the next layer
+                dP = P[i + 1] - P[i];
+                ti = (dP * p.ws[0]) * b;
+                n = 0;
+            }
+        }
+    }
+    if (!tiles && L.live) out[L.j] = D;
+}
+
 __global__ __launch_bounds__(256) void k_fill(int64_t n, double base, const double *__restrict__ extra, double *__restrict__ sigma)
 {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -322,11 +322,38 @@ int cs_rebalance_ranges(int64_t nnu, const double *nu, int ngas, const int64_t *
  * In the last two modes the [np, nnu] planes are never allocated.  The host-pointer entry points (cs_fluxes_discretized, _members,
  * _multi) know planes or nothing -- their M pointers are [np, nnu] -- and never re-use a resident column of another mode;
  * cs_column_batch returns band fluxes only, whatever the mode.
+ *
+ * `want_tau` of cs_column_setup says likewise what the column keeps of the optical depths and what cs_column_fetch writes through its
+ * `tau` pointer (tau of a CS_TAU_NONE column is CS_ESTATE):
+ *   CS_TAU_NONE   nothing;
+ *   CS_TAU_LAYERS the layer depths, [np - 1, nnu] column-major, as dDepth! forms them and the sweeps use them: floored at 1e-6 per
+ *                 layer (discretized.jl:147,174) -- every non-zero value that is none of the two below means this one;
+ *   CS_TAU_TOTAL  [nnu]: D(nu_j) = sum_i tau_i m, the slant optical depth of the whole column, opticaldepth(P::Vector, g, T, mu, theta,
+ *                 absorbers...) of fluxes.jl:68-97 with theta = the column's theta_s.  tau_i = sum_n (dP_i ws_n) beta_{i (nlob - 1) + n}
+ *                 with beta = C (sigma / mu), the sum dDepth! forms BEFORE its floor: there is no floor here (dDepth, discretized.jl:
+ *                 92-134); m = 1 / cos(theta_s), a correctly rounded division; D_0 = 0, D_{i + 1} = D_i + tau_i m layer by layer from the
+ *                 top, D = D_{np - 1};
+ *   CS_TAU_TILES  [np, ntile] column-major, level fastest, ntile = (nnu + 63) / 64: per level i and 64-point tile (the tiles of
+ *                 CS_M_TILES) sum_j w_j exp(-D_i(nu_j)) with the column's weights (`wts`, or the trapezoid weights of `nu`) -- the
+ *                 transmittance to space of every level, integrated over the tile.  Row 0 is sum_j w_j, so a band of whole tiles
+ *                 divided by the same tiles of row 0 is its band transmission function; with the column's stellar angle it is the
+ *                 share of the direct beam that reaches the level.  The exponential is the library's exp.  The tiles of nu-shards cut
+ *                 at multiples of 64 points are the tiles of the whole grid.
+ * In the last two modes the [np - 1, nnu] plane is never allocated for the caller, the step runs the separate flux kernels (flux form 0:
+ * its finished cross-sections are in HBM) and one more kernel, k_depth, after them; cs_column_sigma_run launches it after the
+ * cross-section stage, with no sweep at all.  The depths are those of the plane as that call leaves it: unclamped after cs_column_run,
+ * clamped after cs_column_sigma_run for a column with a code-4, 6 or 7 gas (the two planes described with shape code 4 above).  The
+ * host-pointer entry points know layers or nothing and never re-use a resident column of another tau mode; cs_column_batch returns band
+ * fluxes only.
  */
 #define CS_M_NONE 0
 #define CS_M_PLANES 1
 #define CS_M_EDGES 2
 #define CS_M_TILES 3
+#define CS_TAU_NONE 0
+#define CS_TAU_LAYERS 1
+#define CS_TAU_TOTAL 2
+#define CS_TAU_TILES 3
 int cs_column_setup(cs_ctx *ctx, int64_t nnu, const double *nu, const double *wts, int np, const double *P,
                     double g, int nlobatto, const double *T_nodes, const double *mu_nodes, const double *T_levels,
                     int ngas, const int *gas_slots, const int *shapes, const double *dnu_cuts, const double *conc,

@@ -894,6 +894,52 @@ function hipspectra(kind::Symbol, P::AbstractVector{<:Real}, g::Real, T, Î¼, ð’
     return Fâº, Fâ», Mâº, Mâ»
 end
 
+# opticaldepth(P::Vector, g, T, Î¼, Î¸, absorbers...; nlobatto) [fluxes.jl:68-97] and transmittance [:109] on the device: a resident
+# column whose `want_tau` is CS_TAU_TOTAL (2) [include/clearsky_hip.h] with theta_s = Î¸, cs_column_sigma_run -- the cross-section stage and
+# k_depth, no sweep -- then cs_column_fetch, whose `tau` is [nÎ½] in that mode: ð’¹depth's unfloored layer sums times 1/cos Î¸, accumulated
+# from the top.  One device; members as hipcolumn! takes them.  (The scalar-pressure method opticaldepth(Pâ‚, Pâ‚‚, ...; tol) belongs to the
+# Radau core and is not offered.)
+function hipopticaldepth(P::AbstractVector{<:Real}, g::Real, T, Î¼, Î¸::Real, absorbers...; nlobatto::Int=4)
+    ð’œ, Î½, nÎ½ = ClearSky.unifyabsorbers(absorbers)
+    ð’œ isa AcceleratedAbsorber && error("hipopticaldepth takes the absorbers themselves, not an AcceleratedAbsorber")
+    ð’»T, ð’»Î¼ = formprofiles(P, T, Î¼)
+    Pv = sort(collect(Float64, P))                      # (let pressure be ascending, fluxes.jl:80)
+    Tn, Î¼n = lobattoevaluations(Pv, ð’»T, ð’»Î¼, nlobatto)
+    Tn = Matrix{Float64}(Tn); Î¼n = Matrix{Float64}(Î¼n)
+    Tlev = Float64[ð’»T(p) for p in Pv]
+    hipcheckpressures(ð’œ, Pv[end], Pv[1])
+    checkazimuth(Î¸)
+    np = length(Pv)
+    Pk, Tk = nodestates(Pv, Tn, nlobatto)
+    ctx = context(0)
+    m = members(ctx, ð’œ, Tk, Pk)
+    Î½v = collect(Float64, Î½)
+    D = Vector{Float64}(undef, nÎ½)
+    extra = m.extra
+    GC.@preserve Î½v Pv Tn Î¼n Tlev m extra D begin
+        check(ccall((:cs_column_setup, LIB), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Float64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Float64, Cint, Cint, Cint),
+            ctx.handle, nÎ½, Î½v, C_NULL, np, Pv, Float64(g), nlobatto, Tn, Î¼n, Tlev, length(m.slots), m.slots, m.shapes, m.cuts, m.conc,
+            m.Ïƒgray, extra === nothing ? C_NULL : pointer(extra), C_NULL, C_NULL, Float64(Î¸), 5, 2, 0))      # CS_TAU_TOTAL, CS_M_NONE
+        isempty(m.tslots) || check(ccall((:cs_column_set_tables, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Float64}),
+            ctx.handle, length(m.tslots), m.tslots, m.conctab))
+        isempty(m.cslots) || check(ccall((:cs_column_set_cia, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}),
+            ctx.handle, length(m.cslots), m.cslots, m.cflags, m.Pâ‚, m.Pâ‚‚))
+        check(ccall((:cs_column_sigma_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.handle, C_NULL))
+        # nnu and np are the COLUMN's sizes (the size check); in this mode `tau` is filled with nÎ½ doubles
+        check(ccall((:cs_column_fetch, LIB), Cint,
+            (Ptr{Cvoid}, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            ctx.handle, nÎ½, np, D, C_NULL, C_NULL, C_NULL, C_NULL))
+    end
+    return D
+end
+
+function hiptransmittance(args...; kwargs...)
+    return exp.(-hipopticaldepth(args...; kwargs...))
+end
+
 # jacobian! [radiative_convective.jl:154-171] as ONE device batch: the band fluxes of B temperature profiles on the column of the
 # last monochromaticfluxes! call of this thread's context (same grid, levels and members).  Ts[b] is whatever `T` was in that call
 # (vector at the levels or a function of P).  Returns Fâº, Fâ» as [np, B].
@@ -934,6 +980,6 @@ function batchfluxes(core::HIPDiscretized, P::AbstractVector{<:Real}, Ts::Abstra
 end
 
 export HIPDiscretized, DirectGas, HIPGas, HIPCIA, Continuum, hipvoigt!, hiplorentz!, hipdoppler!, hipPHCO2!, hipvoigtCKD!, hipvoigtVVH!, hipvoigtCKDVVH!, hipbake!, hipshapepoints, batchfluxes,
-       hipfluxes, hipnetfluxes, hipspectra
+       hipfluxes, hipnetfluxes, hipspectra, hipopticaldepth, hiptransmittance
 
 end # module
